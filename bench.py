@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- MPC control steps/s of the batched convex-MPC contact-force solve on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps once and prints the headline line (`value`, `ms_per_step`).  Everything else the
+benchmark measures -- repeated blocks, solver statistics, roofline and traffic figures, the device clock, the secondary configurations,
+the control-loop legs, the CPU baseline and its error against OSQP, and for N > 1 the exchange legs -- runs only with --full.
+--dump-outputs DIR writes what the last timed step returned (`torques` and `forces` of the controller seam, `forces` and `info` of the
+solver seam) as DIR/<name>.npy.
 
 A "step" = one pass of the hot path over one batch of synthetic input = SURVEY.md 8(d)'s unit of work for every robot of the batch: one
 ``controller.run(dof_states, body_states, commands) -> torques`` call (the reference's batch seam, RL_Environment/tasks/aliengo.py:246-256) on
@@ -99,7 +105,8 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-control-loop", action="store_true", help="skip the secondary legs (profiling runs)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary single-GPU lines of the other configurations")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps each; `value` is the MEDIAN block (one block of ~20 steps is an 18 ms sample)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed blocks of --steps steps each; `value` is the MEDIAN block (one block of ~20 steps is an 18 ms sample; "
+                                                              "default: 1, with --full 5)")
     ap.add_argument("--robots-total", type=int, default=None, help="(strong-scaling configurations: overrides the total that is sharded over the ranks)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of the N > 1 launch (nccl = RCCL; gloo only with --emulate)")
     ap.add_argument("--exchange", default="rccl", choices=["rccl", "peer", "both"],
@@ -108,7 +115,13 @@ def parse_args():
     ap.add_argument("--emulate", action="store_true",
                     help="CPU dry run of this script's control flow (self-launch, sharding, barriers, gather leg, rank-0 JSON) with the host emulation of the "
                          "kernels (tests/emu) standing in for the HIP library: for tests/test_bench_multirank.py, the numbers mean nothing")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: solver statistics, roofline, device clock, the secondary lines, "
+                                                        "control loops, CPU baseline (trimmed by the --no-* options) and, for N > 1, the exchange legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays of the last timed step to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 class _EmulatedSolver:
@@ -127,10 +140,12 @@ class _EmulatedSolver:
     def solve(self, d_in, forces=None, info=None):
         import torch
         f = self.e.solve(d_in.numpy(), nthreads=2)
+        f, i = torch.from_numpy(np.nan_to_num(f)), torch.from_numpy(self.e.info.copy())
         if forces is not None:
-            forces.copy_(torch.from_numpy(np.nan_to_num(f)))
+            forces.copy_(f)
         if info is not None:
-            info.copy_(torch.from_numpy(self.e.info))
+            info.copy_(i)
+        return f, i
 
     def kernel_times(self, k):
         return np.full(k, 1e-3, np.float32), np.full(k, 1e-3, np.float32)
@@ -186,18 +201,21 @@ CTRL_DT = 0.02      # controller.run period of the ctrl seam: iterationsBetweenM
                     # an MPC update of every robot, with the reference's dtMPC = 0.02 (its own 0.01 x 2, ConvexMPCLocomotion.py:58)
 
 
-def run_leg_ctrl(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=False):
+def run_leg_ctrl(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=False, detail=True):
     """`value`'s leg: K timed controller.run calls (every robot due on every call) after W warm-up calls, `repeats` blocks, each bracketed by
-    barrier + synchronize; then ONE untimed replay of the same block that fetches, per step, what the solver was handed and what it did
-    (records, info) -- the solves are deterministic, so the replay's are the timed block's."""
+    barrier + synchronize.  detail: HIP-event kernel times, and ONE untimed replay of the same block that fetches, per step, what the solver was
+    handed and what it did (records, info) -- the solves are deterministic, so the replay's are the timed block's."""
     import torch
     from rl_mpc_locomotion_amd import layout as L
     from rl_mpc_locomotion_amd.synthetic import ControlStepStream
 
     R = max(1, repeats)
     cs = ControlStepStream(n, h=h, seed=1000 + rank, config=cfg_id)            # this rank's shard: its own seeded robots
-    host = [cs.step(s) for s in range(W + K)]
-    ins = [tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in t) for t in host]     # resident in HBM before timing
+    ins, first_dof = [], None
+    for s, t in enumerate(cs.steps(W + K, workers=usable_cores())):
+        ins.append(tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in t))     # resident in HBM before timing
+        if s == W:
+            first_dof = t[0]
     if emulate:
         ctl = _EmulatedLocomotion(cs, h, CTRL_DT)
         sync = lambda: None
@@ -206,12 +224,13 @@ def run_leg_ctrl(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=
         ctl = BatchedLocomotion(cs.robot_type, cs.gait_id, horizon=h, controller_dt=CTRL_DT, device=dev)
         assert ctl.iterations_between_mpc == 1
         sync = lambda: torch.cuda.synchronize(dev)
-    ctl.enable_timing()
+    if detail:
+        ctl.enable_timing()
     # config 3: Parameters.cmpc_gait CYCLES Trot -> Walk -> Bound every 50 steps; the ids of every switch inside the sequence are resident in HBM
     # before timing and handed over as device tensors (mpc_ctrl_set_gait_device: stream-ordered, no host round trip), inside the timed region when it falls there
     gaits = {s: torch.from_numpy(cs.gait_at(s)).to(dev) for s in range(W + K) if s == 0 or cs.gait_switch_at(s)} if cs.gait_at(0) is not None else {}
     block_s, prep_ms, solve_ms = [], [], []
-    for r in range(R + 1):                       # block R is the untimed replay
+    for r in range(R + 1 if detail else R):      # block R is the untimed replay
         replay = r == R
         ctl.reset()
         ctl.set_iteration(cs.iteration0)
@@ -230,7 +249,7 @@ def run_leg_ctrl(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=
         for s in range(K):
             if W + s in gaits:
                 ctl.set_gait(gaits[W + s])
-            ctl.run(*ins[W + s])
+            tau = ctl.run(*ins[W + s])
             if replay:
                 recs.append(ctl.solver_record()); infos.append(ctl.solver_info())
                 if s == 0:
@@ -245,8 +264,13 @@ def run_leg_ctrl(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=
             from rl_mpc_locomotion_amd.sharding import max_over_ranks
             elapsed = max_over_ranks(elapsed, dev)
         block_s.append(elapsed)
-        a, b = ctl.kernel_times(min(K, 64))
-        prep_ms.append(a.astype(np.float64)); solve_ms.append(b.astype(np.float64))
+        outputs = {"torques": tau.cpu().numpy().copy(), "forces": ctl.solver_forces()}      # what the last timed step returned
+        if detail:
+            a, b = ctl.kernel_times(min(K, 64))
+            prep_ms.append(a.astype(np.float64)); solve_ms.append(b.astype(np.float64))
+    m = dict(block_s=np.array(block_s), elapsed=float(np.median(block_s)), outputs=outputs)
+    if not detail:
+        return m
     prep_ms, solve_ms = np.concatenate(prep_ms), np.concatenate(solve_ms)
     info = np.stack(infos)                                           # [K, n, 8]
     flops = asm_flops = exec_flops = 0.0
@@ -256,13 +280,15 @@ def run_leg_ctrl(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=
         fa, fs = algorithmic_flops(h, contact, it, nf)
         flops += fs; asm_flops += fa
         exec_flops += executed_flops(h, it, nf)
-    return dict(gait_switches_timed=sum(1 for s in gaits if s >= W and s > 0), wl=_Model(cs.robot_type, CTRL_DT, 1e-5), batches=recs, solver=ctl, block_s=np.array(block_s), elapsed=float(np.median(block_s)), prep_ms=prep_ms, first_dof=host[W][0], robot_type=cs.robot_type,
-                solve_ms=solve_ms, info=info, first_forces=first_forces, flops_per_launch=flops / K, prep_flops_per_launch=asm_flops / K, exec_flops=exec_flops / K)
+    m.update(gait_switches_timed=sum(1 for s in gaits if s >= W and s > 0), wl=_Model(cs.robot_type, CTRL_DT, 1e-5), batches=recs, solver=ctl, prep_ms=prep_ms,
+             first_dof=first_dof, robot_type=cs.robot_type, solve_ms=solve_ms, info=info, first_forces=first_forces, flops_per_launch=flops / K,
+             prep_flops_per_launch=asm_flops / K, exec_flops=exec_flops / K)
+    return m
 
 
-def run_leg(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=False):
+def run_leg(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=False, detail=True):
     """Warm up, then time `repeats` blocks of exactly K steps, each bracketed by barrier + synchronize; returns the raw measurements
-    of this rank (block times already reduced to the slowest rank)."""
+    of this rank (block times already reduced to the slowest rank).  detail: HIP-event kernel times and the solver statistics of every timed step."""
     import torch
     from rl_mpc_locomotion_amd import layout as L
     from rl_mpc_locomotion_amd.synthetic import make_solver_workload, perturb_workload
@@ -283,9 +309,10 @@ def run_leg(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=False
         inertia9 = np.zeros((n, 9)); inertia9[:, 0], inertia9[:, 4], inertia9[:, 8] = wl.inertia_diag.T
         solver = BatchedConvexMpc(wl.mass, inertia9, h, wl.dt_mpc, wl.alpha, device=dev)
         sync = lambda: torch.cuda.synchronize(dev)
-    solver.enable_timing()                       # HIP events inside the library, around each kernel, on the launch stream
-    infos = [torch.zeros((n, 8), dtype=torch.int32, device=dev) for _ in range(K)]
-    first_out = torch.zeros((n, 12 * h), dtype=torch.float64, device=dev)
+    if detail:
+        solver.enable_timing()                   # HIP events inside the library, around each kernel, on the launch stream
+        infos = [torch.zeros((n, 8), dtype=torch.int32, device=dev) for _ in range(K)]
+        first_out = torch.zeros((n, 12 * h), dtype=torch.float64, device=dev)
 
     # Every block is the SAME experiment -- cold start, the W warm-up steps, then the K timed steps on the same seeded sequence -- so the
     # blocks are repeated samples of one quantity and their median is meaningful (a longer sequence would drift: the states random-walk).
@@ -301,7 +328,10 @@ def run_leg(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=False
         sync()
         t0 = time.perf_counter()
         for s in range(K):
-            solver.solve(d_in[W + s], forces=first_out if s == 0 else None, info=infos[s])
+            if detail:
+                f, i = solver.solve(d_in[W + s], forces=first_out if s == 0 else None, info=infos[s])
+            else:
+                f, i = solver.solve(d_in[W + s])
         sync()
         if dist is not None:
             dist.barrier()
@@ -310,8 +340,13 @@ def run_leg(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=False
             from rl_mpc_locomotion_amd.sharding import max_over_ranks
             elapsed = max_over_ranks(elapsed, dev)
         block_s.append(elapsed)
-        a, b = solver.kernel_times(min(K, 64))
-        prep_ms.append(a.astype(np.float64)); solve_ms.append(b.astype(np.float64))
+        outputs = {"forces": f.cpu().numpy().copy(), "info": i.cpu().numpy().astype(np.float64)}      # what the last timed step returned
+        if detail:
+            a, b = solver.kernel_times(min(K, 64))
+            prep_ms.append(a.astype(np.float64)); solve_ms.append(b.astype(np.float64))
+    m = dict(block_s=np.array(block_s), elapsed=float(np.median(block_s)), outputs=outputs)
+    if not detail:
+        return m
     prep_ms, solve_ms = np.concatenate(prep_ms), np.concatenate(solve_ms)
     info = torch.stack(infos).cpu().numpy()                         # [K, n, 8] (the last block's; every block solves the same problems)
     flops = asm_flops = exec_flops = 0.0
@@ -321,8 +356,9 @@ def run_leg(cfg_id, n, h, K, W, dev, rank, world, dist, repeats=1, emulate=False
         fa, fs = algorithmic_flops(h, contact, it, nf)
         flops += fs; asm_flops += fa
         exec_flops += executed_flops(h, it, nf)
-    return dict(wl=wl, batches=batches, solver=solver, block_s=np.array(block_s), elapsed=float(np.median(block_s)), prep_ms=prep_ms, solve_ms=solve_ms, info=info,
-                first_forces=first_out.cpu().numpy(), flops_per_launch=flops / K, prep_flops_per_launch=asm_flops / K, exec_flops=exec_flops / K)
+    m.update(wl=wl, batches=batches, solver=solver, prep_ms=prep_ms, solve_ms=solve_ms, info=info, first_forces=first_out.cpu().numpy(),
+             flops_per_launch=flops / K, prep_flops_per_launch=asm_flops / K, exec_flops=exec_flops / K)
+    return m
 
 
 def main():
@@ -376,28 +412,23 @@ def main():
     # configs 4 / 5 specify the solver's terrain-normal argument directly, so their default seam is the solver's; `--seam ctrl` runs them
     # through controller.run as well (16- / 20-segment gaits, the ground normal from the estimator's foot-contact fit: `secondary.config4_ctrl` / `config5_ctrl`)
     seam = args.seam or ("ctrl" if args.config in (2, 3) else "solver")
-    clock0 = device_state(local_rank) if not args.emulate and rank == 0 else None
+    full = args.full
+    clock0 = device_state(local_rank) if full and not args.emulate and rank == 0 else None
     leg = run_leg_ctrl if seam == "ctrl" else run_leg
-    m = leg(args.config, n, h, K, W, dev, rank, world, dist, repeats=args.repeats, emulate=args.emulate)
-    clock1 = device_state(local_rank, smi=False) if not args.emulate and rank == 0 else None
-    gather = all_gather_leg(n, n_total, dev, dist) if dist is not None else None
-    if dist is not None and args.exchange in ("peer", "both") and not args.emulate:
+    m = leg(args.config, n, h, K, W, dev, rank, world, dist, repeats=args.repeats, emulate=args.emulate, detail=full)
+    clock1 = device_state(local_rank, smi=False) if full and not args.emulate and rank == 0 else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["outputs"], "" if world == 1 else f"_rank{rank}", DUMP_BYTES // world)
+    gather = all_gather_leg(n, n_total, dev, dist) if dist is not None and full else None
+    if gather is not None and args.exchange in ("peer", "both") and not args.emulate:
         gather["peer_write"] = peer_write_leg(n, n_total, rank, world, dev, dist)
-    if dist is not None and seam == "ctrl":
+    if gather is not None and seam == "ctrl":
         gather["sharded_loop"] = sharded_loop_leg(args.config, n_total, h, dev, dist, emulate=args.emulate)
 
     if rank != 0:
         dist.destroy_process_group()
         return
 
-    info, solve_ms, prep_ms = m["info"], m["solve_ms"], m["prep_ms"]
-    achieved_tflops = m["flops_per_launch"] / (solve_ms.mean() * 1e-3) / 1e12
-    # HBM-side traffic is a rocprofv3 PMC measurement of THIS command, taken in separate --pmc passes (tools/pmc_passes.sh ->
-    # profiles/<TRAFFIC_PROFILE>_pmc_summary[_prep]_h10.json; bench.py cannot run the profiler on itself).  The files are named here, not
-    # searched for, and quoted only if they were measured on the kernel sources of this tree (their kernel_source_sha256).
-    traffic, traffic_parts = None, None
-    if n == 4096 and h == 10 and args.config == 2 and not args.emulate:
-        traffic, traffic_parts = traffic_from_profile()
     value = n_total * K / m["elapsed"]
     out = {
         "metric": f"MPC control steps/sec (whole node) @ horizon={h}, {n} robots; max |GRF| err vs OSQP",   # BASELINE.json's metric at the default configuration
@@ -423,36 +454,47 @@ def main():
                        "one compute_contact_forces (QP build + solve) per robot per step, warm-started seeded sequence, SURVEY.md 8(d); the bare solver batch "
                        "(a2-a13), no controller around it"),
                    "seam": seam, "robots_per_gpu": n, "robots_total": n_total, "horizon": h, "parallelism": f"robot-sharded x{world}"},
-        "solved_fraction": float((info[..., 1] == 1).mean()),
-        "mean_admm_iters": float(info[..., 0].mean()),
-        "mean_factorisations": float(info[..., 4].mean()),
-        "roofline": {"bound": "vector_fp64", "achieved": achieved_tflops, "peak": FP32_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved_tflops / FP32_VECTOR_PEAK_TFLOPS, "traffic": traffic,
-                     "traffic_parts": traffic_parts,
-                     # "and rocprof-measured HBM GB/s / 8 TB/s, side by side": the fabric-side bytes of a step over the step's two solver kernels
-                     "hbm": None if traffic is None else {"gb_per_s": traffic / ((prep_ms + solve_ms).mean() * 1e-3) / 1e9, "peak_gb_per_s": 8000.0,
-                                                           "frac": traffic / ((prep_ms + solve_ms).mean() * 1e-3) / 8e12,
-                                                           "algorithmic_gb_per_s": 47.7e6 * (n / 4096.0) / ((prep_ms + solve_ms).mean() * 1e-3) / 1e9,
-                                                           "note": "<< 1 by design (SURVEY 8d: the path is not HBM-bound); the bytes are an upper bound on HBM traffic (Infinity-Cache hits included)"},
-                     "traffic_note": "HBM-side bytes per step, BOTH kernels (prep + solve), from rocprofv3 PMC (profiles/*_pmc_summary*_h10.json, measured offline on this command); "
-                                     "algorithmic bytes per step: input 384 B + forces 960 B + state 2 x 5136 B per robot = 47.7 MB",
-                     "note": "vector-FP bound, no MFMA / HBM roofline applies (SURVEY 8d): algorithmic flops (n_r formula, solve-kernel share) / "
-                             "mean duration of the solve kernel (mpc_solve_jobs_kernel) from HIP events on the launch stream; `peak` is the FP32 vector rate SURVEY 8(d) "
-                             "prescribes, the kernel's arithmetic is fp64 (frac_fp64_peak, peak 78.6 TF)",
-                     "kernel": "mpc_solve_jobs_kernel<10> (persistent: ADMM and polish jobs of every robot)", "kernel_ms": float(solve_ms.mean()), "prep_kernel_ms": float(prep_ms.mean()),
-                     "step_ms_all_kernels": float((prep_ms + solve_ms).mean()), "step_ms_outside_the_two_solver_kernels": float(m["elapsed"] / K * 1e3 - (prep_ms + solve_ms).mean()),
-                     "flops_per_launch": m["flops_per_launch"],
-                     "prep_kernel_flops_per_launch": m["prep_flops_per_launch"],
-                     "frac_fp64_peak": achieved_tflops / FP64_VECTOR_PEAK_TFLOPS,
-                     "mfma": {"utilisation_of_this_kernel": 0.0,
-                              "note": "by design: the one GEMM-shaped contraction of the reference's assembly (B_qp^T Q B_qp) is removed algebraically (P = alpha I + BB^T Theta BB, "
-                                      "DESIGN.md 3.1) and fp64 MFMA issues at the vector rate on gfx950; the matrix pipe is used where it cuts INSTRUCTIONS: the weight policy's "
-                                      "actor (v_mfma_f32_32x32x2_f32, `policy`) and the exact mode's seeded Gram inverse (v_mfma_f64_16x16x4_f64, `secondary.exact`)"},
-                     "executed": {"flops_per_launch": m["exec_flops"], "tflops": m["exec_flops"] / (solve_ms.mean() * 1e-3) / 1e12,
-                                  "frac_fp64_peak": m["exec_flops"] / (solve_ms.mean() * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
-                                  "note": "operations the solve kernel executes (bench.py executed_flops: OSQP on all 12 h variables through the 6 h x 6 h "
-                                          "wrench-space core), for orientation only -- `achieved` / `frac` use the SURVEY 8(d) minimal-algorithm count"}},
     }
+    if full:
+        info, solve_ms, prep_ms = m["info"], m["solve_ms"], m["prep_ms"]
+        achieved_tflops = m["flops_per_launch"] / (solve_ms.mean() * 1e-3) / 1e12
+        # HBM-side traffic is a rocprofv3 PMC measurement of THIS command, taken in separate --pmc passes (tools/pmc_passes.sh ->
+        # profiles/<TRAFFIC_PROFILE>_pmc_summary[_prep]_h10.json; bench.py cannot run the profiler on itself).  The files are named here, not
+        # searched for, and quoted only if they were measured on the kernel sources of this tree (their kernel_source_sha256).
+        traffic, traffic_parts = None, None
+        if n == 4096 and h == 10 and args.config == 2 and not args.emulate:
+            traffic, traffic_parts = traffic_from_profile()
+        out.update({
+            "solved_fraction": float((info[..., 1] == 1).mean()),
+            "mean_admm_iters": float(info[..., 0].mean()),
+            "mean_factorisations": float(info[..., 4].mean()),
+            "roofline": {"bound": "vector_fp64", "achieved": achieved_tflops, "peak": FP32_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "frac": achieved_tflops / FP32_VECTOR_PEAK_TFLOPS, "traffic": traffic,
+                         "traffic_parts": traffic_parts,
+                         # "and rocprof-measured HBM GB/s / 8 TB/s, side by side": the fabric-side bytes of a step over the step's two solver kernels
+                         "hbm": None if traffic is None else {"gb_per_s": traffic / ((prep_ms + solve_ms).mean() * 1e-3) / 1e9, "peak_gb_per_s": 8000.0,
+                                                               "frac": traffic / ((prep_ms + solve_ms).mean() * 1e-3) / 8e12,
+                                                               "algorithmic_gb_per_s": 47.7e6 * (n / 4096.0) / ((prep_ms + solve_ms).mean() * 1e-3) / 1e9,
+                                                               "note": "<< 1 by design (SURVEY 8d: the path is not HBM-bound); the bytes are an upper bound on HBM traffic (Infinity-Cache hits included)"},
+                         "traffic_note": "HBM-side bytes per step, BOTH kernels (prep + solve), from rocprofv3 PMC (profiles/*_pmc_summary*_h10.json, measured offline on this command); "
+                                         "algorithmic bytes per step: input 384 B + forces 960 B + state 2 x 5136 B per robot = 47.7 MB",
+                         "note": "vector-FP bound, no MFMA / HBM roofline applies (SURVEY 8d): algorithmic flops (n_r formula, solve-kernel share) / "
+                                 "mean duration of the solve kernel (mpc_solve_jobs_kernel) from HIP events on the launch stream; `peak` is the FP32 vector rate SURVEY 8(d) "
+                                 "prescribes, the kernel's arithmetic is fp64 (frac_fp64_peak, peak 78.6 TF)",
+                         "kernel": "mpc_solve_jobs_kernel<10> (persistent: ADMM and polish jobs of every robot)", "kernel_ms": float(solve_ms.mean()), "prep_kernel_ms": float(prep_ms.mean()),
+                         "step_ms_all_kernels": float((prep_ms + solve_ms).mean()), "step_ms_outside_the_two_solver_kernels": float(m["elapsed"] / K * 1e3 - (prep_ms + solve_ms).mean()),
+                         "flops_per_launch": m["flops_per_launch"],
+                         "prep_kernel_flops_per_launch": m["prep_flops_per_launch"],
+                         "frac_fp64_peak": achieved_tflops / FP64_VECTOR_PEAK_TFLOPS,
+                         "mfma": {"utilisation_of_this_kernel": 0.0,
+                                  "note": "by design: the one GEMM-shaped contraction of the reference's assembly (B_qp^T Q B_qp) is removed algebraically (P = alpha I + BB^T Theta BB, "
+                                          "DESIGN.md 3.1) and fp64 MFMA issues at the vector rate on gfx950; the matrix pipe is used where it cuts INSTRUCTIONS: the weight policy's "
+                                          "actor (v_mfma_f32_32x32x2_f32, `policy`) and the exact mode's seeded Gram inverse (v_mfma_f64_16x16x4_f64, `secondary.exact`)"},
+                         "executed": {"flops_per_launch": m["exec_flops"], "tflops": m["exec_flops"] / (solve_ms.mean() * 1e-3) / 1e12,
+                                      "frac_fp64_peak": m["exec_flops"] / (solve_ms.mean() * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
+                                      "note": "operations the solve kernel executes (bench.py executed_flops: OSQP on all 12 h variables through the 6 h x 6 h "
+                                              "wrench-space core), for orientation only -- `achieved` / `frac` use the SURVEY 8(d) minimal-algorithm count"}},
+        })
     if clock0 is not None:
         out["device_state"] = {"before": clock0, "after": clock1,
                                "note": "shader_clock_ghz: mpc_device_clock -- shader cycles / HIP-event time of ~20 ms of dependent fp64 FMAs, one wave per SIMD on every CU "
@@ -461,7 +503,7 @@ def main():
         out["data"] = "synthetic; EMULATED kernels on the CPU (control-flow dry run: the numbers mean nothing)"
     if gather is not None:
         out["all_gather_torques"] = gather
-    if args.emulate:
+    if args.emulate or not full:
         print(json.dumps(out))
         if dist is not None:
             dist.destroy_process_group()
@@ -499,6 +541,24 @@ def main():
     print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = (64 << 20) - (1 << 16)      # --dump-outputs: at most 64 MB over all files (less room for the .npy headers)
+
+
+def dump_outputs(path, arrays, suffix, limit):
+    """--dump-outputs: every array of the last timed step as path/<name><suffix>.npy, float32 kept, everything else as float64.  Above `limit`
+    bytes in all, the same fixed sample of rows (robots) of every array, drawn with seed 0, and the sampled row indices as rows<suffix>.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        rows = np.sort(np.random.default_rng(0).choice(n, limit // (total // n + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + suffix + ".npy"), a)
 
 
 TRAFFIC_PROFILE = "r06"      # profiles/r06_pmc_summary_h10.json + ..._prep_h10.json: the PMC passes that `roofline.traffic` quotes

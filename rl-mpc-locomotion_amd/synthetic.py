@@ -264,21 +264,50 @@ class ControlStepStream(_GaitSchedule):
 
     def step(self, s):
         assert s == self._s, "ControlStepStream.step: steps in order (rewind() to start again)"
+        walk, noise = self._draws(s)
+        self._walk(walk)
+        return self._emit(self._q, self._rpy, self._vel, self._omega, noise)
+
+    def steps(self, count, workers=8, chunk=64):
+        """step(s) for the next `count` steps, bit for bit, in order.  The draws of a step come from generators seeded by the step alone,
+        so they and the conversion to the seam's arrays run on `workers` threads (numpy releases the GIL in both); the random walk stays
+        in order."""
+        from concurrent.futures import ThreadPoolExecutor
+        end = self._s + count
+        with ThreadPoolExecutor(max(1, workers)) as ex:
+            while self._s < end:
+                states = []
+                for walk, noise in ex.map(self._draws, range(self._s, min(self._s + chunk, end))):
+                    self._walk(walk)
+                    states.append((self._q.copy(), self._rpy.copy(), self._vel.copy(), self._omega.copy(), noise))
+                yield from ex.map(lambda st: self._emit(*st), states)
+
+    def _draws(self, s):
         n = self.n
+        walk = None
         if s > 0:
             rng = np.random.default_rng((self.seed + 1) * 100003 + s)
-            self._vel += rng.standard_normal((n, 3)) * 0.1
-            self._omega += rng.standard_normal((n, 3)) * 0.05
-            self._q += rng.standard_normal((n, 12)) * 0.03
-            self._rpy += rng.standard_normal((n, 3)) * 0.01
-        self._s += 1
+            walk = (rng.standard_normal((n, 3)) * 0.1, rng.standard_normal((n, 3)) * 0.05, rng.standard_normal((n, 12)) * 0.03,
+                    rng.standard_normal((n, 3)) * 0.01)
         rng2 = np.random.default_rng((self.seed + 7) * 7919 + s)
-        dof = np.stack([self._q, rng2.standard_normal((n, 12)) * 0.5], axis=2).astype(np.float32)
-        r, p, y = self._rpy[:, 0], self._rpy[:, 1], self._rpy[:, 2]
+        return walk, rng2.standard_normal((n, 12)) * 0.5
+
+    def _walk(self, walk):
+        if walk is not None:
+            self._vel += walk[0]
+            self._omega += walk[1]
+            self._q += walk[2]
+            self._rpy += walk[3]
+        self._s += 1
+
+    def _emit(self, q, rpy, vel, omega, noise):
+        n = self.n
+        dof = np.stack([q, noise], axis=2).astype(np.float32)
+        r, p, y = rpy[:, 0], rpy[:, 1], rpy[:, 2]
         cy, sy, cp, sp, cr, sr = np.cos(y / 2), np.sin(y / 2), np.cos(p / 2), np.sin(p / 2), np.cos(r / 2), np.sin(r / 2)
         body = np.zeros((n, 13), dtype=np.float32)
         body[:, 2] = self.z
         body[:, 3:7] = np.stack([sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy], -1)
-        body[:, 7:10] = self._vel
-        body[:, 10:13] = self._omega
+        body[:, 7:10] = vel
+        body[:, 10:13] = omega
         return dof, body, self.cmd

@@ -12,10 +12,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*flags, gpus=2):
+def _run(*flags, gpus=2, full=True):
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--backend", "gloo", "--emulate", "--steps", "2", "--warmup", "1",
-                          "--repeats", "2", *flags], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                          "--repeats", "2", *(("--full",) if full else ()), *flags], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, out.stdout          # rank 0 only
@@ -54,6 +54,38 @@ def test_strong_scaling_configs_shard_unevenly(config, h):
     assert b["n_gpus"] == 2 and b["scaling"] == "strong" and b["config"]["horizon"] == h
     assert b["config"]["robots_total"] == 5 and b["config"]["robots_per_gpu"] == 3            # rank 0 holds 3 of the 5
     assert b["all_gather_torques"]["shape_ok"] and b["all_gather_torques"]["robots_total"] == 5
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline keys only, no exchange leg; --dump-outputs writes each rank's torques and solver forces of the last timed
+    step, and the --full run of the same arguments computes the same arrays."""
+    import numpy as np
+    b = _run("--robots", "5", "--dump-outputs", str(tmp_path / "plain"), full=False)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert key in b, key
+    assert b["steps"] == 2 and b["repeats"] == 2 and abs(b["value"] - 10 * 2 / (b["ms_per_step"] * 2e-3)) < 1e-6 * b["value"]
+    assert "all_gather_torques" not in b and "roofline" not in b and "solved_fraction" not in b
+    _run("--robots", "5", "--dump-outputs", str(tmp_path / "full"))
+    for name, shape, dtype in (("torques", (5, 12), np.float32), ("forces", (5, 120), np.float64)):
+        for rank in (0, 1):
+            a = np.load(tmp_path / "plain" / f"{name}_rank{rank}.npy")
+            assert a.shape == shape and a.dtype == dtype and np.isfinite(a).all()
+            assert np.array_equal(a, np.load(tmp_path / "full" / f"{name}_rank{rank}.npy"))
+    assert sorted(os.listdir(tmp_path / "plain")) == ["forces_rank0.npy", "forces_rank1.npy", "torques_rank0.npy", "torques_rank1.npy"]
+
+
+def test_threaded_control_step_stream_is_the_sequential_one():
+    """bench.py draws its controller inputs with ControlStepStream.steps (threads): bit for bit the arrays of step(0), step(1), ..."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from rl_mpc_locomotion_amd.synthetic import ControlStepStream
+    for config in (2, 3):
+        a, b = ControlStepStream(37, seed=5, config=config), ControlStepStream(37, seed=5, config=config)
+        seq = [tuple(x.copy() for x in a.step(s)) for s in range(70)]
+        par = list(b.steps(70, workers=3, chunk=16))
+        assert len(par) == 70 and b._s == 70
+        for x, y in zip(seq, par):
+            assert all(u.dtype == v.dtype and np.array_equal(u, v) for u, v in zip(x, y))
 
 
 def test_world_size_must_match_gpus():

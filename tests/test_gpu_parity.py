@@ -410,10 +410,10 @@ def test_one_infeasible_robot_does_not_hold_the_launch():
 
 @pytest.mark.gpu
 def test_bench_contract_line():
-    """`python bench.py` prints ONE JSON line with the keys the driver reads (small sizes; the CPU baseline leg uses the oracle)."""
+    """`python bench.py --full` prints ONE JSON line with the keys the driver reads (small sizes; the CPU baseline leg uses the oracle)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--robots", "256", "--steps", "3", "--warmup", "2", "--no-secondary", "--no-control-loop"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--robots", "256", "--steps", "3", "--warmup", "2", "--full", "--no-secondary", "--no-control-loop"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -428,3 +428,27 @@ def test_bench_contract_line():
     c = b["cpu_baseline"]
     assert c["kind"] == "reference" and c["cores"] >= 1 and c["value"] > 0 and c["one_core"]["cores"] == 1
     assert b["solved_fraction"] == 1.0 and b["max_grf_err_vs_osqp"] < 1e-5
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_outputs(tmp_path):
+    """`python bench.py` without --full: the headline line alone, and --dump-outputs writes the last timed step's torques and solver forces,
+    the same arrays on every run of the same arguments."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--robots", "256", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        b = json.loads(lines[0])
+        assert b["metric"].startswith("MPC control steps/sec (whole node) @ horizon=10, 256 robots") and b["unit"] == "control steps/s" and b["dtype"] == "f64"
+        assert b["higher_is_better"] is True and b["steps"] == 3 and b["repeats"] == 1 and abs(b["value"] - 256 * 3 / (b["ms_per_step"] * 3e-3)) < 1e-6 * b["value"]
+        assert "roofline" not in b and "cpu_baseline" not in b and "secondary" not in b
+        dumps.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("torques", "forces")})
+    assert dumps[0]["torques"].shape == (256, 12) and dumps[0]["torques"].dtype == np.float32 and np.isfinite(dumps[0]["torques"]).all()
+    assert dumps[0]["forces"].shape == (256, 120) and dumps[0]["forces"].dtype == np.float64
+    for k in ("torques", "forces"):
+        assert np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True), k

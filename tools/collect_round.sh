@@ -1,12 +1,13 @@
 #!/bin/bash
-# After tools/gpu/final.sh (through gpurun): copy the round's artefacts from gpurun_out/ to profiles/ and condense the PMC passes.
+# After tools/gpu/final.sh: copy the round's artefacts from $RESULTS (default results/) to profiles/ and condense the PMC passes.
 set -e
 cd "$(dirname "$0")/.."
+RESULTS=${RESULTS:-results}
 TAG=${TAG:-r06}
-for f in bench_n1.json kernel_stats_bench_steps10.csv kernel_stats_config4_4096xh16.csv kernel_stats_config5_4096xh20.csv exact_mode_sweep.json parity_sweep.json controller_parity.json; do cp gpurun_out/${TAG}_$f profiles/${TAG}_$f; done
+for f in bench_n1.json kernel_stats_bench_steps10.csv kernel_stats_config4_4096xh16.csv kernel_stats_config5_4096xh20.csv exact_mode_sweep.json parity_sweep.json controller_parity.json; do cp $RESULTS/${TAG}_$f profiles/${TAG}_$f; done
 for h in 10 16 20; do
   d=$(mktemp -d)
-  for p in fetch write sq1 sq2; do cp gpurun_out/${TAG}_pmc_h${h}_$p.csv profiles/; cp gpurun_out/${TAG}_pmc_h${h}_$p.csv $d/; done; cp gpurun_out/${TAG}_pmc_h${h}_source.sha256 $d/
+  for p in fetch write sq1 sq2; do cp $RESULTS/${TAG}_pmc_h${h}_$p.csv profiles/; cp $RESULTS/${TAG}_pmc_h${h}_$p.csv $d/; done; cp $RESULTS/${TAG}_pmc_h${h}_source.sha256 $d/
   python tools/pmc_summary.py $d profiles/${TAG}_pmc_summary_h$h.json 4096 $h mpc_solve_jobs_kernel > /dev/null
   python tools/pmc_summary.py $d profiles/${TAG}_pmc_summary_prep_h$h.json 4096 $h mpc_prep_kernel > /dev/null
   rm -rf $d

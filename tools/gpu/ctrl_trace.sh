@@ -1,6 +1,6 @@
 # Kernel trace of the control-loop leg of bench.py (controller kernels around the two solver kernels).
-export TMPDIR=/tmp; cd /tmp && rm -rf /tmp/ctl
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ctl -o k -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --repeats 1 --no-cpu-baseline --no-secondary > /dev/null 2>&1
+ROOT=$(cd "$(dirname "$0")/../.." && pwd); export TMPDIR=/tmp; cd /tmp && rm -rf /tmp/ctl
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ctl -o k -- python $ROOT/bench.py --full --steps 2 --warmup 1 --repeats 1 --no-cpu-baseline --no-secondary > /dev/null 2>&1
 python - <<'PY'
 import csv, glob
 f = glob.glob('/tmp/ctl/**/*kernel_stats.csv', recursive=True)[0]
