@@ -80,6 +80,7 @@ struct mpc_batch {
   int *d_ready = nullptr;
   int *d_seed = nullptr;         // [n, 4 h] exact mode: the working set each robot's previous call ended on (seeds the active-set method; MPC_EXACT_WARM=0: never)
   bool warm_sets = true;
+  bool f32_seed = false;         // MPC_EXACT_F32_SEED=1 (tuning hook, default off): the exact mode's seed comes from the float32 search of the call (mpc_exact32.h)
   int job_slots = 0;             // wave slots of the device for the persistent job kernel (0: one workgroup per robot)
   bool timing = false;           // mpc_batch_enable_timing: HIP events around the two kernels of each launch
   hipEvent_t ev[kTimingRing][3];
@@ -105,7 +106,8 @@ static int launch_solver(mpc_batch *b, const float *d_in, double *d_forces, int 
   if (b->exact) HIP_TRY(hipMemsetAsync(b->d_state, 0, sizeof(double) * (size_t)b->n * b->state_len, st));   // no warm start in that branch (mpc_osqp.cc:906-919)
   hipEvent_t *ev = b->timing ? b->ev[b->launches % kTimingRing] : nullptr;
   const LaunchArgs a{b->n, b->d_models, d_in, d_in64, d_in16, b->d_state, b->d_qp, b->d_sc, d_forces, d_info, b->d_prof, d_active, b->d_order, b->d_hist, slot, ev, st, b->exact,
-                     b->max_iter, b->d_sched, b->d_ready, b->job_slots, b->warm_sets ? b->d_seed : nullptr};
+                     b->max_iter, b->d_sched, b->d_ready, b->job_slots, b->warm_sets ? b->d_seed : nullptr,
+                     b->warm_sets && b->f32_seed};
   const hipError_t e = (hipError_t)b->ops->launch(a);
   if (e != hipSuccess) return fail(MPC_E_HIP, std::string("solver launch: ") + hipGetErrorString(e));
   b->launches++;
@@ -184,6 +186,7 @@ int mpc_batch_create(mpc_batch **out, int n, int horizon, double timestep, doubl
     }
   }
   if (const char *ew = getenv("MPC_EXACT_WARM")) b->warm_sets = !(ew[0] == '0' && ew[1] == '\0');      // tuning hook: 0 = the exact mode's active-set method starts empty on every call
+  if (const char *fs = getenv("MPC_EXACT_F32_SEED")) b->f32_seed = fs[0] == '1' && fs[1] == '\0';   // tuning hook: 1 = seed from the float32 search
   b->bytes = (long long)(sizeof(RobotModel) * n + sizeof(double) * (size_t)n * (b->state_len + qp_len + sc_len) + sizeof(int) * (size_t)n * kInfoLen);
   *out = b;
   return MPC_OK;

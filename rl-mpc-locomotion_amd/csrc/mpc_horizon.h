@@ -39,6 +39,7 @@ struct LaunchArgs {        // one solver launch on n robots: the prep kernel, th
   int *sched, *ready;
   int job_slots;
   int *seed;               // [n, 4 h] exact mode: the working set each robot's previous call ended on (mpc_wrench.h seed_working_set), or null: every call starts empty
+  int f32_seed;            // exact mode with a seed: the float32 search of the call writes it first (mpc_exact32.h; tuning hook MPC_EXACT_F32_SEED)
 };
 
 struct HorizonOps {

@@ -10,6 +10,7 @@
 #include "mpc_horizon.h"
 #include "mpc_device.h"
 #include "mpc_wrench.h"
+#include "mpc_exact32.h"
 
 using namespace mpc;
 
@@ -278,6 +279,8 @@ int launch(const LaunchArgs &a) {
                      a.hist_slot, a.sched, a.ready);
   if (a.ev) (void)hipEventRecord(a.ev[1], a.stream);
   if (a.exact) {
+    // MPC_EXACT_F32_SEED=1: the float32 search writes this call's working set as the seed of the fp64 active-set kernel (mpc_exact32.h)
+    if (a.f32_seed && a.seed) hipLaunchKernelGGL((mpc_exact32_kernel<H>), dim3(a.n), dim3(64), 0, a.stream, a.models, a.qp, a.sc, a.order, a.sched, a.seed);
     hipLaunchKernelGGL((mpc_exact_kernel<H>), dim3(a.n), dim3(Cfg<H>::TW), 0, a.stream, a.models, a.state, a.qp, a.sc, a.forces, a.info, a.prof, a.order, a.sched, a.ready, a.seed);
     hipLaunchKernelGGL((mpc_solve_kernel<H, true>), dim3(a.n), dim3(Cfg<H>::TW), 0, a.stream, a.n, a.models, a.state, a.qp, a.sc, a.forces, a.info, a.prof, a.order, a.sched, a.ready,
                        a.max_iter);
