@@ -4,4 +4,4 @@ Only what the path needs lives here: ``csrc/`` (HIP kernels + the C-ABI library)
 mirror of the reference's plugin interface (``mpc_osqp`` shim, batched stepper), the constant tables
 and the synthetic workload generator.  See DESIGN.md.
 """
-__all__ = ["layout", "quadruped", "gait", "synthetic"]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim"]

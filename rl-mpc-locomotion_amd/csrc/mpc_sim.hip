@@ -1,0 +1,236 @@
+// mpc_sim.hip -- the C ABI of include/mpc_sim.h: the batched toy plant (toy_sim.h) on the device, one lane per robot.
+// The state is structure-of-arrays in HBM (entry j of robot r at [j * n + r]: the lanes of a wave load and store consecutive words); a tick
+// loads a robot's 49 doubles and 9 ints into registers, runs toy_step and writes the state back and the float32 observation out.
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/mpc_sim.h"
+#include "toy_sim.h"
+
+using namespace toysim;
+
+namespace {
+thread_local std::string g_serr;
+int sfail(int code, const std::string &m) { g_serr = m; return code; }
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
+  DeviceGuard(const DeviceGuard &) = delete;
+  DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+#define SIM_TRY(expr)                                                                               \
+  do {                                                                                              \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess) return sfail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+constexpr int kSimThreads = 64;      // one wave per workgroup: 4096 robots are 64 waves on 64 CUs
+
+struct SimArgs {
+  int n;
+  double dt;
+  double *f64;                       // [kF64][n]
+  int *i32;                          // [kI32][n]
+  const int *type;                   // [n]
+  const double *slope;               // [n][2]
+  const double *yaw0;                // [n]
+  const Params *params;              // [n_types]
+};
+
+__device__ __forceinline__ void write_obs(const State &s, int r, float *dof, float *root) {
+  float d[24], b[13];
+  observe(s, d, b);
+  if (dof) {
+#pragma unroll
+    for (int i = 0; i < 24; ++i) dof[(size_t)r * 24 + i] = d[i];
+  }
+  if (root) {
+#pragma unroll
+    for (int i = 0; i < 13; ++i) root[(size_t)r * 13 + i] = b[i];
+  }
+}
+
+// (re)initialise robots ids[0 .. k) (all n when ids is null)
+__global__ __launch_bounds__(kSimThreads) void sim_init_kernel(SimArgs a, const int *ids, int k) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  const int r = ids ? ids[i] : i;
+  if (r < 0 || r >= a.n) return;
+  State s;
+  toy_init(s, a.params[a.type[r]], a.yaw0[r], a.slope[2 * r], a.slope[2 * r + 1]);
+  pack(s, a.f64 + r, a.i32 + r, a.n);
+}
+
+__global__ __launch_bounds__(kSimThreads) void sim_step_kernel(SimArgs a, const float *__restrict__ tau, float *dof, float *root) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.n) return;
+  State s;
+  unpack(s, a.f64 + r, a.i32 + r, a.n);
+  if (!s.fell) {
+    double t[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) t[i] = (double)tau[(size_t)r * 12 + i];
+    toy_step(s, a.params[a.type[r]], t, a.dt, a.slope[2 * r], a.slope[2 * r + 1]);
+    pack(s, a.f64 + r, a.i32 + r, a.n);
+  }
+  write_obs(s, r, dof, root);
+}
+
+__global__ __launch_bounds__(kSimThreads) void sim_observe_kernel(SimArgs a, float *dof, float *root) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.n) return;
+  State s;
+  unpack(s, a.f64 + r, a.i32 + r, a.n);
+  write_obs(s, r, dof, root);
+}
+
+__global__ __launch_bounds__(kSimThreads) void sim_flags_kernel(int n, const int *i32, unsigned char *contact, unsigned char *fell) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  if (contact) {
+#pragma unroll
+    for (int l = 0; l < 4; ++l) contact[(size_t)r * 4 + l] = i32[(size_t)l * n + r] != 0;
+  }
+  if (fell) fell[r] = i32[(size_t)8 * n + r] != 0;
+}
+}  // namespace
+
+struct mpc_sim {
+  int n = 0, device = 0;
+  SimArgs a{};
+  double *d_f64 = nullptr;
+  int *d_i32 = nullptr, *d_type = nullptr;
+  double *d_slope = nullptr, *d_yaw = nullptr;
+  Params *d_params = nullptr;
+};
+
+static dim3 sim_grid(int k) { return dim3((unsigned)((k + kSimThreads - 1) / kSimThreads)); }
+
+extern "C" {
+
+const char *mpc_sim_last_error(void) { return g_serr.c_str(); }
+
+void mpc_sim_destroy(mpc_sim *s) {
+  if (!s) return;
+  DeviceGuard guard_(s->device);
+  (void)hipDeviceSynchronize();
+  void *ptrs[] = {s->d_f64, s->d_i32, s->d_type, s->d_slope, s->d_yaw, s->d_params};
+  for (void *p : ptrs) if (p) (void)hipFree(p);
+  delete s;
+}
+
+int mpc_sim_create(mpc_sim **out, int n, const int *robot_type, int n_types, const double *table, const double *slope, const double *yaw0, double dt) {
+  if (!out || n <= 0 || !robot_type || n_types <= 0 || !table || !(dt > 0.0)) return sfail(MPC_E_ARG, "mpc_sim_create: bad argument");
+  for (int r = 0; r < n; ++r)
+    if (robot_type[r] < 0 || robot_type[r] >= n_types) return sfail(MPC_E_ARG, "mpc_sim_create: robot_type out of range");
+  std::vector<Params> params(n_types);
+  for (int t = 0; t < n_types; ++t) {
+    const double *row = table + (size_t)kRobotCols * t;
+    if (!(row[kColMass] > 0.0) || !(row[kColInertia] > 0.0) || !(row[kColInertia + 1] > 0.0) || !(row[kColInertia + 2] > 0.0))
+      return sfail(MPC_E_ARG, "mpc_sim_create: robot table row with a non-positive mass or inertia");
+    params_from_row(params[t], row);
+  }
+  std::vector<double> sl(2 * (size_t)n, 0.0), yaw(n, 0.0);
+  if (slope) for (size_t i = 0; i < sl.size(); ++i) sl[i] = slope[i];
+  if (yaw0) for (int r = 0; r < n; ++r) yaw[r] = yaw0[r];
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sfail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device");
+  mpc_sim *s = new mpc_sim();
+  s->n = n;
+  if (hipGetDevice(&s->device) != hipSuccess) { delete s; return sfail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device"); }
+  hipError_t e;
+  if ((e = hipMalloc(&s->d_f64, sizeof(double) * kF64 * (size_t)n)) != hipSuccess || (e = hipMalloc(&s->d_i32, sizeof(int) * kI32 * (size_t)n)) != hipSuccess ||
+      (e = hipMalloc(&s->d_type, sizeof(int) * (size_t)n)) != hipSuccess || (e = hipMalloc(&s->d_slope, sizeof(double) * 2 * (size_t)n)) != hipSuccess ||
+      (e = hipMalloc(&s->d_yaw, sizeof(double) * (size_t)n)) != hipSuccess || (e = hipMalloc(&s->d_params, sizeof(Params) * n_types)) != hipSuccess ||
+      (e = hipMemcpy(s->d_type, robot_type, sizeof(int) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(s->d_slope, sl.data(), sizeof(double) * sl.size(), hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(s->d_yaw, yaw.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(s->d_params, params.data(), sizeof(Params) * n_types, hipMemcpyHostToDevice)) != hipSuccess) {
+    mpc_sim_destroy(s);
+    return sfail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
+  }
+  s->a = SimArgs{n, dt, s->d_f64, s->d_i32, s->d_type, s->d_slope, s->d_yaw, s->d_params};
+  hipLaunchKernelGGL(sim_init_kernel, sim_grid(n), dim3(kSimThreads), 0, nullptr, s->a, (const int *)nullptr, n);
+  if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
+    mpc_sim_destroy(s);
+    return sfail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
+  }
+  *out = s;
+  return MPC_OK;
+}
+
+int mpc_sim_size(mpc_sim *s) { return s ? s->n : 0; }
+
+int mpc_sim_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, void *stream) {
+  if (!s || !d_tau) return sfail(MPC_E_ARG, "mpc_sim_step: bad argument");
+  DeviceGuard guard_(s->device);
+  hipLaunchKernelGGL(sim_step_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), s->a, d_tau, d_dof, d_root);
+  SIM_TRY(hipGetLastError());
+  return MPC_OK;
+}
+
+int mpc_sim_observe(mpc_sim *s, float *d_dof, float *d_root, void *stream) {
+  if (!s || (!d_dof && !d_root)) return sfail(MPC_E_ARG, "mpc_sim_observe: bad argument");
+  DeviceGuard guard_(s->device);
+  hipLaunchKernelGGL(sim_observe_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), s->a, d_dof, d_root);
+  SIM_TRY(hipGetLastError());
+  return MPC_OK;
+}
+
+int mpc_sim_reset_device(mpc_sim *s, const int *d_ids, int k, void *stream) {
+  if (!s || !d_ids || k < 0) return sfail(MPC_E_ARG, "mpc_sim_reset_device: bad argument");
+  if (k == 0) return MPC_OK;
+  DeviceGuard guard_(s->device);
+  hipLaunchKernelGGL(sim_init_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), s->a, d_ids, k);
+  SIM_TRY(hipGetLastError());
+  return MPC_OK;
+}
+
+int mpc_sim_get_state(mpc_sim *s, double *h_f64, int *h_i32) {
+  if (!s || !h_f64 || !h_i32) return sfail(MPC_E_ARG, "mpc_sim_get_state: bad argument");
+  DeviceGuard guard_(s->device);
+  const size_t n = (size_t)s->n;
+  std::vector<double> f(kF64 * n);
+  std::vector<int> k(kI32 * n);
+  SIM_TRY(hipDeviceSynchronize());
+  SIM_TRY(hipMemcpy(f.data(), s->d_f64, sizeof(double) * f.size(), hipMemcpyDeviceToHost));
+  SIM_TRY(hipMemcpy(k.data(), s->d_i32, sizeof(int) * k.size(), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < n; ++r) {
+    for (int j = 0; j < kF64; ++j) h_f64[r * kF64 + j] = f[j * n + r];
+    for (int j = 0; j < kI32; ++j) h_i32[r * kI32 + j] = k[j * n + r];
+  }
+  return MPC_OK;
+}
+
+int mpc_sim_set_state(mpc_sim *s, const double *h_f64, const int *h_i32) {
+  if (!s || !h_f64 || !h_i32) return sfail(MPC_E_ARG, "mpc_sim_set_state: bad argument");
+  DeviceGuard guard_(s->device);
+  const size_t n = (size_t)s->n;
+  std::vector<double> f(kF64 * n);
+  std::vector<int> k(kI32 * n);
+  for (size_t r = 0; r < n; ++r) {
+    for (int j = 0; j < kF64; ++j) f[j * n + r] = h_f64[r * kF64 + j];
+    for (int j = 0; j < kI32; ++j) k[j * n + r] = h_i32[r * kI32 + j];
+  }
+  SIM_TRY(hipDeviceSynchronize());
+  SIM_TRY(hipMemcpy(s->d_f64, f.data(), sizeof(double) * f.size(), hipMemcpyHostToDevice));
+  SIM_TRY(hipMemcpy(s->d_i32, k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice));
+  SIM_TRY(hipDeviceSynchronize());
+  return MPC_OK;
+}
+
+int mpc_sim_flags(mpc_sim *s, unsigned char *d_contact, unsigned char *d_fell, void *stream) {
+  if (!s || (!d_contact && !d_fell)) return sfail(MPC_E_ARG, "mpc_sim_flags: bad argument");
+  DeviceGuard guard_(s->device);
+  hipLaunchKernelGGL(sim_flags_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), s->n, s->d_i32, d_contact, d_fell);
+  SIM_TRY(hipGetLastError());
+  return MPC_OK;
+}
+
+}  // extern "C"

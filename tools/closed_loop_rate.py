@@ -1,0 +1,89 @@
+"""Closed-loop rate on the device: BatchedLocomotion.run + BatchedToySim.step for 4096 robots, h = 10 (Aliengo trotting, and the three
+robot types mixed), no host round trip per tick.  Reports robot-ticks / s of the whole loop over K ticks, the toy plant's step time from
+HIP events (mpc_sim_step alone, 4096 robots), and the fraction of robots fallen after 1000 ticks, with the shader clock as bench.py --full
+records it (device_state).  Command: trot at 0.5 m/s with the MPC weights of the closed-loop golden's trot cases (and, for the fallen
+fraction only, the robot table's default weights).
+    python tools/closed_loop_rate.py [--ticks 1000] [--out profiles/r07_toy_sim.json]
+The kernel-trace stats of the same loop: rocprofv3 --kernel-trace --stats ... -- python tools/closed_loop_rate.py --ticks 50 --quick"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import rl_mpc_locomotion_amd  # noqa: E402,F401
+from rl_mpc_locomotion_amd import _lib  # noqa: E402
+from rl_mpc_locomotion_amd.locomotion import BatchedLocomotion  # noqa: E402
+from rl_mpc_locomotion_amd.toy_sim import BatchedToySim  # noqa: E402
+from bench import device_state  # noqa: E402
+
+TROT = 0
+# the command record of the closed-loop golden's trot cases (tests/golden/closed_loop_h10.npz: vx, vy, wz, then 12 MPC weights and 0).  The
+# robot table's default Aliengo weights leave roll and pitch unweighted: in this toy such a robot tips over (the `default_weights` leg).
+GOLDEN_TROT_CMD = [0.5, 0.0, 0.0, 5, 5, 5, 50, 50, 50, 1, 1, 1, 1, 1, 1, 0]
+
+
+def run(robot_type, ticks, dev, default_weights=False):
+    n = len(robot_type)
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    sim = BatchedToySim(robot_type, yaw0=yaw, device=dev)
+    ctl = BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=True, device=dev)
+    cmd = torch.tensor(GOLDEN_TROT_CMD[:3] if default_weights else GOLDEN_TROT_CMD, dtype=torch.float32, device=dev).repeat(n, 1).contiguous()
+    view = sim.dof_state.view(n, 12, 2)
+    for _ in range(10):            # warm-up (first solves are cold)
+        sim.step(ctl.run(view, sim.root_states, cmd))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(ticks):
+        sim.step(ctl.run(view, sim.root_states, cmd))
+    torch.cuda.synchronize()
+    loop_s = time.perf_counter() - t0
+    _, fell = sim.flags()
+    fell = fell.cpu().numpy()
+    rt = np.asarray(robot_type)
+    out = {"robots": n, "ticks": ticks, "weights": "robot table defaults" if default_weights else "closed-loop golden trot", "loop_s": loop_s,
+           "robot_ticks_per_s": n * ticks / loop_s, "ms_per_tick": loop_s / ticks * 1e3, "fallen_fraction": float(fell.mean()),
+           "fallen_fraction_per_robot_type": {int(t): float(fell[rt == t].mean()) for t in np.unique(rt)}}
+    if default_weights:
+        return out
+    # the plant alone, HIP events around mpc_sim_step inside the same closed loop (a fresh batch: every robot standing at the start)
+    sim = BatchedToySim(robot_type, yaw0=yaw, device=dev)
+    ctl = BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=True, device=dev)
+    view = sim.dof_state.view(n, 12, 2)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(ticks)]
+    for a, b in ev:
+        tau = ctl.run(view, sim.root_states, cmd)
+        a.record(); sim.step(tau); b.record()
+    torch.cuda.synchronize()
+    ms = np.array([a.elapsed_time(b) for a, b in ev])
+    out.update({"sim_step_ms_median": float(np.median(ms)), "sim_step_ms_mean": float(ms.mean()), "sim_step_ms_min": float(ms.min()),
+                "sim_step_ms_max": float(ms.max()), "sim_step_events": len(ms)})
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ticks", type=int, default=1000)
+    ap.add_argument("--robots", type=int, default=4096)
+    ap.add_argument("--quick", action="store_true", help="the mixed-type loop only (for a kernel trace)")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    dev = "cuda:0"
+    n = args.robots
+    res = {"kernel_source_sha256": _lib.kernel_source_hash()}
+    clock0 = None if args.quick else device_state(0)
+    mixed = [i % 3 for i in range(n)]
+    legs = {"mixed_types": (mixed, False)} if args.quick else {"aliengo": ([0] * n, False), "mixed_types": (mixed, False), "mixed_types_default_weights": (mixed, True)}
+    for name, (rt, dw) in legs.items():
+        res[name] = run(rt, args.ticks, dev, default_weights=dw)
+        print(name, json.dumps(res[name]), flush=True)
+    if clock0 is not None:
+        res["device_state"] = {"before": clock0, "after": device_state(0, smi=False)}
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
