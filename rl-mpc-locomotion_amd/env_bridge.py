@@ -5,6 +5,9 @@ Mirror of what ``VecTask.pre_physics_step`` / ``reset_idx`` do when ``Parameters
 run ``controller.run`` for every environment, and reset the controllers of the environments that are being reset.  The
 reference copies four tensors to the host and loops over Python controllers; here nothing leaves the GPU.  The simulator
 calls themselves (``gym.set_dof_actuation_force_tensor`` ...) stay with the caller: Isaac Gym is not part of this package.
+
+``post_physics_step`` is the other half of the tick (vec_task.py:326-337, aliengo.py:273-349): episode counter, time-outs, resets with fresh
+commands, observations, reward -- two kernels of rl_task.py on the caller's tensors, again with nothing leaving the GPU.
 """
 from .locomotion import BatchedLocomotion
 from .weight_policy import MPC_PARAM_CONST, MPC_PARAM_SCALE
@@ -12,7 +15,7 @@ from .weight_policy import MPC_PARAM_CONST, MPC_PARAM_SCALE
 
 class MpcEnvBridge:
     def __init__(self, robot_type, gait_id, horizon=10, controller_dt=0.01, flat_ground=False, device=None,
-                 param_scale=MPC_PARAM_SCALE, param_const=MPC_PARAM_CONST):
+                 param_scale=MPC_PARAM_SCALE, param_const=MPC_PARAM_CONST, task_cfg=None):
         import numpy as np
         import torch
         self.ctl = BatchedLocomotion(robot_type, gait_id, horizon=horizon, controller_dt=controller_dt, flat_ground=flat_ground, device=device)
@@ -22,6 +25,7 @@ class MpcEnvBridge:
         if self._scale.shape != (12,) or self._const.shape != (12,):
             raise ValueError("param_scale / param_const: twelve entries each (Parameters.py:25-33)")
         self._cmd = torch.zeros((self.n, 16), dtype=torch.float32, device=self.device)
+        self._task_cfg, self.task = task_cfg, None      # rl_task.TaskPostPhysics, made by the first post_physics_step
 
     def pre_physics_step(self, actions, dof_state, root_states, commands):
         """actions [N,12] in [-1,1], dof_state [N*12,2] (or [N,12,2]), root_states [N,13], commands [N,3] -> torques [N,12]
@@ -43,3 +47,21 @@ class MpcEnvBridge:
         """``for idx in env_ids: self.controllers[idx].reset()`` (aliengo.py:330-334)."""
         if len(env_ids):
             self.ctl.reset(env_ids)
+
+    def post_physics_step(self, actions, torques, dof_state, root_states, contact_forces=None, base_index=0, knee_indices=None, hip_indices=None,
+                          fell=None, reset_simulator=None):
+        """The tick after ``gym.simulate`` (vec_task.py:326-337 with aliengo.py:273-349) -> (obs_buf, rew_buf, reset_buf, time_outs).  The task's
+        buffers live in ``self.task`` (rl_task.TaskPostPhysics, configured by the constructor's ``task_cfg``): pass ``self.task.commands`` to
+        ``pre_physics_step``.  The controllers of the environments being reset are reset here; ``reset_simulator(ids)`` is called in between
+        with the device id array (int32 [N]: r where environment r is being reset, -1 elsewhere -- no count reaches the host) for the caller
+        to reset its simulator, after which the caller's dof_state / root_states must hold the new state.  Contacts: rl_task.TaskPostPhysics.finish."""
+        if self.task is None:
+            from .rl_task import TaskPostPhysics
+            self.task = TaskPostPhysics(self.n, self._task_cfg, device=self.device)
+        ids = self.task.begin()
+        self.ctl.reset(ids)
+        if reset_simulator is not None:
+            reset_simulator(ids)
+        obs, rew, reset = self.task.finish(root_states, dof_state, actions, torques, contact_forces=contact_forces, base_index=base_index,
+                                           knee_indices=knee_indices, hip_indices=hip_indices, fell=fell)
+        return obs, rew, reset, self.task.timeout_buf

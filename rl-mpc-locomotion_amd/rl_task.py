@@ -1,0 +1,256 @@
+"""The second half of the RL task's tick, and a batched rollout environment, on the device (include/mpc_task.h, csrc/mpc_task.hip,
+csrc/rl_task.h).
+
+``MpcEnvBridge.pre_physics_step`` covers the reference's tick up to the torques.  What follows the simulator there is ``VecTask.step``
+(RL_Environment/tasks/base/vec_task.py:298-339) and the task's ``post_physics_step`` (RL_Environment/tasks/aliengo.py:273-349, the same
+text in a1.py / go1.py): the episode counter, the time-out flag, the reset of flagged environments with fresh commands,
+``compute_robot_observations`` (the 48 observations the policy trains on), ``compute_robot_reward`` (reward and next reset flags) and
+the observation clip.  Here that is two kernels, ``begin`` and ``finish``, and nothing reaches the host: where the reference takes
+``reset_buf.nonzero()``, ``begin`` writes an id array with one entry per environment (its id, or -1), which every device reset entry
+point of this package takes as it is because ids outside [0, n) are ignored.
+
+    task = BatchedRLTask(robot_type, gait_id)            # MpcEnvBridge + BatchedToySim + the two kernels
+    obs = task.reset()
+    for _ in range(ticks):
+        obs, rew, reset, extras = task.step(policy(obs))
+
+Callers with a simulator of their own use ``MpcEnvBridge.post_physics_step`` (env_bridge.py), which runs the same two kernels on their
+tensors, Isaac Gym's net contact force tensor included.
+
+Not the reference's: commands are drawn by a counter-based generator keyed by (seed, environment, episode index), not by torch's
+generator, so parity with ``torch_rand_float`` (aliengo.py:344-346) is in distribution only.
+
+What the toy plant cannot do (BatchedRLTask only): base contact is taken to be the toy's ``fell`` flag; it has no knee or hip contacts, so
+the collision term and those two reset causes never fire; and a reset puts the robot back standing on its ground plane -- it does not
+use the randomised joint angles and velocities of aliengo.py:322-326.
+
+Like every class here these need the GPU (MpcLibraryError without one) and have no CPU fallback.
+"""
+import ctypes as C
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _lib
+
+NUM_OBS = 48
+# the order of the sum at aliengo.py:398
+REWARD_TERMS = ("lin_vel_xy", "lin_vel_z", "ang_vel_xy", "ang_vel_z", "torque", "collision")
+
+# the entry points of include/mpc_task.h (bound here, not in _lib.SYMBOLS, which lists include/mpc_batch.h)
+SYMBOLS = ["mpc_task_create", "mpc_task_destroy", "mpc_task_buffers", "mpc_task_begin", "mpc_task_finish", "mpc_task_last_error"]
+_BOUND = None
+
+
+class _Config(C.Structure):            # mpc_task_config
+    _fields_ = [("lin_vel_scale", C.c_double), ("ang_vel_scale", C.c_double), ("dof_pos_scale", C.c_double), ("dof_vel_scale", C.c_double),
+                ("rew_scale", C.c_double * 6), ("command_range", (C.c_double * 2) * 3), ("clip_observations", C.c_double),
+                ("default_dof_pos", C.c_double * 12), ("max_episode_length", C.c_longlong), ("seed", C.c_ulonglong)]
+
+
+class _BufferSet(C.Structure):         # mpc_task_buffer_set
+    _fields_ = [(name, C.c_void_p) for name in ("d_progress", "d_reset", "d_timeout", "d_reset_ids", "d_commands", "d_obs", "d_rew")]
+
+
+def lib():
+    """libmpc_batch.so with the task entry points bound."""
+    global _BOUND
+    L = _lib.lib()
+    if _BOUND is not L:
+        vp, ci = C.c_void_p, C.c_int
+        L.mpc_task_create.argtypes = [C.POINTER(vp), ci, vp]; L.mpc_task_create.restype = ci
+        L.mpc_task_destroy.argtypes = [vp]; L.mpc_task_destroy.restype = None
+        L.mpc_task_buffers.argtypes = [vp, vp]; L.mpc_task_buffers.restype = ci
+        L.mpc_task_begin.argtypes = [vp, vp]; L.mpc_task_begin.restype = ci
+        L.mpc_task_finish.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]; L.mpc_task_finish.restype = ci
+        L.mpc_task_last_error.argtypes = []; L.mpc_task_last_error.restype = C.c_char_p
+        _BOUND = L
+    return L
+
+
+def check(rc, what):
+    if rc != _lib.MPC_OK:
+        raise _lib.MpcLibraryError(f"{what} failed ({rc}): {lib().mpc_task_last_error().decode()}")
+
+
+@dataclass
+class TaskConfig:
+    """cfg/task/Aliengo.yaml restated as numbers; A1.yaml and Go1.yaml carry the same values (they differ in the base's initial height only,
+    which belongs to the simulator)."""
+    # learn: normalisation
+    lin_vel_scale: float = 1.0
+    ang_vel_scale: float = 1.0
+    dof_pos_scale: float = 1.0
+    dof_vel_scale: float = 1.0
+    # learn: reward scales, per second (multiplied by dt where they are used, aliengo.py:78-79)
+    rew_lin_vel_xy: float = 1.0
+    rew_ang_vel_z: float = 0.5
+    rew_torque: float = -0.000025
+    rew_lin_vel_z: float = -4.0
+    rew_ang_vel_xy: float = -0.05
+    rew_collision: float = 0.0
+    # randomCommandVelocityRanges
+    command_x_range: tuple = (-2.5, 2.5)
+    command_y_range: tuple = (-1.0, 1.0)
+    command_yaw_range: tuple = (-2.5, 2.5)
+    clip_observations: float = 5.0
+    clip_actions: float = 1.0
+    episode_length_s: float = 20.0
+    dt: float = 0.01                   # sim.dt
+    # defaultJointAngles in dof order: legs x (hip 0.0, thigh 0.8, calf -1.6)
+    default_dof_pos: tuple = field(default_factory=lambda: (0.0, 0.8, -1.6) * 4)
+    seed: int = 0                      # of the command generator
+
+    @property
+    def max_episode_length(self):
+        return int(self.episode_length_s / self.dt + 0.5)        # aliengo.py:73-74
+
+    def reward_scales(self):
+        """The six scales x dt, in REWARD_TERMS order (aliengo.py:78-79: a Python float product)."""
+        per_s = dict(lin_vel_xy=self.rew_lin_vel_xy, lin_vel_z=self.rew_lin_vel_z, ang_vel_xy=self.rew_ang_vel_xy, ang_vel_z=self.rew_ang_vel_z,
+                     torque=self.rew_torque, collision=self.rew_collision)
+        return [float(per_s[k]) * float(self.dt) for k in REWARD_TERMS]
+
+    def _struct(self):
+        c = _Config()
+        c.lin_vel_scale, c.ang_vel_scale, c.dof_pos_scale, c.dof_vel_scale = (float(self.lin_vel_scale), float(self.ang_vel_scale),
+                                                                              float(self.dof_pos_scale), float(self.dof_vel_scale))
+        for i, v in enumerate(self.reward_scales()):
+            c.rew_scale[i] = v
+        for a, rng in enumerate((self.command_x_range, self.command_y_range, self.command_yaw_range)):
+            c.command_range[a][0], c.command_range[a][1] = float(rng[0]), float(rng[1])
+        c.clip_observations = float(self.clip_observations)
+        if len(self.default_dof_pos) != 12:
+            raise ValueError("default_dof_pos: twelve joint angles")
+        for i, v in enumerate(self.default_dof_pos):
+            c.default_dof_pos[i] = float(v)
+        c.max_episode_length = self.max_episode_length
+        c.seed = int(self.seed) & (2 ** 64 - 1)
+        return c
+
+
+def _f32(t, numel, name):
+    import torch
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name} must be a contiguous cuda float32 tensor with {numel} elements")
+    return t
+
+
+class TaskPostPhysics:
+    """The task's buffers and the two kernels, for N environments.  ``commands`` [N,3], ``progress_buf``, ``reset_buf``, ``timeout_buf`` [N]
+    (int64, as the reference's), ``obs_buf`` [N,48] and ``rew_buf`` [N] are public cuda tensors; a caller may overwrite ``commands``.
+    ``reset_buf`` starts at 1 (vec_task.py:240): the first tick resets every environment."""
+
+    def __init__(self, n, cfg=None, device=None):
+        import torch
+        if not torch.cuda.is_available():
+            raise _lib.MpcLibraryError("TaskPostPhysics needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        torch.cuda.set_device(self.device)
+        self.cfg = cfg if cfg is not None else TaskConfig()
+        self.n = int(n)
+        self._handle = C.c_void_p()
+        cs = self.cfg._struct()
+        check(lib().mpc_task_create(C.byref(self._handle), self.n, C.addressof(cs)), "mpc_task_create")
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)
+        self.obs_buf, self.rew_buf = z((self.n, NUM_OBS), torch.float32), z((self.n,), torch.float32)
+        self.reset_buf = torch.ones((self.n,), dtype=torch.long, device=self.device)
+        self.progress_buf, self.timeout_buf = z((self.n,), torch.long), z((self.n,), torch.long)
+        self.commands = z((self.n, 3), torch.float32)
+        self.reset_ids = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+        bs = _BufferSet(self.progress_buf.data_ptr(), self.reset_buf.data_ptr(), self.timeout_buf.data_ptr(), self.reset_ids.data_ptr(),
+                        self.commands.data_ptr(), self.obs_buf.data_ptr(), self.rew_buf.data_ptr())
+        check(lib().mpc_task_buffers(self._handle, C.addressof(bs)), "mpc_task_buffers")
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h and _lib is not None and _lib._LIB is not None:
+            _lib._LIB.mpc_task_destroy(h)
+            self._handle = None
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def begin(self):
+        """vec_task.py:326 and aliengo.py:274-278, :344-349: ``timeout_buf``, ``progress_buf += 1``, and for the environments whose ``reset_buf``
+        is set fresh ``commands`` and ``progress_buf = 0``.  Returns ``reset_ids`` [N] int32 (r where environment r is being reset, -1 elsewhere)
+        for the device reset entry points; stream-ordered, no host synchronisation."""
+        check(lib().mpc_task_begin(self._handle, self._stream()), "mpc_task_begin")
+        return self.reset_ids
+
+    def finish(self, root_states, dof_state, actions, torques, contact_forces=None, base_index=0, knee_indices=None, hip_indices=None, fell=None):
+        """compute_observations + compute_reward + the clip into ``obs_buf``, ``rew_buf``, ``reset_buf``.  root_states [N,13], dof_state [N*12,2],
+        actions [N,12], torques [N,12]: contiguous cuda float32.  contact_forces [N,bodies,3] with base_index, knee_indices [4], hip_indices [4]
+        is Isaac Gym's net contact force tensor; fell [N] (bool / uint8) is the toy plant's flag, taken as base contact."""
+        import torch
+        n = self.n
+        _f32(root_states, n * 13, "root_states"); _f32(dof_state, n * 24, "dof_state"); _f32(actions, n * 12, "actions"); _f32(torques, n * 12, "torques")
+        cf_ptr, bodies, knee, hip = None, 0, None, None
+        if contact_forces is not None:
+            if contact_forces.dim() != 3 or contact_forces.shape[0] != n or contact_forces.shape[2] != 3:
+                raise ValueError("contact_forces: [N, bodies, 3] expected")
+            bodies = int(contact_forces.shape[1])
+            _f32(contact_forces, n * bodies * 3, "contact_forces")
+            if knee_indices is None or hip_indices is None:
+                raise ValueError("contact_forces need knee_indices and hip_indices")
+            knee = np.ascontiguousarray(knee_indices.cpu().numpy() if hasattr(knee_indices, "cpu") else knee_indices, dtype=np.int32).reshape(-1)
+            hip = np.ascontiguousarray(hip_indices.cpu().numpy() if hasattr(hip_indices, "cpu") else hip_indices, dtype=np.int32).reshape(-1)
+            if len(knee) != 4 or len(hip) != 4:
+                raise ValueError("knee_indices and hip_indices: four body indices each")
+            cf_ptr = contact_forces.data_ptr()
+        fell_ptr = None
+        if fell is not None:
+            if fell.dtype not in (torch.bool, torch.uint8) or not fell.is_cuda or not fell.is_contiguous() or fell.numel() != n:
+                raise ValueError(f"fell must be a contiguous cuda bool / uint8 tensor with {n} elements")
+            fell_ptr = fell.data_ptr()
+        check(lib().mpc_task_finish(self._handle, root_states.data_ptr(), dof_state.data_ptr(), actions.data_ptr(), torques.data_ptr(), cf_ptr, bodies,
+                                    int(base_index), None if knee is None else knee.ctypes.data, None if hip is None else hip.ctypes.data, fell_ptr,
+                                    self._stream()), "mpc_task_finish")
+        return self.obs_buf, self.rew_buf, self.reset_buf
+
+
+class BatchedRLTask:
+    """``VecTask.step`` / ``reset`` for N robots on the toy plant: MpcEnvBridge (actions -> torques), BatchedToySim (the simulator), and
+    the two task kernels.  See the module text for what the toy cannot do."""
+
+    def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, **bridge_args):
+        import torch
+        if not torch.cuda.is_available():
+            raise _lib.MpcLibraryError("BatchedRLTask needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        from .env_bridge import MpcEnvBridge
+        from .toy_sim import BatchedToySim
+        self.cfg = cfg if cfg is not None else TaskConfig()
+        self.bridge = MpcEnvBridge(robot_type, gait_id, horizon=horizon, controller_dt=self.cfg.dt, flat_ground=flat_ground, device=device, **bridge_args)
+        self.device, self.n = self.bridge.device, self.bridge.n
+        self.num_envs, self.num_obs, self.num_actions = self.n, NUM_OBS, 12
+        self.sim = BatchedToySim(robot_type, slope=slope, yaw0=yaw0, dt=self.cfg.dt, device=self.device)
+        self.task = TaskPostPhysics(self.n, self.cfg, device=self.device)
+        t = self.task
+        self.commands, self.progress_buf, self.reset_buf, self.timeout_buf = t.commands, t.progress_buf, t.reset_buf, t.timeout_buf
+        self.obs_buf, self.rew_buf = t.obs_buf, t.rew_buf
+        self.actions = torch.zeros((self.n, 12), dtype=torch.float32, device=self.device)
+        self.torques = self.bridge.ctl.torques
+        self.extras = {}
+
+    def step(self, actions):
+        """``VecTask.step`` (vec_task.py:298-339): actions [N,12] -> (obs_buf, rew_buf, reset_buf, {"time_outs": timeout_buf}).  The returned
+        tensors are the task's own buffers, rewritten by the next step.  Nothing is copied to the host and nothing waits for the device."""
+        import torch
+        sim, t = self.sim, self.task
+        torch.clamp(actions.to(self.device, torch.float32).reshape(self.n, 12), -self.cfg.clip_actions, self.cfg.clip_actions, out=self.actions)    # :312
+        self.torques = self.bridge.pre_physics_step(self.actions, sim.dof_state, sim.root_states, self.commands)                # aliengo.py:227-263
+        sim.step(self.torques)                                                                                                  # gym.simulate
+        ids = t.begin()                                                                                                         # :326, aliengo.py:274-278
+        self.bridge.ctl.reset(ids)                                                                                              # aliengo.py:330-334
+        sim.reset_idx(ids)                                                                                                      # aliengo.py:336-342
+        _, fell = sim.flags()              # after the reset: a robot that has just been put back standing is not flagged a second time
+        t.finish(sim.root_states, sim.dof_state, self.actions, self.torques, fell=fell)                                         # aliengo.py:280-281, :337
+        self.extras["time_outs"] = self.timeout_buf
+        return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
+
+    def reset(self):
+        """``VecTask.reset`` (vec_task.py:351-363): one step with zero actions; returns obs_buf."""
+        import torch
+        self.step(torch.zeros((self.n, 12), dtype=torch.float32, device=self.device))
+        return self.obs_buf
