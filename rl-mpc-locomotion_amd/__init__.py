@@ -6,4 +6,14 @@ and the synthetic workload generator.  See DESIGN.md.
 """
 from .rl_task import BatchedRLTask, TaskConfig, TaskPostPhysics  # noqa: E402,F401
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics"]
+_PPO = ("ActorCritic", "RolloutStorage", "PPO", "PPOConfig", "PPOTrainer")
+
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO]
+
+
+def __getattr__(name):
+    # the PPO classes subclass torch.nn.Module: ppo.py imports torch, which this package otherwise leaves to the first call that needs it
+    if name in _PPO:
+        from . import ppo
+        return getattr(ppo, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,413 @@
+"""PPO training of the weight policy: device rollouts, GAE, trainer (include/mpc_ppo.h, csrc/mpc_ppo.hip, csrc/ppo_rollout.h).
+
+The reference trains through rsl_rl's ``OnPolicyRunner`` (RL_Environment/train.py:61-81, hyper-parameters in
+RL_Environment/tasks/legged_config_ppo.py); rsl_rl itself is an empty submodule there.  This module restates rsl_rl v1.0.2's
+``ActorCritic``, ``RolloutStorage``, ``PPO`` and runner by their published formulas, split where the work splits:
+
+* the **collection half** of an iteration runs once per environment tick and is HIP: ``ActorCritic.act`` is one launch (actor and critic
+  side by side, sampling and log-prob in the actor's epilogue) that writes straight into slot t of the storage, ``RolloutStorage.add`` is
+  one kernel (time-out bootstrap and done flag, read from the task's int64 buffers), ``compute_returns`` is two (GAE, normalisation).
+  The kernels read the torch parameters where the optimiser updates them in place: no weight copy is made, ever.
+* the **update half** (``PPO.update``: mini-batch Adam steps) is GEMMs with autograd and is plain torch, on whatever device the storage
+  lives on.
+
+    env = BatchedRLTask(robot_type, gait_id)
+    trainer = PPOTrainer(env)
+    trainer.learn(num_iterations)
+    trainer.save("model.pt")
+    policy = WeightPolicy.from_state_dict(torch.load("model.pt")["model_state_dict"])
+
+Not rsl_rl's: the exploration noise is a counter-based generator keyed by (seed, environment, step, action pair), not torch's, so parity
+with ``Normal.sample`` is in distribution only, and |eps| <= 5.768 (ppo_rollout.h).  Not built: observation normalisation, recurrent
+policies, privileged critic observations (the reference uses none), logging.
+
+The device entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import torch
+from torch import nn
+
+from . import _lib
+
+NUM_ACTIONS = 12
+
+# the entry points of include/mpc_ppo.h (bound here, not in _lib.SYMBOLS, which lists include/mpc_batch.h)
+SYMBOLS = ["mpc_ac_create", "mpc_ac_destroy", "mpc_ac_bind", "mpc_ac_act", "mpc_ac_evaluate", "mpc_ac_act_inference", "mpc_rollout_add",
+           "mpc_rollout_returns", "mpc_ppo_last_error"]
+_BOUND = None
+
+
+def lib():
+    """libmpc_batch.so with the PPO entry points bound."""
+    global _BOUND
+    L = _lib.lib()
+    if _BOUND is not L:
+        vp, ci, cd = C.c_void_p, C.c_int, C.c_double
+        L.mpc_ac_create.argtypes = [C.POINTER(vp), ci, vp, ci, vp]; L.mpc_ac_create.restype = ci
+        L.mpc_ac_destroy.argtypes = [vp]; L.mpc_ac_destroy.restype = None
+        L.mpc_ac_bind.argtypes = [vp, vp, vp, vp, vp, vp]; L.mpc_ac_bind.restype = ci
+        L.mpc_ac_act.argtypes = [vp, ci, vp, C.c_ulonglong, C.c_uint, vp, vp, vp, vp, vp, vp, vp]; L.mpc_ac_act.restype = ci
+        L.mpc_ac_evaluate.argtypes = [vp, ci, vp, vp, vp]; L.mpc_ac_evaluate.restype = ci
+        L.mpc_ac_act_inference.argtypes = [vp, ci, vp, vp, vp]; L.mpc_ac_act_inference.restype = ci
+        L.mpc_rollout_add.argtypes = [ci, cd, vp, vp, vp, vp, vp, vp, vp]; L.mpc_rollout_add.restype = ci
+        L.mpc_rollout_returns.argtypes = [ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp]; L.mpc_rollout_returns.restype = ci
+        L.mpc_ppo_last_error.argtypes = []; L.mpc_ppo_last_error.restype = C.c_char_p
+        _BOUND = L
+    return L
+
+
+def check(rc, what):
+    if rc != _lib.MPC_OK:
+        raise _lib.MpcLibraryError(f"{what} failed ({rc}): {lib().mpc_ppo_last_error().decode()}")
+
+
+def _need_gpu(what, *tensors):
+    if not torch.cuda.is_available():
+        raise _lib.MpcLibraryError(f"{what} needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+    for t in tensors:
+        if not t.is_cuda:
+            raise _lib.MpcLibraryError(f"{what} runs on the device: a tensor on {t.device} was given; no CPU fallback")
+
+
+def _f32(t, numel, name):
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name} must be a contiguous cuda float32 tensor with {numel} elements")
+    return t
+
+
+def _i64(t, numel, name):
+    if t.dtype != torch.long or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name} must be a contiguous cuda int64 tensor with {numel} elements")
+    return t
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+@dataclass
+class PPOConfig:
+    """``LeggedCfgPPO`` (RL_Environment/tasks/legged_config_ppo.py) restated as numbers."""
+    seed: int = 1                                  # :2
+    # policy
+    init_noise_std: float = 1.0                    # :5
+    actor_hidden_dims: tuple = (512, 256, 128)     # :6
+    critic_hidden_dims: tuple = (512, 256, 128)    # :7
+    activation: str = "elu"                        # :8  (the only one built)
+    # algorithm
+    value_loss_coef: float = 1.0                   # :12
+    use_clipped_value_loss: bool = True            # :13
+    clip_param: float = 0.2                        # :14
+    entropy_coef: float = 0.01                     # :15
+    num_learning_epochs: int = 5                   # :16
+    num_mini_batches: int = 4                      # :17  mini-batch size = num_envs * num_steps_per_env / num_mini_batches
+    learning_rate: float = 1.0e-3                  # :18
+    schedule: str = "adaptive"                     # :19  'adaptive' or 'fixed'
+    gamma: float = 0.99                            # :20
+    lam: float = 0.95                              # :21
+    desired_kl: float = 0.01                       # :22
+    max_grad_norm: float = 1.0                     # :23
+    # runner
+    num_steps_per_env: int = 24                    # :28  per iteration
+    max_iterations: int = 5000                     # :29
+    save_interval: int = 100                       # :32
+
+
+def mlp(num_in, hidden, num_out):
+    layers, d = [], num_in
+    for h in hidden:
+        layers += [nn.Linear(d, h), nn.ELU()]
+        d = h
+    layers.append(nn.Linear(d, num_out))
+    return nn.Sequential(*layers)
+
+
+class ActorCritic(nn.Module):
+    """rsl_rl's ``ActorCritic`` with ELU: ``actor`` and ``critic`` are ``nn.Sequential`` stacks of Linear / ELU, ``std`` is the
+    state-independent action noise, so ``state_dict()`` has rsl_rl's keys (``std``, ``actor.{0,2,..}.{weight,bias}``,
+    ``critic.{0,2,..}.{weight,bias}``) and loads through ``WeightPolicy.from_state_dict``.
+
+    ``act``, ``evaluate`` and ``act_inference`` run the device kernels on the parameters where they are (no gradient flows through
+    them); ``log_prob_entropy_value`` is the differentiable torch path of the update."""
+
+    def __init__(self, num_obs=48, num_actions=NUM_ACTIONS, actor_hidden_dims=(512, 256, 128), critic_hidden_dims=(512, 256, 128), init_noise_std=1.0):
+        super().__init__()
+        if num_actions != NUM_ACTIONS:
+            raise ValueError("the sampling kernel draws six Box-Muller pairs: twelve actions (the MPC weights)")
+        self.num_obs, self.num_actions = int(num_obs), int(num_actions)
+        self.actor = mlp(num_obs, actor_hidden_dims, num_actions)
+        self.critic = mlp(num_obs, critic_hidden_dims, 1)
+        self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
+        self._handle, self._bound_ptrs = None, None
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h and _lib is not None and _lib._LIB is not None:
+            _lib._LIB.mpc_ac_destroy(h)
+            self._handle = None
+
+    # ---- the device path -----------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _linears(seq):
+        return [m for m in seq if isinstance(m, nn.Linear)]
+
+    def _ready(self, what, obs):
+        """The handle, bound to the parameters' current device addresses (checked on every call: ``.to()`` moves them, an optimiser step
+        or ``load_state_dict`` does not)."""
+        _need_gpu(what, obs, self.std)
+        la, lc = self._linears(self.actor), self._linears(self.critic)
+        params = [m.weight for m in la] + [m.bias for m in la] + [m.weight for m in lc] + [m.bias for m in lc] + [self.std]
+        ptrs = tuple(p.data_ptr() for p in params)
+        if self._handle is None:
+            dims = lambda ls: [ls[0].in_features] + [m.out_features for m in ls]
+            da, dc = dims(la), dims(lc)
+            h = C.c_void_p()
+            check(lib().mpc_ac_create(C.byref(h), len(la), C.cast((C.c_int * len(da))(*da), C.c_void_p), len(lc),
+                                      C.cast((C.c_int * len(dc))(*dc), C.c_void_p)), "mpc_ac_create")
+            self._handle = h
+        if ptrs != self._bound_ptrs:
+            for p in params:
+                if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.std.device:
+                    raise ValueError("ActorCritic parameters must be contiguous float32 tensors on one device")
+            na, nc = len(la), len(lc)
+            arr = lambda v: C.cast((C.c_void_p * len(v))(*v), C.c_void_p)
+            with torch.cuda.device(self.std.device):
+                check(lib().mpc_ac_bind(self._handle, arr(ptrs[:na]), arr(ptrs[na:2 * na]), arr(ptrs[2 * na:2 * na + nc]),
+                                        arr(ptrs[2 * na + nc:2 * na + 2 * nc]), ptrs[-1]), "mpc_ac_bind")
+            self._bound_ptrs = ptrs
+        n = obs.shape[0]
+        _f32(obs, n * self.num_obs, "obs")
+        return n
+
+    def act(self, obs, seed, step, out=None, return_eps=False):
+        """``ActorCritic.act`` + ``evaluate`` in one launch: obs [n, num_obs] -> a dict of ``actions`` [n,12], ``actions_log_prob`` [n,1],
+        ``values`` [n,1], ``mu`` [n,12], ``sigma`` [n,12] (and ``eps`` [n,12] if asked).  ``out``: the same dict of caller's tensors to write
+        into (slot t of a RolloutStorage: ``storage.slot(t)``).  The noise of environment r is a function of (seed, r, step) alone."""
+        n = self._ready("ActorCritic.act", obs)
+        dev = obs.device
+        if out is None:
+            e = lambda k: torch.empty((n, k), dtype=torch.float32, device=dev)
+            out = dict(actions=e(12), actions_log_prob=e(1), values=e(1), mu=e(12), sigma=e(12))
+        else:
+            for k, w in (("actions", 12), ("actions_log_prob", 1), ("values", 1), ("mu", 12), ("sigma", 12)):
+                _f32(out[k], n * w, k)
+        eps = torch.empty((n, 12), dtype=torch.float32, device=dev) if return_eps else None
+        check(lib().mpc_ac_act(self._handle, n, obs.data_ptr(), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, out["actions"].data_ptr(),
+                               out["actions_log_prob"].data_ptr(), out["values"].data_ptr(), out["mu"].data_ptr(), out["sigma"].data_ptr(),
+                               eps.data_ptr() if return_eps else None, _stream(dev)), "mpc_ac_act")
+        if return_eps:
+            out = dict(out, eps=eps)
+        return out
+
+    def evaluate(self, obs, out=None):
+        """The critic alone: obs [n, num_obs] -> values [n, 1]."""
+        n = self._ready("ActorCritic.evaluate", obs)
+        values = torch.empty((n, 1), dtype=torch.float32, device=obs.device) if out is None else _f32(out, n, "out")
+        check(lib().mpc_ac_evaluate(self._handle, n, obs.data_ptr(), values.data_ptr(), _stream(obs.device)), "mpc_ac_evaluate")
+        return values
+
+    def act_inference(self, obs):
+        """The actor's mean: obs [n, num_obs] -> [n, 12], bit for bit the raw action of ``WeightPolicy.step`` on the same weights."""
+        n = self._ready("ActorCritic.act_inference", obs)
+        mean = torch.empty((n, 12), dtype=torch.float32, device=obs.device)
+        check(lib().mpc_ac_act_inference(self._handle, n, obs.data_ptr(), mean.data_ptr(), _stream(obs.device)), "mpc_ac_act_inference")
+        return mean
+
+    # ---- the differentiable path of the update ---------------------------------------------------------------------------------------------
+    def log_prob_entropy_value(self, obs, actions):
+        """(log-prob [B], entropy [B], value [B,1], mu [B,12], sigma [B,12]) of ``actions`` under the current parameters, in plain torch with
+        autograd: ``Normal(actor(obs), std)`` as rsl_rl's ``update_distribution`` builds it."""
+        mu = self.actor(obs)
+        dist = torch.distributions.Normal(mu, mu * 0. + self.std)
+        return dist.log_prob(actions).sum(dim=-1), dist.entropy().sum(dim=-1), self.critic(obs), mu, dist.stddev
+
+
+class RolloutStorage:
+    """rsl_rl's ``RolloutStorage`` without its staging: [T, N, ...] float32 tensors ``observations`` [T,N,num_obs], ``actions``, ``mu``,
+    ``sigma`` [T,N,12], ``values``, ``rewards``, ``dones``, ``actions_log_prob``, ``returns``, ``advantages`` [T,N,1].  ``ActorCritic.act``
+    writes into ``slot(t)``; ``add`` and ``compute_returns`` are device kernels (a storage on the CPU can be filled by hand and read by
+    ``PPO.update``, which is plain torch)."""
+
+    def __init__(self, n, T, device, num_obs=48, num_actions=NUM_ACTIONS):
+        self.n, self.T, self.device = int(n), int(T), torch.device(device)
+        z = lambda k: torch.zeros((self.T, self.n, k), dtype=torch.float32, device=self.device)
+        self.observations, self.actions, self.mu, self.sigma = z(num_obs), z(num_actions), z(num_actions), z(num_actions)
+        self.values, self.rewards, self.dones, self.actions_log_prob, self.returns, self.advantages = z(1), z(1), z(1), z(1), z(1), z(1)
+        self.step = 0
+
+    def slot(self, t):
+        """The views of slot t that ``ActorCritic.act(..., out=)`` writes."""
+        return dict(actions=self.actions[t], actions_log_prob=self.actions_log_prob[t], values=self.values[t], mu=self.mu[t], sigma=self.sigma[t])
+
+    def add(self, rew, reset, time_outs, gamma, obs=None):
+        """``PPO.process_env_step`` + ``add_transitions`` for the slot ``act`` has just written (``self.step``, then advanced): rewards[t] = rew +
+        gamma * (values[t] * time_outs), dones[t] = reset, read from the task's own buffers (rew float32, reset and time_outs int64) before its next
+        step rewrites them; ``obs``, the observations ``act`` was given, are copied into observations[t]."""
+        _need_gpu("RolloutStorage.add", rew, self.rewards)
+        t = self.step
+        if t >= self.T:
+            raise RuntimeError("rollout storage overflow: clear() after compute_returns")
+        _f32(rew, self.n, "rew"); _i64(reset, self.n, "reset"); _i64(time_outs, self.n, "time_outs")
+        if obs is not None:
+            self.observations[t].copy_(obs)
+        check(lib().mpc_rollout_add(self.n, float(gamma), rew.data_ptr(), reset.data_ptr(), time_outs.data_ptr(), self.values[t].data_ptr(),
+                                    self.rewards[t].data_ptr(), self.dones[t].data_ptr(), _stream(self.device)), "mpc_rollout_add")
+        self.step += 1
+
+    def compute_returns(self, last_values, gamma, lam):
+        """``RolloutStorage.compute_returns``: GAE over the T slots into ``returns``, then ``advantages`` = returns - values normalised over all
+        T N values."""
+        _need_gpu("RolloutStorage.compute_returns", last_values, self.rewards)
+        _f32(last_values, self.n, "last_values")
+        check(lib().mpc_rollout_returns(self.n, self.T, float(gamma), float(lam), self.rewards.data_ptr(), self.dones.data_ptr(), self.values.data_ptr(),
+                                        last_values.data_ptr(), self.returns.data_ptr(), self.advantages.data_ptr(), _stream(self.device)),
+              "mpc_rollout_returns")
+
+    def mini_batch_generator(self, num_mini_batches, num_epochs=8):
+        """rsl_rl's: one ``torch.randperm`` over T N for all epochs, mini-batch size T N // num_mini_batches.  Yields (obs, actions, values,
+        advantages, returns, old log-prob, old mu, old sigma)."""
+        batch = self.n * self.T
+        size = batch // num_mini_batches
+        idx = torch.randperm(num_mini_batches * size, device=self.device)
+        flat = [x.flatten(0, 1) for x in (self.observations, self.actions, self.values, self.advantages, self.returns, self.actions_log_prob, self.mu,
+                                          self.sigma)]
+        for _ in range(num_epochs):
+            for i in range(num_mini_batches):
+                b = idx[i * size:(i + 1) * size]
+                yield tuple(x[b] for x in flat)
+
+    def clear(self):
+        self.step = 0
+
+
+class PPO:
+    """rsl_rl's ``PPO.update`` in plain torch (autograd + Adam) on whatever device the storage lives on."""
+
+    def __init__(self, actor_critic, cfg=None):
+        self.cfg = cfg if cfg is not None else PPOConfig()
+        self.actor_critic = actor_critic
+        self.learning_rate = float(self.cfg.learning_rate)
+        self.optimizer = torch.optim.Adam(actor_critic.parameters(), lr=self.learning_rate)
+        self.last_terms = None
+
+    def adapt_learning_rate(self, kl_mean):
+        """The adaptive schedule: lr / 1.5 (not below 1e-5) if kl > 2 desired_kl, lr * 1.5 (not above 1e-2) if 0 < kl < desired_kl / 2."""
+        c = self.cfg
+        if kl_mean > c.desired_kl * 2.0:
+            self.learning_rate = max(1e-5, self.learning_rate / 1.5)
+        elif kl_mean < c.desired_kl / 2.0 and kl_mean > 0.0:
+            self.learning_rate = min(1e-2, self.learning_rate * 1.5)
+        for group in self.optimizer.param_groups:
+            group["lr"] = self.learning_rate
+
+    def losses(self, batch):
+        """(surrogate, value loss, mean entropy, mean kl) of one mini-batch of ``RolloutStorage.mini_batch_generator``; kl carries no gradient."""
+        c = self.cfg
+        obs, actions, old_values, adv, returns, old_logp, old_mu, old_sigma = batch
+        logp, entropy, value, mu, sigma = self.actor_critic.log_prob_entropy_value(obs, actions)
+        with torch.no_grad():
+            kl = torch.sum(torch.log(sigma / old_sigma + 1.e-5) + (torch.square(old_sigma) + torch.square(old_mu - mu)) / (2.0 * torch.square(sigma)) - 0.5,
+                           axis=-1).mean()
+        ratio = torch.exp(logp - torch.squeeze(old_logp))
+        a = torch.squeeze(adv)
+        surrogate = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - c.clip_param, 1.0 + c.clip_param)).mean()
+        if c.use_clipped_value_loss:
+            clipped = old_values + (value - old_values).clamp(-c.clip_param, c.clip_param)
+            value_loss = torch.max((value - returns).pow(2), (clipped - returns).pow(2)).mean()
+        else:
+            value_loss = (returns - value).pow(2).mean()
+        return surrogate, value_loss, entropy.mean(), kl
+
+    def update(self, storage):
+        """One update over the storage: num_learning_epochs x num_mini_batches Adam steps.  The only host read per mini-batch is the kl of the
+        adaptive schedule (as in rsl_rl).  Returns device tensors (mean value loss, mean surrogate loss)."""
+        c = self.cfg
+        mean_value, mean_surrogate, k = 0.0, 0.0, 0
+        for batch in storage.mini_batch_generator(c.num_mini_batches, c.num_learning_epochs):
+            surrogate, value_loss, entropy, kl = self.losses(batch)
+            if c.desired_kl is not None and c.schedule == "adaptive":
+                self.adapt_learning_rate(kl.item())
+            loss = surrogate + c.value_loss_coef * value_loss - c.entropy_coef * entropy
+            self.optimizer.zero_grad()
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(self.actor_critic.parameters(), c.max_grad_norm)
+            self.optimizer.step()
+            self.last_terms = (surrogate.detach(), value_loss.detach(), entropy.detach(), kl)
+            mean_value, mean_surrogate, k = mean_value + value_loss.detach(), mean_surrogate + surrogate.detach(), k + 1
+        storage.clear()
+        return mean_value / k, mean_surrogate / k
+
+
+class PPOTrainer:
+    """rsl_rl's ``OnPolicyRunner`` for an environment with ``BatchedRLTask``'s members: ``num_envs``, ``num_obs``, ``num_actions``, ``reset()``,
+    ``step(actions) -> (obs, rew, reset, extras)`` with ``extras["time_outs"]`` (rew float32, reset and time_outs int64, cuda).
+
+    An iteration: T times ``act`` into slot t, ``env.step``, ``add``; then ``evaluate`` and ``compute_returns`` -- nothing of that is copied to
+    the host or waits for the device -- and ``PPO.update``.  ``seed`` seeds torch's global generator (weight initialisation, the update's
+    ``randperm``), as the reference's train.py does, and the exploration noise."""
+
+    def __init__(self, env, cfg=None, seed=1, device=None):
+        if not torch.cuda.is_available():
+            raise _lib.MpcLibraryError("PPOTrainer needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        self.cfg = cfg if cfg is not None else PPOConfig()
+        self.env, self.seed = env, int(seed)
+        self.device = torch.device(device if device is not None else getattr(env, "device", f"cuda:{torch.cuda.current_device()}"))
+        torch.manual_seed(self.seed)
+        c = self.cfg
+        self.actor_critic = ActorCritic(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std).to(self.device)
+        self.alg = PPO(self.actor_critic, c)
+        self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions)
+        self.iteration, self.tick, self.obs = 0, 0, None
+        self.infos = []
+
+    def collect(self, record_eps=None):
+        """The collection half of one iteration (T ticks), entirely on the device.  ``record_eps``: a list that receives each tick's noise."""
+        c, st = self.cfg, self.storage
+        if self.obs is None:
+            self.obs = self.env.reset()
+        st.clear()
+        with torch.no_grad():
+            for t in range(st.T):
+                obs = self.obs
+                out = self.actor_critic.act(obs, self.seed, self.tick, out=st.slot(t), return_eps=record_eps is not None)
+                if record_eps is not None:
+                    record_eps.append(out["eps"])
+                st.observations[t].copy_(obs)
+                self.obs, rew, reset, extras = self.env.step(st.actions[t])
+                st.add(rew, reset, extras["time_outs"], c.gamma)
+                self.tick += 1
+            self.last_values = self.actor_critic.evaluate(self.obs)
+            st.compute_returns(self.last_values, c.gamma, c.lam)
+
+    def learn(self, num_iterations):
+        """``num_iterations`` of collection + update.  Appends one record per iteration to ``infos`` (read from the device once, after the
+        update) and returns the list."""
+        for _ in range(int(num_iterations)):
+            self.collect()
+            mean_reward, done_rate = self.storage.rewards.mean(), self.storage.dones.mean()
+            value_loss, surrogate = self.alg.update(self.storage)
+            stats = torch.stack((mean_reward, done_rate, value_loss, surrogate, self.actor_critic.std.detach().mean())).tolist()
+            self.iteration += 1
+            self.infos.append(dict(iter=self.iteration, mean_reward=stats[0], done_rate=stats[1], value_loss=stats[2], surrogate_loss=stats[3],
+                                   mean_noise_std=stats[4], learning_rate=self.alg.learning_rate))
+        return self.infos
+
+    def save(self, path):
+        """The checkpoint as rsl_rl writes it; ``WeightPolicy.from_state_dict(torch.load(path)["model_state_dict"])`` loads its actor."""
+        torch.save({"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(), "iter": self.iteration,
+                    "infos": self.infos}, path)
+
+    def load(self, path, load_optimizer=True):
+        ck = torch.load(path, map_location=self.device)
+        self.actor_critic.load_state_dict(ck["model_state_dict"])      # (in place: the kernels keep reading the same addresses)
+        if load_optimizer:
+            self.alg.optimizer.load_state_dict(ck["optimizer_state_dict"])
+        self.iteration = ck["iter"]
+        self.infos = list(ck["infos"]) if ck.get("infos") else []
+        return ck["infos"]
+
+    def get_inference_policy(self):
+        """obs [n, num_obs] -> the actor's mean [n, 12] (``ActorCritic.act_inference``)."""
+        return self.actor_critic.act_inference

@@ -1,0 +1,178 @@
+"""What a PPO iteration costs: 4096 Aliengo robots trotting, h = 10, T = 24, the reference's nets (48-512-256-128-12 / -1).
+Per tick, from HIP events (median over ticks x repeats): `ActorCritic.act` (one launch), `RolloutStorage.add` (the observation copy + one kernel); per
+iteration: `evaluate` + `compute_returns`, the whole 24-tick collection with `BatchedRLTask.step` inside, 24 bare `step`s, the torch update, one
+full iteration.  In the same call, alternating repeat by repeat, the TORCH COMPOSITION of the collection half on the same buffers: the two
+nn.Sequential, Normal(...).sample / log_prob, the storage copies, the time-out bootstrap and rsl_rl's GAE loop.  The shader clock is recorded as
+bench.py --full records it (device_state).
+    python tools/ppo_rate.py [--repeats 7] [--out profiles/r09_ppo.json]
+The kernel-trace stats: rocprofv3 --kernel-trace --stats ... -- python tools/ppo_rate.py --quick   (3 collections and one update)"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import rl_mpc_locomotion_amd  # noqa: E402,F401
+from rl_mpc_locomotion_amd import _lib  # noqa: E402
+from rl_mpc_locomotion_amd.ppo import PPOConfig, PPOTrainer, RolloutStorage  # noqa: E402
+from rl_mpc_locomotion_amd.rl_task import BatchedRLTask, TaskConfig  # noqa: E402
+
+TROT = 0
+
+
+def make_env(n, dev):
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    return BatchedRLTask([0] * n, [TROT] * n, cfg=TaskConfig(), horizon=10, yaw0=yaw, flat_ground=True, device=dev)
+
+
+def torch_act(ac, st, t, obs):
+    """rsl_rl's PPO.act: ActorCritic.act / evaluate and the copies of RolloutStorage.add_transitions"""
+    with torch.no_grad():
+        mean = ac.actor(obs)
+        dist = torch.distributions.Normal(mean, mean * 0. + ac.std)
+        actions = dist.sample()
+        st.actions[t].copy_(actions)
+        st.values[t].copy_(ac.critic(obs))
+        st.actions_log_prob[t].copy_(dist.log_prob(actions).sum(dim=-1).view(-1, 1))
+        st.mu[t].copy_(mean)
+        st.sigma[t].copy_(dist.stddev)
+        st.observations[t].copy_(obs)
+
+
+def torch_add(st, t, rew, reset, time_outs, gamma):
+    """rsl_rl's PPO.process_env_step: the time-out bootstrap and the two copies"""
+    rewards = rew.clone()
+    rewards += gamma * torch.squeeze(st.values[t] * time_outs.unsqueeze(1), 1)
+    st.rewards[t].copy_(rewards.view(-1, 1))
+    st.dones[t].copy_(reset.view(-1, 1))
+
+
+def torch_returns(ac, st, obs, gamma, lam):
+    """rsl_rl's evaluate + RolloutStorage.compute_returns"""
+    with torch.no_grad():
+        last_values = ac.critic(obs)
+        advantage = 0
+        for step in reversed(range(st.T)):
+            next_values = last_values if step == st.T - 1 else st.values[step + 1]
+            next_is_not_terminal = 1.0 - st.dones[step].float()
+            delta = st.rewards[step] + next_is_not_terminal * gamma * next_values - st.values[step]
+            advantage = delta + next_is_not_terminal * gamma * lam * advantage
+            st.returns[step] = advantage + st.values[step]
+        adv = st.returns - st.values
+        st.advantages = (adv - adv.mean()) / (adv.std() + 1e-8)
+
+
+def ev():
+    return torch.cuda.Event(enable_timing=True)
+
+
+def stats(x):
+    x = np.asarray(x, dtype=np.float64)
+    return {"median_ms": float(np.median(x)), "min_ms": float(x.min()), "max_ms": float(x.max()), "p10_ms": float(np.percentile(x, 10)),
+            "p90_ms": float(np.percentile(x, 90)), "samples": int(x.size)}
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--robots", type=int, default=4096)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--quick", action="store_true", help="3 collections and one update only (for a kernel trace)")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("ppo_rate.py measures on the GPU; none is visible")
+    dev, n = "cuda:0", args.robots
+    cfg = PPOConfig()
+    T = cfg.num_steps_per_env
+    env = make_env(n, dev)
+    trainer = PPOTrainer(env, cfg, seed=1)
+    ac, st = trainer.actor_critic, trainer.storage
+    if args.quick:
+        for _ in range(3):
+            trainer.collect()
+        trainer.alg.update(st)
+        torch.cuda.synchronize()
+        sys.exit(0)
+    from bench import device_state  # noqa: E402
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "num_steps_per_env": T, "repeats": args.repeats,
+           "nets": {"actor": [48, *cfg.actor_hidden_dims, 12], "critic": [48, *cfg.critic_hidden_dims, 1]}, "mini_batches_per_update": cfg.num_learning_epochs * cfg.num_mini_batches,
+           "device_state": {"before": device_state(0)}}
+    st_torch = RolloutStorage(n, T, dev)
+    # warm-up: cold solves, code objects, torch's kernels and its GEMM choices, Adam's state
+    trainer.learn(2)
+    obs = trainer.obs
+    _, rew, reset, extras = env.step(st.actions[0])
+    time_outs = extras["time_outs"]
+    for t in range(T):
+        torch_act(ac, st_torch, t, obs); torch_add(st_torch, t, rew, reset, time_outs, cfg.gamma)
+    torch_returns(ac, st_torch, obs, cfg.gamma, cfg.lam)
+    torch.cuda.synchronize()
+
+    t_act, t_add, t_ret, t_tact, t_tadd, t_tret, t_collect, t_steps, t_update, t_iter = ([] for _ in range(10))
+    for _ in range(args.repeats):
+        # the pieces on fixed inputs (the environment's current buffers), fused and torch alternating
+        for fused in (True, False):
+            e = [[ev() for _ in range(3)] for _ in range(T)]
+            s = st if fused else st_torch
+            st.clear()
+            for t in range(T):
+                e[t][0].record()
+                if fused:
+                    ac.act(obs, trainer.seed, trainer.tick + t, out=s.slot(t))
+                else:
+                    torch_act(ac, s, t, obs)
+                e[t][1].record()
+                if fused:
+                    s.add(rew, reset, time_outs, cfg.gamma, obs=obs)
+                else:
+                    torch_add(s, t, rew, reset, time_outs, cfg.gamma)
+                e[t][2].record()
+            r0, r1 = ev(), ev()
+            r0.record()
+            if fused:
+                s.compute_returns(ac.evaluate(obs), cfg.gamma, cfg.lam)
+            else:
+                torch_returns(ac, s, obs, cfg.gamma, cfg.lam)
+            r1.record()
+            torch.cuda.synchronize()
+            (t_act if fused else t_tact).extend(x[0].elapsed_time(x[1]) for x in e)
+            (t_add if fused else t_tadd).extend(x[1].elapsed_time(x[2]) for x in e)
+            (t_ret if fused else t_tret).append(r0.elapsed_time(r1))
+        st.clear()
+        # the whole iteration, and T bare steps of the environment
+        a, b, c, d, f = ev(), ev(), ev(), ev(), ev()
+        a.record()
+        trainer.collect()
+        b.record()
+        trainer.alg.update(st)
+        c.record()
+        torch.cuda.synchronize()
+        d.record()
+        for t in range(T):
+            env.step(st.actions[t])
+        f.record()
+        torch.cuda.synchronize()
+        trainer.obs = env.obs_buf
+        t_collect.append(a.elapsed_time(b)); t_update.append(b.elapsed_time(c)); t_iter.append(a.elapsed_time(c)); t_steps.append(d.elapsed_time(f))
+    res["fused"] = {"act": stats(t_act), "add_with_observation_copy": stats(t_add), "evaluate_and_compute_returns": stats(t_ret)}
+    res["torch_composition"] = {"act": stats(t_tact), "add": stats(t_tadd), "evaluate_and_compute_returns": stats(t_tret)}
+    res["iteration"] = {"collection_24_ticks": stats(t_collect), "bare_24_steps": stats(t_steps), "update": stats(t_update), "full": stats(t_iter)}
+    m = lambda x: float(np.median(x))
+    tick_fused = np.array(t_act) + np.array(t_add)
+    tick_torch = np.array(t_tact) + np.array(t_tadd)
+    res["act_plus_add_per_tick"] = {"fused": stats(tick_fused), "torch": stats(tick_torch), "fused_over_torch": m(tick_fused) / m(tick_torch)}
+    res["compute_returns_fused_over_torch"] = m(t_ret) / m(t_tret)
+    res["collection_added_per_tick_ms"] = (m(t_collect) - m(t_steps)) / T
+    res["collection_added_share_of_a_step_tick"] = (m(t_collect) - m(t_steps)) / m(t_steps)
+    res["update_share_of_iteration"] = m(t_update) / m(t_iter)
+    res["robot_ticks_per_s_training"] = n * T / (m(t_iter) * 1e-3)
+    res["device_state"]["after"] = device_state(0, smi=False)
+    print(json.dumps(res, indent=1))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
