@@ -1,0 +1,60 @@
+/*
+ * include/mpc_ppo_update.h -- C ABI of the update half of a PPO iteration (rsl_rl v1.0.2's PPO.update, as rl_mpc_locomotion_amd.ppo.PPO.losses /
+ * update state it) on the device: for one mini-batch after another on one stream, with no host synchronisation, no atomics and no graph capture.
+ *
+ *   mpc_ppo_update_grads   forward of both nets over the rows named by an index slice (read straight from the rollout storage), the loss head, the
+ *                          backward pass: the gradient of  surrogate + value_loss_coef * value_loss - entropy_coef * entropy  into the bound .grad
+ *                          tensors, the four loss terms, and the adaptive schedule's decision applied to a float64 learning rate on the device
+ *   mpc_ppo_update_apply   the total gradient norm, clip_grad_norm_'s coefficient and torch.optim.Adam's step over all parameter tensors, the
+ *                          learning rate read from the device
+ *
+ * The GEMMs run on the exact-fp32 MFMA pipe (rl-mpc-locomotion_amd/csrc/ppo_gemm.h); the scalar arithmetic is csrc/ppo_update.h, float32 in
+ * rsl_rl's and torch's operation order.  Every sum over rows or elements is taken in a fixed order: a rerun is bit-identical.
+ *
+ * Nothing is copied: the parameters are read and written at the addresses the mpc_ac holds (mpc_ac_bind), so mpc_ac_act sees an update at once; the
+ * gradients and Adam's moments are the caller's tensors (mpc_ppo_update_bind), so torch's optimizer.state_dict() stays the checkpoint.
+ *
+ * All pointers named d_* are DEVICE pointers; `stream` is a hipStream_t (0 = default stream).  Functions return 0 (MPC_OK) on success, a negative
+ * MPC_E_* code of include/mpc_batch.h otherwise; mpc_ppo_last_error() (include/mpc_ppo.h) gives the text.  Every call validates its arguments before
+ * the device is touched, and none synchronises.
+ */
+#ifndef MPC_PPO_UPDATE_H
+#define MPC_PPO_UPDATE_H
+
+#include "mpc_ppo.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct mpc_ppo_update mpc_ppo_update;
+
+/* A handle over an existing, bound mpc_ac (which must outlive it), on the mpc_ac's device.  It owns the workspace for mini-batches of up to max_rows
+ * rows: the activations and their gradients, the per-chunk weight-gradient partials, the reduction partials. */
+int mpc_ppo_update_create(mpc_ppo_update **out, mpc_ac *ac, int max_rows);
+void mpc_ppo_update_destroy(mpc_ppo_update *u);
+/* Number of parameter tensors: 2 (actor layers + critic layers) + 1, in mpc_ac_bind's order: actor weights, actor biases, critic weights, critic
+ * biases, std.  -1 for a null handle. */
+int mpc_ppo_update_tensors(const mpc_ppo_update *u);
+/* The gradient tensors and Adam's moments (exp_avg, exp_avg_sq), each a host array of mpc_ppo_update_tensors() DEVICE pointers in that order, shaped
+ * like their parameters, non-null and 16-byte aligned.  Kept, not copied.  d_exp_avg and d_exp_avg_sq may both be NULL: mpc_ppo_update_apply then
+ * refuses. */
+int mpc_ppo_update_bind(mpc_ppo_update *u, float *const *d_grads, float *const *d_exp_avg, float *const *d_exp_avg_sq);
+/* The flat rollout storage, total_rows = T N rows: d_obs [.][actor_dims[0]], d_actions, d_mu, d_sigma [.][12], d_values, d_advantages, d_returns,
+ * d_log_prob [.]. */
+int mpc_ppo_update_set_storage(mpc_ppo_update *u, long long total_rows, const float *d_obs, const float *d_actions, const float *d_values,
+                               const float *d_advantages, const float *d_returns, const float *d_log_prob, const float *d_mu, const float *d_sigma);
+/* One mini-batch: rows 1 .. max_rows, d_idx [rows] int64 row numbers into the storage (values outside [0, total_rows) are clamped into it).  Writes the
+ * bound gradients, d_terms [4] = (surrogate, value loss, mean entropy, mean kl) as float32, and, if adaptive != 0, *d_lr (float64) by
+ * PPO.adapt_learning_rate's rule with desired_kl > 0.  clip_param > 0. */
+int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, double clip_param, double value_loss_coef, double entropy_coef,
+                         int use_clipped_value_loss, int adaptive, double desired_kl, double *d_lr, float *d_terms, void *stream);
+/* clip_grad_norm_(max_norm) over the bound gradients (they are scaled in place, as torch scales them), then Adam's step number `step` (>= 1, the
+ * host's count) with the learning rate *d_lr. */
+int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, double beta2, double eps, int step, const double *d_lr, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* MPC_PPO_UPDATE_H */

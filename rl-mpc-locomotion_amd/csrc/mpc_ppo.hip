@@ -15,6 +15,7 @@
 #include <string>
 
 #include "../../include/mpc_ppo.h"
+#include "mpc_ac_internal.h"
 #include "ppo_rollout.h"
 
 // policy_mlp.h defines its kernels with external linkage and mpc_batch.hip has them already: inside this unit's unnamed namespace the second copy
@@ -180,6 +181,26 @@ struct mpc_ac {
   int device = -1;
   bool bound = false;
 };
+
+// mpc_ac_internal.h: the handle as the update unit (mpc_ppo_update.hip) sees it
+bool mpc_ac_get_view(const mpc_ac *ac, mpc_ac_view *out) {
+  if (!ac || !out) return false;
+  for (int k = 0; k < 2; ++k) {
+    const policy::Net &net = ac->nets.net[k];
+    out->n_layers[k] = net.n_layers;
+    for (int l = 0; l <= net.n_layers; ++l) out->dims[k][l] = net.dims[l];
+    for (int l = 0; l < net.n_layers; ++l) {
+      out->w[k][l] = net.w[l];
+      out->b[k][l] = net.b[l];
+    }
+  }
+  out->std = ac->nets.std;
+  out->device = ac->device;
+  out->bound = ac->bound;
+  return true;
+}
+
+int mpc_ppo_set_error(int code, const char *message) { return pfail(code, message); }
 
 extern "C" {
 

@@ -8,8 +8,10 @@ RL_Environment/tasks/legged_config_ppo.py); rsl_rl itself is an empty submodule 
   side by side, sampling and log-prob in the actor's epilogue) that writes straight into slot t of the storage, ``RolloutStorage.add`` is
   one kernel (time-out bootstrap and done flag, read from the task's int64 buffers), ``compute_returns`` is two (GAE, normalisation).
   The kernels read the torch parameters where the optimiser updates them in place: no weight copy is made, ever.
-* the **update half** (``PPO.update``: mini-batch Adam steps) is GEMMs with autograd and is plain torch, on whatever device the storage
-  lives on.
+* the **update half** (``PPO.update``: mini-batch Adam steps) is GEMMs with autograd and is plain torch by default, on whatever device the
+  storage lives on; ``PPO(..., backend="hip")`` / ``PPOTrainer(..., update="hip")`` select the device update (include/mpc_ppo_update.h,
+  csrc/mpc_ppo_update.hip, csrc/ppo_gemm.h, csrc/ppo_update.h): forward and backward GEMMs on the fp32 MFMA pipe, the loss head, the gradient
+  clip and Adam, on the parameters, ``.grad`` tensors and optimiser moments where torch keeps them, with no host read per mini-batch.
 
     env = BatchedRLTask(robot_type, gait_id)
     trainer = PPOTrainer(env)
@@ -55,6 +57,29 @@ def lib():
         L.mpc_rollout_returns.argtypes = [ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp]; L.mpc_rollout_returns.restype = ci
         L.mpc_ppo_last_error.argtypes = []; L.mpc_ppo_last_error.restype = C.c_char_p
         _BOUND = L
+    return L
+
+
+# the entry points of include/mpc_ppo_update.h, with a binding of their own
+UPDATE_SYMBOLS = ["mpc_ppo_update_create", "mpc_ppo_update_destroy", "mpc_ppo_update_tensors", "mpc_ppo_update_bind", "mpc_ppo_update_set_storage",
+                  "mpc_ppo_update_grads", "mpc_ppo_update_apply"]
+_UPDATE_BOUND = None
+
+
+def update_lib():
+    """libmpc_batch.so with the entry points of the device update bound (and those of ``lib()``)."""
+    global _UPDATE_BOUND
+    L = lib()
+    if _UPDATE_BOUND is not L:
+        vp, ci, cd, ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+        L.mpc_ppo_update_create.argtypes = [C.POINTER(vp), vp, ci]; L.mpc_ppo_update_create.restype = ci
+        L.mpc_ppo_update_destroy.argtypes = [vp]; L.mpc_ppo_update_destroy.restype = None
+        L.mpc_ppo_update_tensors.argtypes = [vp]; L.mpc_ppo_update_tensors.restype = ci
+        L.mpc_ppo_update_bind.argtypes = [vp, vp, vp, vp]; L.mpc_ppo_update_bind.restype = ci
+        L.mpc_ppo_update_set_storage.argtypes = [vp, ll] + [vp] * 8; L.mpc_ppo_update_set_storage.restype = ci
+        L.mpc_ppo_update_grads.argtypes = [vp, ci, vp, cd, cd, cd, ci, ci, cd, vp, vp, vp]; L.mpc_ppo_update_grads.restype = ci
+        L.mpc_ppo_update_apply.argtypes = [vp, cd, cd, cd, cd, ci, vp, vp]; L.mpc_ppo_update_apply.restype = ci
+        _UPDATE_BOUND = L
     return L
 
 
@@ -181,6 +206,11 @@ class ActorCritic(nn.Module):
         _f32(obs, n * self.num_obs, "obs")
         return n
 
+    def bind_order(self):
+        """The parameters in ``mpc_ac_bind``'s order: actor weights, actor biases, critic weights, critic biases, std."""
+        la, lc = self._linears(self.actor), self._linears(self.critic)
+        return [m.weight for m in la] + [m.bias for m in la] + [m.weight for m in lc] + [m.bias for m in lc] + [self.std]
+
     def act(self, obs, seed, step, out=None, return_eps=False):
         """``ActorCritic.act`` + ``evaluate`` in one launch: obs [n, num_obs] -> a dict of ``actions`` [n,12], ``actions_log_prob`` [n,1],
         ``values`` [n,1], ``mu`` [n,12], ``sigma`` [n,12] (and ``eps`` [n,12] if asked).  ``out``: the same dict of caller's tensors to write
@@ -283,14 +313,35 @@ class RolloutStorage:
 
 
 class PPO:
-    """rsl_rl's ``PPO.update`` in plain torch (autograd + Adam) on whatever device the storage lives on."""
+    """rsl_rl's ``PPO.update``.  ``backend="torch"`` (the default): plain torch (autograd + Adam) on whatever device the storage lives on.
+    ``backend="hip"``: the device update of include/mpc_ppo_update.h on the same parameters, ``.grad`` tensors and optimiser state, with no host
+    read: the learning rate of the adaptive schedule lives on the device (``lr_device``, float64) and ``learning_rate`` / the param groups' ``lr``
+    are what the caller last copied from it (``sync_learning_rate``; ``PPOTrainer.learn`` does it once per iteration)."""
 
-    def __init__(self, actor_critic, cfg=None):
+    def __init__(self, actor_critic, cfg=None, backend="torch"):
+        if backend not in ("torch", "hip"):
+            raise ValueError("backend is 'torch' or 'hip'")
         self.cfg = cfg if cfg is not None else PPOConfig()
         self.actor_critic = actor_critic
+        self.backend = backend
         self.learning_rate = float(self.cfg.learning_rate)
         self.optimizer = torch.optim.Adam(actor_critic.parameters(), lr=self.learning_rate)
         self.last_terms = None
+        self._handle, self._max_rows, self._bound, self._storage_ptrs, self._ac_ptrs = None, 0, None, None, None
+        self.lr_device, self.record_lr, self.lr_trace = None, False, None       # record_lr (for tests): keep the rate after every decision in lr_trace
+        if backend == "hip":
+            _need_gpu('PPO(backend="hip")', actor_critic.std)
+            group = self.optimizer.param_groups[0]
+            if group["amsgrad"] or group["weight_decay"] != 0 or group["maximize"]:
+                raise ValueError("the device update restates plain Adam: no amsgrad, weight decay or maximize")
+            update_lib()
+            self.lr_device = torch.full((1,), self.learning_rate, dtype=torch.float64, device=actor_critic.std.device)
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h and _lib is not None and _lib._LIB is not None:
+            _lib._LIB.mpc_ppo_update_destroy(h)
+            self._handle = None
 
     def adapt_learning_rate(self, kl_mean):
         """The adaptive schedule: lr / 1.5 (not below 1e-5) if kl > 2 desired_kl, lr * 1.5 (not above 1e-2) if 0 < kl < desired_kl / 2."""
@@ -320,9 +371,120 @@ class PPO:
             value_loss = (returns - value).pow(2).mean()
         return surrogate, value_loss, entropy.mean(), kl
 
-    def update(self, storage):
-        """One update over the storage: num_learning_epochs x num_mini_batches Adam steps.  The only host read per mini-batch is the kl of the
-        adaptive schedule (as in rsl_rl).  Returns device tensors (mean value loss, mean surrogate loss)."""
+    # ---- the device update ----------------------------------------------------------------------------------------------------------
+    def set_learning_rate(self, lr):
+        """Sets the learning rate everywhere it lives: here, in the param groups and (hip backend) on the device."""
+        self.learning_rate = float(lr)
+        for group in self.optimizer.param_groups:
+            group["lr"] = self.learning_rate
+        if self.lr_device is not None:
+            self.lr_device.fill_(self.learning_rate)
+
+    def sync_learning_rate(self, lr=None):
+        """hip backend: ``learning_rate`` and the param groups' ``lr`` from the device value (``lr``: that value if the caller has fetched it
+        already, otherwise it is read here, which waits for the device)."""
+        self.learning_rate = float(self.lr_device.item() if lr is None else lr)
+        for group in self.optimizer.param_groups:
+            group["lr"] = self.learning_rate
+
+    def _device_state(self, rows):
+        """The handle, sized for ``rows`` and bound to the current addresses of the gradients and moments (created here, on the first step, as
+        torch creates them); returns the common step count."""
+        ac = self.actor_critic
+        dev = ac.std.device
+        ac._ready("PPO.update", torch.empty((1, ac.num_obs), dtype=torch.float32, device=dev))
+        params = ac.bind_order()
+        steps = set()
+        for p in params:
+            st = self.optimizer.state[p]
+            if len(st) == 0:                                                      # torch.optim.Adam._init_group
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            elif st["step"].is_cuda:                                             # (a checkpoint loaded with map_location: one read, then it is the host's)
+                st["step"] = st["step"].cpu()
+            steps.add(int(st["step"]))
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        if len(steps) != 1:
+            raise ValueError("the device update steps every parameter together: the optimiser's step counts differ")
+        if self._handle is None or rows > self._max_rows or self._ac_ptrs != ac._bound_ptrs:
+            if self._handle is not None:
+                update_lib().mpc_ppo_update_destroy(self._handle)
+                self._handle = None
+            h = C.c_void_p()
+            with torch.cuda.device(dev):
+                check(update_lib().mpc_ppo_update_create(C.byref(h), ac._handle, int(rows)), "mpc_ppo_update_create")
+            self._handle, self._max_rows, self._bound, self._storage_ptrs, self._ac_ptrs = h, int(rows), None, None, ac._bound_ptrs
+        tensors = [[p.grad for p in params], [self.optimizer.state[p]["exp_avg"] for p in params], [self.optimizer.state[p]["exp_avg_sq"] for p in params]]
+        ptrs = tuple(tuple(t.data_ptr() for t in ts) for ts in tensors)
+        if ptrs != self._bound:
+            for ts in tensors:
+                for t, p in zip(ts, params):
+                    if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.shape != p.shape:
+                        raise ValueError("gradients and Adam's moments must be contiguous float32 tensors shaped like their parameters, on their device")
+            arr = lambda v: C.cast((C.c_void_p * len(v))(*v), C.c_void_p)
+            check(update_lib().mpc_ppo_update_bind(self._handle, arr(ptrs[0]), arr(ptrs[1]), arr(ptrs[2])), "mpc_ppo_update_bind")
+            self._bound = ptrs
+        return steps.pop()
+
+    def _update_hip(self, storage, indices=None):
+        c = self.cfg
+        dev = self.actor_critic.std.device
+        _need_gpu("PPO.update", storage.observations, self.actor_critic.std)
+        if storage.device != dev:
+            raise _lib.MpcLibraryError("PPO.update: the storage and the parameters live on different devices")
+        total = storage.n * storage.T
+        size = total // c.num_mini_batches
+        if size < 1:
+            raise ValueError("fewer rows than mini-batches")
+        if indices is None:
+            indices = torch.randperm(c.num_mini_batches * size, device=dev)
+        _i64(indices, c.num_mini_batches * size, "indices")
+        step = self._device_state(size)
+        L = update_lib()
+        flat = (storage.observations, storage.actions, storage.values, storage.advantages, storage.returns, storage.actions_log_prob, storage.mu, storage.sigma)
+        widths = (self.actor_critic.num_obs, NUM_ACTIONS, 1, 1, 1, 1, NUM_ACTIONS, NUM_ACTIONS)
+        ptrs = tuple(_f32(t, total * w, "storage").data_ptr() for t, w in zip(flat, widths))
+        if ptrs != self._storage_ptrs:
+            check(L.mpc_ppo_update_set_storage(self._handle, total, *ptrs), "mpc_ppo_update_set_storage")
+            self._storage_ptrs = ptrs
+        adaptive = c.desired_kl is not None and c.schedule == "adaptive"
+        group = self.optimizer.param_groups[0]
+        beta1, beta2 = group["betas"]
+        k = c.num_learning_epochs * c.num_mini_batches
+        terms = torch.empty((k, 4), dtype=torch.float32, device=dev)
+        if self.record_lr:
+            self.lr_trace = torch.empty(k, dtype=torch.float64, device=dev)
+        stream = _stream(dev)
+        params = self.actor_critic.bind_order()
+        with torch.cuda.device(dev):
+            for e in range(c.num_learning_epochs):
+                for i in range(c.num_mini_batches):
+                    j = e * c.num_mini_batches + i
+                    check(L.mpc_ppo_update_grads(self._handle, size, indices.data_ptr() + 8 * i * size, float(c.clip_param), float(c.value_loss_coef),
+                                                 float(c.entropy_coef), int(bool(c.use_clipped_value_loss)), int(adaptive),
+                                                 float(c.desired_kl) if adaptive else 0.0, self.lr_device.data_ptr(), terms[j].data_ptr(), stream),
+                          "mpc_ppo_update_grads")
+                    if self.record_lr:
+                        self.lr_trace[j:j + 1].copy_(self.lr_device)
+                    step += 1
+                    check(L.mpc_ppo_update_apply(self._handle, float(c.max_grad_norm), float(beta1), float(beta2), float(group["eps"]), step,
+                                                 self.lr_device.data_ptr(), stream), "mpc_ppo_update_apply")
+        for p in params:
+            self.optimizer.state[p]["step"] += float(k)                          # (host tensors: no device work)
+        self.last_terms = tuple(terms[k - 1, q] for q in range(4))
+        storage.clear()
+        return terms[:, 1].mean(), terms[:, 0].mean()
+
+    def update(self, storage, indices=None):
+        """One update over the storage: num_learning_epochs x num_mini_batches Adam steps.  Returns device tensors (mean value loss, mean
+        surrogate loss).  torch backend: the only host read per mini-batch is the kl of the adaptive schedule (as in rsl_rl).  hip backend: no host
+        read at all; ``indices`` (for tests) replaces the ``torch.randperm`` over the num_mini_batches * (T N // num_mini_batches) rows."""
+        if self.backend == "hip":
+            return self._update_hip(storage, indices)
+        if indices is not None:
+            raise ValueError("indices are taken by the hip backend only")
         c = self.cfg
         mean_value, mean_surrogate, k = 0.0, 0.0, 0
         for batch in storage.mini_batch_generator(c.num_mini_batches, c.num_learning_epochs):
@@ -348,7 +510,7 @@ class PPOTrainer:
     the host or waits for the device -- and ``PPO.update``.  ``seed`` seeds torch's global generator (weight initialisation, the update's
     ``randperm``), as the reference's train.py does, and the exploration noise."""
 
-    def __init__(self, env, cfg=None, seed=1, device=None):
+    def __init__(self, env, cfg=None, seed=1, device=None, update="torch"):
         if not torch.cuda.is_available():
             raise _lib.MpcLibraryError("PPOTrainer needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
         self.cfg = cfg if cfg is not None else PPOConfig()
@@ -357,7 +519,7 @@ class PPOTrainer:
         torch.manual_seed(self.seed)
         c = self.cfg
         self.actor_critic = ActorCritic(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std).to(self.device)
-        self.alg = PPO(self.actor_critic, c)
+        self.alg = PPO(self.actor_critic, c, backend=update)
         self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions)
         self.iteration, self.tick, self.obs = 0, 0, None
         self.infos = []
@@ -388,7 +550,12 @@ class PPOTrainer:
             self.collect()
             mean_reward, done_rate = self.storage.rewards.mean(), self.storage.dones.mean()
             value_loss, surrogate = self.alg.update(self.storage)
-            stats = torch.stack((mean_reward, done_rate, value_loss, surrogate, self.actor_critic.std.detach().mean())).tolist()
+            stats = torch.stack((mean_reward, done_rate, value_loss, surrogate, self.actor_critic.std.detach().mean()))
+            if self.alg.backend == "hip":                                        # the device's learning rate rides along in the one read
+                stats = torch.cat((stats.double(), self.alg.lr_device)).tolist()
+                self.alg.sync_learning_rate(stats[5])
+            else:
+                stats = stats.tolist()
             self.iteration += 1
             self.infos.append(dict(iter=self.iteration, mean_reward=stats[0], done_rate=stats[1], value_loss=stats[2], surrogate_loss=stats[3],
                                    mean_noise_std=stats[4], learning_rate=self.alg.learning_rate))
@@ -404,6 +571,8 @@ class PPOTrainer:
         self.actor_critic.load_state_dict(ck["model_state_dict"])      # (in place: the kernels keep reading the same addresses)
         if load_optimizer:
             self.alg.optimizer.load_state_dict(ck["optimizer_state_dict"])
+            if self.alg.backend == "hip":                                        # the device's copy of the learning rate follows the checkpoint's
+                self.alg.set_learning_rate(self.alg.optimizer.param_groups[0]["lr"])
         self.iteration = ck["iter"]
         self.infos = list(ck["infos"]) if ck.get("infos") else []
         return ck["infos"]

@@ -1,0 +1,237 @@
+"""The update half of a PPO iteration (csrc/ppo_update.h, include/mpc_ppo_update.h, rl_mpc_locomotion_amd.ppo.PPO(backend="hip")) on the CPU: the
+header's scalar arithmetic is compiled with g++ into a small shim and driven through ctypes, against float64 autograd and torch.optim.Adam; the
+ABI's symbols and argument checks; the kernels' resource usage.
+
+The tolerance is the project's rule (tests/test_ppo.py): a quantity may differ from the float64 reference by at most 4 x the distance of torch's own
+float32 evaluation from it, computed here on the same inputs.  A single scalar's distance is one draw of a rounding error and can be next to nothing,
+so scalars are pooled: the surrogate, the value loss and the entropy share the largest of their three relative gaps; the kl, whose terms cancel and
+whose relative gap is two orders larger, stands alone.  Whole tensors (hundreds of elements) are compared by their relative L2 distance."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import rl_mpc_locomotion_amd  # noqa: F401
+from rl_mpc_locomotion_amd import _lib, ppo as P
+from tests import ppo_update_ref as ref
+from tests.helpers import ROOT
+from tests.test_ppo import _filled_storage
+
+CSRC = os.path.join(ROOT, "rl-mpc-locomotion_amd", "csrc")
+HEADER = os.path.join(ROOT, "include", "mpc_ppo_update.h")
+HIPCC = "/opt/rocm/bin/hipcc"
+
+SHIM = r"""
+#include "ppo_update.h"
+using namespace ppo;
+extern "C" {
+// the head as the device runs it: head_row per row, float64 sums in row order; terms[4] = surrogate, value loss, mean entropy, mean kl
+void shim_head(int rows, float clip, float value_coef, float entropy_coef, int clipped, const float *mu, const float *V, const float *std,
+               const float *actions, const float *old_values, const float *adv, const float *ret, const float *old_logp, const float *old_mu,
+               const float *old_sigma, float *terms, float *dmu, float *dV, float *dstd) {
+  HeadCfg c{clip, value_coef, entropy_coef, clipped, 1.0f / (float)rows};
+  double s[3] = {0, 0, 0}, ds[kActions] = {0};
+  for (int r = 0; r < rows; ++r) {
+    HeadRow o;
+    head_row(c, mu + 12 * r, V[r], std, actions + 12 * r, old_values[r], adv[r], ret[r], old_logp[r], old_mu + 12 * r, old_sigma + 12 * r, o);
+    s[0] += o.surrogate; s[1] += o.value_loss; s[2] += o.kl;
+    for (int k = 0; k < kActions; ++k) { dmu[12 * r + k] = o.dmu[k]; ds[k] += o.dstd[k]; }
+    dV[r] = o.dv;
+  }
+  terms[0] = (float)(s[0] / rows); terms[1] = (float)(s[1] / rows); terms[2] = entropy_row(std); terms[3] = (float)(s[2] / rows);
+  for (int k = 0; k < kActions; ++k) dstd[k] = (float)ds[k] + entropy_dstd(entropy_coef, std[k]);
+}
+double shim_adapt_lr(double lr, double kl, double desired) { return adapt_lr(lr, kl, desired); }
+// clip_grad_norm_ + one Adam step over n elements, the norm as the device forms it (float64 sum of squares, rounded once)
+void shim_adam(int n, double max_norm, double lr, double beta1, double beta2, double eps, int step, float *p, float *g, float *m, float *v) {
+  double q = 0;
+  for (int i = 0; i < n; ++i) q += (double)g[i] * (double)g[i];
+  const float coef = clip_coef((float)sqrt(q), (float)max_norm);
+  AdamCfg c{beta1, beta2, eps, 1.0 - pow(beta1, (double)step), pow(1.0 - pow(beta2, (double)step), 0.5)};
+  for (int i = 0; i < n; ++i) adam_element(c, lr, coef, p[i], g[i], m[i], v[i]);
+}
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    d = tmp_path_factory.mktemp("ppo_update_shim")
+    src, so = d / "shim.cpp", d / "shim.so"
+    src.write_text(SHIM)
+    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, str(src), "-o", str(so)],
+                   check=True)
+    L = C.CDLL(str(so))
+    vp, ci, cf, cd = C.c_void_p, C.c_int, C.c_float, C.c_double
+    L.shim_head.argtypes = [ci, cf, cf, cf, ci] + [vp] * 14; L.shim_head.restype = None
+    L.shim_adapt_lr.argtypes = [cd, cd, cd]; L.shim_adapt_lr.restype = cd
+    L.shim_adam.argtypes = [ci, cd, cd, cd, cd, cd, ci] + [vp] * 4; L.shim_adam.restype = None
+    return L
+
+
+def _head_torch(inputs, cfg, dtype):
+    """The head in torch with the mean, the value and std as leaves: (terms [4], d loss / d mu, / d V, / d std, clipped fractions)."""
+    mu, V, std, actions, old_values, adv, returns, old_logp, old_mu, old_sigma = (x.to(dtype) for x in inputs)
+    mu, V, std = mu.clone().requires_grad_(), V.clone().requires_grad_(), std.clone().requires_grad_()
+    dist = torch.distributions.Normal(mu, mu * 0. + std)
+    logp, entropy, sigma = dist.log_prob(actions).sum(dim=-1), dist.entropy().sum(dim=-1), dist.stddev
+    with torch.no_grad():
+        kl = torch.sum(torch.log(sigma / old_sigma + 1.e-5) + (torch.square(old_sigma) + torch.square(old_mu - mu)) / (2.0 * torch.square(sigma)) - 0.5,
+                       axis=-1).mean()
+    ratio = torch.exp(logp - torch.squeeze(old_logp))
+    a = torch.squeeze(adv)
+    surrogate = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - cfg.clip_param, 1.0 + cfg.clip_param)).mean()
+    if cfg.use_clipped_value_loss:
+        clipped = old_values + (V - old_values).clamp(-cfg.clip_param, cfg.clip_param)
+        value_loss = torch.max((V - returns).pow(2), (clipped - returns).pow(2)).mean()
+    else:
+        value_loss = (returns - V).pow(2).mean()
+    (surrogate + cfg.value_loss_coef * value_loss - cfg.entropy_coef * entropy.mean()).backward()
+    frac = (float(((ratio - 1).abs() > cfg.clip_param).double().mean()), float(((V - old_values).abs() > cfg.clip_param).double().mean()))
+    return [float(x.detach()) for x in (surrogate, value_loss, entropy.mean(), kl)], mu.grad, V.grad, std.grad, frac
+
+
+def check_terms(got, t32, t64, what):
+    """The four terms under the pooled rule of the module docstring; returns the largest ratio error / gap."""
+    rel = lambda x, r: abs(x - r) / abs(r)
+    gap3 = max(rel(t32[q], t64[q]) for q in range(3))
+    gap_kl = rel(t32[3], t64[3])
+    worst = 0.0
+    for q, name in enumerate(("surrogate", "value loss", "entropy", "kl")):
+        gap = gap_kl if q == 3 else gap3
+        err = rel(got[q], t64[q])
+        print(f"{what}: {name} {got[q]:.9g} float64 {t64[q]:.9g}: off by {err:.3e} (bound {4 * gap:.3e})")
+        assert gap > 0 and err <= 4 * gap, f"{what}: {name} off by {err:.3e} > {4 * gap:.3e}"
+        worst = max(worst, err / gap)
+    return worst
+
+
+@pytest.mark.parametrize("clipped_value", (True, False))
+def test_head_matches_float64_autograd(shim, clipped_value):
+    torch.manual_seed(5)
+    cfg = P.PPOConfig(actor_hidden_dims=(32, 16), critic_hidden_dims=(64,), init_noise_std=0.7, use_clipped_value_loss=clipped_value, value_loss_coef=0.8)
+    ac = P.ActorCritic(48, 12, cfg.actor_hidden_dims, cfg.critic_hidden_dims, cfg.init_noise_std)
+    st = _filled_storage(ac, n=65, T=6, seed=6)
+    obs = st.observations.flatten(0, 1)
+    with torch.no_grad():
+        big = ref.clone(ac, torch.float64)
+        mu, V = big.actor(obs.double()).float(), big.critic(obs.double()).float()      # one float32 mean and value for all three evaluations
+        std = ac.std.detach() * torch.linspace(0.8, 1.3, 12)
+    inputs = [mu, V, std] + [getattr(st, f).flatten(0, 1) for f in ("actions", "values", "advantages", "returns", "actions_log_prob", "mu", "sigma")]
+    t64, dmu64, dV64, dstd64, frac = _head_torch(inputs, cfg, torch.float64)
+    t32, dmu32, dV32, dstd32, _ = _head_torch(inputs, cfg, torch.float32)
+    assert 0.05 < frac[0] < 0.95 and 0.05 < frac[1] < 0.95, frac                     # both branches of both clips are taken
+    rows = mu.shape[0]
+    a = lambda t: np.ascontiguousarray(t.detach().numpy(), dtype=np.float32)
+    arrs = [a(x) for x in inputs]
+    terms, dmu, dV, dstd = np.zeros(4, np.float32), np.zeros((rows, 12), np.float32), np.zeros((rows, 1), np.float32), np.zeros(12, np.float32)
+    shim.shim_head(rows, cfg.clip_param, cfg.value_loss_coef, cfg.entropy_coef, int(clipped_value), *[x.ctypes.data for x in arrs], terms.ctypes.data,
+                   dmu.ctypes.data, dV.ctypes.data, dstd.ctypes.data)
+    check_terms([float(x) for x in terms], t32, t64, "host head")
+    for name, got, g32, g64 in (("d mu", dmu, dmu32, dmu64), ("d V", dV, dV32, dV64), ("d std", dstd, dstd32, dstd64)):
+        gap, err = ref.rel_l2(g32, g64), ref.rel_l2(torch.from_numpy(got), g64)
+        print(f"host head: {name} off by {err:.3e} (bound {4 * gap:.3e})")
+        assert gap > 0 and err <= 4 * gap, (name, err, gap)
+    # a row outside a clip has no gradient through it, exactly
+    assert (dmu[(dmu64 == 0).all(-1).numpy()] == 0).all() and (dV[(dV64 == 0).numpy()] == 0).all()
+
+
+def test_lr_rule_is_adapt_learning_rate_bit_for_bit(shim):
+    ac = P.ActorCritic(48, 12, (16,), (16,))
+    for desired in (0.01, 0.06, 1.0):
+        alg = P.PPO(ac, P.PPOConfig(desired_kl=desired))
+        lr = alg.learning_rate
+        scale = desired / 0.01
+        kls = [0.021, 0.0049, 0.01, 0.005, 0.02, 0.0, -1e-9] + [1.0] * 40 + [1e-6] * 40 + [0.021] * 3
+        seen = set()
+        for kl in kls:
+            kl = kl * scale
+            alg.adapt_learning_rate(kl)
+            lr = shim.shim_adapt_lr(lr, kl, desired)
+            assert lr == alg.learning_rate, (kl, lr, alg.learning_rate)
+            seen.add(lr)
+        assert 1e-5 in seen and 1e-2 in seen and len(seen) > 10
+
+
+def test_adam_element_matches_torch_adam(shim):
+    g = torch.Generator().manual_seed(3)
+    n = 300
+    p0 = torch.randn(n, generator=g) * 0.1
+    grads = [torch.randn(n, generator=g) * s for s in (0.05, 0.5, 0.02)]                # norms 0.9, 8.7, 0.35: max_norm 0.5 clips two of three
+    for max_norm in (0.5, 1e3):
+        runs = {}
+        for dtype in (torch.float32, torch.float64):
+            p = torch.nn.Parameter(p0.to(dtype).clone())
+            opt = torch.optim.Adam([p], lr=1e-3 / 1.5)
+            out = []
+            for gr in grads:
+                p.grad = gr.to(dtype).clone()
+                torch.nn.utils.clip_grad_norm_([p], max_norm)
+                opt.step()
+                out.append((p.detach().clone() - p0.to(dtype), opt.state[p]["exp_avg"].clone(), opt.state[p]["exp_avg_sq"].clone()))
+            runs[dtype] = out
+        p, m, v = p0.numpy().copy(), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        gaps, errs = [], []
+        for step, gr in enumerate(grads, 1):
+            gbuf = gr.numpy().copy()
+            shim.shim_adam(n, max_norm, 1e-3 / 1.5, 0.9, 0.999, 1e-8, step, p.ctypes.data, gbuf.ctypes.data, m.ctypes.data, v.ctypes.data)
+            for got, r32, r64 in zip((torch.from_numpy(p) - p0, torch.from_numpy(m), torch.from_numpy(v)), runs[torch.float32][step - 1], runs[torch.float64][step - 1]):
+                gaps.append(ref.rel_l2(r32, r64)); errs.append(ref.rel_l2(got, r64))
+        print(f"host adam, max_norm {max_norm}: errors {max(errs):.3e}, largest gap {max(gaps):.3e}")
+        assert max(gaps) > 0 and max(errs) <= 4 * max(gaps), (errs, gaps)
+
+
+def test_abi_symbols_and_argument_checks():
+    names = sorted(set(re.findall(r"\b(mpc_ppo_update_[a-z_]+)\s*\(", open(HEADER).read())))
+    assert names == sorted(P.UPDATE_SYMBOLS)
+    assert not set(names) & set(_lib.SYMBOLS) and not set(names) & set(P.SYMBOLS)
+    L = P.update_lib()
+    for s in P.UPDATE_SYMBOLS:
+        assert getattr(L, s).argtypes is not None, s
+    E_ARG = -1
+    ints = lambda v: C.cast((C.c_int * len(v))(*v), C.c_void_p)
+    ac, h = C.c_void_p(), C.c_void_p()
+    assert P.lib().mpc_ac_create(C.byref(ac), 2, ints([48, 32, 12]), 2, ints([48, 16, 1])) == 0
+    assert L.mpc_ppo_update_create(None, ac, 64) == E_ARG and L.mpc_ppo_update_create(C.byref(h), None, 64) == E_ARG
+    assert L.mpc_ppo_update_create(C.byref(h), ac, 0) == E_ARG and b"max_rows" in L.mpc_ppo_last_error()
+    assert L.mpc_ppo_update_create(C.byref(h), ac, 64) == E_ARG and b"bound" in L.mpc_ppo_last_error()      # binding is what needs the device
+    assert not h.value
+    p = 0x1000
+    assert L.mpc_ppo_update_tensors(None) == -1
+    assert L.mpc_ppo_update_bind(None, p, p, p) == E_ARG
+    assert L.mpc_ppo_update_set_storage(None, 8, p, p, p, p, p, p, p, p) == E_ARG
+    assert L.mpc_ppo_update_grads(None, 8, p, 0.2, 1.0, 0.01, 1, 1, 0.01, p, p, None) == E_ARG and b"mpc_ppo_update_grads" in L.mpc_ppo_last_error()
+    assert L.mpc_ppo_update_apply(None, 1.0, 0.9, 0.999, 1e-8, 1, p, None) == E_ARG and b"mpc_ppo_update_apply" in L.mpc_ppo_last_error()
+    L.mpc_ppo_update_destroy(None)
+    P.lib().mpc_ac_destroy(ac)
+
+
+def test_hip_backend_raises_without_a_gpu(monkeypatch):
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    ac = P.ActorCritic(48, 12, (16,), (16,))
+    with pytest.raises(_lib.MpcLibraryError):
+        P.PPO(ac, P.PPOConfig(), backend="hip")
+    with pytest.raises(ValueError):
+        P.PPO(ac, P.PPOConfig(), backend="triton")
+    assert P.PPO(ac).backend == "torch" and P.PPO(ac, P.PPOConfig(), "torch").lr_device is None
+
+    class Env:
+        num_envs, num_obs, num_actions = 4, 48, 12
+    with pytest.raises(_lib.MpcLibraryError):
+        P.PPOTrainer(Env(), update="hip")
+
+
+def test_kernels_compile_for_gfx950_without_scratch(tmp_path):
+    out = tmp_path / "mpc_ppo_update.o"
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
+                        "-c", os.path.join(CSRC, "mpc_ppo_update.hip"), "-o", str(out)], check=True, capture_output=True, text=True)
+    found = {}
+    for name, scratch in re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stderr, re.S):
+        found[name] = int(scratch)
+    assert len(found) >= 11 and all(s == 0 for s in found.values()), found           # six GEMM instances and five other kernels
+    for kernel in ("gemm_kernel", "reduce_kernel", "head_kernel", "head_reduce_kernel", "norm_kernel", "adam_kernel"):
+        assert any(kernel in k for k in found), (kernel, found)

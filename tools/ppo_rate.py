@@ -1,11 +1,12 @@
 """What a PPO iteration costs: 4096 Aliengo robots trotting, h = 10, T = 24, the reference's nets (48-512-256-128-12 / -1).
 Per tick, from HIP events (median over ticks x repeats): `ActorCritic.act` (one launch), `RolloutStorage.add` (the observation copy + one kernel); per
-iteration: `evaluate` + `compute_returns`, the whole 24-tick collection with `BatchedRLTask.step` inside, 24 bare `step`s, the torch update, one
-full iteration.  In the same call, alternating repeat by repeat, the TORCH COMPOSITION of the collection half on the same buffers: the two
+iteration: `evaluate` + `compute_returns`, the whole 24-tick collection with `BatchedRLTask.step` inside, 24 bare `step`s, the update with each
+backend (torch autograd + Adam, and the device update of include/mpc_ppo_update.h: `PPO(backend="hip")`) and one full iteration with each, the two
+backends alternating repeat by repeat on the same actor-critic and storage.  In the same call, alternating repeat by repeat, the TORCH COMPOSITION of the collection half on the same buffers: the two
 nn.Sequential, Normal(...).sample / log_prob, the storage copies, the time-out bootstrap and rsl_rl's GAE loop.  The shader clock is recorded as
 bench.py --full records it (device_state).
-    python tools/ppo_rate.py [--repeats 7] [--out profiles/r09_ppo.json]
-The kernel-trace stats: rocprofv3 --kernel-trace --stats ... -- python tools/ppo_rate.py --quick   (3 collections and one update)"""
+    python tools/ppo_rate.py [--repeats 7] [--out profiles/r10_ppo_update.json]
+The kernel-trace stats: rocprofv3 --kernel-trace --stats ... -- python tools/ppo_rate.py --quick   (3 collections and one update per backend)"""
 import argparse
 import json
 import os
@@ -18,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rl_mpc_locomotion_amd  # noqa: E402,F401
 from rl_mpc_locomotion_amd import _lib  # noqa: E402
-from rl_mpc_locomotion_amd.ppo import PPOConfig, PPOTrainer, RolloutStorage  # noqa: E402
+from rl_mpc_locomotion_amd.ppo import PPO, PPOConfig, PPOTrainer, RolloutStorage  # noqa: E402
 from rl_mpc_locomotion_amd.rl_task import BatchedRLTask, TaskConfig  # noqa: E402
 
 TROT = 0
@@ -91,10 +92,14 @@ if __name__ == "__main__":
     env = make_env(n, dev)
     trainer = PPOTrainer(env, cfg, seed=1)
     ac, st = trainer.actor_critic, trainer.storage
+    # the device update on the same actor-critic, with an optimiser of its own
+    algs = {"torch": trainer.alg, "hip": PPO(ac, cfg, backend="hip")}
     if args.quick:
         for _ in range(3):
             trainer.collect()
-        trainer.alg.update(st)
+        for alg in algs.values():
+            st.step = st.T
+            alg.update(st)
         torch.cuda.synchronize()
         sys.exit(0)
     from bench import device_state  # noqa: E402
@@ -104,6 +109,9 @@ if __name__ == "__main__":
     st_torch = RolloutStorage(n, T, dev)
     # warm-up: cold solves, code objects, torch's kernels and its GEMM choices, Adam's state
     trainer.learn(2)
+    for _ in range(2):
+        st.step = st.T
+        algs["hip"].update(st)
     obs = trainer.obs
     _, rew, reset, extras = env.step(st.actions[0])
     time_outs = extras["time_outs"]
@@ -113,7 +121,8 @@ if __name__ == "__main__":
     torch.cuda.synchronize()
 
     t_act, t_add, t_ret, t_tact, t_tadd, t_tret, t_collect, t_steps, t_update, t_iter = ([] for _ in range(10))
-    for _ in range(args.repeats):
+    t_backend = {k: {"collect": [], "update": [], "full": []} for k in algs}
+    for rep in range(args.repeats):
         # the pieces on fixed inputs (the environment's current buffers), fused and torch alternating
         for fused in (True, False):
             e = [[ev() for _ in range(3)] for _ in range(T)]
@@ -143,25 +152,36 @@ if __name__ == "__main__":
             (t_add if fused else t_tadd).extend(x[1].elapsed_time(x[2]) for x in e)
             (t_ret if fused else t_tret).append(r0.elapsed_time(r1))
         st.clear()
-        # the whole iteration, and T bare steps of the environment
-        a, b, c, d, f = ev(), ev(), ev(), ev(), ev()
-        a.record()
-        trainer.collect()
-        b.record()
-        trainer.alg.update(st)
-        c.record()
-        torch.cuda.synchronize()
+        # the whole iteration with each backend (which one goes first alternates), and T bare steps of the environment
+        for name in (("torch", "hip") if rep % 2 == 0 else ("hip", "torch")):
+            a, b, c = ev(), ev(), ev()
+            a.record()
+            trainer.collect()
+            b.record()
+            algs[name].update(st)
+            c.record()
+            torch.cuda.synchronize()
+            tb = t_backend[name]
+            tb["collect"].append(a.elapsed_time(b)); tb["update"].append(b.elapsed_time(c)); tb["full"].append(a.elapsed_time(c))
+        t_collect.append(t_backend["torch"]["collect"][-1]); t_update.append(t_backend["torch"]["update"][-1]); t_iter.append(t_backend["torch"]["full"][-1])
+        d, f = ev(), ev()
         d.record()
         for t in range(T):
             env.step(st.actions[t])
         f.record()
         torch.cuda.synchronize()
         trainer.obs = env.obs_buf
-        t_collect.append(a.elapsed_time(b)); t_update.append(b.elapsed_time(c)); t_iter.append(a.elapsed_time(c)); t_steps.append(d.elapsed_time(f))
+        t_steps.append(d.elapsed_time(f))
     res["fused"] = {"act": stats(t_act), "add_with_observation_copy": stats(t_add), "evaluate_and_compute_returns": stats(t_ret)}
     res["torch_composition"] = {"act": stats(t_tact), "add": stats(t_tadd), "evaluate_and_compute_returns": stats(t_tret)}
     res["iteration"] = {"collection_24_ticks": stats(t_collect), "bare_24_steps": stats(t_steps), "update": stats(t_update), "full": stats(t_iter)}
     m = lambda x: float(np.median(x))
+    ut, uh = stats(t_backend["torch"]["update"]), stats(t_backend["hip"]["update"])
+    res["update"] = {"torch": ut, "hip": uh, "hip_over_torch": uh["median_ms"] / ut["median_ms"], "hip_p90_below_torch_p10": uh["p90_ms"] < ut["p10_ms"],
+                     "per_mini_batch_ms": {"torch": ut["median_ms"] / res["mini_batches_per_update"], "hip": uh["median_ms"] / res["mini_batches_per_update"]}}
+    res["iteration_hip"] = {k: stats(v) for k, v in t_backend["hip"].items()}
+    res["update_share_of_iteration_hip"] = m(t_backend["hip"]["update"]) / m(t_backend["hip"]["full"])
+    res["robot_ticks_per_s_training_hip"] = n * T / (m(t_backend["hip"]["full"]) * 1e-3)
     tick_fused = np.array(t_act) + np.array(t_add)
     tick_torch = np.array(t_tact) + np.array(t_tadd)
     res["act_plus_add_per_tick"] = {"fused": stats(tick_fused), "torch": stats(tick_torch), "fused_over_torch": m(tick_fused) / m(tick_torch)}
