@@ -191,43 +191,21 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamTable t, ppo::AdamCfg cfg
 bool aligned16(const void *p) { return p && (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 int round16(int x) { return (x + 15) / 16 * 16; }
 
+// the plan (tile, backward-weight chunking, grid) is ppo_gemm_plan.h's; this fills it into the launch and starts the instantiation it names
 template <int KIND>
 int launch_gemm(pgemm::Launch &L, hipStream_t s) {
-  // backward weight: the largest chunk of 1024, 512, 256 rows that gives the chip two workgroups per CU (a chunk's workgroup walks its rows alone)
-  if (KIND == pgemm::kBackwardWeight) {
-    int rows_per = pgemm::kChunk;
-    for (;; rows_per /= 2) {
-      long long wgs = 0;
-      for (auto &p : L.p)
-        if (p.M > 0) wgs += (long long)((p.M + 127) / 128) * ((p.N + 63) / 64) * ((p.K + rows_per - 1) / rows_per);
-      if (wgs >= 512 || rows_per == pgemm::kMinChunk) break;
-    }
-    for (auto &p : L.p) {
-      p.chunk_rows = rows_per;
-      p.chunks = p.M > 0 ? (p.K + rows_per - 1) / rows_per : 1;
-    }
+  const pgemm::Shape shape[2] = {{L.p[0].M, L.p[0].N, L.p[0].K}, {L.p[1].M, L.p[1].N, L.p[1].K}};
+  const pgemm::Plan plan = pgemm::plan_gemm(KIND, shape);
+  for (int k = 0; k < 2; ++k) {
+    pgemm::Problem &p = L.p[k];
+    p.tiles_m = plan.p[k].tiles_m;
+    p.tiles_n = plan.p[k].tiles_n;
+    p.chunks = plan.p[k].chunks;
+    if (KIND == pgemm::kBackwardWeight) p.chunk_rows = plan.chunk_rows;
   }
-  // 128 x 128 tiles where every problem's columns fill them and there is a tile for every CU; 128 x 64 otherwise
-  bool wide = true;
-  long long tiles128 = 0;
-  for (auto &p : L.p) {
-    if (p.M <= 0) continue;
-    if (p.N % 128 != 0) wide = false;
-    tiles128 += (long long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.chunks;
-  }
-  if (tiles128 < 256) wide = false;
-  const int bn = wide ? 128 : 64;
-  unsigned gx = 0;
-  for (auto &p : L.p) {
-    if (p.M <= 0) { p.tiles_m = p.tiles_n = 0; p.chunks = 1; continue; }
-    p.tiles_m = (p.M + 127) / 128;
-    p.tiles_n = (p.N + bn - 1) / bn;
-    const unsigned g = (unsigned)(p.tiles_m * p.tiles_n * p.chunks);
-    gx = g > gx ? g : gx;
-  }
-  if (gx == 0) return MPC_OK;
-  if (wide) hipLaunchKernelGGL((pgemm::gemm_kernel<KIND, 2, 2>), dim3(gx, 2), dim3(pgemm::kThreads), 0, s, L);
-  else hipLaunchKernelGGL((pgemm::gemm_kernel<KIND, 2, 1>), dim3(gx, 2), dim3(pgemm::kThreads), 0, s, L);
+  if (plan.grid_x == 0) return MPC_OK;
+  if (plan.wide) hipLaunchKernelGGL((pgemm::gemm_kernel<KIND, 2, 2>), dim3(plan.grid_x, 2), dim3(pgemm::kThreads), 0, s, L);
+  else hipLaunchKernelGGL((pgemm::gemm_kernel<KIND, 2, 1>), dim3(plan.grid_x, 2), dim3(pgemm::kThreads), 0, s, L);
   UPD_TRY(hipGetLastError());
   return MPC_OK;
 }
@@ -366,7 +344,8 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int maxl = u->nl[0] > u->nl[1] ? u->nl[0] : u->nl[1];
 
-  // forward: layer l of both nets side by side
+  // forward: layer l of both nets side by side.  (tests/test_ppo_gemm_plan.py restates this sequence of launches and their (M, N, K), here and in the
+  // backward loop below, to pin which kernels the tests reach: a launch added, dropped or reshaped here has to be restated there)
   for (int l = 0; l < maxl; ++l) {
     pgemm::Launch L{};
     for (int k = 0; k < 2; ++k) {

@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ppo_gemm_plan.h"      // Kind, kChunk, kMinChunk and the launch plan (no HIP in it)
+
 namespace pgemm {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -24,10 +26,7 @@ constexpr int kThreads = 256;
 constexpr int kBK = 32;                // reduction rows per LDS tile
 constexpr int kKQ = kBK / 4;          // 16-byte loads along one row of a reduction-contiguous tile
 constexpr int kPad = 4;
-constexpr int kChunk = 1024;          // most rows per backward-weight chunk: the longest fp32 chain
-constexpr int kMinChunk = 256;        // fewest (a launch takes the largest of 1024, 512, 256 that gives the chip two workgroups per CU)
-
-enum Kind { kForward = 0, kBackwardData = 1, kBackwardWeight = 2 };
+// kChunk (most rows per backward-weight chunk: the longest fp32 chain) and kMinChunk (fewest: what sizes the workspace) are ppo_gemm_plan.h's
 
 struct Problem {
   const float *A, *B;                 // see the loaders below for each kind's layout

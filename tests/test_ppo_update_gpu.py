@@ -4,7 +4,11 @@ torch.optim.Adam in float64 on the CPU (tests/ppo_update_ref.py), on the same st
 The tolerance is the project's rule: at most 4 x the distance of torch's own float32 run from the float64 run, which this module computes.  The
 distance is pooled, because a single tensor's is one draw of a rounding error: gradients, parameter changes and moments are compared tensor by
 tensor in relative L2, each held to 4 x the largest per-tensor gap over all row-count cases (and mini-batches, steps) of the same net pair; the
-scalar terms as tests/test_ppo_update.py pools them, over the same cases.  Largest measured ratios error / gap: DESIGN.md section 8.3."""
+scalar terms as tests/test_ppo_update.py pools them, over the same cases.  Largest measured ratios error / gap: DESIGN.md section 8.3.
+
+Those row counts all plan the 128 x 64 tile and 256-row weight-gradient chunks (csrc/ppo_gemm_plan.h).  BIG_ROWS x BIG_NETS are the cases that reach what
+the training workload runs -- the 128 x 128 tile in all three kinds and chunks of 1024 and 512 rows -- with a pool of their own, so the cases above keep
+their gaps; tests/test_ppo_gemm_plan.py pins which kernel each of this module's shapes reaches."""
 import numpy as np
 import pytest
 import torch
@@ -20,18 +24,21 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NETS = {"reference": ((512, 256, 128), (512, 256, 128)), "uneven": ((32, 16), (64,)), "odd": ((80, 48), (144,))}
 ROWS = {"single": (1, 1, 1), "ragged": (65, 6, 4), "chunked": (65, 16, 1)}        # n, T, mini-batches: 1 row; 4 x 97 rows, 2 left out; 1040 rows
+BIG_NETS = {"reference": NETS["reference"], "square": ((256, 256), (256, 256))}
+BIG_ROWS = {"production": (3277, 5, 1)}                                           # 16 385 rows in one mini-batch: 17 chunks of 1024, 33 of 512, the last of 1 row
+ALL_NETS, ALL_ROWS = {**NETS, **BIG_NETS}, {**ROWS, **BIG_ROWS}
 DESIRED_KL = (0.01, 0.06, 1.0)                                                    # first-step kl 0.048 .. 0.076: down, unchanged, up
 
 
 def _cfg(nets, mini_batches=1, **kw):
-    return P.PPOConfig(actor_hidden_dims=NETS[nets][0], critic_hidden_dims=NETS[nets][1], init_noise_std=0.7, num_mini_batches=mini_batches, **kw)
+    return P.PPOConfig(actor_hidden_dims=ALL_NETS[nets][0], critic_hidden_dims=ALL_NETS[nets][1], init_noise_std=0.7, num_mini_batches=mini_batches, **kw)
 
 
 def _fixture(nets, rows):
     """(CPU actor-critic, CPU storage, injected permutation) as tests/test_ppo.py builds them."""
-    n, T, mb = ROWS[rows]
+    n, T, mb = ALL_ROWS[rows]
     torch.manual_seed(5)
-    ac = P.ActorCritic(48, 12, *NETS[nets], init_noise_std=0.7)
+    ac = P.ActorCritic(48, 12, *ALL_NETS[nets], init_noise_std=0.7)
     st = _filled_storage(ac, n=n, T=T, seed=6)
     size = n * T // mb
     perm = torch.randperm(n * T, generator=torch.Generator().manual_seed(7))[:mb * size].contiguous()
@@ -130,6 +137,92 @@ def test_grads_match_float64_autograd(grads_reference, nets, rows):
     alg.lr_device.fill_(1e-3)
     P.check(L.mpc_ppo_update_grads(alg._handle, size, idx.data_ptr(), 0.2, 1.0, 0.01, 1, 0, 0.0, None, terms.data_ptr(), None), "grads")
     assert float(alg.lr_device) == 1e-3
+
+
+@pytest.fixture(scope="module")
+def big_reference():
+    """Per net pair and BIG_ROWS case: the fixture and the float64 and float32 gradients and terms of its one mini-batch, computed once."""
+    cache = {}
+
+    def get(nets):
+        if nets not in cache:
+            cases = {}
+            for rows in BIG_ROWS:
+                assert BIG_ROWS[rows][2] == 1
+                ac, st, perm = _fixture(nets, rows)
+                cfg = _cfg(nets, 1, desired_kl=0.06)
+                cases[rows] = (ac, st, perm, ref.grads_of(ac, cfg, st, perm, torch.float64), ref.grads_of(ac, cfg, st, perm, torch.float32))
+            cache[nets] = cases
+        return cache[nets]
+    return get
+
+
+def _device_grads(alg, dst, perm, size):
+    """One mpc_ppo_update_grads over the first `size` rows of perm on alg's handle: (gradients, terms, learning rate) on the host."""
+    L = P.update_lib()
+    P.check(L.mpc_ppo_update_set_storage(alg._handle, dst.n * dst.T, *[getattr(dst, f).data_ptr() for f in ref.FIELDS]), "set_storage")
+    idx = perm.to(DEV)
+    terms = torch.zeros(4, device=DEV)
+    alg.lr_device.fill_(1e-3)
+    c = alg.cfg
+    P.check(L.mpc_ppo_update_grads(alg._handle, size, idx.data_ptr(), c.clip_param, c.value_loss_coef, c.entropy_coef, 1, 1, c.desired_kl,
+                                   alg.lr_device.data_ptr(), terms.data_ptr(), None), "grads")
+    return [p.grad.cpu().clone() for p in alg.actor_critic.bind_order()], terms.cpu().clone(), float(alg.lr_device)
+
+
+@pytest.mark.parametrize("rows", sorted(BIG_ROWS))
+@pytest.mark.parametrize("nets", sorted(BIG_NETS))
+def test_grads_on_the_production_plan_match_float64_autograd(big_reference, nets, rows):
+    """test_grads_match_float64_autograd's rule (desired_kl = 0.06) at a row count that plans the wide tile and the long chunks; the float32 gap is
+    pooled over the BIG_ROWS cases of this net pair only."""
+    cases = big_reference(nets)
+    gap = max(ref.rel_l2(g32, g64) for _, _, _, (g64s, _, _), (g32s, _, _) in cases.values() for g32, g64 in zip(g32s, g64s))
+    rel = lambda x, r: abs(x - r) / abs(r)
+    pool3 = max(rel(b[1][q], a[1][q]) for _, _, _, a, b in cases.values() for q in range(3))
+    pool_kl = max(rel(b[1][3], a[1][3]) for _, _, _, a, b in cases.values())
+    ac, st, perm, (g64s, t64, frac), _ = cases[rows]
+    assert 0.05 < frac[0] < 0.95 and 0.05 < frac[1] < 0.95, frac
+    dev, dst = _to_device(ac, st)
+    alg = P.PPO(dev, _cfg(nets, 1, desired_kl=0.06), backend="hip")
+    alg._device_state(len(perm))
+    got, terms, lr = _device_grads(alg, dst, perm, len(perm))
+    assert lr == ref.adapt(1e-3, t64[3], alg.cfg), t64[3]
+    for q, name in enumerate(("surrogate", "value loss", "entropy", "kl")):
+        g = pool_kl if q == 3 else pool3
+        err = rel(float(terms[q]), t64[q])
+        print(f"{nets} {rows}: {name} off by {err:.3e} (bound {4 * g:.3e}, ratio {err / g:.3f})")
+        assert g > 0 and err <= 4 * g, (name, err, g)
+    names = _names(ac)
+    for k in range(len(names)):
+        print(f"{nets} {rows}: {names[k]} off by {ref.rel_l2(got[k], g64s[k]):.3e}, its own float32 gap {ref.rel_l2(cases[rows][4][0][k], g64s[k]):.3e}")
+    _pooled([(names[k], ref.rel_l2(got[k], g64s[k]), gap) for k in range(len(names))], f"{nets} {rows}: gradients")
+
+
+@pytest.mark.parametrize("nets", sorted(BIG_NETS))
+def test_a_smaller_batch_on_a_used_handle_reads_no_stale_workspace(big_reference, nets):
+    """The 1040-row case on a handle that has just run 16 385 rows (rows < max_rows: the workspace still holds that run's longer activations and
+    more chunk partials) is bit-identical to the same call on a fresh handle made for 1040 rows."""
+    ac, st, perm, _, _ = big_reference(nets)["production"]
+    small_ac, small_st, small_perm = _fixture(nets, "chunked")
+    assert all(torch.equal(a, b) for a, b in zip(ac.bind_order(), small_ac.bind_order()))         # the same nets with the same weights
+    rows = len(small_perm)
+    assert rows == 1040 < len(perm)
+    dev, dst = _to_device(ac, st)
+    _, small_dst = _to_device(small_ac, small_st)
+    used = P.PPO(dev, _cfg(nets, 1, desired_kl=0.06), backend="hip")
+    used._device_state(len(perm))
+    handle = used._handle.value
+    _device_grads(used, dst, perm, len(perm))
+    used._device_state(rows)
+    assert used._handle.value == handle and used._max_rows == len(perm)                         # the handle of the large run, not a new one
+    a = _device_grads(used, small_dst, small_perm, rows)
+    fresh_dev, _ = _to_device(small_ac, small_st)
+    fresh = P.PPO(fresh_dev, _cfg(nets, 1, desired_kl=0.06), backend="hip")
+    fresh._device_state(rows)
+    assert fresh._max_rows == rows
+    b = _device_grads(fresh, small_dst, small_perm, rows)
+    assert all(torch.equal(x, y) for x, y in zip(a[0], b[0])) and torch.equal(a[1], b[1]) and a[2] == b[2]
+    assert all(float(g.abs().max()) > 0 for g in a[0])
 
 
 @pytest.fixture(scope="module")
