@@ -7,30 +7,22 @@
 #include <vector>
 
 #include "../../include/mpc_sim.h"
+#include "mpc_sim_internal.h"
 #include "toy_sim.h"
 
 using namespace toysim;
+using simint::DeviceGuard;
+using simint::kSimThreads;
+using simint::sim_grid;
 
 namespace {
 thread_local std::string g_serr;
 int sfail(int code, const std::string &m) { g_serr = m; return code; }
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
 #define SIM_TRY(expr)                                                                               \
   do {                                                                                              \
     hipError_t e_ = (expr);                                                                         \
     if (e_ != hipSuccess) return sfail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
-
-constexpr int kSimThreads = 64;      // one wave per workgroup: 4096 robots are 64 waves on 64 CUs
 
 struct SimArgs {
   int n;
@@ -63,7 +55,7 @@ __global__ __launch_bounds__(kSimThreads) void sim_init_kernel(SimArgs a, const 
   const int r = ids ? ids[i] : i;
   if (r < 0 || r >= a.n) return;
   State s;
-  toy_init(s, a.params[a.type[r]], a.yaw0[r], a.slope[2 * r], a.slope[2 * r + 1]);
+  toy_init(s, a.params[a.type[r]], a.yaw0[r], Plane{a.slope[2 * r], a.slope[2 * r + 1]});
   pack(s, a.f64 + r, a.i32 + r, a.n);
 }
 
@@ -101,16 +93,8 @@ __global__ __launch_bounds__(kSimThreads) void sim_flags_kernel(int n, const int
 }
 }  // namespace
 
-struct mpc_sim {
-  int n = 0, device = 0;
-  SimArgs a{};
-  double *d_f64 = nullptr;
-  int *d_i32 = nullptr, *d_type = nullptr;
-  double *d_slope = nullptr, *d_yaw = nullptr;
-  Params *d_params = nullptr;
-};
-
-static dim3 sim_grid(int k) { return dim3((unsigned)((k + kSimThreads - 1) / kSimThreads)); }
+// (struct mpc_sim: mpc_sim_internal.h)
+static SimArgs sim_args(const mpc_sim *s) { return SimArgs{s->n, s->dt, s->d_f64, s->d_i32, s->d_type, s->d_slope, s->d_yaw, s->d_params}; }
 
 extern "C" {
 
@@ -120,7 +104,7 @@ void mpc_sim_destroy(mpc_sim *s) {
   if (!s) return;
   DeviceGuard guard_(s->device);
   (void)hipDeviceSynchronize();
-  void *ptrs[] = {s->d_f64, s->d_i32, s->d_type, s->d_slope, s->d_yaw, s->d_params};
+  void *ptrs[] = {s->d_f64, s->d_i32, s->d_type, s->d_slope, s->d_yaw, s->d_params, s->d_heights, s->d_origin};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   delete s;
 }
@@ -143,6 +127,7 @@ int mpc_sim_create(mpc_sim **out, int n, const int *robot_type, int n_types, con
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sfail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device");
   mpc_sim *s = new mpc_sim();
   s->n = n;
+  s->dt = dt;
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return sfail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device"); }
   hipError_t e;
   if ((e = hipMalloc(&s->d_f64, sizeof(double) * kF64 * (size_t)n)) != hipSuccess || (e = hipMalloc(&s->d_i32, sizeof(int) * kI32 * (size_t)n)) != hipSuccess ||
@@ -155,8 +140,7 @@ int mpc_sim_create(mpc_sim **out, int n, const int *robot_type, int n_types, con
     mpc_sim_destroy(s);
     return sfail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
   }
-  s->a = SimArgs{n, dt, s->d_f64, s->d_i32, s->d_type, s->d_slope, s->d_yaw, s->d_params};
-  hipLaunchKernelGGL(sim_init_kernel, sim_grid(n), dim3(kSimThreads), 0, nullptr, s->a, (const int *)nullptr, n);
+  hipLaunchKernelGGL(sim_init_kernel, sim_grid(n), dim3(kSimThreads), 0, nullptr, sim_args(s), (const int *)nullptr, n);
   if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
     mpc_sim_destroy(s);
     return sfail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
@@ -170,7 +154,11 @@ int mpc_sim_size(mpc_sim *s) { return s ? s->n : 0; }
 int mpc_sim_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, void *stream) {
   if (!s || !d_tau) return sfail(MPC_E_ARG, "mpc_sim_step: bad argument");
   DeviceGuard guard_(s->device);
-  hipLaunchKernelGGL(sim_step_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), s->a, d_tau, d_dof, d_root);
+  if (s->d_heights) {                  // a terrain is attached (mpc_terrain_attach): the height-field instantiation
+    SIM_TRY(simint::terrain_launch_step(s, d_tau, d_dof, d_root, reinterpret_cast<hipStream_t>(stream)));
+    return MPC_OK;
+  }
+  hipLaunchKernelGGL(sim_step_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), sim_args(s), d_tau, d_dof, d_root);
   SIM_TRY(hipGetLastError());
   return MPC_OK;
 }
@@ -178,7 +166,7 @@ int mpc_sim_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, vo
 int mpc_sim_observe(mpc_sim *s, float *d_dof, float *d_root, void *stream) {
   if (!s || (!d_dof && !d_root)) return sfail(MPC_E_ARG, "mpc_sim_observe: bad argument");
   DeviceGuard guard_(s->device);
-  hipLaunchKernelGGL(sim_observe_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), s->a, d_dof, d_root);
+  hipLaunchKernelGGL(sim_observe_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), sim_args(s), d_dof, d_root);
   SIM_TRY(hipGetLastError());
   return MPC_OK;
 }
@@ -187,7 +175,11 @@ int mpc_sim_reset_device(mpc_sim *s, const int *d_ids, int k, void *stream) {
   if (!s || !d_ids || k < 0) return sfail(MPC_E_ARG, "mpc_sim_reset_device: bad argument");
   if (k == 0) return MPC_OK;
   DeviceGuard guard_(s->device);
-  hipLaunchKernelGGL(sim_init_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), s->a, d_ids, k);
+  if (s->d_heights) {
+    SIM_TRY(simint::terrain_launch_init(s, d_ids, k, reinterpret_cast<hipStream_t>(stream)));
+    return MPC_OK;
+  }
+  hipLaunchKernelGGL(sim_init_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), sim_args(s), d_ids, k);
   SIM_TRY(hipGetLastError());
   return MPC_OK;
 }

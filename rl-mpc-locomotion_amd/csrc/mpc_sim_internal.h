@@ -1,0 +1,46 @@
+// mpc_sim_internal.h -- what the library's other units may know of an mpc_sim (include/mpc_sim.h): its device buffers and, once
+// mpc_terrain_attach (include/mpc_terrain.h) has run, its height field.  mpc_sim.hip owns the handle and the plane kernels; mpc_terrain.hip
+// holds the height-field instantiations of toy_sim.h and is what mpc_sim_step / mpc_sim_reset_device launch for a sim with a terrain
+// (a host-side branch on the handle).  Not part of the C ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "toy_sim.h"
+
+struct mpc_sim {
+  int n = 0, device = 0;
+  double dt = 0.0;
+  double *d_f64 = nullptr;             // [kF64][n]
+  int *d_i32 = nullptr, *d_type = nullptr;
+  double *d_slope = nullptr, *d_yaw = nullptr;
+  toysim::Params *d_params = nullptr;  // [n_types]
+  // the terrain (null / 0 until mpc_terrain_attach): the sim's own copies
+  short *d_heights = nullptr;          // [rows][cols]
+  double *d_origin = nullptr;          // [n][2]
+  int rows = 0, cols = 0;
+  double hscale = 0.0, vscale = 0.0, x0 = 0.0, y0 = 0.0;
+};
+
+namespace simint {
+
+constexpr int kSimThreads = 64;        // one wave per workgroup: 4096 robots are 64 waves on 64 CUs
+
+inline dim3 sim_grid(int k) { return dim3((unsigned)((k + kSimThreads - 1) / kSimThreads)); }
+
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
+  DeviceGuard(const DeviceGuard &) = delete;
+  DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+
+// the terrain instantiations' launches (mpc_terrain.hip); the caller has set the device.  ids null = all n robots.
+hipError_t terrain_launch_init(mpc_sim *s, const int *d_ids, int k, hipStream_t stream);
+hipError_t terrain_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream);
+
+}  // namespace simint

@@ -1,0 +1,177 @@
+// mpc_terrain.hip -- the C ABI of include/mpc_terrain.h: toy_sim.h's HeightField instantiations of toy_init / toy_step on the device, one lane
+// per robot as in mpc_sim.hip, and a point query of the surface.  The field is int16 in HBM, read with plain 2-byte loads (four per lookup): a
+// 500 x 500 field is 500 KB and stays in the caches.  mpc_sim.hip owns the handle (mpc_sim_internal.h) and launches these through
+// simint::terrain_launch_* once a terrain is attached.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/mpc_terrain.h"
+#include "mpc_sim_internal.h"
+#include "toy_sim.h"
+
+using namespace toysim;
+using simint::DeviceGuard;
+using simint::kSimThreads;
+using simint::sim_grid;
+
+namespace {
+thread_local std::string g_terr;
+int tfail(int code, const std::string &m) { g_terr = m; return code; }
+#define TERRAIN_TRY(expr)                                                                           \
+  do {                                                                                              \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess) return tfail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+struct TerrainArgs {
+  int n;
+  double dt;
+  double *f64;                       // [kF64][n]
+  int *i32;                          // [kI32][n]
+  const int *type;                   // [n]
+  const double *yaw0;                // [n]
+  const Params *params;              // [n_types]
+  const double *origin;              // [n][2]
+  const short *h;                    // [rows][cols]
+  int rows, cols;
+  double hscale, vscale, x0, y0;
+};
+
+__device__ __forceinline__ HeightField field_of(const TerrainArgs &a, int r) {
+  return HeightField{a.h, a.rows, a.cols, a.hscale, a.vscale, a.x0, a.y0, a.origin[2 * r], a.origin[2 * r + 1]};
+}
+
+__device__ __forceinline__ void write_obs(const State &s, int r, float *dof, float *root) {
+  float d[24], b[13];
+  observe(s, d, b);
+  if (dof) {
+#pragma unroll
+    for (int i = 0; i < 24; ++i) dof[(size_t)r * 24 + i] = d[i];
+  }
+  if (root) {
+#pragma unroll
+    for (int i = 0; i < 13; ++i) root[(size_t)r * 13 + i] = b[i];
+  }
+}
+
+// (re)initialise robots ids[0 .. k) (all n when ids is null) standing on the terrain
+__global__ __launch_bounds__(kSimThreads) void terrain_init_kernel(TerrainArgs a, const int *ids, int k) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  const int r = ids ? ids[i] : i;
+  if (r < 0 || r >= a.n) return;
+  State s;
+  toy_init(s, a.params[a.type[r]], a.yaw0[r], field_of(a, r));
+  pack(s, a.f64 + r, a.i32 + r, a.n);
+}
+
+__global__ __launch_bounds__(kSimThreads) void terrain_step_kernel(TerrainArgs a, const float *__restrict__ tau, float *dof, float *root) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.n) return;
+  State s;
+  unpack(s, a.f64 + r, a.i32 + r, a.n);
+  if (!s.fell) {
+    double t[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) t[i] = (double)tau[(size_t)r * 12 + i];
+    toy_step(s, a.params[a.type[r]], t, a.dt, field_of(a, r));
+    pack(s, a.f64 + r, a.i32 + r, a.n);
+  }
+  write_obs(s, r, dof, root);
+}
+
+// the surface at k points of the terrain's own frame
+__global__ __launch_bounds__(kSimThreads) void terrain_query_kernel(TerrainArgs a, const double *__restrict__ xy, int k, double *z, double *normal) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  const HeightField g{a.h, a.rows, a.cols, a.hscale, a.vscale, a.x0, a.y0, 0.0, 0.0};
+  const double p[2] = {xy[2 * (size_t)i], xy[2 * (size_t)i + 1]};
+  z[i] = g.height(p);
+  if (normal) {
+    double nn[3];
+    g.normal(p, nn);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) normal[3 * (size_t)i + j] = nn[j];
+  }
+}
+
+TerrainArgs terrain_args(const mpc_sim *s) {
+  return TerrainArgs{s->n, s->dt, s->d_f64, s->d_i32, s->d_type, s->d_yaw, s->d_params, s->d_origin, s->d_heights, s->rows, s->cols,
+                     s->hscale, s->vscale, s->x0, s->y0};
+}
+}  // namespace
+
+namespace simint {
+
+hipError_t terrain_launch_init(mpc_sim *s, const int *d_ids, int k, hipStream_t stream) {
+  hipLaunchKernelGGL(terrain_init_kernel, sim_grid(k), dim3(kSimThreads), 0, stream, terrain_args(s), d_ids, k);
+  return hipGetLastError();
+}
+
+hipError_t terrain_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream) {
+  hipLaunchKernelGGL(terrain_step_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, terrain_args(s), d_tau, d_dof, d_root);
+  return hipGetLastError();
+}
+
+}  // namespace simint
+
+extern "C" {
+
+const char *mpc_terrain_last_error(void) { return g_terr.c_str(); }
+
+int mpc_terrain_attach(mpc_sim *s, int rows, int cols, const short *h_heights, double hscale, double vscale, double x0, double y0,
+                       const double *origin) {
+  // everything that does not need the handle first, so that each check can be met without a device
+  if (rows < MPC_TERRAIN_MIN_NODES || rows > MPC_TERRAIN_MAX_NODES || cols < MPC_TERRAIN_MIN_NODES || cols > MPC_TERRAIN_MAX_NODES)
+    return tfail(MPC_E_ARG, "mpc_terrain_attach: rows and cols must be in 2 .. 4096");
+  if (!std::isfinite(hscale) || !(hscale > 0.0) || !std::isfinite(vscale) || !(vscale > 0.0))
+    return tfail(MPC_E_ARG, "mpc_terrain_attach: hscale and vscale must be finite and > 0");
+  if (!std::isfinite(x0) || !std::isfinite(y0)) return tfail(MPC_E_ARG, "mpc_terrain_attach: x0 and y0 must be finite");
+  if (!h_heights) return tfail(MPC_E_ARG, "mpc_terrain_attach: null heights");
+  if (!s) return tfail(MPC_E_ARG, "mpc_terrain_attach: null sim handle");
+  const size_t n = (size_t)s->n, cells = (size_t)rows * (size_t)cols;
+  std::vector<double> org(2 * n, 0.0);
+  if (origin)
+    for (size_t i = 0; i < org.size(); ++i) {
+      if (!std::isfinite(origin[i])) return tfail(MPC_E_ARG, "mpc_terrain_attach: origin of robot " + std::to_string(i / 2) + " is not finite");
+      org[i] = origin[i];
+    }
+  DeviceGuard guard_(s->device);
+  short *d_h = nullptr;
+  double *d_o = nullptr;
+  hipError_t e;
+  if ((e = hipDeviceSynchronize()) != hipSuccess || (e = hipMalloc(&d_h, sizeof(short) * cells)) != hipSuccess ||
+      (e = hipMalloc(&d_o, sizeof(double) * org.size())) != hipSuccess ||
+      (e = hipMemcpy(d_h, h_heights, sizeof(short) * cells, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d_o, org.data(), sizeof(double) * org.size(), hipMemcpyHostToDevice)) != hipSuccess) {
+    if (d_h) (void)hipFree(d_h);
+    if (d_o) (void)hipFree(d_o);
+    return tfail(MPC_E_HIP, std::string("mpc_terrain_attach: ") + hipGetErrorString(e));
+  }
+  // (a terrain attached earlier is replaced; the device is idle after the synchronisation above)
+  if (s->d_heights) (void)hipFree(s->d_heights);
+  if (s->d_origin) (void)hipFree(s->d_origin);
+  s->d_heights = d_h; s->d_origin = d_o;
+  s->rows = rows; s->cols = cols;
+  s->hscale = hscale; s->vscale = vscale; s->x0 = x0; s->y0 = y0;
+  TERRAIN_TRY(simint::terrain_launch_init(s, nullptr, s->n, nullptr));
+  TERRAIN_TRY(hipDeviceSynchronize());
+  return MPC_OK;
+}
+
+int mpc_terrain_query(mpc_sim *s, const double *d_xy, int k, double *d_z, double *d_normal, void *stream) {
+  if (k < 0) return tfail(MPC_E_ARG, "mpc_terrain_query: negative point count");
+  if (!d_xy || !d_z) return tfail(MPC_E_ARG, "mpc_terrain_query: null points or heights");
+  if (!s) return tfail(MPC_E_ARG, "mpc_terrain_query: null sim handle");
+  if (!s->d_heights) return tfail(MPC_E_ARG, "mpc_terrain_query: the sim has no terrain attached");
+  if (k == 0) return MPC_OK;
+  DeviceGuard guard_(s->device);
+  hipLaunchKernelGGL(terrain_query_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), terrain_args(s), d_xy, k, d_z, d_normal);
+  TERRAIN_TRY(hipGetLastError());
+  return MPC_OK;
+}
+
+}  // extern "C"

@@ -4,7 +4,12 @@
 // A TOY, not a physics engine: one rigid body under gravity; a leg in contact holds its foot at a world anchor (no slip) and pushes the
 // body with F = -R J^-T tau, its joint angles following from the anchor by inverse kinematics; a leg that would pull on the ground by more
 // than RELEASE_N lets go; a leg in the air is three independent damped joints of inertia I_J (massless for the body) and touches down where
-// its foot path crosses the plane z = gx x + gy y.  No articulated dynamics, no joint limits, no friction cone on the plant side.
+// its foot path crosses the ground.  No articulated dynamics, no joint limits, no friction cone on the plant side.
+//
+// The ground is a template parameter of toy_init / toy_step: Plane (z = gx x + gy y, the numpy ToyRobot's) or HeightField (an int16 grid
+// meshed into triangles as Isaac Gym's convert_heightfield_to_trimesh splits its cells; tests/toy_terrain.py's ToyTerrainRobot).  It appears
+// in two roles: its height (initial stance, touch-down test and crossing, the anchor's z, the fall test under the base) and its normal for the
+// lift-off test f . n, taken under the leg's anchor.  The (..., gx, gy) signatures are wrappers over Plane.
 //
 // toy_init / toy_step restate ToyRobot.__init__ / ToyRobot.step of the numpy model operation for operation in float64 (same order of the
 // sums, legs 0..3, +0.0 start; 4 IK iterations per substep, 20 at initialisation; 3 x 3 systems solved as LAPACK's dgesv does: partial
@@ -171,6 +176,70 @@ MPC_HD void leg_fk(const double *q, double side, const Params &P, double *p) {
 
 MPC_HD double ground(double gx, double gy, const double *p) { return gx * p[0] + gy * p[1]; }
 
+// one plane per robot, z = gx x + gy y
+struct Plane {
+  static constexpr bool kUniformNormal = true;      // toy_step takes the normal once per tick
+  double gx, gy;
+  MPC_HD double height(const double *p) const { return ground(gx, gy, p); }
+  MPC_HD void normal(const double *, double *n) const {
+    n[0] = -gx; n[1] = -gy; n[2] = 1.0;
+    const double nn = norm3(n);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) n[i] = n[i] / nn;
+  }
+};
+
+// the cell index and the fraction inside it of coordinate x (+ the robot's origin o) along one axis of a height field with `count` nodes, the
+// first at x0, hscale apart.  The clamp is in floating point BEFORE the integer conversion: NaN and -inf land on 0, +inf and 1e300 on the last
+// node, so 0 <= i <= count - 2 and 0 <= f <= 1 for every input and no lookup leaves the field; outside it the border's heights continue.
+MPC_HD void terrain_index(double x, double o, double x0, double hscale, int count, int &i, double &f) {
+  double u = ((x + o) - x0) / hscale;
+  if (!(u > 0)) u = 0;
+  if (u > count - 1) u = count - 1;
+  i = (int)u;
+  if (i > count - 2) i = count - 2;
+  f = u - i;
+}
+
+// H[rows][cols] int16 (row index along x), hscale m per cell, vscale m per unit, node (0, 0) at (x0, y0); the robot's own coordinates are local
+// and the field is sampled at local + (ox, oy).  A cell is split along the diagonal (i, j) - (i + 1, j + 1), as Isaac Gym's
+// convert_heightfield_to_trimesh does (its slope_threshold correction is not modelled).  rows, cols >= 2.
+struct HeightField {
+  static constexpr bool kUniformNormal = false;     // the normal of the triangle under each anchor, in the substep that uses it
+  const short *h;
+  int rows, cols;
+  double hscale, vscale, x0, y0, ox, oy;
+  // height z and gradient (gx, gy) at p
+  MPC_HD void surface(const double *p, double &z, double &gx, double &gy) const {
+    int i, j;
+    double fu, fv;
+    terrain_index(p[0], ox, x0, hscale, rows, i, fu);
+    terrain_index(p[1], oy, y0, hscale, cols, j, fv);
+    const short *c = h + (long)i * cols + j;
+    const double z00 = vscale * c[0], z10 = vscale * c[cols], z01 = vscale * c[1], z11 = vscale * c[cols + 1];
+    if (fu >= fv) {
+      z = z00 + fu * (z10 - z00) + fv * (z11 - z10);
+      gx = (z10 - z00) / hscale; gy = (z11 - z10) / hscale;
+    } else {
+      z = z00 + fv * (z01 - z00) + fu * (z11 - z01);
+      gx = (z11 - z01) / hscale; gy = (z01 - z00) / hscale;
+    }
+  }
+  MPC_HD double height(const double *p) const {
+    double z, gx, gy;
+    surface(p, z, gx, gy);
+    return z;
+  }
+  MPC_HD void normal(const double *p, double *n) const {
+    double z, gx, gy;
+    surface(p, z, gx, gy);
+    n[0] = -gx; n[1] = -gy; n[2] = 1.0;
+    const double nn = norm3(n);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) n[i] = n[i] / nn;
+  }
+};
+
 // ToyRobot._ik: q <- q + solve(J + 1e-9 I, target - p), `iters` times
 MPC_HD void leg_ik(int l, const Params &P, const double *target, double *q, int iters) {
 #pragma unroll 1
@@ -186,8 +255,9 @@ MPC_HD void leg_ik(int l, const Params &P, const double *target, double *q, int 
   }
 }
 
-// ToyRobot.__init__(row, yaw0, slope)
-MPC_HD void toy_init(State &s, const Params &P, double yaw0, double gx, double gy) {
+// ToyRobot.__init__(row, yaw0, slope) on ground g
+template <class Ground>
+MPC_HD void toy_init(State &s, const Params &P, double yaw0, const Ground &g) {
 #pragma unroll
   for (int l = 0; l < 4; ++l) {
     s.q[l][0] = 0.0; s.q[l][1] = 0.8; s.q[l][2] = -1.6;
@@ -210,10 +280,10 @@ MPC_HD void toy_init(State &s, const Params &P, double yaw0, double gx, double g
     mat_vec(R, hp, feet[l]);
   }
   // Python's max() over a generator: the first of the largest
-  double z = ground(gx, gy, feet[0]) - feet[0][2];
+  double z = g.height(feet[0]) - feet[0][2];
 #pragma unroll
   for (int l = 1; l < 4; ++l) {
-    const double c = ground(gx, gy, feet[l]) - feet[l][2];
+    const double c = g.height(feet[l]) - feet[l][2];
     z = c > z ? c : z;
   }
   s.pos[2] = z;
@@ -222,7 +292,7 @@ MPC_HD void toy_init(State &s, const Params &P, double yaw0, double gx, double g
     double a[3], d[3], t[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) a[i] = s.pos[i] + feet[l][i];
-    a[2] = ground(gx, gy, a);
+    a[2] = g.height(a);
 #pragma unroll
     for (int i = 0; i < 3; ++i) { s.anchor[l][i] = a[i]; d[i] = a[i] - s.pos[i]; }
     mat_t_vec(R, d, t);
@@ -235,15 +305,14 @@ MPC_HD void toy_init(State &s, const Params &P, double yaw0, double gx, double g
   s.fell = 0;
 }
 
-// ToyRobot.step(tau, dt): one tick of kSubsteps substeps
-MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, double gx, double gy) {
+MPC_HD void toy_init(State &s, const Params &P, double yaw0, double gx, double gy) { toy_init(s, P, yaw0, Plane{gx, gy}); }
+
+// ToyRobot.step(tau, dt) on ground g: one tick of kSubsteps substeps
+template <class Ground>
+MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, const Ground &g) {
   const double h = dt / kSubsteps;
-  double n[3] = {-gx, -gy, 1.0};
-  {
-    const double nn = norm3(n);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) n[i] = n[i] / nn;
-  }
+  double n[3];
+  if constexpr (Ground::kUniformNormal) g.normal(s.pos, n);
 #pragma unroll 1
   for (int sub = 0; sub < kSubsteps; ++sub) {
     double R[3][3];
@@ -267,6 +336,7 @@ MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, do
       double f[3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) f[i] = (-R[i][0]) * x[0] + (-R[i][1]) * x[1] + (-R[i][2]) * x[2];
+      if constexpr (!Ground::kUniformNormal) g.normal(s.anchor[l], n);
       const double fn = dot3(f, n);
       if (fn < -kReleaseN) {             // the leg pulls on the ground (a swing command): it lets go
         s.contact[l] = 0;
@@ -357,13 +427,13 @@ MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, do
       mat_vec(R2, hp2, rp);
 #pragma unroll
       for (int i = 0; i < 3; ++i) p_new[i] = s.pos[i] + rp[i];
-      const double d_old = p_old[2] - ground(gx, gy, p_old), d_new = p_new[2] - ground(gx, gy, p_new);
+      const double d_old = p_old[2] - g.height(p_old), d_new = p_new[2] - g.height(p_new);
       if (d_new <= 0.0) {                // touch-down: the anchor is where the foot path crosses the ground
         const double sc = d_old <= 0.0 ? 1.0 : d_old / (d_old - d_new);
         double a[3], d[3], t[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) a[i] = p_old[i] + sc * (p_new[i] - p_old[i]);
-        a[2] = ground(gx, gy, a);
+        a[2] = g.height(a);
 #pragma unroll
         for (int i = 0; i < 3; ++i) { s.anchor[l][i] = a[i]; d[i] = a[i] - s.pos[i]; }
         s.contact[l] = 1;
@@ -379,8 +449,10 @@ MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, do
   double R[3][3];
   quat_to_rot(s.quat, R);
   const bool finite = isfinite(s.pos[0]) && isfinite(s.pos[1]) && isfinite(s.pos[2]);
-  if (!finite || R[2][2] < 0.3 || fabs(s.pos[2] - ground(gx, gy, s.pos)) > 3 * P.height) s.fell = 1;
+  if (!finite || R[2][2] < 0.3 || fabs(s.pos[2] - g.height(s.pos)) > 3 * P.height) s.fell = 1;
 }
+
+MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, double gx, double gy) { toy_step(s, P, tau, dt, Plane{gx, gy}); }
 
 // the state record of include/mpc_sim.h: f64[kF64], i32[kI32]; `stride` = distance between two consecutive entries of ONE robot
 // (1 on the host; the batch size on the device, whose state is structure-of-arrays)

@@ -21,7 +21,7 @@ Not the reference's: commands are drawn by a counter-based generator keyed by (s
 generator, so parity with ``torch_rand_float`` (aliengo.py:344-346) is in distribution only.
 
 What the toy plant cannot do (BatchedRLTask only): base contact is taken to be the toy's ``fell`` flag; it has no knee or hip contacts, so
-the collision term and those two reset causes never fire; and a reset puts the robot back standing on its ground plane -- it does not
+the collision term and those two reset causes never fire; and a reset puts the robot back standing on its ground (plane or terrain) -- it does not
 use the randomised joint angles and velocities of aliengo.py:322-326.
 
 Like every class here these need the GPU (MpcLibraryError without one) and have no CPU fallback.
@@ -212,9 +212,11 @@ class TaskPostPhysics:
 
 class BatchedRLTask:
     """``VecTask.step`` / ``reset`` for N robots on the toy plant: MpcEnvBridge (actions -> torques), BatchedToySim (the simulator), and
-    the two task kernels.  See the module text for what the toy cannot do."""
+    the two task kernels.  ``terrain`` / ``origin`` put the robots on a height field (BatchedToySim).  See the module text for what the toy
+    cannot do."""
 
-    def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, **bridge_args):
+    def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
+                 **bridge_args):
         import torch
         if not torch.cuda.is_available():
             raise _lib.MpcLibraryError("BatchedRLTask needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
@@ -224,7 +226,7 @@ class BatchedRLTask:
         self.bridge = MpcEnvBridge(robot_type, gait_id, horizon=horizon, controller_dt=self.cfg.dt, flat_ground=flat_ground, device=device, **bridge_args)
         self.device, self.n = self.bridge.device, self.bridge.n
         self.num_envs, self.num_obs, self.num_actions = self.n, NUM_OBS, 12
-        self.sim = BatchedToySim(robot_type, slope=slope, yaw0=yaw0, dt=self.cfg.dt, device=self.device)
+        self.sim = BatchedToySim(robot_type, slope=slope, yaw0=yaw0, dt=self.cfg.dt, device=self.device, terrain=terrain, origin=origin)
         self.task = TaskPostPhysics(self.n, self.cfg, device=self.device)
         t = self.task
         self.commands, self.progress_buf, self.reset_buf, self.timeout_buf = t.commands, t.progress_buf, t.reset_buf, t.timeout_buf

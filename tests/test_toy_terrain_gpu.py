@@ -1,0 +1,235 @@
+"""The toy plant on a height field on the MI355X (include/mpc_terrain.h, BatchedToySim(terrain=...)): the surface query, initial state and reset
+against the numpy model (tests/toy_terrain.py), one-step consistency inside a device closed loop, the zero field against the plane kernel, batch
+independence, and the rollout task and the trainer on a terrain.  Tolerances, the tie rule and IK_LOST: tests/test_toy_sim.py and
+tests/test_toy_terrain.py."""
+import copy
+
+import numpy as np
+import pytest
+
+import rl_mpc_locomotion_amd  # noqa: F401
+from rl_mpc_locomotion_amd import terrain as TR
+from rl_mpc_locomotion_amd.quadruped import ROBOT_TABLE64
+from tests import toy_terrain as TT
+from tests.test_toy_sim import TIE, compare, to_record
+from tests.test_toy_sim_gpu import from_record
+from tests.test_toy_terrain import IK_LOST
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+TROT = 0
+TROT_WEIGHTS = [5, 5, 5, 50, 50, 50, 1, 1, 1, 1, 1, 1, 0]          # the closed-loop golden's trot cases' MPC weights (cmd columns 3 .. 15)
+
+
+def _sim(rt, terrain=None, origin=None, yaw=None):
+    from rl_mpc_locomotion_amd.toy_sim import BatchedToySim
+    return BatchedToySim(rt, yaw0=yaw, device=DEV, terrain=terrain, origin=origin)
+
+
+def _ctl(rt):
+    from rl_mpc_locomotion_amd.locomotion import BatchedLocomotion
+    return BatchedLocomotion(rt, [TROT] * len(rt), horizon=10, flat_ground=False, device=DEV)
+
+
+def _cmd(n, vx=0.3):
+    import torch
+    return torch.tensor([vx, 0.0, 0.0] + TROT_WEIGHTS, dtype=torch.float32, device=DEV).repeat(n, 1).contiguous()
+
+
+def _mild(seed=3):
+    return TR.Terrain.mild(seed, rows=128, cols=128)
+
+
+def test_query_equals_numpy():
+    import torch
+    t = TT.surface_test_field()
+    pts = TT.surface_test_points(t)
+    assert pts.shape == (4133, 2)                      # 65 workgroups, the last one with 37 lanes
+    sim = _sim([0, 1], terrain=t)
+    z, n = sim.terrain_query(torch.from_numpy(pts).to(DEV))
+    z, n = z.cpu().numpy(), n.cpu().numpy()
+    assert np.isfinite(z).all() and np.array_equal(z, t.height(pts[:, 0], pts[:, 1]))
+    np.testing.assert_allclose(n, t.normal(pts[:, 0], pts[:, 1]), rtol=0, atol=1e-12)
+    z2, none = sim.terrain_query(torch.from_numpy(pts).to(DEV), normals=False)
+    assert none is None and np.array_equal(z2.cpu().numpy(), z)
+
+
+def _population(n, t):
+    """Three robot types, yaws and distinct origins on t, the last origin outside the field."""
+    rng = np.random.default_rng(130)
+    (xa, xb), (ya, yb) = t.extent
+    rt = [i % 3 for i in range(n)]
+    yaw = rng.uniform(-np.pi, np.pi, n)
+    origin = np.stack([rng.uniform(xa + 0.5, xb - 0.5, n), rng.uniform(ya + 0.5, yb - 0.5, n)], 1)
+    origin[-1] = (xb + 35.0, ya - 7.0)
+    return rt, yaw, origin
+
+
+def test_initial_state_and_reset():
+    import torch
+    n = 130
+    t = TT.stance_test_field()
+    rt, yaw, origin = _population(n, t)
+    sim = _sim(rt, t, origin, yaw)
+    fresh = sim.get_state()
+    for i in range(n):
+        m = TT.ToyTerrainRobot(ROBOT_TABLE64[rt[i]], t, origin[i], yaw0=yaw[i])
+        assert m.ik_residual < 1e-12
+        rf, rk = to_record(m)
+        assert (fresh["i32"][i] == rk).all()
+        np.testing.assert_allclose(fresh["f64"][i], rf, rtol=0, atol=1e-12, err_msg=f"robot {i} type {rt[i]} origin {origin[i]}")
+    assert len(np.unique(np.round(fresh["f64"][:, 2], 6))) > 20          # (the stance depends on where the robot stands)
+    contact, fell = sim.flags()
+    assert contact.all().item() and not fell.any().item()
+    # a few ticks without torque move every robot; then a reset of a subset
+    zero = torch.zeros((n, 12), dtype=torch.float32, device=DEV)
+    for _ in range(5):
+        sim.step(zero)
+    before = sim.get_state()
+    assert (before["f64"] != fresh["f64"]).any(1).all()
+    ids = [0, 3, 63, 64, 65, 100, 129]
+    sim.reset_idx(torch.tensor(ids + [-1, n + 5], dtype=torch.int32, device=DEV))          # (ids outside [0, n) are ignored)
+    after = sim.get_state()
+    others = [i for i in range(n) if i not in ids]
+    assert np.array_equal(after["f64"][others], before["f64"][others]) and np.array_equal(after["i32"][others], before["i32"][others])
+    assert np.array_equal(after["f64"][ids], fresh["f64"][ids]) and np.array_equal(after["i32"][ids], fresh["i32"][ids])
+    assert np.array_equal(sim.root_states[ids].cpu().numpy(), fresh["f64"][ids][:, :13].astype(np.float32))
+
+
+def test_one_step_consistency_in_a_device_closed_loop():
+    n = 195                                            # 3 types x 65: four waves, the last with 3 lanes
+    rng = np.random.default_rng(195)
+    t = _mild()
+    rt = [i % 3 for i in range(n)]
+    yaw = rng.uniform(-np.pi, np.pi, n)
+    origin = TR.spread_origins(n, t, margin=2.0)
+    sim, ctl = _sim(rt, t, origin, yaw), _ctl(rt)
+    cmd = _cmd(n)
+    probe = {10, 25, 40, 55, 70, 85, 100, 115}
+    compared = ties = 0
+    kinds = set()
+    for k in range(116):
+        tau = ctl.run(sim.dof_state.view(n, 12, 2), sim.root_states, cmd)
+        if k in probe:
+            pre, tau_h = sim.get_state(), tau.cpu().numpy().copy()
+        sim.step(tau)
+        if k not in probe:
+            continue
+        post = sim.get_state()
+        alive = np.flatnonzero(pre["i32"][:, 8] == 0)          # (a fallen robot stays frozen)
+        taken = 0
+        for i in rng.permutation(alive):
+            m = from_record(TT.ToyTerrainRobot(ROBOT_TABLE64[rt[i]], t, origin[i], yaw0=yaw[i]), pre["f64"][i], pre["i32"][i])
+            m0 = copy.deepcopy(m)
+            m.ik_residual = 0.0
+            m.step(tau_h[i])
+            if m.ik_residual > IK_LOST:                # a tumbling robot whose anchors are out of reach: not a sample (IK_LOST; the model alone decides)
+                continue
+            same, dpos, dvel = compare(post["f64"][i], post["i32"][i], m)
+            compared += 1
+            taken += 1
+            kinds |= {bool(m0.ground_normal(m0.anchor[l])[2]) for l in range(4) if m0.contact[l]}
+            if not same:
+                margin = TT.decision_margin(m0, tau_h[i])
+                assert margin < TIE, f"tick {k} robot {i}: contact / lift / fell differ with a numpy decision margin of {margin:.3e}"
+                ties += 1
+            else:
+                assert dpos <= 1e-9 and dvel <= 1e-7, f"tick {k} robot {i}: |dpos| {dpos:.3e}, |dvel| {dvel:.3e}"
+            if taken == 20:
+                break
+        assert taken == 20, f"tick {k}: only {taken} robots to compare"
+    print(f"{compared} robot steps compared, {ties} decision ties, triangle kinds {sorted(kinds)}")
+    assert compared == 8 * 20 and kinds == {False, True}
+    assert ties <= 0.02 * compared
+
+
+def test_zero_field_equals_the_plane_kernel():
+    import torch
+    n = 130
+    rng = np.random.default_rng(7)
+    rt = [i % 3 for i in range(n)]
+    yaw = rng.uniform(-np.pi, np.pi, n)
+    t = TR.Terrain(np.zeros((96, 80), np.int16), 0.1, 0.005, -3.3, -2.9)
+    origin = rng.uniform(-1.0, 3.0, (n, 2))
+    plane, field, ctl = _sim(rt, yaw=yaw), _sim(rt, t, origin, yaw), _ctl(rt)
+    cmd = _cmd(n)
+    a, b = plane.get_state(), field.get_state()
+    assert np.array_equal(a["f64"], b["f64"]) and np.array_equal(a["i32"], b["i32"])
+    for k in range(200):
+        tau = ctl.run(plane.dof_state.view(n, 12, 2), plane.root_states, cmd)          # the plane sim's loop; the field sim takes the same torques
+        plane.step(tau); field.step(tau)
+        if k % 20 == 19 or k == 199:
+            a, b = plane.get_state(), field.get_state()
+            assert np.array_equal(a["i32"], b["i32"]), f"tick {k}"
+            assert np.array_equal(a["f64"], b["f64"]), f"tick {k}: fields {np.unique(np.nonzero(a['f64'] != b['f64'])[1])}"      # (== : a zero's sign may differ)
+            assert torch.equal(plane.root_states, field.root_states) and torch.equal(plane.dof_state, field.dof_state)
+    assert (a["f64"][:, 0] != 0).all()
+
+
+def test_batch_independence():
+    import torch
+    n, pick = 195, 131
+    rng = np.random.default_rng(11)
+    t = _mild()
+    rt = [i % 3 for i in range(n)]
+    yaw = rng.uniform(-np.pi, np.pi, n)
+    origin = TR.spread_origins(n, t, margin=2.0)
+    traj = []
+    for idx in (list(range(n)), [pick]):
+        k_ = len(idx)
+        sim, ctl = _sim([rt[i] for i in idx], t, origin[idx], yaw[idx]), _ctl([rt[i] for i in idx])
+        cmd = _cmd(k_)
+        j = idx.index(pick)
+        rec = torch.zeros((100, 13), dtype=torch.float32, device=DEV)
+        trq = torch.zeros((100, 12), dtype=torch.float32, device=DEV)
+        for k in range(100):
+            tau = ctl.run(sim.dof_state.view(k_, 12, 2), sim.root_states, cmd)
+            sim.step(tau)
+            rec[k].copy_(sim.root_states[j]); trq[k].copy_(tau[j])
+        st = sim.get_state()
+        traj.append((rec.cpu().numpy(), trq.cpu().numpy(), st["f64"][j], st["i32"][j]))
+    (r0, t0, f0, k0), (r1, t1, f1, k1) = traj
+    assert np.array_equal(t0, t1) and np.array_equal(r0, r1) and np.array_equal(f0, f1) and np.array_equal(k0, k1)
+
+
+def test_task_and_trainer_on_a_terrain():
+    import torch
+    from rl_mpc_locomotion_amd import ppo as P, rl_task as R
+    n = 64
+    t = _mild()
+    rt = [i % 3 for i in range(n)]
+    origin = TR.spread_origins(n, t, margin=2.0)
+    task = R.BatchedRLTask(rt, [TROT] * n, cfg=R.TaskConfig(episode_length_s=0.4, seed=4), device=DEV, terrain=t, origin=origin)
+    assert task.cfg.max_episode_length == 40
+    fresh = task.sim.get_state()["f64"]
+    rng = np.random.default_rng(2)
+    actions = torch.from_numpy(rng.uniform(-1, 1, (100, n, 12)).astype(np.float32)).to(DEV)
+    obs = torch.zeros((100, n, 48), dtype=torch.float32, device=DEV)
+    rew = torch.zeros((100, n), dtype=torch.float32, device=DEV)
+    progress = torch.zeros((100, n), dtype=torch.long, device=DEV)
+    base_z = torch.zeros((100, n), dtype=torch.float32, device=DEV)
+    task.reset()
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")            # a torch call that waits for the device or copies to the host raises from here on
+    try:
+        for k in range(100):
+            o, r, d, _ = task.step(actions[k])
+            obs[k].copy_(o); rew[k].copy_(r); progress[k].copy_(task.progress_buf); base_z[k].copy_(task.sim.root_states[:, 2])
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert torch.isfinite(obs).all().item() and torch.isfinite(rew).all().item()
+    # a reset puts a robot back standing on its own origin's ground: the base's height above the terrain under it is the fresh init's
+    progress, base_z = progress.cpu().numpy(), base_z.cpu().numpy()
+    was_reset = progress == 0
+    assert (was_reset.sum(0) >= 2).all()               # every environment times out after 40 ticks, twice in 100
+    under = t.height(np.zeros(n), np.zeros(n), origin=(origin[:, 0], origin[:, 1]))
+    assert len(np.unique(np.round(under, 6))) > 10
+    want = (fresh[:, 2] - under).astype(np.float32)
+    for k in range(100):
+        got = base_z[k][was_reset[k]] - under[was_reset[k]].astype(np.float32)
+        np.testing.assert_allclose(got, want[was_reset[k]], rtol=0, atol=1e-6)
+    assert np.array_equal(base_z[99][was_reset[99]], fresh[was_reset[99], 2].astype(np.float32))
+    cfg = P.PPOConfig(num_steps_per_env=8, actor_hidden_dims=(64, 32), critic_hidden_dims=(64, 32), init_noise_std=0.5)
+    for update in ("torch", "hip"):
+        infos = P.PPOTrainer(task, cfg, seed=3, update=update).learn(1)
+        assert len(infos) == 1 and np.isfinite(list(infos[0].values())).all(), update

@@ -4,6 +4,11 @@ HIP events (mpc_sim_step alone, 4096 robots), and the fraction of robots fallen 
 records it (device_state).  Command: trot at 0.5 m/s with the MPC weights of the closed-loop golden's trot cases (and, for the fallen
 fraction only, the robot table's default weights).
     python tools/closed_loop_rate.py [--ticks 1000] [--out profiles/r07_toy_sim.json]
+With --terrain reference|mild|zero (one or more) the robots stand on a height field (rl_mpc_locomotion_amd.terrain: the reference's 5 cm random
+uniform terrain, the same generator with 1 cm steps, or an all-zero field: the plane's trajectories through the terrain kernel), spread over it on a grid, the controller estimates the ground normal
+(flat_ground=False), and the report gains, per terrain and beside the same legs on the plane, the loop rate, the fallen fraction and the
+plant's step on the plane and on the terrain measured alternately, repeat by repeat, in one process (HIP events: median, p10, p90).
+    python tools/closed_loop_rate.py --terrain reference mild --out profiles/r11_toy_terrain.json
 The kernel-trace stats of the same loop: rocprofv3 --kernel-trace --stats ... -- python tools/closed_loop_rate.py --ticks 50 --quick"""
 import argparse
 import json
@@ -19,6 +24,7 @@ sys.path.insert(0, ROOT)
 import rl_mpc_locomotion_amd  # noqa: E402,F401
 from rl_mpc_locomotion_amd import _lib  # noqa: E402
 from rl_mpc_locomotion_amd.locomotion import BatchedLocomotion  # noqa: E402
+from rl_mpc_locomotion_amd.terrain import Terrain, spread_origins  # noqa: E402
 from rl_mpc_locomotion_amd.toy_sim import BatchedToySim  # noqa: E402
 from bench import device_state  # noqa: E402
 
@@ -28,11 +34,56 @@ TROT = 0
 GOLDEN_TROT_CMD = [0.5, 0.0, 0.0, 5, 5, 5, 50, 50, 50, 1, 1, 1, 1, 1, 1, 0]
 
 
-def run(robot_type, ticks, dev, default_weights=False):
+def make_terrain(kind, n, seed=0):
+    """(Terrain, origins [n,2]) of --terrain `kind`, or (None, None)."""
+    if kind == "none":
+        return None, None
+    if kind == "zero":                 # the plane's trajectories through the terrain kernel: its own cost, without the rough ground's divergence
+        t = Terrain(np.zeros((500, 500), np.int16), 0.1, 0.005, -50.0 / 3, -50.0 / 3)
+    else:
+        t = Terrain.reference(seed) if kind == "reference" else Terrain.mild(seed)
+    return t, spread_origins(n, t, margin=3.0)
+
+
+def step_ab(robot_type, dev, terrain, origin, repeats=10, block=50):
+    """The plant's step on the plane and on the terrain, alternating repeat by repeat in one process: two closed loops (each sim with its own
+    controller, flat_ground=False), `block` ticks of one, then of the other, HIP events around mpc_sim_step alone.  Robots that have fallen are
+    frozen and cost nothing, so each side's fallen fraction at the end is reported with its time."""
     n = len(robot_type)
     yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
-    sim = BatchedToySim(robot_type, yaw0=yaw, device=dev)
-    ctl = BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=True, device=dev)
+    cmd = torch.tensor(GOLDEN_TROT_CMD, dtype=torch.float32, device=dev).repeat(n, 1).contiguous()
+    sides = {}
+    for name, kw in (("plane", {}), ("terrain", {"terrain": terrain, "origin": origin})):
+        sim = BatchedToySim(robot_type, yaw0=yaw, device=dev, **kw)
+        ctl = BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=False, device=dev)
+        sides[name] = (sim, ctl, sim.dof_state.view(n, 12, 2), [])
+        for _ in range(10):
+            sim.step(ctl.run(sides[name][2], sim.root_states, cmd))
+    for _ in range(repeats):
+        for name, (sim, ctl, view, ms) in sides.items():
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(block)]
+            for a, b in ev:
+                tau = ctl.run(view, sim.root_states, cmd)
+                a.record(); sim.step(tau); b.record()
+            torch.cuda.synchronize()
+            ms.append([a.elapsed_time(b) for a, b in ev])
+    out = {"repeats": repeats, "ticks_per_repeat": block, "robots": n}
+    for name, (sim, _, _, ms) in sides.items():
+        m = np.array(ms)
+        out[name] = {"step_ms_median": float(np.median(m)), "step_ms_p10": float(np.percentile(m, 10)), "step_ms_p90": float(np.percentile(m, 90)),
+                     "step_ms_median_per_repeat": [float(x) for x in np.median(m, 1)], "fallen_fraction_at_end": float(sim.flags()[1].float().mean().item())}
+    out["terrain_over_plane_median"] = out["terrain"]["step_ms_median"] / out["plane"]["step_ms_median"]
+    # the first repeat alone: before robots have had the time to fall on the rougher ground
+    out["terrain_over_plane_first_repeat"] = out["terrain"]["step_ms_median_per_repeat"][0] / out["plane"]["step_ms_median_per_repeat"][0]
+    return out
+
+
+def run(robot_type, ticks, dev, default_weights=False, terrain=None, origin=None, flat_ground=True):
+    n = len(robot_type)
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    ground = {} if terrain is None else {"terrain": terrain, "origin": origin}
+    sim = BatchedToySim(robot_type, yaw0=yaw, device=dev, **ground)
+    ctl = BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=flat_ground, device=dev)
     cmd = torch.tensor(GOLDEN_TROT_CMD[:3] if default_weights else GOLDEN_TROT_CMD, dtype=torch.float32, device=dev).repeat(n, 1).contiguous()
     view = sim.dof_state.view(n, 12, 2)
     for _ in range(10):            # warm-up (first solves are cold)
@@ -46,10 +97,10 @@ def run(robot_type, ticks, dev, default_weights=False):
     _, fell = sim.flags()
     fell = fell.cpu().numpy()
     rt = np.asarray(robot_type)
-    out = {"robots": n, "ticks": ticks, "weights": "robot table defaults" if default_weights else "closed-loop golden trot", "loop_s": loop_s,
+    out = {"robots": n, "ticks": ticks, "flat_ground": flat_ground, "weights": "robot table defaults" if default_weights else "closed-loop golden trot", "loop_s": loop_s,
            "robot_ticks_per_s": n * ticks / loop_s, "ms_per_tick": loop_s / ticks * 1e3, "fallen_fraction": float(fell.mean()),
            "fallen_fraction_per_robot_type": {int(t): float(fell[rt == t].mean()) for t in np.unique(rt)}}
-    if default_weights:
+    if default_weights or terrain is not None or not flat_ground:       # (with --terrain the plant's step is step_ab's)
         return out
     # the plant alone, HIP events around mpc_sim_step inside the same closed loop (a fresh batch: every robot standing at the start)
     sim = BatchedToySim(robot_type, yaw0=yaw, device=dev)
@@ -71,6 +122,9 @@ if __name__ == "__main__":
     ap.add_argument("--ticks", type=int, default=1000)
     ap.add_argument("--robots", type=int, default=4096)
     ap.add_argument("--quick", action="store_true", help="the mixed-type loop only (for a kernel trace)")
+    ap.add_argument("--terrain", nargs="+", choices=["none", "reference", "mild", "zero"], default=["none"],
+                    help="height fields to run on beside the plane (the controller then runs with flat_ground=False)")
+    ap.add_argument("--terrain-seed", type=int, default=0)
     ap.add_argument("--out")
     args = ap.parse_args()
     dev = "cuda:0"
@@ -82,6 +136,22 @@ if __name__ == "__main__":
     for name, (rt, dw) in legs.items():
         res[name] = run(rt, args.ticks, dev, default_weights=dw)
         print(name, json.dumps(res[name]), flush=True)
+    aliengo = [0] * n
+    for kind in [k for k in args.terrain if k != "none"]:
+        t, origin = make_terrain(kind, n, args.terrain_seed)
+        res.setdefault("plane_flat_ground_false", {})
+        for name, rt in (("aliengo", aliengo), ("mixed_types", mixed)):
+            if name not in res["plane_flat_ground_false"]:
+                res["plane_flat_ground_false"][name] = run(rt, args.ticks, dev, flat_ground=False)
+                print("plane_flat_ground_false", name, json.dumps(res["plane_flat_ground_false"][name]), flush=True)
+        res["terrain_" + kind] = {"field": {"rows": t.rows, "cols": t.cols, "hscale": t.hscale, "vscale": t.vscale, "x0": t.x0, "y0": t.y0,
+                                            "seed": args.terrain_seed, "min_units": int(t.heights.min()), "max_units": int(t.heights.max()),
+                                            "max_cell_slope": t.max_cell_slope()}}
+        for name, rt in (("aliengo", aliengo), ("mixed_types", mixed)):
+            leg = run(rt, args.ticks, dev, terrain=t, origin=origin, flat_ground=False)
+            leg["step_plane_vs_terrain"] = step_ab(rt, dev, t, origin)
+            res["terrain_" + kind][name] = leg
+            print("terrain_" + kind, name, json.dumps(leg), flush=True)
     if clock0 is not None:
         res["device_state"] = {"before": clock0, "after": device_state(0, smi=False)}
     if args.out:
