@@ -7,8 +7,9 @@ and the synthetic workload generator.  See DESIGN.md.
 from .rl_task import BatchedRLTask, TaskConfig, TaskPostPhysics  # noqa: E402,F401
 
 _PPO = ("ActorCritic", "RolloutStorage", "PPO", "PPOConfig", "PPOTrainer")
+_EPISODE = ("EpisodeStats",)
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE]
 
 
 def __getattr__(name):
@@ -16,4 +17,7 @@ def __getattr__(name):
     if name in _PPO:
         from . import ppo
         return getattr(ppo, name)
+    if name in _EPISODE:
+        from . import episode
+        return getattr(episode, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

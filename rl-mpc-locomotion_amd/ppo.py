@@ -21,7 +21,8 @@ RL_Environment/tasks/legged_config_ppo.py); rsl_rl itself is an empty submodule 
 
 Not rsl_rl's: the exploration noise is a counter-based generator keyed by (seed, environment, step, action pair), not torch's, so parity
 with ``Normal.sample`` is in distribution only, and |eps| <= 5.768 (ppo_rollout.h).  Not built: observation normalisation, recurrent
-policies, privileged critic observations (the reference uses none), logging.
+policies, privileged critic observations (the reference uses none), logging beyond ``infos``.  The runner's episode statistics (mean return and
+length over the last 100 finished episodes) are kept on the device by ``episode.EpisodeStats``; ``PPOTrainer.evaluate`` is the reference's ``cfg.test`` loop.
 
 The device entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
 """
@@ -32,6 +33,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .episode import S_EPISODES, S_MEAN_LENGTH, S_MEAN_RETURN, S_WINDOW_COUNT, S_WINDOW_TIMEOUTS, EpisodeStats, random_progress
 
 NUM_ACTIONS = 12
 
@@ -521,6 +523,7 @@ class PPOTrainer:
         self.actor_critic = ActorCritic(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std).to(self.device)
         self.alg = PPO(self.actor_critic, c, backend=update)
         self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions)
+        self.episode_stats = EpisodeStats(env.num_envs, device=self.device)      # rsl_rl's rewbuffer / lenbuffer (deque(maxlen=100)), on the device
         self.iteration, self.tick, self.obs = 0, 0, None
         self.infos = []
 
@@ -539,27 +542,65 @@ class PPOTrainer:
                 st.observations[t].copy_(obs)
                 self.obs, rew, reset, extras = self.env.step(st.actions[t])
                 st.add(rew, reset, extras["time_outs"], c.gamma)
+                self.episode_stats.add(rew, reset, extras["time_outs"])
                 self.tick += 1
             self.last_values = self.actor_critic.evaluate(self.obs)
             st.compute_returns(self.last_values, c.gamma, c.lam)
 
-    def learn(self, num_iterations):
+    def learn(self, num_iterations, init_at_random_ep_len=False):
         """``num_iterations`` of collection + update.  Appends one record per iteration to ``infos`` (read from the device once, after the
-        update) and returns the list."""
+        update) and returns the list.  Besides the losses a record carries rsl_rl's episode statistics: ``mean_episode_return`` and
+        ``mean_episode_length`` over the last 100 finished episodes (0.0 while there are none), ``episodes_in_window``, ``timeouts_in_window`` and
+        the cumulative ``episodes_finished``.  ``init_at_random_ep_len``: before the first collection ``env.progress_buf`` is set to integers
+        uniform on [0, ``env.cfg.max_episode_length``), drawn from the trainer's seed, so that the environments do not time out on one tick.  As in
+        rsl_rl's ``learn``, this happens at the start of EVERY call that sets the flag (the same draw each time: it moves episodes that are under way),
+        so set it on the first call only."""
+        if init_at_random_ep_len:
+            progress, max_len = getattr(self.env, "progress_buf", None), getattr(getattr(self.env, "cfg", None), "max_episode_length", None)
+            if progress is None or max_len is None:
+                raise ValueError("init_at_random_ep_len needs an environment with progress_buf and cfg.max_episode_length")
+            if self.obs is None:
+                self.obs = self.env.reset()                                      # (the first step resets every environment, the draw comes after it)
+            random_progress(progress, max_len, self.seed)
         for _ in range(int(num_iterations)):
             self.collect()
             mean_reward, done_rate = self.storage.rewards.mean(), self.storage.dones.mean()
             value_loss, surrogate = self.alg.update(self.storage)
-            stats = torch.stack((mean_reward, done_rate, value_loss, surrogate, self.actor_critic.std.detach().mean()))
-            if self.alg.backend == "hip":                                        # the device's learning rate rides along in the one read
-                stats = torch.cat((stats.double(), self.alg.lr_device)).tolist()
+            stats = torch.stack((mean_reward, done_rate, value_loss, surrogate, self.actor_critic.std.detach().mean())).double()
+            episodes = self.episode_stats.summary                                # float64, on the device: rides along in the one read
+            if self.alg.backend == "hip":                                        # and so does the device's learning rate
+                stats = torch.cat((stats, self.alg.lr_device, episodes)).tolist()
                 self.alg.sync_learning_rate(stats[5])
+                ep = stats[6:]
             else:
-                stats = stats.tolist()
+                stats = torch.cat((stats, episodes)).tolist()
+                ep = stats[5:]
             self.iteration += 1
             self.infos.append(dict(iter=self.iteration, mean_reward=stats[0], done_rate=stats[1], value_loss=stats[2], surrogate_loss=stats[3],
-                                   mean_noise_std=stats[4], learning_rate=self.alg.learning_rate))
+                                   mean_noise_std=stats[4], learning_rate=self.alg.learning_rate, mean_episode_return=ep[S_MEAN_RETURN],
+                                   mean_episode_length=ep[S_MEAN_LENGTH], episodes_in_window=int(ep[S_WINDOW_COUNT]),
+                                   episodes_finished=int(ep[S_EPISODES]), timeouts_in_window=int(ep[S_WINDOW_TIMEOUTS])))
         return self.infos
+
+    def evaluate(self, num_ticks, groups=None, num_groups=1):
+        """The reference's ``cfg.test`` loop: ``num_ticks`` of ``act_inference`` (the mean action) and ``env.step`` on the trainer's environment,
+        with no storage write and no update, counted by a fresh ``EpisodeStats`` (``groups`` / ``num_groups``: e.g. the robot type of each
+        environment); one host read at the end.  Returns the overall totals -- ``episodes``, ``time_outs``, ``terminations`` (episodes minus
+        time-outs: on the toy plant, falls), ``mean_return``, ``mean_length`` -- and the same per group under ``groups``.  ``tick`` and the noise
+        sequence are untouched; the training statistics drop the episodes under way (``restart``), which the evaluation has cut in two."""
+        stats = EpisodeStats(self.env.num_envs, groups=groups, num_groups=num_groups, device=self.device)
+        if self.obs is None:
+            self.obs = self.env.reset()
+        with torch.no_grad():
+            for _ in range(int(num_ticks)):
+                self.obs, rew, reset, extras = self.env.step(self.actor_critic.act_inference(self.obs))
+                stats.add(rew, reset, extras["time_outs"])
+        out = stats.read()
+        self.episode_stats.restart()
+        keys = ("episodes", "time_outs", "terminations", "mean_return", "mean_length")
+        result = {k: out[k] for k in keys}
+        result["groups"] = [{k: g[k] for k in keys} for g in out["groups"]]
+        return result
 
     def save(self, path):
         """The checkpoint as rsl_rl writes it; ``WeightPolicy.from_state_dict(torch.load(path)["model_state_dict"])`` loads its actor."""
