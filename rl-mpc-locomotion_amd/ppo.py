@@ -20,8 +20,9 @@ RL_Environment/tasks/legged_config_ppo.py); rsl_rl itself is an empty submodule 
     policy = WeightPolicy.from_state_dict(torch.load("model.pt")["model_state_dict"])
 
 Not rsl_rl's: the exploration noise is a counter-based generator keyed by (seed, environment, step, action pair), not torch's, so parity
-with ``Normal.sample`` is in distribution only, and |eps| <= 5.768 (ppo_rollout.h).  Not built: observation normalisation, recurrent
-policies, privileged critic observations (the reference uses none), logging beyond ``infos``.  The runner's episode statistics (mean return and
+with ``Normal.sample`` is in distribution only, and |eps| <= 5.768 (ppo_rollout.h).  Observation normalisation (rsl_rl 2.x's
+``EmpiricalNormalization``) is opt-in: ``PPOTrainer(..., normalize_obs=True)`` puts ``obs_norm.ObsNormalizer`` between the environment and everything
+that reads an observation.  Not built: recurrent policies, privileged critic observations (the reference uses none), logging beyond ``infos``.  The runner's episode statistics (mean return and
 length over the last 100 finished episodes) are kept on the device by ``episode.EpisodeStats``; ``PPOTrainer.evaluate`` is the reference's ``cfg.test`` loop.
 
 The device entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
@@ -34,6 +35,7 @@ from torch import nn
 
 from . import _lib
 from .episode import S_EPISODES, S_MEAN_LENGTH, S_MEAN_RETURN, S_WINDOW_COUNT, S_WINDOW_TIMEOUTS, EpisodeStats, random_progress
+from .obs_norm import ObsNormalizer
 
 NUM_ACTIONS = 12
 
@@ -510,9 +512,14 @@ class PPOTrainer:
 
     An iteration: T times ``act`` into slot t, ``env.step``, ``add``; then ``evaluate`` and ``compute_returns`` -- nothing of that is copied to
     the host or waits for the device -- and ``PPO.update``.  ``seed`` seeds torch's global generator (weight initialisation, the update's
-    ``randperm``), as the reference's train.py does, and the exploration noise."""
+    ``randperm``), as the reference's train.py does, and the exploration noise.
 
-    def __init__(self, env, cfg=None, seed=1, device=None, update="torch"):
+    ``normalize_obs=True`` (off by default): every observation the environment returns goes once through an ``ObsNormalizer`` (``obs_norm``; ``obs_norm_eps``,
+    ``obs_norm_until`` are its ``eps`` and ``until``) -- counted once, normalised once with the statistics that include it, written by the normalising
+    launch where the tick's ``copy_`` would have written -- and ``act``, the storage, ``evaluate`` and both update backends see the normalised
+    tensor; ``self.obs`` is then the normalised observation.  ``evaluate`` and ``get_inference_policy`` normalise without updating."""
+
+    def __init__(self, env, cfg=None, seed=1, device=None, update="torch", normalize_obs=False, obs_norm_eps=1e-2, obs_norm_until=None):
         if not torch.cuda.is_available():
             raise _lib.MpcLibraryError("PPOTrainer needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
         self.cfg = cfg if cfg is not None else PPOConfig()
@@ -526,21 +533,34 @@ class PPOTrainer:
         self.episode_stats = EpisodeStats(env.num_envs, device=self.device)      # rsl_rl's rewbuffer / lenbuffer (deque(maxlen=100)), on the device
         self.iteration, self.tick, self.obs = 0, 0, None
         self.infos = []
+        self.obs_norm = None
+        if normalize_obs:
+            self.obs_norm = ObsNormalizer(env.num_obs, eps=obs_norm_eps, until=obs_norm_until, device=self.device)
+            self._obs_held = torch.zeros((env.num_envs, env.num_obs), dtype=torch.float32, device=self.device)      # the normalised observation between collections
+
+    def _first_obs(self):
+        """``env.reset()``'s observation, normalised (and counted) when normalisation is on."""
+        obs = self.env.reset()
+        return obs if self.obs_norm is None else self.obs_norm(obs, out=self._obs_held)
 
     def collect(self, record_eps=None):
         """The collection half of one iteration (T ticks), entirely on the device.  ``record_eps``: a list that receives each tick's noise."""
         c, st = self.cfg, self.storage
         if self.obs is None:
-            self.obs = self.env.reset()
+            self.obs = self._first_obs()
         st.clear()
+        norm = self.obs_norm
         with torch.no_grad():
             for t in range(st.T):
                 obs = self.obs
                 out = self.actor_critic.act(obs, self.seed, self.tick, out=st.slot(t), return_eps=record_eps is not None)
                 if record_eps is not None:
                     record_eps.append(out["eps"])
-                st.observations[t].copy_(obs)
+                if norm is None or t == 0:
+                    st.observations[t].copy_(obs)
                 self.obs, rew, reset, extras = self.env.step(st.actions[t])
+                if norm is not None:                                             # update, then normalise, into the slot the next tick reads
+                    self.obs = norm(self.obs, out=st.observations[t + 1] if t + 1 < st.T else self._obs_held)
                 st.add(rew, reset, extras["time_outs"], c.gamma)
                 self.episode_stats.add(rew, reset, extras["time_outs"])
                 self.tick += 1
@@ -560,7 +580,7 @@ class PPOTrainer:
             if progress is None or max_len is None:
                 raise ValueError("init_at_random_ep_len needs an environment with progress_buf and cfg.max_episode_length")
             if self.obs is None:
-                self.obs = self.env.reset()                                      # (the first step resets every environment, the draw comes after it)
+                self.obs = self._first_obs()                                     # (the first step resets every environment, the draw comes after it)
             random_progress(progress, max_len, self.seed)
         for _ in range(int(num_iterations)):
             self.collect()
@@ -590,10 +610,13 @@ class PPOTrainer:
         sequence are untouched; the training statistics drop the episodes under way (``restart``), which the evaluation has cut in two."""
         stats = EpisodeStats(self.env.num_envs, groups=groups, num_groups=num_groups, device=self.device)
         if self.obs is None:
-            self.obs = self.env.reset()
+            self.obs = self._first_obs()
+        norm = self.obs_norm
         with torch.no_grad():
             for _ in range(int(num_ticks)):
                 self.obs, rew, reset, extras = self.env.step(self.actor_critic.act_inference(self.obs))
+                if norm is not None:                                             # the statistics stay as training left them
+                    self.obs = norm(self.obs, out=self._obs_held, update=False)
                 stats.add(rew, reset, extras["time_outs"])
         out = stats.read()
         self.episode_stats.restart()
@@ -603,12 +626,23 @@ class PPOTrainer:
         return result
 
     def save(self, path):
-        """The checkpoint as rsl_rl writes it; ``WeightPolicy.from_state_dict(torch.load(path)["model_state_dict"])`` loads its actor."""
-        torch.save({"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(), "iter": self.iteration,
-                    "infos": self.infos}, path)
+        """The checkpoint as rsl_rl writes it; ``WeightPolicy.from_state_dict(torch.load(path)["model_state_dict"])`` loads its actor.  With
+        normalisation on it also carries ``obs_norm_state_dict`` (rsl_rl 2.x's key), and the actor expects normalised observations:
+        ``obs_norm.fold_normalizer(ck["model_state_dict"], ck["obs_norm_state_dict"])`` gives the state dict for raw ones."""
+        ck = {"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(), "iter": self.iteration,
+              "infos": self.infos}
+        if self.obs_norm is not None:
+            ck["obs_norm_state_dict"] = self.obs_norm.state_dict()
+        torch.save(ck, path)
 
     def load(self, path, load_optimizer=True):
         ck = torch.load(path, map_location=self.device)
+        if ("obs_norm_state_dict" in ck) != (self.obs_norm is not None):
+            raise ValueError("the checkpoint was written with observation normalisation and this trainer has none" if self.obs_norm is None else
+                             "this trainer normalises observations and the checkpoint carries no obs_norm_state_dict")
+        if self.obs_norm is not None:
+            self.obs_norm.load_state_dict(ck["obs_norm_state_dict"])
+            self.obs = None                                                      # (normalised with the statistics before the load)
         self.actor_critic.load_state_dict(ck["model_state_dict"])      # (in place: the kernels keep reading the same addresses)
         if load_optimizer:
             self.alg.optimizer.load_state_dict(ck["optimizer_state_dict"])
@@ -619,5 +653,8 @@ class PPOTrainer:
         return ck["infos"]
 
     def get_inference_policy(self):
-        """obs [n, num_obs] -> the actor's mean [n, 12] (``ActorCritic.act_inference``)."""
-        return self.actor_critic.act_inference
+        """obs [n, num_obs] -> the actor's mean [n, 12] (``ActorCritic.act_inference``; with normalisation on, of the observation normalised with
+        the statistics as they are, without updating them)."""
+        if self.obs_norm is None:
+            return self.actor_critic.act_inference
+        return lambda obs: self.actor_critic.act_inference(self.obs_norm(obs, update=False))
