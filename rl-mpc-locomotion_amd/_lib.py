@@ -9,20 +9,87 @@ LIB_PATH = os.environ.get("MPC_LIB_PATH", os.path.join(_HERE, "csrc", "libmpc_ba
 _LIB = None
 
 MPC_OK = 0
-SYMBOLS = [
-    "mpc_input_len", "mpc_supported_horizons", "mpc_batch_create", "mpc_batch_destroy", "mpc_batch_solve",
-    "mpc_batch_set_solver", "mpc_batch_set_max_iter", "mpc_batch_solve_f64", "mpc_batch_solve_f16", "mpc_batch_reset", "mpc_batch_reset_device", "mpc_batch_solve_host", "mpc_batch_solve_host_f64", "mpc_batch_size", "mpc_batch_horizon", "mpc_batch_device_bytes",
-    "mpc_batch_state_len", "mpc_batch_get_state", "mpc_batch_set_state", "mpc_batch_qp_len", "mpc_batch_scale_len", "mpc_batch_get_qp", "mpc_batch_get_scale", "mpc_batch_get_profile", "mpc_batch_enable_timing",
-    "mpc_batch_kernel_times", "mpc_last_error",
-    "mpc_ctrl_create", "mpc_ctrl_destroy", "mpc_ctrl_step", "mpc_ctrl_run", "mpc_ctrl_reset", "mpc_ctrl_reset_device", "mpc_ctrl_set_gait", "mpc_ctrl_set_gait_device", "mpc_ctrl_set_solver", "mpc_ctrl_solver_info", "mpc_ctrl_solver_record", "mpc_ctrl_solver_forces", "mpc_ctrl_solver", "mpc_ctrl_set_iteration", "mpc_device_clock",
-    "mpc_ctrl_fsm_init", "mpc_ctrl_run_fsm", "mpc_ctrl_fsm_reset", "mpc_ctrl_fsm_reset_device", "mpc_ctrl_fsm_state",
-    "mpc_policy_create", "mpc_policy_destroy", "mpc_policy_step", "mpc_policy_observations", "mpc_ctrl_estimate", "mpc_ctrl_update_estimate", "mpc_pack_commands", "mpc_pack_commands_scaled", "mpc_ctrl_policy_observations", "mpc_ctrl_run_fsm_estimated",
-    "mpc_peer_create", "mpc_peer_handle", "mpc_peer_connect", "mpc_peer_put", "mpc_peer_wait", "mpc_peer_timeouts", "mpc_peer_destroy", "mpc_peer_last_error",
-]
+vp, ci, cd, ll, pvp, text = C.c_void_p, C.c_int, C.c_double, C.c_longlong, C.POINTER(C.c_void_p), C.c_char_p
+# the entry points of include/mpc_batch.h: name -> (restype, argtypes).  Every module that calls into the library declares its header's entry
+# points in a table like this one, once; its SYMBOLS and its lib() (binder) follow from the table.
+DECLS = {
+    "mpc_input_len": (ci, [ci]),
+    "mpc_supported_horizons": (ci, [vp, ci]),
+    "mpc_batch_create": (ci, [pvp, ci, ci, cd, cd, vp, vp]),
+    "mpc_batch_destroy": (None, [vp]),
+    "mpc_batch_solve": (ci, [vp, vp, vp, vp, vp]),
+    "mpc_batch_set_solver": (ci, [vp, ci]),
+    "mpc_batch_set_max_iter": (ci, [vp, ci]),
+    "mpc_batch_solve_f64": (ci, [vp, vp, vp, vp, vp]),
+    "mpc_batch_solve_f16": (ci, [vp, vp, vp, vp, vp]),
+    "mpc_batch_reset": (ci, [vp, vp, ci, vp]),
+    "mpc_batch_reset_device": (ci, [vp, vp, ci, vp]),
+    "mpc_batch_solve_host": (ci, [vp, vp, vp, vp]),
+    "mpc_batch_solve_host_f64": (ci, [vp, vp, vp, vp]),
+    "mpc_batch_size": (ci, [vp]),
+    "mpc_batch_horizon": (ci, [vp]),
+    "mpc_batch_device_bytes": (ll, [vp]),
+    "mpc_batch_state_len": (ci, [vp]),
+    "mpc_batch_get_state": (ci, [vp, vp]),
+    "mpc_batch_set_state": (ci, [vp, vp]),
+    "mpc_batch_qp_len": (ci, [vp]),
+    "mpc_batch_scale_len": (ci, [vp]),
+    "mpc_batch_get_qp": (ci, [vp, vp]),
+    "mpc_batch_get_scale": (ci, [vp, vp]),
+    "mpc_batch_get_profile": (ci, [vp, vp]),
+    "mpc_batch_enable_timing": (ci, [vp]),
+    "mpc_batch_kernel_times": (ci, [vp, ci, vp, vp]),
+    "mpc_last_error": (text, []),
+    "mpc_ctrl_create": (ci, [pvp, ci, ci, cd, ci, cd, ci, vp, vp, ci, vp, vp, vp]),
+    "mpc_ctrl_destroy": (None, [vp]),
+    "mpc_ctrl_step": (ci, [vp, vp, vp, vp, vp, vp]),
+    "mpc_ctrl_run": (ci, [vp, vp, vp, vp, vp, vp]),
+    "mpc_ctrl_reset": (ci, [vp, vp, ci, vp]),
+    "mpc_ctrl_reset_device": (ci, [vp, vp, ci, vp]),
+    "mpc_ctrl_set_gait": (ci, [vp, vp, vp]),
+    "mpc_ctrl_set_gait_device": (ci, [vp, vp, vp]),
+    "mpc_ctrl_set_solver": (ci, [vp, ci]),
+    "mpc_ctrl_solver_info": (ci, [vp, vp]),
+    "mpc_ctrl_solver_record": (ci, [vp, vp]),
+    "mpc_ctrl_solver_forces": (ci, [vp, vp]),
+    "mpc_ctrl_solver": (vp, [vp]),
+    "mpc_ctrl_set_iteration": (ci, [vp, vp, vp]),
+    "mpc_device_clock": (ci, [ci, ci, vp, vp]),
+    "mpc_ctrl_fsm_init": (ci, [vp, vp, ci, ci, vp]),
+    "mpc_ctrl_run_fsm": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+    "mpc_ctrl_fsm_reset": (ci, [vp, vp, ci, vp, vp]),
+    "mpc_ctrl_fsm_reset_device": (ci, [vp, vp, ci, vp]),
+    "mpc_ctrl_fsm_state": (ci, [vp, vp]),
+    "mpc_policy_create": (ci, [pvp, ci, vp, vp, vp, vp, vp]),
+    "mpc_policy_destroy": (None, [vp]),
+    "mpc_policy_step": (ci, [vp, ci, vp, vp, vp, vp]),
+    "mpc_policy_observations": (ci, [ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mpc_ctrl_estimate": (ci, [vp, vp, vp, vp]),
+    "mpc_ctrl_update_estimate": (ci, [vp, vp, vp]),
+    "mpc_pack_commands": (ci, [ci, vp, vp, vp, vp]),
+    "mpc_pack_commands_scaled": (ci, [ci, vp, vp, vp, vp, vp, vp]),
+    "mpc_ctrl_policy_observations": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+    "mpc_ctrl_run_fsm_estimated": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+    "mpc_peer_create": (ci, [pvp, ci, ci, ci, ci]),
+    "mpc_peer_handle": (ci, [vp, vp]),
+    "mpc_peer_connect": (ci, [vp, vp]),
+    "mpc_peer_put": (ci, [vp, vp, ci, ci, vp]),
+    "mpc_peer_wait": (ci, [vp, vp, vp]),
+    "mpc_peer_timeouts": (ci, [vp, vp]),
+    "mpc_peer_destroy": (None, [vp]),
+    "mpc_peer_last_error": (text, []),
+}
+SYMBOLS = list(DECLS)
 
 
 class MpcLibraryError(RuntimeError):
     pass
+
+
+def bind(L, decls):
+    for name, (restype, argtypes) in decls.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
 
 
 def lib():
@@ -37,74 +104,66 @@ def lib():
         # with a second runtime that sees no device ("mpc_batch_create: no HIP device").
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        vp, ci, cd = C.c_void_p, C.c_int, C.c_double
-        L.mpc_input_len.argtypes = [ci]; L.mpc_input_len.restype = ci
-        L.mpc_supported_horizons.argtypes = [vp, ci]; L.mpc_supported_horizons.restype = ci
-        L.mpc_batch_create.argtypes = [C.POINTER(vp), ci, ci, cd, cd, vp, vp]; L.mpc_batch_create.restype = ci
-        L.mpc_batch_destroy.argtypes = [vp]; L.mpc_batch_destroy.restype = None
-        L.mpc_batch_solve.argtypes = [vp, vp, vp, vp, vp]; L.mpc_batch_solve.restype = ci
-        L.mpc_batch_reset.argtypes = [vp, vp, ci, vp]; L.mpc_batch_reset.restype = ci
-        L.mpc_batch_reset_device.argtypes = [vp, vp, ci, vp]; L.mpc_batch_reset_device.restype = ci
-        L.mpc_batch_solve_host.argtypes = [vp, vp, vp, vp]; L.mpc_batch_solve_host.restype = ci
-        L.mpc_batch_solve_host_f64.argtypes = [vp, vp, vp, vp]; L.mpc_batch_solve_host_f64.restype = ci
-        L.mpc_batch_solve_f64.argtypes = [vp, vp, vp, vp, vp]; L.mpc_batch_solve_f64.restype = ci
-        L.mpc_batch_solve_f16.argtypes = [vp, vp, vp, vp, vp]; L.mpc_batch_solve_f16.restype = ci
-        L.mpc_batch_set_solver.argtypes = [vp, ci]; L.mpc_batch_set_solver.restype = ci
-        L.mpc_batch_set_max_iter.argtypes = [vp, ci]; L.mpc_batch_set_max_iter.restype = ci
-        L.mpc_batch_size.argtypes = [vp]; L.mpc_batch_size.restype = ci
-        L.mpc_batch_horizon.argtypes = [vp]; L.mpc_batch_horizon.restype = ci
-        L.mpc_batch_device_bytes.argtypes = [vp]; L.mpc_batch_device_bytes.restype = C.c_longlong
-        L.mpc_batch_state_len.argtypes = [vp]; L.mpc_batch_state_len.restype = ci
-        L.mpc_batch_get_state.argtypes = [vp, vp]; L.mpc_batch_get_state.restype = ci
-        L.mpc_batch_set_state.argtypes = [vp, vp]; L.mpc_batch_set_state.restype = ci
-        L.mpc_batch_get_profile.argtypes = [vp, vp]; L.mpc_batch_get_profile.restype = ci
-        L.mpc_batch_qp_len.argtypes = [vp]; L.mpc_batch_qp_len.restype = ci
-        L.mpc_batch_scale_len.argtypes = [vp]; L.mpc_batch_scale_len.restype = ci
-        L.mpc_batch_get_qp.argtypes = [vp, vp]; L.mpc_batch_get_qp.restype = ci
-        L.mpc_batch_get_scale.argtypes = [vp, vp]; L.mpc_batch_get_scale.restype = ci
-        L.mpc_batch_enable_timing.argtypes = [vp]; L.mpc_batch_enable_timing.restype = ci
-        L.mpc_batch_kernel_times.argtypes = [vp, ci, vp, vp]; L.mpc_batch_kernel_times.restype = ci
-        L.mpc_ctrl_create.argtypes = [C.POINTER(vp), ci, ci, cd, ci, cd, ci, vp, vp, ci, vp, vp, vp]; L.mpc_ctrl_create.restype = ci
-        L.mpc_ctrl_destroy.argtypes = [vp]; L.mpc_ctrl_destroy.restype = None
-        L.mpc_ctrl_step.argtypes = [vp, vp, vp, vp, vp, vp]; L.mpc_ctrl_step.restype = ci
-        L.mpc_ctrl_run.argtypes = [vp, vp, vp, vp, vp, vp]; L.mpc_ctrl_run.restype = ci
-        L.mpc_ctrl_reset.argtypes = [vp, vp, ci, vp]; L.mpc_ctrl_reset.restype = ci
-        L.mpc_ctrl_reset_device.argtypes = [vp, vp, ci, vp]; L.mpc_ctrl_reset_device.restype = ci
-        L.mpc_ctrl_set_gait.argtypes = [vp, vp, vp]; L.mpc_ctrl_set_gait.restype = ci
-        L.mpc_ctrl_set_gait_device.argtypes = [vp, vp, vp]; L.mpc_ctrl_set_gait_device.restype = ci
-        L.mpc_ctrl_set_solver.argtypes = [vp, ci]; L.mpc_ctrl_set_solver.restype = ci
-        L.mpc_ctrl_solver_info.argtypes = [vp, vp]; L.mpc_ctrl_solver_info.restype = ci
-        L.mpc_ctrl_solver_record.argtypes = [vp, vp]; L.mpc_ctrl_solver_record.restype = ci
-        L.mpc_ctrl_solver_forces.argtypes = [vp, vp]; L.mpc_ctrl_solver_forces.restype = ci
-        L.mpc_ctrl_solver.argtypes = [vp]; L.mpc_ctrl_solver.restype = vp
-        L.mpc_ctrl_set_iteration.argtypes = [vp, vp, vp]; L.mpc_ctrl_set_iteration.restype = ci
-        L.mpc_device_clock.argtypes = [ci, ci, vp, vp]; L.mpc_device_clock.restype = ci
-        L.mpc_ctrl_fsm_init.argtypes = [vp, vp, ci, ci, vp]; L.mpc_ctrl_fsm_init.restype = ci
-        L.mpc_ctrl_run_fsm.argtypes = [vp, vp, vp, vp, vp, vp, vp]; L.mpc_ctrl_run_fsm.restype = ci
-        L.mpc_ctrl_fsm_reset.argtypes = [vp, vp, ci, vp, vp]; L.mpc_ctrl_fsm_reset.restype = ci
-        L.mpc_ctrl_fsm_reset_device.argtypes = [vp, vp, ci, vp]; L.mpc_ctrl_fsm_reset_device.restype = ci
-        L.mpc_ctrl_fsm_state.argtypes = [vp, vp]; L.mpc_ctrl_fsm_state.restype = ci
-        L.mpc_policy_create.argtypes = [C.POINTER(vp), ci, vp, vp, vp, vp, vp]; L.mpc_policy_create.restype = ci
-        L.mpc_policy_destroy.argtypes = [vp]; L.mpc_policy_destroy.restype = None
-        L.mpc_policy_step.argtypes = [vp, ci, vp, vp, vp, vp]; L.mpc_policy_step.restype = ci
-        L.mpc_policy_observations.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp]; L.mpc_policy_observations.restype = ci
-        L.mpc_ctrl_update_estimate.argtypes = [vp, vp, vp]; L.mpc_ctrl_update_estimate.restype = ci
-        L.mpc_ctrl_estimate.argtypes = [vp, vp, vp, vp]; L.mpc_ctrl_estimate.restype = ci
-        L.mpc_pack_commands.argtypes = [ci, vp, vp, vp, vp]; L.mpc_pack_commands.restype = ci
-        L.mpc_pack_commands_scaled.argtypes = [ci, vp, vp, vp, vp, vp, vp]; L.mpc_pack_commands_scaled.restype = ci
-        L.mpc_ctrl_policy_observations.argtypes = [vp, vp, vp, vp, vp, vp, vp]; L.mpc_ctrl_policy_observations.restype = ci
-        L.mpc_ctrl_run_fsm_estimated.argtypes = [vp, vp, vp, vp, vp, vp, vp]; L.mpc_ctrl_run_fsm_estimated.restype = ci
-        L.mpc_peer_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci]; L.mpc_peer_create.restype = ci
-        L.mpc_peer_handle.argtypes = [vp, vp]; L.mpc_peer_handle.restype = ci
-        L.mpc_peer_connect.argtypes = [vp, vp]; L.mpc_peer_connect.restype = ci
-        L.mpc_peer_put.argtypes = [vp, vp, ci, ci, vp]; L.mpc_peer_put.restype = ci
-        L.mpc_peer_wait.argtypes = [vp, vp, vp]; L.mpc_peer_wait.restype = ci
-        L.mpc_peer_timeouts.argtypes = [vp, vp]; L.mpc_peer_timeouts.restype = ci
-        L.mpc_peer_destroy.argtypes = [vp]; L.mpc_peer_destroy.restype = None
-        L.mpc_peer_last_error.argtypes = []; L.mpc_peer_last_error.restype = C.c_char_p
-        L.mpc_last_error.argtypes = []; L.mpc_last_error.restype = C.c_char_p
+        bind(L, DECLS)
         _LIB = L
     return _LIB
+
+
+def binder(decls, base=lib):
+    """The lib() of a module whose entry points are `decls`: base() with them bound as well, once per loaded library object."""
+    bound = None
+
+    def module_lib():
+        nonlocal bound
+        L = base()
+        if bound is not L:
+            bind(L, decls)
+            bound = L
+        return L
+    return module_lib
+
+
+def checker(lib, last_error):
+    """check(rc, what) for the entry points whose message is behind the `last_error` symbol of lib()."""
+    def check(rc, what):
+        if rc != MPC_OK:
+            raise MpcLibraryError(f"{what} failed ({rc}): {getattr(lib(), last_error)().decode()}")
+    return check
+
+
+check = checker(lib, "mpc_last_error")
+
+
+def finalizer(destroy, attr="_handle"):
+    """A __del__ that hands the handle in `attr` to the `destroy` entry point -- unless the library was never loaded or, at interpreter
+    exit, this module's globals are gone already."""
+    def __del__(self):
+        h = getattr(self, attr, None)
+        if h and _LIB is not None:
+            getattr(_LIB, destroy)(h)
+            setattr(self, attr, None)
+    return __del__
+
+
+def need_gpu(what, *tensors):
+    import torch
+    if not torch.cuda.is_available():
+        raise MpcLibraryError(f"{what} needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+    for t in tensors:
+        if not t.is_cuda:
+            raise MpcLibraryError(f"{what} runs on the device: a tensor on {t.device} was given; no CPU fallback")
+
+
+def tensor_arg(t, dtype, numel, name):
+    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name} must be a contiguous cuda {str(dtype).replace('torch.', '')} tensor with {numel} elements")
+    return t
+
+
+def stream(device):
+    """The raw handle of torch's current stream on `device`: what every stream-ordered entry point takes."""
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 def kernel_source_hash():
@@ -125,8 +184,3 @@ def device_clock(device=0, busy_ms=20):
     ghz, ms = C.c_double(0.0), C.c_double(0.0)
     check(lib().mpc_device_clock(int(device), int(busy_ms), C.addressof(ghz), C.addressof(ms)), "mpc_device_clock")
     return ghz.value, ms.value
-
-
-def check(rc, what):
-    if rc != MPC_OK:
-        raise MpcLibraryError(f"{what} failed ({rc}): {lib().mpc_last_error().decode()}")

@@ -22,8 +22,7 @@ class BatchedConvexMpc:
         """mass: [N] floats; inertia9: [N, 9] row-major 3x3 body inertias (host arrays).
         solver: "osqp" = the reference's OSQP branch (BASELINE's comparator), "exact" = its qpOASES branch (the QP's optimum, cold every call)."""
         import torch
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("BatchedConvexMpc needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        _lib.need_gpu("BatchedConvexMpc")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         torch.cuda.set_device(self.device)
         mass = np.ascontiguousarray(mass, dtype=np.float64).reshape(-1)
@@ -40,11 +39,7 @@ class BatchedConvexMpc:
         self.forces = torch.zeros((self.n, 12 * self.h), dtype=torch.float64, device=self.device)
         self.info = torch.zeros((self.n, 8), dtype=torch.int32, device=self.device)
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib is not None and _lib._LIB is not None:   # module globals may be gone at interpreter exit
-            _lib._LIB.mpc_batch_destroy(h)
-            self._handle = None
+    __del__ = _lib.finalizer("mpc_batch_destroy")
 
     def solve(self, inputs, forces=None, info=None):
         """inputs: cuda [N, 56+4h] (layout.py) -- float32 (what the reference's Python holds), float64 (what pybind11 widens it to) or
@@ -58,7 +53,7 @@ class BatchedConvexMpc:
             raise ValueError(f"inputs must be a contiguous cuda float32 / float64 / float16 tensor of shape {(self.n, self.in_len)}")
         forces = self.forces if forces is None else forces
         info = self.info if info is None else info
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         _lib.check(getattr(_lib.lib(), entry)(self._handle, inputs.data_ptr(), forces.data_ptr(), info.data_ptr(), stream), entry)
         return forces, info
 
@@ -68,7 +63,7 @@ class BatchedConvexMpc:
 
     def reset(self, env_ids=None):
         import torch
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         if env_ids is None:
             _lib.check(_lib.lib().mpc_batch_reset(self._handle, None, 0, stream), "mpc_batch_reset")
             return

@@ -13,10 +13,12 @@
 #include "controller.h"
 #include "mpc_core.h"
 #include "mpc_horizon.h"
+#include "mpc_host.h"
 #include "mpc_model.h"
 #include "policy_mlp.h"
 
 using namespace mpc;
+using mpchost::DeviceGuard;
 
 #define MPC_DECL_OPS(HH) extern "C" const mpc::HorizonOps *mpc_horizon_ops_##HH(void);
 MPC_HORIZON_LIST(MPC_DECL_OPS)
@@ -24,25 +26,8 @@ MPC_HORIZON_LIST(MPC_DECL_OPS)
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string &msg) { g_err = msg; return code; }
-// Every entry point works on the device its handle was created on and leaves the caller's current device as it found it
-// (a process may hold handles on several GPUs, and the caller -- torch -- has a current device of its own).
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+thread_local mpchost::ErrorSlot g_err;
+int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
 constexpr int kWaitVm0 = 0x0F70;   // s_waitcnt vmcnt(0) (gfx9 encoding: vmcnt = simm16[3:0] | [15:14], expcnt [6:4] = 7, lgkmcnt [11:8] = 15: not waited for)
 

@@ -19,26 +19,14 @@
 
 #include "../../include/mpc_episode.h"
 #include "episode_stats.h"
+#include "mpc_host.h"
+
+using mpchost::DeviceGuard;
+using mpchost::round16;
 
 namespace {
-thread_local std::string g_eerr;
-int efail(int code, const std::string &m) { g_eerr = m; return code; }
-#define EP_TRY(expr)                                                                                \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return efail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
+thread_local mpchost::ErrorSlot g_err;
+int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
 constexpr int kWave = 64;
 constexpr int kGridThreads = 256;      // 4096 environments are 16 workgroups
@@ -214,7 +202,6 @@ __global__ __launch_bounds__(kGridThreads) void random_progress_kernel(long long
   if (i < n) progress[i] = episode::random_progress(seed, (uint32_t)i, max_len);
 }
 
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 }  // namespace
 
 struct mpc_episode {
@@ -230,13 +217,13 @@ struct mpc_episode {
 
 extern "C" {
 
-const char *mpc_episode_last_error(void) { return g_eerr.c_str(); }
+const char *mpc_episode_last_error(void) { return g_err.c_str(); }
 
 int mpc_episode_create(mpc_episode **out, int n, int cap, int num_groups) {
-  if (!out) return efail(MPC_E_ARG, "mpc_episode_create: bad argument");
-  if (n < 1) return efail(MPC_E_ARG, "mpc_episode_create: n must be at least 1");
-  if (cap < 1) return efail(MPC_E_ARG, "mpc_episode_create: the window holds at least one entry");
-  if (num_groups < 1 || num_groups > MPC_EPISODE_MAX_GROUPS) return efail(MPC_E_ARG, "mpc_episode_create: 1 .. 64 groups");
+  if (!out) return fail(MPC_E_ARG, "mpc_episode_create: bad argument");
+  if (n < 1) return fail(MPC_E_ARG, "mpc_episode_create: n must be at least 1");
+  if (cap < 1) return fail(MPC_E_ARG, "mpc_episode_create: the window holds at least one entry");
+  if (num_groups < 1 || num_groups > MPC_EPISODE_MAX_GROUPS) return fail(MPC_E_ARG, "mpc_episode_create: 1 .. 64 groups");
   mpc_episode *ep = new mpc_episode();
   ep->n = n; ep->cap = cap; ep->num_groups = num_groups;
   *out = ep;
@@ -253,11 +240,11 @@ void mpc_episode_destroy(mpc_episode *ep) {
 }
 
 int mpc_episode_bind(mpc_episode *ep, const mpc_episode_buffers_t *b) {
-  if (!ep || !b) return efail(MPC_E_ARG, "mpc_episode_bind: bad argument");
+  if (!ep || !b) return fail(MPC_E_ARG, "mpc_episode_bind: bad argument");
   if (!b->d_cur_return || !b->d_cur_length || !b->d_win_return || !b->d_win_length || !b->d_win_timed_out || !b->d_counters || !b->d_sums || !b->d_summary)
-    return efail(MPC_E_ARG, "mpc_episode_bind: every buffer but d_groups must be non-null");
+    return fail(MPC_E_ARG, "mpc_episode_bind: every buffer but d_groups must be non-null");
   int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return efail(MPC_E_NODEVICE, "mpc_episode_bind: no HIP device");
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return fail(MPC_E_NODEVICE, "mpc_episode_bind: no HIP device");
   if (ep->workspace && ep->device != dev) {
     DeviceGuard guard_(ep->device);
     (void)hipFree(ep->workspace);
@@ -266,7 +253,7 @@ int mpc_episode_bind(mpc_episode *ep, const mpc_episode_buffers_t *b) {
   if (!ep->workspace) {
     const size_t blocks = ((size_t)ep->n + kGridThreads - 1) / kGridThreads;
     const size_t parts = round16(blocks * (size_t)(ep->num_groups + 1) * sizeof(Part)), offsets = round16(blocks * sizeof(int));
-    EP_TRY(hipMalloc(&ep->workspace, parts + offsets + 2 * sizeof(long long)));
+    HIP_TRY(hipMalloc(&ep->workspace, parts + offsets + 2 * sizeof(long long)));
     char *w = static_cast<char *>(ep->workspace);
     ep->parts = reinterpret_cast<Part *>(w);
     ep->offsets = reinterpret_cast<int *>(w + parts);
@@ -279,61 +266,61 @@ int mpc_episode_bind(mpc_episode *ep, const mpc_episode_buffers_t *b) {
 }
 
 int mpc_episode_add(mpc_episode *ep, const float *d_rew, const long long *d_reset, const long long *d_timeout, void *stream) {
-  if (!ep || !d_rew || !d_reset || !d_timeout) return efail(MPC_E_ARG, "mpc_episode_add: bad argument");
-  if (!ep->bound) return efail(MPC_E_ARG, "mpc_episode_add: no buffers bound (mpc_episode_bind)");
+  if (!ep || !d_rew || !d_reset || !d_timeout) return fail(MPC_E_ARG, "mpc_episode_add: bad argument");
+  if (!ep->bound) return fail(MPC_E_ARG, "mpc_episode_add: no buffers bound (mpc_episode_bind)");
   DeviceGuard guard_(ep->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const Tick a{ep->n, ep->cap, ep->num_groups, ep->buf, d_rew, d_reset, d_timeout, ep->parts, ep->offsets, ep->tick};
   const int blocks = (ep->n + kGridThreads - 1) / kGridThreads;
   hipLaunchKernelGGL(accumulate_kernel, dim3((unsigned)blocks), dim3(kGridThreads), 0, s, a);
-  EP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kGridThreads), 0, s, a, blocks);
-  EP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(place_kernel, dim3((unsigned)blocks), dim3(kGridThreads), 0, s, a);
-  EP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_episode_summary(mpc_episode *ep, void *stream) {
-  if (!ep) return efail(MPC_E_ARG, "mpc_episode_summary: bad argument");
-  if (!ep->bound) return efail(MPC_E_ARG, "mpc_episode_summary: no buffers bound (mpc_episode_bind)");
+  if (!ep) return fail(MPC_E_ARG, "mpc_episode_summary: bad argument");
+  if (!ep->bound) return fail(MPC_E_ARG, "mpc_episode_summary: no buffers bound (mpc_episode_bind)");
   DeviceGuard guard_(ep->device);
   hipLaunchKernelGGL(summary_kernel, dim3(1), dim3(kSummaryThreads), 0, reinterpret_cast<hipStream_t>(stream), ep->num_groups, ep->buf);
-  EP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_episode_restart(mpc_episode *ep, void *stream) {
-  if (!ep) return efail(MPC_E_ARG, "mpc_episode_restart: bad argument");
-  if (!ep->bound) return efail(MPC_E_ARG, "mpc_episode_restart: no buffers bound (mpc_episode_bind)");
+  if (!ep) return fail(MPC_E_ARG, "mpc_episode_restart: bad argument");
+  if (!ep->bound) return fail(MPC_E_ARG, "mpc_episode_restart: no buffers bound (mpc_episode_bind)");
   DeviceGuard guard_(ep->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  EP_TRY(hipMemsetAsync(ep->buf.d_cur_return, 0, (size_t)ep->n * sizeof(float), s));
-  EP_TRY(hipMemsetAsync(ep->buf.d_cur_length, 0, (size_t)ep->n * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(ep->buf.d_cur_return, 0, (size_t)ep->n * sizeof(float), s));
+  HIP_TRY(hipMemsetAsync(ep->buf.d_cur_length, 0, (size_t)ep->n * sizeof(int), s));
   return MPC_OK;
 }
 
 int mpc_episode_clear(mpc_episode *ep, void *stream) {
   if (int rc = mpc_episode_restart(ep, stream))          // (a HIP error keeps its own text)
-    return rc == MPC_E_ARG ? efail(rc, "mpc_episode_clear: bad argument or no buffers bound (mpc_episode_bind)") : rc;
+    return rc == MPC_E_ARG ? fail(rc, "mpc_episode_clear: bad argument or no buffers bound (mpc_episode_bind)") : rc;
   DeviceGuard guard_(ep->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t blocks = (size_t)ep->num_groups + 1;
-  EP_TRY(hipMemsetAsync(ep->buf.d_win_return, 0, (size_t)ep->cap * sizeof(float), s));
-  EP_TRY(hipMemsetAsync(ep->buf.d_win_length, 0, (size_t)ep->cap * sizeof(int), s));
-  EP_TRY(hipMemsetAsync(ep->buf.d_win_timed_out, 0, (size_t)ep->cap * sizeof(int), s));
-  EP_TRY(hipMemsetAsync(ep->buf.d_counters, 0, (MPC_EPISODE_COUNTERS + MPC_EPISODE_COUNTER_STRIDE * blocks) * sizeof(long long), s));
-  EP_TRY(hipMemsetAsync(ep->buf.d_sums, 0, blocks * sizeof(double), s));
-  EP_TRY(hipMemsetAsync(ep->buf.d_summary, 0, (MPC_EPISODE_SUMMARY_TOTALS + MPC_EPISODE_SUMMARY_STRIDE * blocks) * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(ep->buf.d_win_return, 0, (size_t)ep->cap * sizeof(float), s));
+  HIP_TRY(hipMemsetAsync(ep->buf.d_win_length, 0, (size_t)ep->cap * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(ep->buf.d_win_timed_out, 0, (size_t)ep->cap * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(ep->buf.d_counters, 0, (MPC_EPISODE_COUNTERS + MPC_EPISODE_COUNTER_STRIDE * blocks) * sizeof(long long), s));
+  HIP_TRY(hipMemsetAsync(ep->buf.d_sums, 0, blocks * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(ep->buf.d_summary, 0, (MPC_EPISODE_SUMMARY_TOTALS + MPC_EPISODE_SUMMARY_STRIDE * blocks) * sizeof(double), s));
   return MPC_OK;
 }
 
 int mpc_episode_random_progress(long long *d_progress, int n, long long max_len, unsigned long long seed, void *stream) {
-  if (!d_progress || n < 1) return efail(MPC_E_ARG, "mpc_episode_random_progress: bad argument");
-  if (max_len < 1 || max_len > (1ll << 31)) return efail(MPC_E_ARG, "mpc_episode_random_progress: max_len must lie in [1, 2^31]");
+  if (!d_progress || n < 1) return fail(MPC_E_ARG, "mpc_episode_random_progress: bad argument");
+  if (max_len < 1 || max_len > (1ll << 31)) return fail(MPC_E_ARG, "mpc_episode_random_progress: max_len must lie in [1, 2^31]");
   hipLaunchKernelGGL(random_progress_kernel, dim3((unsigned)((n + kGridThreads - 1) / kGridThreads)), dim3(kGridThreads), 0, reinterpret_cast<hipStream_t>(stream),
                      d_progress, n, max_len, seed);
-  EP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 

@@ -20,29 +20,17 @@
 #include <string>
 
 #include "../../include/mpc_obs_norm.h"
+#include "mpc_host.h"
 #include "obs_norm.h"
 
 static_assert(MPC_OBSNORM_MAX_OBS == obs_norm::kMaxObs && MPC_OBSNORM_BLOCK_ROWS == obs_norm::kBlockRows, "include/mpc_obs_norm.h and obs_norm.h disagree");
 
-namespace {
-thread_local std::string g_oerr;
-int ofail(int code, const std::string &m) { g_oerr = m; return code; }
-#define ON_TRY(expr)                                                                                \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return ofail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+using mpchost::DeviceGuard;
+using mpchost::round16;
 
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
+namespace {
+thread_local mpchost::ErrorSlot g_err;
+int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
 using obs_norm::kBlockRows;
 using obs_norm::kMaxObs;
@@ -155,7 +143,6 @@ __global__ __launch_bounds__(kThreads) void clear_kernel(int D, mpc_obsnorm_buff
   if (threadIdx.x == 0) buf.d_count[0] = 0;
 }
 
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 }  // namespace
 
 struct mpc_obsnorm {
@@ -171,12 +158,12 @@ struct mpc_obsnorm {
 
 extern "C" {
 
-const char *mpc_obsnorm_last_error(void) { return g_oerr.c_str(); }
+const char *mpc_obsnorm_last_error(void) { return g_err.c_str(); }
 
 int mpc_obsnorm_create(mpc_obsnorm **out, int num_obs, float eps, long long until) {
-  if (!out) return ofail(MPC_E_ARG, "mpc_obsnorm_create: bad argument");
-  if (num_obs < 1 || num_obs > MPC_OBSNORM_MAX_OBS) return ofail(MPC_E_ARG, "mpc_obsnorm_create: num_obs must lie in [1, 256]");
-  if (!std::isfinite(eps) || eps < 0.0f) return ofail(MPC_E_ARG, "mpc_obsnorm_create: eps must be finite and not negative");
+  if (!out) return fail(MPC_E_ARG, "mpc_obsnorm_create: bad argument");
+  if (num_obs < 1 || num_obs > MPC_OBSNORM_MAX_OBS) return fail(MPC_E_ARG, "mpc_obsnorm_create: num_obs must lie in [1, 256]");
+  if (!std::isfinite(eps) || eps < 0.0f) return fail(MPC_E_ARG, "mpc_obsnorm_create: eps must be finite and not negative");
   mpc_obsnorm *h = new mpc_obsnorm();
   h->D = num_obs; h->eps = eps; h->until = until < 0 ? -1 : until;
   *out = h;
@@ -193,10 +180,10 @@ void mpc_obsnorm_destroy(mpc_obsnorm *h) {
 }
 
 int mpc_obsnorm_bind(mpc_obsnorm *h, const mpc_obsnorm_buffers_t *b) {
-  if (!h || !b) return ofail(MPC_E_ARG, "mpc_obsnorm_bind: bad argument");
-  if (!b->d_state || !b->d_count || !b->d_mean || !b->d_var || !b->d_std) return ofail(MPC_E_ARG, "mpc_obsnorm_bind: every buffer must be non-null");
+  if (!h || !b) return fail(MPC_E_ARG, "mpc_obsnorm_bind: bad argument");
+  if (!b->d_state || !b->d_count || !b->d_mean || !b->d_var || !b->d_std) return fail(MPC_E_ARG, "mpc_obsnorm_bind: every buffer must be non-null");
   int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return ofail(MPC_E_NODEVICE, "mpc_obsnorm_bind: no HIP device");
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return fail(MPC_E_NODEVICE, "mpc_obsnorm_bind: no HIP device");
   if (h->workspace && h->device != dev) {
     DeviceGuard guard_(h->device);
     (void)hipFree(h->workspace);
@@ -210,9 +197,9 @@ int mpc_obsnorm_bind(mpc_obsnorm *h, const mpc_obsnorm_buffers_t *b) {
 }
 
 int mpc_obsnorm_apply(mpc_obsnorm *h, const float *d_x, float *d_y, long long n, int update, void *stream) {
-  if (!h || !d_x || !d_y) return ofail(MPC_E_ARG, "mpc_obsnorm_apply: bad argument");
-  if (n < 1 || n > (long long)INT_MAX) return ofail(MPC_E_ARG, "mpc_obsnorm_apply: n must lie in [1, 2^31 - 1]");
-  if (!h->bound) return ofail(MPC_E_ARG, "mpc_obsnorm_apply: no buffers bound (mpc_obsnorm_bind)");
+  if (!h || !d_x || !d_y) return fail(MPC_E_ARG, "mpc_obsnorm_apply: bad argument");
+  if (n < 1 || n > (long long)INT_MAX) return fail(MPC_E_ARG, "mpc_obsnorm_apply: n must lie in [1, 2^31 - 1]");
+  if (!h->bound) return fail(MPC_E_ARG, "mpc_obsnorm_apply: no buffers bound (mpc_obsnorm_bind)");
   DeviceGuard guard_(h->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long long blocks = (n + kBlockRows - 1) / kBlockRows;
@@ -223,7 +210,7 @@ int mpc_obsnorm_apply(mpc_obsnorm *h, const float *d_x, float *d_y, long long n,
       h->workspace = nullptr;
       h->capacity = 0;
       const size_t counts = round16((size_t)blocks * sizeof(long long)), cols = round16((size_t)blocks * (size_t)h->D * sizeof(double));
-      ON_TRY(hipMalloc(&h->workspace, counts + 2 * cols));
+      HIP_TRY(hipMalloc(&h->workspace, counts + 2 * cols));
       h->capacity = blocks;
     }
     char *w = static_cast<char *>(h->workspace);
@@ -232,21 +219,21 @@ int mpc_obsnorm_apply(mpc_obsnorm *h, const float *d_x, float *d_y, long long n,
     a.part_mean = reinterpret_cast<double *>(w + counts);
     a.part_m2 = reinterpret_cast<double *>(w + counts + cols);
     hipLaunchKernelGGL(partial_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
-    ON_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(merge_kernel, dim3(1), dim3(kThreads), 0, s, a, blocks);
-    ON_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
-  ON_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_obsnorm_clear(mpc_obsnorm *h, void *stream) {
-  if (!h) return ofail(MPC_E_ARG, "mpc_obsnorm_clear: bad argument");
-  if (!h->bound) return ofail(MPC_E_ARG, "mpc_obsnorm_clear: no buffers bound (mpc_obsnorm_bind)");
+  if (!h) return fail(MPC_E_ARG, "mpc_obsnorm_clear: bad argument");
+  if (!h->bound) return fail(MPC_E_ARG, "mpc_obsnorm_clear: no buffers bound (mpc_obsnorm_bind)");
   DeviceGuard guard_(h->device);
   hipLaunchKernelGGL(clear_kernel, dim3(1), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), h->D, h->buf);
-  ON_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 

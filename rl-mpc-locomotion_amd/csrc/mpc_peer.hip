@@ -12,15 +12,11 @@
 #include <vector>
 
 #include "../../include/mpc_batch.h"
+#include "mpc_host.h"
 
 namespace {
-thread_local std::string g_perr;
-int pfail(int code, const std::string &m) { g_perr = m; return code; }
-#define PEER_TRY(expr)                                                                               \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) return pfail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+thread_local mpchost::ErrorSlot g_err;
+int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
 constexpr int kMaxRanks = 16;
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
@@ -83,16 +79,16 @@ struct mpc_peer {
 
 extern "C" {
 
-const char *mpc_peer_last_error(void) { return g_perr.c_str(); }
+const char *mpc_peer_last_error(void) { return g_err.c_str(); }
 
 int mpc_peer_create(mpc_peer **out, int rank, int world, int n_rows_total, int row_bytes) {
-  if (!out || world < 1 || world > kMaxRanks || rank < 0 || rank >= world || n_rows_total <= 0 || row_bytes <= 0) return pfail(MPC_E_ARG, "mpc_peer_create: bad argument (at most 16 ranks)");
+  if (!out || world < 1 || world > kMaxRanks || rank < 0 || rank >= world || n_rows_total <= 0 || row_bytes <= 0) return fail(MPC_E_ARG, "mpc_peer_create: bad argument (at most 16 ranks)");
   mpc_peer *p = new mpc_peer();
   p->rank = rank; p->world = world; p->rows = (size_t)n_rows_total; p->row_bytes = (size_t)row_bytes;
   p->data_bytes = ((p->rows * p->row_bytes + 255) / 256) * 256;
   p->flag_off = 2 * p->data_bytes;
   p->total = p->flag_off + sizeof(unsigned) * 3 * kMaxRanks;
-  if (hipGetDevice(&p->device) != hipSuccess) { delete p; return pfail(MPC_E_NODEVICE, "mpc_peer_create: no HIP device"); }
+  if (hipGetDevice(&p->device) != hipSuccess) { delete p; return fail(MPC_E_NODEVICE, "mpc_peer_create: no HIP device"); }
   hipError_t e;
   // fine-grained device memory: peers' stores and this device's loads meet without a kernel boundary in between
   if ((e = hipExtMallocWithFlags(reinterpret_cast<void **>(&p->mine), p->total, hipDeviceMallocFinegrained)) != hipSuccess ||
@@ -101,7 +97,7 @@ int mpc_peer_create(mpc_peer **out, int rank, int world, int n_rows_total, int r
     if (p->mine) (void)hipFree(p->mine);
     if (p->d_timeouts) (void)hipFree(p->d_timeouts);
     delete p;
-    return pfail(MPC_E_HIP, std::string("mpc_peer_create: ") + hipGetErrorString(e));
+    return fail(MPC_E_HIP, std::string("mpc_peer_create: ") + hipGetErrorString(e));
   }
   p->peers.buf[rank] = p->mine;
   *out = p;
@@ -109,22 +105,22 @@ int mpc_peer_create(mpc_peer **out, int rank, int world, int n_rows_total, int r
 }
 
 int mpc_peer_handle(mpc_peer *p, void *handle64) {
-  if (!p || !handle64) return pfail(MPC_E_ARG, "mpc_peer_handle: bad argument");
+  if (!p || !handle64) return fail(MPC_E_ARG, "mpc_peer_handle: bad argument");
   static_assert(sizeof(hipIpcMemHandle_t) == MPC_PEER_HANDLE_BYTES, "the IPC handle is passed around as 64 bytes");
   hipIpcMemHandle_t h;
-  PEER_TRY(hipIpcGetMemHandle(&h, p->mine));
+  HIP_TRY(hipIpcGetMemHandle(&h, p->mine));
   std::memcpy(handle64, &h, sizeof h);
   return MPC_OK;
 }
 
 int mpc_peer_connect(mpc_peer *p, const void *handles) {
-  if (!p || (!handles && p->world > 1)) return pfail(MPC_E_ARG, "mpc_peer_connect: bad argument");
+  if (!p || (!handles && p->world > 1)) return fail(MPC_E_ARG, "mpc_peer_connect: bad argument");
   for (int r = 0; r < p->world; ++r) {
     if (r == p->rank || p->opened[r]) continue;
     hipIpcMemHandle_t h;
     std::memcpy(&h, static_cast<const unsigned char *>(handles) + (size_t)r * sizeof h, sizeof h);
     void *ptr = nullptr;
-    PEER_TRY(hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess));
+    HIP_TRY(hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess));
     p->peers.buf[r] = static_cast<unsigned char *>(ptr);
     p->opened[r] = true;
   }
@@ -132,37 +128,37 @@ int mpc_peer_connect(mpc_peer *p, const void *handles) {
 }
 
 int mpc_peer_put(mpc_peer *p, const void *d_local, int row_lo, int n_rows, void *stream) {
-  if (!p || !d_local || row_lo < 0 || n_rows < 0 || (size_t)row_lo + (size_t)n_rows > p->rows) return pfail(MPC_E_ARG, "mpc_peer_put: bad argument");
-  for (int r = 0; r < p->world; ++r) if (!p->peers.buf[r]) return pfail(MPC_E_ARG, "mpc_peer_put: mpc_peer_connect first");
-  if ((reinterpret_cast<uintptr_t>(d_local) & 15) || ((size_t)row_lo * p->row_bytes & 15)) return pfail(MPC_E_ARG, "mpc_peer_put: the block must start on a 16-byte boundary");
+  if (!p || !d_local || row_lo < 0 || n_rows < 0 || (size_t)row_lo + (size_t)n_rows > p->rows) return fail(MPC_E_ARG, "mpc_peer_put: bad argument");
+  for (int r = 0; r < p->world; ++r) if (!p->peers.buf[r]) return fail(MPC_E_ARG, "mpc_peer_put: mpc_peer_connect first");
+  if ((reinterpret_cast<uintptr_t>(d_local) & 15) || ((size_t)row_lo * p->row_bytes & 15)) return fail(MPC_E_ARG, "mpc_peer_put: the block must start on a 16-byte boundary");
   const unsigned epoch = ++p->epoch;
   const size_t nbytes = (size_t)n_rows * p->row_bytes, off = (epoch & 1) * p->data_bytes + (size_t)row_lo * p->row_bytes;
   int blocks = (int)((nbytes / 16 + 255) / 256);
   blocks = blocks < 1 ? 1 : (blocks > 64 ? 64 : blocks);
   hipLaunchKernelGGL(peer_put_kernel, dim3(blocks, p->world), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p->peers, p->world, p->rank,
                      static_cast<const unsigned char *>(d_local), off, nbytes, p->flag_off, epoch);
-  PEER_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_peer_wait(mpc_peer *p, void *d_out, void *stream) {
-  if (!p) return pfail(MPC_E_ARG, "mpc_peer_wait: bad argument");
-  if (p->epoch == 0) return pfail(MPC_E_ARG, "mpc_peer_wait: mpc_peer_put first");
-  if (reinterpret_cast<uintptr_t>(d_out) & 15) return pfail(MPC_E_ARG, "mpc_peer_wait: the output must start on a 16-byte boundary");
+  if (!p) return fail(MPC_E_ARG, "mpc_peer_wait: bad argument");
+  if (p->epoch == 0) return fail(MPC_E_ARG, "mpc_peer_wait: mpc_peer_put first");
+  if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(MPC_E_ARG, "mpc_peer_wait: the output must start on a 16-byte boundary");
   const long long max_cycles = (long long)(p->timeout_s * 100e6);      // wall_clock64: 100 MHz
   const size_t nbytes = p->rows * p->row_bytes;
   int blocks = (int)((nbytes / 16 + 255) / 256);
   blocks = !d_out || blocks < 1 ? 1 : (blocks > 64 ? 64 : blocks);
   hipLaunchKernelGGL(peer_wait_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p->mine, p->world, (p->epoch & 1) * p->data_bytes, nbytes, p->flag_off, p->epoch,
                      max_cycles, p->d_timeouts, static_cast<unsigned char *>(d_out));
-  PEER_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_peer_timeouts(mpc_peer *p, int *count) {
-  if (!p || !count) return pfail(MPC_E_ARG, "mpc_peer_timeouts: bad argument");
-  PEER_TRY(hipDeviceSynchronize());
-  PEER_TRY(hipMemcpy(count, p->d_timeouts, sizeof(int), hipMemcpyDeviceToHost));
+  if (!p || !count) return fail(MPC_E_ARG, "mpc_peer_timeouts: bad argument");
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(count, p->d_timeouts, sizeof(int), hipMemcpyDeviceToHost));
   return MPC_OK;
 }
 

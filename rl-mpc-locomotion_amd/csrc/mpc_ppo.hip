@@ -16,6 +16,7 @@
 
 #include "../../include/mpc_ppo.h"
 #include "mpc_ac_internal.h"
+#include "mpc_host.h"
 #include "ppo_rollout.h"
 
 // policy_mlp.h defines its kernels with external linkage and mpc_batch.hip has them already: inside this unit's unnamed namespace the second copy
@@ -24,25 +25,11 @@ namespace {
 #include "policy_mlp.h"
 }
 
-namespace {
-thread_local std::string g_perr;
-int pfail(int code, const std::string &m) { g_perr = m; return code; }
-#define PPO_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return pfail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+using mpchost::DeviceGuard;
 
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
+namespace {
+thread_local mpchost::ErrorSlot g_err;
+int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
 constexpr int kLaneThreads = 64;       // the per-environment kernels: one wave per workgroup, 4096 environments are 64 waves
 constexpr int kNormThreads = 1024;
@@ -200,19 +187,19 @@ bool mpc_ac_get_view(const mpc_ac *ac, mpc_ac_view *out) {
   return true;
 }
 
-int mpc_ppo_set_error(int code, const char *message) { return pfail(code, message); }
+int mpc_ppo_set_error(int code, const char *message) { return fail(code, message); }
 
 extern "C" {
 
-const char *mpc_ppo_last_error(void) { return g_perr.c_str(); }
+const char *mpc_ppo_last_error(void) { return g_err.c_str(); }
 
 void mpc_ac_destroy(mpc_ac *ac) { delete ac; }      // owns no device memory: the parameters are the caller's
 
 int mpc_ac_create(mpc_ac **out, int n_actor_layers, const int *actor_dims, int n_critic_layers, const int *critic_dims) {
-  if (!out) return pfail(MPC_E_ARG, "mpc_ac_create: bad argument");
-  if (const char *why = check_stack(n_actor_layers, actor_dims, MPC_AC_ACTIONS)) return pfail(MPC_E_ARG, std::string("mpc_ac_create: actor: ") + why);
-  if (const char *why = check_stack(n_critic_layers, critic_dims, 1)) return pfail(MPC_E_ARG, std::string("mpc_ac_create: critic: ") + why);
-  if (actor_dims[0] != critic_dims[0]) return pfail(MPC_E_ARG, "mpc_ac_create: actor and critic read the same observations (equal input widths)");
+  if (!out) return fail(MPC_E_ARG, "mpc_ac_create: bad argument");
+  if (const char *why = check_stack(n_actor_layers, actor_dims, MPC_AC_ACTIONS)) return fail(MPC_E_ARG, std::string("mpc_ac_create: actor: ") + why);
+  if (const char *why = check_stack(n_critic_layers, critic_dims, 1)) return fail(MPC_E_ARG, std::string("mpc_ac_create: critic: ") + why);
+  if (actor_dims[0] != critic_dims[0]) return fail(MPC_E_ARG, "mpc_ac_create: actor and critic read the same observations (equal input widths)");
   mpc_ac *ac = new mpc_ac();
   const int nl[2] = {n_actor_layers, n_critic_layers};
   const int *dims[2] = {actor_dims, critic_dims};
@@ -222,24 +209,24 @@ int mpc_ac_create(mpc_ac **out, int n_actor_layers, const int *actor_dims, int n
     const size_t b = policy::lds_bytes(ac->nets.net[k]);
     ac->lds = b > ac->lds ? b : ac->lds;
   }
-  if (ac->lds > 160 * 1024) { delete ac; return pfail(MPC_E_ARG, "mpc_ac_create: layers too wide for one CU's LDS"); }
+  if (ac->lds > 160 * 1024) { delete ac; return fail(MPC_E_ARG, "mpc_ac_create: layers too wide for one CU's LDS"); }
   *out = ac;
   return MPC_OK;
 }
 
 int mpc_ac_bind(mpc_ac *ac, const float *const *d_actor_weights, const float *const *d_actor_biases, const float *const *d_critic_weights,
                 const float *const *d_critic_biases, const float *d_std) {
-  if (!ac || !d_actor_weights || !d_actor_biases || !d_critic_weights || !d_critic_biases) return pfail(MPC_E_ARG, "mpc_ac_bind: bad argument");
+  if (!ac || !d_actor_weights || !d_actor_biases || !d_critic_weights || !d_critic_biases) return fail(MPC_E_ARG, "mpc_ac_bind: bad argument");
   const float *const *w[2] = {d_actor_weights, d_critic_weights};
   const float *const *b[2] = {d_actor_biases, d_critic_biases};
   for (int k = 0; k < 2; ++k)
     for (int l = 0; l < ac->nets.net[k].n_layers; ++l)
-      if (!aligned16(w[k][l]) || !aligned16(b[k][l])) return pfail(MPC_E_ARG, "mpc_ac_bind: every weight and bias pointer must be non-null and 16-byte aligned");
-  if (!aligned16(d_std)) return pfail(MPC_E_ARG, "mpc_ac_bind: d_std must be non-null and 16-byte aligned");
+      if (!aligned16(w[k][l]) || !aligned16(b[k][l])) return fail(MPC_E_ARG, "mpc_ac_bind: every weight and bias pointer must be non-null and 16-byte aligned");
+  if (!aligned16(d_std)) return fail(MPC_E_ARG, "mpc_ac_bind: d_std must be non-null and 16-byte aligned");
   int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return pfail(MPC_E_NODEVICE, "mpc_ac_bind: no HIP device");
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return fail(MPC_E_NODEVICE, "mpc_ac_bind: no HIP device");
   if (hipFuncSetAttribute(reinterpret_cast<const void *>(ac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ac->lds) != hipSuccess)
-    return pfail(MPC_E_HIP, "mpc_ac_bind: device set-up failed");
+    return fail(MPC_E_HIP, "mpc_ac_bind: device set-up failed");
   for (int k = 0; k < 2; ++k)
     for (int l = 0; l < ac->nets.net[k].n_layers; ++l) {
       ac->nets.net[k].w[l] = w[k][l];
@@ -257,53 +244,53 @@ static int ac_launch(mpc_ac *ac, int n, const float *d_obs, int first_net, int n
   const dim3 grid((unsigned)((n + policy::kRows - 1) / policy::kRows), (unsigned)nets);
   hipLaunchKernelGGL(ac_kernel, grid, dim3(policy::kThreads), ac->lds, reinterpret_cast<hipStream_t>(stream), ac->nets, first_net, sample, n, d_obs, seed,
                      step, o);
-  PPO_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_ac_act(mpc_ac *ac, int n, const float *d_obs, unsigned long long seed, unsigned int step, float *d_actions, float *d_log_prob, float *d_values,
                float *d_mean, float *d_sigma, float *d_eps, void *stream) {
-  if (!ac || n <= 0 || !d_obs || !d_actions || !d_log_prob || !d_values || !d_mean || !d_sigma) return pfail(MPC_E_ARG, "mpc_ac_act: bad argument");
+  if (!ac || n <= 0 || !d_obs || !d_actions || !d_log_prob || !d_values || !d_mean || !d_sigma) return fail(MPC_E_ARG, "mpc_ac_act: bad argument");
   // (rows of twelve floats are written as 8-byte pairs)
   if ((reinterpret_cast<uintptr_t>(d_actions) | reinterpret_cast<uintptr_t>(d_mean) | reinterpret_cast<uintptr_t>(d_sigma) | reinterpret_cast<uintptr_t>(d_eps)) & 7u)
-    return pfail(MPC_E_ARG, "mpc_ac_act: d_actions, d_mean, d_sigma and d_eps must be 8-byte aligned");
-  if (!ac->bound) return pfail(MPC_E_ARG, "mpc_ac_act: no parameters bound (mpc_ac_bind)");
+    return fail(MPC_E_ARG, "mpc_ac_act: d_actions, d_mean, d_sigma and d_eps must be 8-byte aligned");
+  if (!ac->bound) return fail(MPC_E_ARG, "mpc_ac_act: no parameters bound (mpc_ac_bind)");
   return ac_launch(ac, n, d_obs, kActor, 2, 1, seed, step, ActOut{d_actions, d_log_prob, d_values, d_mean, d_sigma, d_eps}, stream);
 }
 
 int mpc_ac_evaluate(mpc_ac *ac, int n, const float *d_obs, float *d_values, void *stream) {
-  if (!ac || n <= 0 || !d_obs || !d_values) return pfail(MPC_E_ARG, "mpc_ac_evaluate: bad argument");
-  if (!ac->bound) return pfail(MPC_E_ARG, "mpc_ac_evaluate: no parameters bound (mpc_ac_bind)");
+  if (!ac || n <= 0 || !d_obs || !d_values) return fail(MPC_E_ARG, "mpc_ac_evaluate: bad argument");
+  if (!ac->bound) return fail(MPC_E_ARG, "mpc_ac_evaluate: no parameters bound (mpc_ac_bind)");
   return ac_launch(ac, n, d_obs, kCritic, 1, 0, 0, 0, ActOut{nullptr, nullptr, d_values, nullptr, nullptr, nullptr}, stream);
 }
 
 int mpc_ac_act_inference(mpc_ac *ac, int n, const float *d_obs, float *d_mean, void *stream) {
-  if (!ac || n <= 0 || !d_obs || !d_mean || (reinterpret_cast<uintptr_t>(d_mean) & 7u)) return pfail(MPC_E_ARG, "mpc_ac_act_inference: bad argument");
-  if (!ac->bound) return pfail(MPC_E_ARG, "mpc_ac_act_inference: no parameters bound (mpc_ac_bind)");
+  if (!ac || n <= 0 || !d_obs || !d_mean || (reinterpret_cast<uintptr_t>(d_mean) & 7u)) return fail(MPC_E_ARG, "mpc_ac_act_inference: bad argument");
+  if (!ac->bound) return fail(MPC_E_ARG, "mpc_ac_act_inference: no parameters bound (mpc_ac_bind)");
   return ac_launch(ac, n, d_obs, kActor, 1, 0, 0, 0, ActOut{nullptr, nullptr, nullptr, d_mean, nullptr, nullptr}, stream);
 }
 
 int mpc_rollout_add(int n, double gamma, const float *d_rew, const long long *d_reset, const long long *d_timeout, const float *d_values_t,
                     float *d_rewards_t, float *d_dones_t, void *stream) {
-  if (n <= 0 || !d_rew || !d_reset || !d_timeout || !d_values_t || !d_rewards_t || !d_dones_t) return pfail(MPC_E_ARG, "mpc_rollout_add: bad argument");
-  if (!unit_interval(gamma)) return pfail(MPC_E_ARG, "mpc_rollout_add: gamma must lie in [0, 1]");
+  if (n <= 0 || !d_rew || !d_reset || !d_timeout || !d_values_t || !d_rewards_t || !d_dones_t) return fail(MPC_E_ARG, "mpc_rollout_add: bad argument");
+  if (!unit_interval(gamma)) return fail(MPC_E_ARG, "mpc_rollout_add: gamma must lie in [0, 1]");
   hipLaunchKernelGGL(rollout_add_kernel, dim3((unsigned)((n + kLaneThreads - 1) / kLaneThreads)), dim3(kLaneThreads), 0, reinterpret_cast<hipStream_t>(stream),
                      n, (float)gamma, d_rew, d_reset, d_timeout, d_values_t, d_rewards_t, d_dones_t);
-  PPO_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_rollout_returns(int n, int T, double gamma, double lam, const float *d_rewards, const float *d_dones, const float *d_values,
                         const float *d_last_values, float *d_returns, float *d_advantages, void *stream) {
   if (n <= 0 || T <= 0 || !d_rewards || !d_dones || !d_values || !d_last_values || !d_returns || !d_advantages)
-    return pfail(MPC_E_ARG, "mpc_rollout_returns: bad argument");
-  if (!unit_interval(gamma) || !unit_interval(lam)) return pfail(MPC_E_ARG, "mpc_rollout_returns: gamma and lam must lie in [0, 1]");
+    return fail(MPC_E_ARG, "mpc_rollout_returns: bad argument");
+  if (!unit_interval(gamma) || !unit_interval(lam)) return fail(MPC_E_ARG, "mpc_rollout_returns: gamma and lam must lie in [0, 1]");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(returns_kernel, dim3((unsigned)((n + kLaneThreads - 1) / kLaneThreads)), dim3(kLaneThreads), 0, s, n, T, (float)gamma, (float)lam,
                      d_rewards, d_dones, d_values, d_last_values, d_returns, d_advantages);
-  PPO_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(normalise_kernel, dim3(1), dim3(kNormThreads), 0, s, (size_t)n * (size_t)T, d_advantages);
-  PPO_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 

@@ -16,27 +16,14 @@
 
 #include "../../include/mpc_ppo_update.h"
 #include "mpc_ac_internal.h"
+#include "mpc_host.h"
 #include "ppo_gemm.h"
 #include "ppo_update.h"
 
-namespace {
-int ufail(int code, const std::string &m) { return mpc_ppo_set_error(code, m.c_str()); }
-#define UPD_TRY(expr)                                                                                \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) return ufail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+using mpchost::DeviceGuard;
 
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
+namespace {
+int fail(int code, const std::string &msg) { return mpc_ppo_set_error(code, msg.c_str()); }      // (mpc_ppo.hip's slot: one mpc_ppo_last_error for both halves)
 
 constexpr int kActor = 0, kCritic = 1;
 constexpr int kHeadThreads = 256;
@@ -206,7 +193,7 @@ int launch_gemm(pgemm::Launch &L, hipStream_t s) {
   if (plan.grid_x == 0) return MPC_OK;
   if (plan.wide) hipLaunchKernelGGL((pgemm::gemm_kernel<KIND, 2, 2>), dim3(plan.grid_x, 2), dim3(pgemm::kThreads), 0, s, L);
   else hipLaunchKernelGGL((pgemm::gemm_kernel<KIND, 2, 1>), dim3(plan.grid_x, 2), dim3(pgemm::kThreads), 0, s, L);
-  UPD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 }  // namespace
@@ -260,9 +247,9 @@ int mpc_ppo_update_tensors(const mpc_ppo_update *u) { return u ? u->n_tensors : 
 
 int mpc_ppo_update_create(mpc_ppo_update **out, mpc_ac *ac, int max_rows) {
   mpc_ac_view v;
-  if (!out || !mpc_ac_get_view(ac, &v)) return ufail(MPC_E_ARG, "mpc_ppo_update_create: bad argument");
-  if (max_rows <= 0) return ufail(MPC_E_ARG, "mpc_ppo_update_create: max_rows must be positive");
-  if (!v.bound) return ufail(MPC_E_ARG, "mpc_ppo_update_create: the mpc_ac has no parameters bound (mpc_ac_bind)");
+  if (!out || !mpc_ac_get_view(ac, &v)) return fail(MPC_E_ARG, "mpc_ppo_update_create: bad argument");
+  if (max_rows <= 0) return fail(MPC_E_ARG, "mpc_ppo_update_create: max_rows must be positive");
+  if (!v.bound) return fail(MPC_E_ARG, "mpc_ppo_update_create: the mpc_ac has no parameters bound (mpc_ac_bind)");
   mpc_ppo_update *u = new mpc_ppo_update();
   u->ac = ac;
   u->device = v.device;
@@ -285,7 +272,7 @@ int mpc_ppo_update_create(mpc_ppo_update **out, mpc_ac *ac, int max_rows) {
   if (hipMalloc(reinterpret_cast<void **>(&u->ws), words * sizeof(float)) != hipSuccess) {
     u->ws = nullptr;
     delete u;
-    return ufail(MPC_E_HIP, "mpc_ppo_update_create: the workspace could not be allocated");
+    return fail(MPC_E_HIP, "mpc_ppo_update_create: the workspace could not be allocated");
   }
   float *w = u->ws;
   u->partials = reinterpret_cast<double *>(w); w += 2 * (size_t)u->head_blocks_max * kHeadStride;
@@ -303,11 +290,11 @@ int mpc_ppo_update_create(mpc_ppo_update **out, mpc_ac *ac, int max_rows) {
 }
 
 int mpc_ppo_update_bind(mpc_ppo_update *u, float *const *d_grads, float *const *d_exp_avg, float *const *d_exp_avg_sq) {
-  if (!u || !d_grads) return ufail(MPC_E_ARG, "mpc_ppo_update_bind: bad argument");
-  if ((d_exp_avg == nullptr) != (d_exp_avg_sq == nullptr)) return ufail(MPC_E_ARG, "mpc_ppo_update_bind: both moments or neither");
+  if (!u || !d_grads) return fail(MPC_E_ARG, "mpc_ppo_update_bind: bad argument");
+  if ((d_exp_avg == nullptr) != (d_exp_avg_sq == nullptr)) return fail(MPC_E_ARG, "mpc_ppo_update_bind: both moments or neither");
   for (int t = 0; t < u->n_tensors; ++t)
     if (!aligned16(d_grads[t]) || (d_exp_avg && (!aligned16(d_exp_avg[t]) || !aligned16(d_exp_avg_sq[t]))))
-      return ufail(MPC_E_ARG, "mpc_ppo_update_bind: every gradient and moment pointer must be non-null and 16-byte aligned");
+      return fail(MPC_E_ARG, "mpc_ppo_update_bind: every gradient and moment pointer must be non-null and 16-byte aligned");
   for (int t = 0; t < u->n_tensors; ++t) {
     u->grad[t] = d_grads[t];
     u->exp_avg[t] = d_exp_avg ? d_exp_avg[t] : nullptr;
@@ -320,9 +307,9 @@ int mpc_ppo_update_bind(mpc_ppo_update *u, float *const *d_grads, float *const *
 
 int mpc_ppo_update_set_storage(mpc_ppo_update *u, long long total_rows, const float *d_obs, const float *d_actions, const float *d_values,
                                const float *d_advantages, const float *d_returns, const float *d_log_prob, const float *d_mu, const float *d_sigma) {
-  if (!u || total_rows <= 0 || !d_values || !d_advantages || !d_returns || !d_log_prob) return ufail(MPC_E_ARG, "mpc_ppo_update_set_storage: bad argument");
+  if (!u || total_rows <= 0 || !d_values || !d_advantages || !d_returns || !d_log_prob) return fail(MPC_E_ARG, "mpc_ppo_update_set_storage: bad argument");
   if (!aligned16(d_obs) || !aligned16(d_actions) || !aligned16(d_mu) || !aligned16(d_sigma))
-    return ufail(MPC_E_ARG, "mpc_ppo_update_set_storage: d_obs, d_actions, d_mu and d_sigma must be non-null and 16-byte aligned");
+    return fail(MPC_E_ARG, "mpc_ppo_update_set_storage: d_obs, d_actions, d_mu and d_sigma must be non-null and 16-byte aligned");
   u->st = Storage{d_obs, d_actions, d_values, d_advantages, d_returns, d_log_prob, d_mu, d_sigma, total_rows};
   u->storage_set = true;
   return MPC_OK;
@@ -330,16 +317,16 @@ int mpc_ppo_update_set_storage(mpc_ppo_update *u, long long total_rows, const fl
 
 int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, double clip_param, double value_loss_coef, double entropy_coef,
                          int use_clipped_value_loss, int adaptive, double desired_kl, double *d_lr, float *d_terms, void *stream) {
-  if (!u || !d_idx || !d_terms) return ufail(MPC_E_ARG, "mpc_ppo_update_grads: bad argument");
-  if (rows <= 0 || rows > u->max_rows) return ufail(MPC_E_ARG, "mpc_ppo_update_grads: rows must lie in 1 .. max_rows");
+  if (!u || !d_idx || !d_terms) return fail(MPC_E_ARG, "mpc_ppo_update_grads: bad argument");
+  if (rows <= 0 || rows > u->max_rows) return fail(MPC_E_ARG, "mpc_ppo_update_grads: rows must lie in 1 .. max_rows");
   if (!std::isfinite(clip_param) || clip_param <= 0.0 || !std::isfinite(value_loss_coef) || !std::isfinite(entropy_coef))
-    return ufail(MPC_E_ARG, "mpc_ppo_update_grads: clip_param must be positive and the coefficients finite");
+    return fail(MPC_E_ARG, "mpc_ppo_update_grads: clip_param must be positive and the coefficients finite");
   if (adaptive && (!d_lr || !(desired_kl > 0.0) || !std::isfinite(desired_kl)))
-    return ufail(MPC_E_ARG, "mpc_ppo_update_grads: the adaptive schedule needs d_lr and a positive desired_kl");
-  if (!u->grads_bound) return ufail(MPC_E_ARG, "mpc_ppo_update_grads: no gradients bound (mpc_ppo_update_bind)");
-  if (!u->storage_set) return ufail(MPC_E_ARG, "mpc_ppo_update_grads: no storage set (mpc_ppo_update_set_storage)");
+    return fail(MPC_E_ARG, "mpc_ppo_update_grads: the adaptive schedule needs d_lr and a positive desired_kl");
+  if (!u->grads_bound) return fail(MPC_E_ARG, "mpc_ppo_update_grads: no gradients bound (mpc_ppo_update_bind)");
+  if (!u->storage_set) return fail(MPC_E_ARG, "mpc_ppo_update_grads: no storage set (mpc_ppo_update_set_storage)");
   mpc_ac_view v;
-  if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return ufail(MPC_E_ARG, "mpc_ppo_update_grads: the mpc_ac has no parameters bound");
+  if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return fail(MPC_E_ARG, "mpc_ppo_update_grads: the mpc_ac has no parameters bound");
   DeviceGuard guard_(u->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int maxl = u->nl[0] > u->nl[1] ? u->nl[0] : u->nl[1];
@@ -371,10 +358,10 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
   const int la = u->nl[kActor] - 1, lc = u->nl[kCritic] - 1;
   hipLaunchKernelGGL(head_kernel, dim3((unsigned)hb), dim3(kHeadThreads), 0, s, rows, d_idx, u->st, cfg, u->Y[kActor][la], u->Y[kCritic][lc], v.std,
                      u->dY[kActor][la], u->dY[kCritic][lc], u->partials);
-  UPD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(kHeadThreads), 0, s, hb, rows, u->partials, v.std, (float)entropy_coef, adaptive ? 1 : 0, desired_kl, d_lr,
                      d_terms, u->grad[u->n_tensors - 1]);
-  UPD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
 
   // backward: from the last layer of each net towards the first; dW partials, then dX into the layer below
   int dw_chunks[2][MPC_AC_MAX_LAYERS] = {};
@@ -420,18 +407,18 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
       maxn = nout * nin > maxn ? nout * nin : maxn;
     }
   hipLaunchKernelGGL(pgemm::reduce_kernel, dim3((unsigned)((maxn + pgemm::kThreads - 1) / pgemm::kThreads), (unsigned)ne), dim3(pgemm::kThreads), 0, s, rt);
-  UPD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, double beta2, double eps, int step, const double *d_lr, void *stream) {
-  if (!u || !d_lr) return ufail(MPC_E_ARG, "mpc_ppo_update_apply: bad argument");
+  if (!u || !d_lr) return fail(MPC_E_ARG, "mpc_ppo_update_apply: bad argument");
   if (!(max_norm > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !std::isfinite(eps))
-    return ufail(MPC_E_ARG, "mpc_ppo_update_apply: max_norm must be positive, the betas in [0, 1), eps not negative");
-  if (step < 1) return ufail(MPC_E_ARG, "mpc_ppo_update_apply: step counts from 1");
-  if (!u->grads_bound || !u->moments_bound) return ufail(MPC_E_ARG, "mpc_ppo_update_apply: no gradients and moments bound (mpc_ppo_update_bind)");
+    return fail(MPC_E_ARG, "mpc_ppo_update_apply: max_norm must be positive, the betas in [0, 1), eps not negative");
+  if (step < 1) return fail(MPC_E_ARG, "mpc_ppo_update_apply: step counts from 1");
+  if (!u->grads_bound || !u->moments_bound) return fail(MPC_E_ARG, "mpc_ppo_update_apply: no gradients and moments bound (mpc_ppo_update_bind)");
   mpc_ac_view v;
-  if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return ufail(MPC_E_ARG, "mpc_ppo_update_apply: the mpc_ac has no parameters bound");
+  if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return fail(MPC_E_ARG, "mpc_ppo_update_apply: the mpc_ac has no parameters bound");
   DeviceGuard guard_(u->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   NormTable nt{};
@@ -450,12 +437,12 @@ int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, doubl
     }
   at.p[u->n_tensors - 1] = const_cast<float *>(v.std);
   hipLaunchKernelGGL(norm_partial_kernel, dim3((unsigned)u->norm_blocks, (unsigned)u->n_tensors), dim3(256), 0, s, nt, u->norm_partials);
-  UPD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(norm_kernel, dim3(1), dim3(kNormThreads), 0, s, u->n_tensors * u->norm_blocks, u->norm_partials, u->norm);
-  UPD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   ppo::AdamCfg cfg{beta1, beta2, eps, 1.0 - std::pow(beta1, (double)step), std::pow(1.0 - std::pow(beta2, (double)step), 0.5)};
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((maxn + 255) / 256), (unsigned)u->n_tensors), dim3(256), 0, s, at, cfg, (float)max_norm, u->norm, d_lr);
-  UPD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 

@@ -7,22 +7,18 @@
 #include <vector>
 
 #include "../../include/mpc_sim.h"
+#include "mpc_host.h"
 #include "mpc_sim_internal.h"
 #include "toy_sim.h"
 
 using namespace toysim;
-using simint::DeviceGuard;
+using mpchost::DeviceGuard;
 using simint::kSimThreads;
 using simint::sim_grid;
 
 namespace {
-thread_local std::string g_serr;
-int sfail(int code, const std::string &m) { g_serr = m; return code; }
-#define SIM_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return sfail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+thread_local mpchost::ErrorSlot g_err;
+int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
 struct SimArgs {
   int n;
@@ -98,7 +94,7 @@ static SimArgs sim_args(const mpc_sim *s) { return SimArgs{s->n, s->dt, s->d_f64
 
 extern "C" {
 
-const char *mpc_sim_last_error(void) { return g_serr.c_str(); }
+const char *mpc_sim_last_error(void) { return g_err.c_str(); }
 
 void mpc_sim_destroy(mpc_sim *s) {
   if (!s) return;
@@ -110,25 +106,25 @@ void mpc_sim_destroy(mpc_sim *s) {
 }
 
 int mpc_sim_create(mpc_sim **out, int n, const int *robot_type, int n_types, const double *table, const double *slope, const double *yaw0, double dt) {
-  if (!out || n <= 0 || !robot_type || n_types <= 0 || !table || !(dt > 0.0)) return sfail(MPC_E_ARG, "mpc_sim_create: bad argument");
+  if (!out || n <= 0 || !robot_type || n_types <= 0 || !table || !(dt > 0.0)) return fail(MPC_E_ARG, "mpc_sim_create: bad argument");
   for (int r = 0; r < n; ++r)
-    if (robot_type[r] < 0 || robot_type[r] >= n_types) return sfail(MPC_E_ARG, "mpc_sim_create: robot_type out of range");
+    if (robot_type[r] < 0 || robot_type[r] >= n_types) return fail(MPC_E_ARG, "mpc_sim_create: robot_type out of range");
   std::vector<Params> params(n_types);
   for (int t = 0; t < n_types; ++t) {
     const double *row = table + (size_t)kRobotCols * t;
     if (!(row[kColMass] > 0.0) || !(row[kColInertia] > 0.0) || !(row[kColInertia + 1] > 0.0) || !(row[kColInertia + 2] > 0.0))
-      return sfail(MPC_E_ARG, "mpc_sim_create: robot table row with a non-positive mass or inertia");
+      return fail(MPC_E_ARG, "mpc_sim_create: robot table row with a non-positive mass or inertia");
     params_from_row(params[t], row);
   }
   std::vector<double> sl(2 * (size_t)n, 0.0), yaw(n, 0.0);
   if (slope) for (size_t i = 0; i < sl.size(); ++i) sl[i] = slope[i];
   if (yaw0) for (int r = 0; r < n; ++r) yaw[r] = yaw0[r];
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sfail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device");
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device");
   mpc_sim *s = new mpc_sim();
   s->n = n;
   s->dt = dt;
-  if (hipGetDevice(&s->device) != hipSuccess) { delete s; return sfail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device"); }
+  if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device"); }
   hipError_t e;
   if ((e = hipMalloc(&s->d_f64, sizeof(double) * kF64 * (size_t)n)) != hipSuccess || (e = hipMalloc(&s->d_i32, sizeof(int) * kI32 * (size_t)n)) != hipSuccess ||
       (e = hipMalloc(&s->d_type, sizeof(int) * (size_t)n)) != hipSuccess || (e = hipMalloc(&s->d_slope, sizeof(double) * 2 * (size_t)n)) != hipSuccess ||
@@ -138,12 +134,12 @@ int mpc_sim_create(mpc_sim **out, int n, const int *robot_type, int n_types, con
       (e = hipMemcpy(s->d_yaw, yaw.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemcpy(s->d_params, params.data(), sizeof(Params) * n_types, hipMemcpyHostToDevice)) != hipSuccess) {
     mpc_sim_destroy(s);
-    return sfail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
+    return fail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
   }
   hipLaunchKernelGGL(sim_init_kernel, sim_grid(n), dim3(kSimThreads), 0, nullptr, sim_args(s), (const int *)nullptr, n);
   if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
     mpc_sim_destroy(s);
-    return sfail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
+    return fail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
   }
   *out = s;
   return MPC_OK;
@@ -152,47 +148,47 @@ int mpc_sim_create(mpc_sim **out, int n, const int *robot_type, int n_types, con
 int mpc_sim_size(mpc_sim *s) { return s ? s->n : 0; }
 
 int mpc_sim_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, void *stream) {
-  if (!s || !d_tau) return sfail(MPC_E_ARG, "mpc_sim_step: bad argument");
+  if (!s || !d_tau) return fail(MPC_E_ARG, "mpc_sim_step: bad argument");
   DeviceGuard guard_(s->device);
   if (s->d_heights) {                  // a terrain is attached (mpc_terrain_attach): the height-field instantiation
-    SIM_TRY(simint::terrain_launch_step(s, d_tau, d_dof, d_root, reinterpret_cast<hipStream_t>(stream)));
+    HIP_TRY(simint::terrain_launch_step(s, d_tau, d_dof, d_root, reinterpret_cast<hipStream_t>(stream)));
     return MPC_OK;
   }
   hipLaunchKernelGGL(sim_step_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), sim_args(s), d_tau, d_dof, d_root);
-  SIM_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_sim_observe(mpc_sim *s, float *d_dof, float *d_root, void *stream) {
-  if (!s || (!d_dof && !d_root)) return sfail(MPC_E_ARG, "mpc_sim_observe: bad argument");
+  if (!s || (!d_dof && !d_root)) return fail(MPC_E_ARG, "mpc_sim_observe: bad argument");
   DeviceGuard guard_(s->device);
   hipLaunchKernelGGL(sim_observe_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), sim_args(s), d_dof, d_root);
-  SIM_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_sim_reset_device(mpc_sim *s, const int *d_ids, int k, void *stream) {
-  if (!s || !d_ids || k < 0) return sfail(MPC_E_ARG, "mpc_sim_reset_device: bad argument");
+  if (!s || !d_ids || k < 0) return fail(MPC_E_ARG, "mpc_sim_reset_device: bad argument");
   if (k == 0) return MPC_OK;
   DeviceGuard guard_(s->device);
   if (s->d_heights) {
-    SIM_TRY(simint::terrain_launch_init(s, d_ids, k, reinterpret_cast<hipStream_t>(stream)));
+    HIP_TRY(simint::terrain_launch_init(s, d_ids, k, reinterpret_cast<hipStream_t>(stream)));
     return MPC_OK;
   }
   hipLaunchKernelGGL(sim_init_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), sim_args(s), d_ids, k);
-  SIM_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_sim_get_state(mpc_sim *s, double *h_f64, int *h_i32) {
-  if (!s || !h_f64 || !h_i32) return sfail(MPC_E_ARG, "mpc_sim_get_state: bad argument");
+  if (!s || !h_f64 || !h_i32) return fail(MPC_E_ARG, "mpc_sim_get_state: bad argument");
   DeviceGuard guard_(s->device);
   const size_t n = (size_t)s->n;
   std::vector<double> f(kF64 * n);
   std::vector<int> k(kI32 * n);
-  SIM_TRY(hipDeviceSynchronize());
-  SIM_TRY(hipMemcpy(f.data(), s->d_f64, sizeof(double) * f.size(), hipMemcpyDeviceToHost));
-  SIM_TRY(hipMemcpy(k.data(), s->d_i32, sizeof(int) * k.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(f.data(), s->d_f64, sizeof(double) * f.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(k.data(), s->d_i32, sizeof(int) * k.size(), hipMemcpyDeviceToHost));
   for (size_t r = 0; r < n; ++r) {
     for (int j = 0; j < kF64; ++j) h_f64[r * kF64 + j] = f[j * n + r];
     for (int j = 0; j < kI32; ++j) h_i32[r * kI32 + j] = k[j * n + r];
@@ -201,7 +197,7 @@ int mpc_sim_get_state(mpc_sim *s, double *h_f64, int *h_i32) {
 }
 
 int mpc_sim_set_state(mpc_sim *s, const double *h_f64, const int *h_i32) {
-  if (!s || !h_f64 || !h_i32) return sfail(MPC_E_ARG, "mpc_sim_set_state: bad argument");
+  if (!s || !h_f64 || !h_i32) return fail(MPC_E_ARG, "mpc_sim_set_state: bad argument");
   DeviceGuard guard_(s->device);
   const size_t n = (size_t)s->n;
   std::vector<double> f(kF64 * n);
@@ -210,18 +206,18 @@ int mpc_sim_set_state(mpc_sim *s, const double *h_f64, const int *h_i32) {
     for (int j = 0; j < kF64; ++j) f[j * n + r] = h_f64[r * kF64 + j];
     for (int j = 0; j < kI32; ++j) k[j * n + r] = h_i32[r * kI32 + j];
   }
-  SIM_TRY(hipDeviceSynchronize());
-  SIM_TRY(hipMemcpy(s->d_f64, f.data(), sizeof(double) * f.size(), hipMemcpyHostToDevice));
-  SIM_TRY(hipMemcpy(s->d_i32, k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice));
-  SIM_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(s->d_f64, f.data(), sizeof(double) * f.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->d_i32, k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipDeviceSynchronize());
   return MPC_OK;
 }
 
 int mpc_sim_flags(mpc_sim *s, unsigned char *d_contact, unsigned char *d_fell, void *stream) {
-  if (!s || (!d_contact && !d_fell)) return sfail(MPC_E_ARG, "mpc_sim_flags: bad argument");
+  if (!s || (!d_contact && !d_fell)) return fail(MPC_E_ARG, "mpc_sim_flags: bad argument");
   DeviceGuard guard_(s->device);
   hipLaunchKernelGGL(sim_flags_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), s->n, s->d_i32, d_contact, d_fell);
-  SIM_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 

@@ -28,17 +28,6 @@ constexpr int kSimThreads = 64;        // one wave per workgroup: 4096 robots ar
 
 inline dim3 sim_grid(int k) { return dim3((unsigned)((k + kSimThreads - 1) / kSimThreads)); }
 
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-
 // the terrain instantiations' launches (mpc_terrain.hip); the caller has set the device.  ids null = all n robots.
 hipError_t terrain_launch_init(mpc_sim *s, const int *d_ids, int k, hipStream_t stream);
 hipError_t terrain_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream);

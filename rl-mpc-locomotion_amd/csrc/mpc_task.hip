@@ -9,28 +9,15 @@
 #include <string>
 
 #include "../../include/mpc_task.h"
+#include "mpc_host.h"
 #include "rl_task.h"
 
 using namespace rltask;
+using mpchost::DeviceGuard;
 
 namespace {
-thread_local std::string g_terr;
-int tfail(int code, const std::string &m) { g_terr = m; return code; }
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-#define TASK_TRY(expr)                                                                              \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return tfail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+thread_local mpchost::ErrorSlot g_err;
+int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
 constexpr int kTaskThreads = 64;     // one wave per workgroup: 4096 environments are 64 waves
 constexpr int kRowPad = kObs + 1;    // LDS row stride: 49 words, so the 64 lanes writing entry j of their rows hit 64 different banks
@@ -115,7 +102,7 @@ static dim3 task_grid(int n) { return dim3((unsigned)((n + kTaskThreads - 1) / k
 
 extern "C" {
 
-const char *mpc_task_last_error(void) { return g_terr.c_str(); }
+const char *mpc_task_last_error(void) { return g_err.c_str(); }
 
 void mpc_task_destroy(mpc_task *t) {
   if (!t) return;
@@ -126,14 +113,14 @@ void mpc_task_destroy(mpc_task *t) {
 }
 
 int mpc_task_create(mpc_task **out, int n, const mpc_task_config *cfg) {
-  if (!out || n <= 0 || !cfg) return tfail(MPC_E_ARG, "mpc_task_create: bad argument");
+  if (!out || n <= 0 || !cfg) return fail(MPC_E_ARG, "mpc_task_create: bad argument");
   if (!finite_all(&cfg->lin_vel_scale, 4) || !finite_all(cfg->rew_scale, MPC_TASK_REW_TERMS) || !finite_all(&cfg->command_range[0][0], 6) ||
       !finite_all(cfg->default_dof_pos, 12))
-    return tfail(MPC_E_ARG, "mpc_task_create: a scale, a command range or a default joint angle is not finite");
+    return fail(MPC_E_ARG, "mpc_task_create: a scale, a command range or a default joint angle is not finite");
   for (int a = 0; a < 3; ++a)
-    if (cfg->command_range[a][0] > cfg->command_range[a][1]) return tfail(MPC_E_ARG, "mpc_task_create: command range with min > max");
-  if (!(cfg->clip_observations > 0.0)) return tfail(MPC_E_ARG, "mpc_task_create: clip_observations must be positive");
-  if (cfg->max_episode_length < 1) return tfail(MPC_E_ARG, "mpc_task_create: max_episode_length must be at least 1");
+    if (cfg->command_range[a][0] > cfg->command_range[a][1]) return fail(MPC_E_ARG, "mpc_task_create: command range with min > max");
+  if (!(cfg->clip_observations > 0.0)) return fail(MPC_E_ARG, "mpc_task_create: clip_observations must be positive");
+  if (cfg->max_episode_length < 1) return fail(MPC_E_ARG, "mpc_task_create: max_episode_length must be at least 1");
   Config c{};
   c.lin_vel_scale = (float)cfg->lin_vel_scale; c.ang_vel_scale = (float)cfg->ang_vel_scale;
   c.dof_pos_scale = (float)cfg->dof_pos_scale; c.dof_vel_scale = (float)cfg->dof_vel_scale;
@@ -144,16 +131,16 @@ int mpc_task_create(mpc_task **out, int n, const mpc_task_config *cfg) {
   c.max_episode_length = cfg->max_episode_length;
   c.seed = cfg->seed;
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return tfail(MPC_E_NODEVICE, "mpc_task_create: no HIP device");
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_task_create: no HIP device");
   mpc_task *t = new mpc_task();
   t->n = n;
   t->c = c;
-  if (hipGetDevice(&t->device) != hipSuccess) { delete t; return tfail(MPC_E_NODEVICE, "mpc_task_create: no HIP device"); }
+  if (hipGetDevice(&t->device) != hipSuccess) { delete t; return fail(MPC_E_NODEVICE, "mpc_task_create: no HIP device"); }
   hipError_t e;
   if ((e = hipMalloc(&t->d_episode, sizeof(int) * (size_t)n)) != hipSuccess || (e = hipMemset(t->d_episode, 0, sizeof(int) * (size_t)n)) != hipSuccess ||
       (e = hipDeviceSynchronize()) != hipSuccess) {
     mpc_task_destroy(t);
-    return tfail(MPC_E_HIP, std::string("mpc_task_create: ") + hipGetErrorString(e));
+    return fail(MPC_E_HIP, std::string("mpc_task_create: ") + hipGetErrorString(e));
   }
   *out = t;
   return MPC_OK;
@@ -161,38 +148,38 @@ int mpc_task_create(mpc_task **out, int n, const mpc_task_config *cfg) {
 
 int mpc_task_buffers(mpc_task *t, const mpc_task_buffer_set *b) {
   if (!t || !b || !b->d_progress || !b->d_reset || !b->d_timeout || !b->d_reset_ids || !b->d_commands || !b->d_obs || !b->d_rew)
-    return tfail(MPC_E_ARG, "mpc_task_buffers: bad argument (all seven buffers are required)");
+    return fail(MPC_E_ARG, "mpc_task_buffers: bad argument (all seven buffers are required)");
   t->b = *b;
   t->bound = true;
   return MPC_OK;
 }
 
 int mpc_task_begin(mpc_task *t, void *stream) {
-  if (!t) return tfail(MPC_E_ARG, "mpc_task_begin: bad argument");
-  if (!t->bound) return tfail(MPC_E_ARG, "mpc_task_begin: no buffers bound (mpc_task_buffers)");
+  if (!t) return fail(MPC_E_ARG, "mpc_task_begin: bad argument");
+  if (!t->bound) return fail(MPC_E_ARG, "mpc_task_begin: no buffers bound (mpc_task_buffers)");
   DeviceGuard guard_(t->device);
   hipLaunchKernelGGL(task_begin_kernel, task_grid(t->n), dim3(kTaskThreads), 0, reinterpret_cast<hipStream_t>(stream), t->c, t->n, t->b.d_progress,
                      t->b.d_reset, t->b.d_timeout, t->d_episode, t->b.d_reset_ids, t->b.d_commands);
-  TASK_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 
 int mpc_task_finish(mpc_task *t, const float *d_root, const float *d_dof, const float *d_actions, const float *d_torques,
                     const float *d_contact_forces, int bodies, int base_index, const int *knee_indices, const int *hip_indices,
                     const unsigned char *d_fell, void *stream) {
-  if (!t || !d_root || !d_dof || !d_actions || !d_torques) return tfail(MPC_E_ARG, "mpc_task_finish: bad argument");
-  if (!t->bound) return tfail(MPC_E_ARG, "mpc_task_finish: no buffers bound (mpc_task_buffers)");
+  if (!t || !d_root || !d_dof || !d_actions || !d_torques) return fail(MPC_E_ARG, "mpc_task_finish: bad argument");
+  if (!t->bound) return fail(MPC_E_ARG, "mpc_task_finish: no buffers bound (mpc_task_buffers)");
   ContactArgs k{};
   k.forces = d_contact_forces;
   k.fell = d_fell;
   if (d_contact_forces) {
     if (bodies <= 0 || !knee_indices || !hip_indices || base_index < 0 || base_index >= bodies)
-      return tfail(MPC_E_ARG, "mpc_task_finish: contact forces need bodies > 0, a base index below it and the knee and hip indices");
+      return fail(MPC_E_ARG, "mpc_task_finish: contact forces need bodies > 0, a base index below it and the knee and hip indices");
     k.bodies = bodies;
     k.base = base_index;
     for (int l = 0; l < kLegs; ++l) {
       if (knee_indices[l] < 0 || knee_indices[l] >= bodies || hip_indices[l] < 0 || hip_indices[l] >= bodies)
-        return tfail(MPC_E_ARG, "mpc_task_finish: knee or hip index outside [0, bodies)");
+        return fail(MPC_E_ARG, "mpc_task_finish: knee or hip index outside [0, bodies)");
       k.knee[l] = knee_indices[l];
       k.hip[l] = hip_indices[l];
     }
@@ -200,7 +187,7 @@ int mpc_task_finish(mpc_task *t, const float *d_root, const float *d_dof, const 
   DeviceGuard guard_(t->device);
   hipLaunchKernelGGL(task_finish_kernel, task_grid(t->n), dim3(kTaskThreads), 0, reinterpret_cast<hipStream_t>(stream), t->c, t->n, d_root, d_dof,
                      (const float *)t->b.d_commands, d_actions, d_torques, k, (const long long *)t->b.d_progress, t->b.d_obs, t->b.d_rew, t->b.d_reset);
-  TASK_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 

@@ -9,22 +9,18 @@
 #include <vector>
 
 #include "../../include/mpc_terrain.h"
+#include "mpc_host.h"
 #include "mpc_sim_internal.h"
 #include "toy_sim.h"
 
 using namespace toysim;
-using simint::DeviceGuard;
+using mpchost::DeviceGuard;
 using simint::kSimThreads;
 using simint::sim_grid;
 
 namespace {
-thread_local std::string g_terr;
-int tfail(int code, const std::string &m) { g_terr = m; return code; }
-#define TERRAIN_TRY(expr)                                                                           \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return tfail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+thread_local mpchost::ErrorSlot g_err;
+int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
 struct TerrainArgs {
   int n;
@@ -120,23 +116,23 @@ hipError_t terrain_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, flo
 
 extern "C" {
 
-const char *mpc_terrain_last_error(void) { return g_terr.c_str(); }
+const char *mpc_terrain_last_error(void) { return g_err.c_str(); }
 
 int mpc_terrain_attach(mpc_sim *s, int rows, int cols, const short *h_heights, double hscale, double vscale, double x0, double y0,
                        const double *origin) {
   // everything that does not need the handle first, so that each check can be met without a device
   if (rows < MPC_TERRAIN_MIN_NODES || rows > MPC_TERRAIN_MAX_NODES || cols < MPC_TERRAIN_MIN_NODES || cols > MPC_TERRAIN_MAX_NODES)
-    return tfail(MPC_E_ARG, "mpc_terrain_attach: rows and cols must be in 2 .. 4096");
+    return fail(MPC_E_ARG, "mpc_terrain_attach: rows and cols must be in 2 .. 4096");
   if (!std::isfinite(hscale) || !(hscale > 0.0) || !std::isfinite(vscale) || !(vscale > 0.0))
-    return tfail(MPC_E_ARG, "mpc_terrain_attach: hscale and vscale must be finite and > 0");
-  if (!std::isfinite(x0) || !std::isfinite(y0)) return tfail(MPC_E_ARG, "mpc_terrain_attach: x0 and y0 must be finite");
-  if (!h_heights) return tfail(MPC_E_ARG, "mpc_terrain_attach: null heights");
-  if (!s) return tfail(MPC_E_ARG, "mpc_terrain_attach: null sim handle");
+    return fail(MPC_E_ARG, "mpc_terrain_attach: hscale and vscale must be finite and > 0");
+  if (!std::isfinite(x0) || !std::isfinite(y0)) return fail(MPC_E_ARG, "mpc_terrain_attach: x0 and y0 must be finite");
+  if (!h_heights) return fail(MPC_E_ARG, "mpc_terrain_attach: null heights");
+  if (!s) return fail(MPC_E_ARG, "mpc_terrain_attach: null sim handle");
   const size_t n = (size_t)s->n, cells = (size_t)rows * (size_t)cols;
   std::vector<double> org(2 * n, 0.0);
   if (origin)
     for (size_t i = 0; i < org.size(); ++i) {
-      if (!std::isfinite(origin[i])) return tfail(MPC_E_ARG, "mpc_terrain_attach: origin of robot " + std::to_string(i / 2) + " is not finite");
+      if (!std::isfinite(origin[i])) return fail(MPC_E_ARG, "mpc_terrain_attach: origin of robot " + std::to_string(i / 2) + " is not finite");
       org[i] = origin[i];
     }
   DeviceGuard guard_(s->device);
@@ -149,7 +145,7 @@ int mpc_terrain_attach(mpc_sim *s, int rows, int cols, const short *h_heights, d
       (e = hipMemcpy(d_o, org.data(), sizeof(double) * org.size(), hipMemcpyHostToDevice)) != hipSuccess) {
     if (d_h) (void)hipFree(d_h);
     if (d_o) (void)hipFree(d_o);
-    return tfail(MPC_E_HIP, std::string("mpc_terrain_attach: ") + hipGetErrorString(e));
+    return fail(MPC_E_HIP, std::string("mpc_terrain_attach: ") + hipGetErrorString(e));
   }
   // (a terrain attached earlier is replaced; the device is idle after the synchronisation above)
   if (s->d_heights) (void)hipFree(s->d_heights);
@@ -157,20 +153,20 @@ int mpc_terrain_attach(mpc_sim *s, int rows, int cols, const short *h_heights, d
   s->d_heights = d_h; s->d_origin = d_o;
   s->rows = rows; s->cols = cols;
   s->hscale = hscale; s->vscale = vscale; s->x0 = x0; s->y0 = y0;
-  TERRAIN_TRY(simint::terrain_launch_init(s, nullptr, s->n, nullptr));
-  TERRAIN_TRY(hipDeviceSynchronize());
+  HIP_TRY(simint::terrain_launch_init(s, nullptr, s->n, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
   return MPC_OK;
 }
 
 int mpc_terrain_query(mpc_sim *s, const double *d_xy, int k, double *d_z, double *d_normal, void *stream) {
-  if (k < 0) return tfail(MPC_E_ARG, "mpc_terrain_query: negative point count");
-  if (!d_xy || !d_z) return tfail(MPC_E_ARG, "mpc_terrain_query: null points or heights");
-  if (!s) return tfail(MPC_E_ARG, "mpc_terrain_query: null sim handle");
-  if (!s->d_heights) return tfail(MPC_E_ARG, "mpc_terrain_query: the sim has no terrain attached");
+  if (k < 0) return fail(MPC_E_ARG, "mpc_terrain_query: negative point count");
+  if (!d_xy || !d_z) return fail(MPC_E_ARG, "mpc_terrain_query: null points or heights");
+  if (!s) return fail(MPC_E_ARG, "mpc_terrain_query: null sim handle");
+  if (!s->d_heights) return fail(MPC_E_ARG, "mpc_terrain_query: the sim has no terrain attached");
   if (k == 0) return MPC_OK;
   DeviceGuard guard_(s->device);
   hipLaunchKernelGGL(terrain_query_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), terrain_args(s), d_xy, k, d_z, d_normal);
-  TERRAIN_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
 

@@ -38,7 +38,7 @@ class MpcEnvBridge:
         commands = commands.to(self.device, torch.float32).contiguous()
         if actions.numel() != self.n * 12 or commands.numel() != self.n * 3:
             raise ValueError("actions [N, 12] and commands [N, 3] expected")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         _lib.check(_lib.lib().mpc_pack_commands_scaled(self.n, commands.data_ptr(), actions.data_ptr(), self._scale.ctypes.data, self._const.ctypes.data,
                                                        self._cmd.data_ptr(), stream), "mpc_pack_commands_scaled")
         return self.ctl.run(dof_state.reshape(self.n, 12, 2).contiguous(), root_states.contiguous(), self._cmd)

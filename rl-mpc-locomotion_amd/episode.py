@@ -20,11 +20,23 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import ci, ll, need_gpu, pvp, tensor_arg, text, vp
 
 # the entry points of include/mpc_episode.h (bound here, not in _lib.SYMBOLS or ppo.SYMBOLS)
-SYMBOLS = ["mpc_episode_create", "mpc_episode_destroy", "mpc_episode_bind", "mpc_episode_add", "mpc_episode_summary",
-           "mpc_episode_restart", "mpc_episode_clear", "mpc_episode_random_progress", "mpc_episode_last_error"]
-_BOUND = None
+DECLS = {
+    "mpc_episode_create": (ci, [pvp, ci, ci, ci]),
+    "mpc_episode_destroy": (None, [vp]),
+    "mpc_episode_bind": (ci, [vp, vp]),
+    "mpc_episode_add": (ci, [vp, vp, vp, vp, vp]),
+    "mpc_episode_summary": (ci, [vp, vp]),
+    "mpc_episode_restart": (ci, [vp, vp]),
+    "mpc_episode_clear": (ci, [vp, vp]),
+    "mpc_episode_random_progress": (ci, [vp, ci, ll, C.c_ulonglong, vp]),
+    "mpc_episode_last_error": (text, []),
+}
+SYMBOLS = list(DECLS)
+lib = _lib.binder(DECLS)             # libmpc_batch.so with the episode entry points bound
+check = _lib.checker(lib, "mpc_episode_last_error")
 
 MAX_GROUPS = 64
 # counters [COUNTERS + COUNTER_STRIDE * (1 + G)] int64: head, the window's count, then per block (0 overall, 1 + g group g) episodes, timed out, sum of lengths
@@ -41,55 +53,13 @@ class _Buffers(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("cur_return", "cur_length", "win_return", "win_length", "win_timed_out", "counters", "sums", "summary", "groups")]
 
 
-def lib():
-    """libmpc_batch.so with the episode entry points bound."""
-    global _BOUND
-    L = _lib.lib()
-    if _BOUND is not L:
-        vp, ci, ll = C.c_void_p, C.c_int, C.c_longlong
-        L.mpc_episode_create.argtypes = [C.POINTER(vp), ci, ci, ci]; L.mpc_episode_create.restype = ci
-        L.mpc_episode_destroy.argtypes = [vp]; L.mpc_episode_destroy.restype = None
-        L.mpc_episode_bind.argtypes = [vp, vp]; L.mpc_episode_bind.restype = ci
-        L.mpc_episode_add.argtypes = [vp, vp, vp, vp, vp]; L.mpc_episode_add.restype = ci
-        L.mpc_episode_summary.argtypes = [vp, vp]; L.mpc_episode_summary.restype = ci
-        L.mpc_episode_restart.argtypes = [vp, vp]; L.mpc_episode_restart.restype = ci
-        L.mpc_episode_clear.argtypes = [vp, vp]; L.mpc_episode_clear.restype = ci
-        L.mpc_episode_random_progress.argtypes = [vp, ci, ll, C.c_ulonglong, vp]; L.mpc_episode_random_progress.restype = ci
-        L.mpc_episode_last_error.argtypes = []; L.mpc_episode_last_error.restype = C.c_char_p
-        _BOUND = L
-    return L
-
-
-def check(rc, what):
-    if rc != _lib.MPC_OK:
-        raise _lib.MpcLibraryError(f"{what} failed ({rc}): {lib().mpc_episode_last_error().decode()}")
-
-
-def _need_gpu(what, *tensors):
-    if not torch.cuda.is_available():
-        raise _lib.MpcLibraryError(f"{what} needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
-    for t in tensors:
-        if not t.is_cuda:
-            raise _lib.MpcLibraryError(f"{what} runs on the device: a tensor on {t.device} was given; no CPU fallback")
-
-
-def _tensor(t, dtype, numel, name):
-    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-        raise ValueError(f"{name} must be a contiguous cuda {dtype} tensor with {numel} elements")
-    return t
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def random_progress(progress, max_len, seed):
     """rsl_rl's ``init_at_random_ep_len``: ``progress`` (contiguous cuda int64, e.g. ``BatchedRLTask.progress_buf``) <- integers uniform on
     [0, max_len), element i a function of (seed, i) alone.  Stream-ordered."""
-    _need_gpu("random_progress", progress)
-    _tensor(progress, torch.long, progress.numel(), "progress")
+    need_gpu("random_progress", progress)
+    tensor_arg(progress, torch.long, progress.numel(), "progress")
     with torch.cuda.device(progress.device):
-        check(lib().mpc_episode_random_progress(progress.data_ptr(), progress.numel(), int(max_len), int(seed) & (2 ** 64 - 1), _stream(progress.device)),
+        check(lib().mpc_episode_random_progress(progress.data_ptr(), progress.numel(), int(max_len), int(seed) & (2 ** 64 - 1), _lib.stream(progress.device)),
               "mpc_episode_random_progress")
     return progress
 
@@ -103,8 +73,7 @@ class EpisodeStats:
     that many spare elements on either side of every one of them."""
 
     def __init__(self, n, window=100, groups=None, num_groups=1, device=None, guard=0):
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("EpisodeStats needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        need_gpu("EpisodeStats")
         self.n, self.window, self.num_groups = int(n), int(window), int(num_groups)
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self._handle = C.c_void_p()
@@ -130,26 +99,22 @@ class EpisodeStats:
         with torch.cuda.device(self.device):
             check(lib().mpc_episode_bind(self._handle, C.addressof(b)), "mpc_episode_bind")
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib is not None and _lib._LIB is not None:
-            _lib._LIB.mpc_episode_destroy(h)
-            self._handle = None
+    __del__ = _lib.finalizer("mpc_episode_destroy")
 
     def add(self, rew, reset, time_outs):
         """One tick, in rsl_rl's order: accumulate, then every finished environment in ascending index appends (return, length, timed out) to the
         window, adds it to the totals and zeroes its accumulators.  Reads the task's buffers as they are; stream-ordered, no host synchronisation."""
-        _need_gpu("EpisodeStats.add", rew, reset, time_outs)
-        _tensor(rew, torch.float32, self.n, "rew"); _tensor(reset, torch.long, self.n, "reset"); _tensor(time_outs, torch.long, self.n, "time_outs")
-        check(lib().mpc_episode_add(self._handle, rew.data_ptr(), reset.data_ptr(), time_outs.data_ptr(), _stream(self.device)), "mpc_episode_add")
+        need_gpu("EpisodeStats.add", rew, reset, time_outs)
+        tensor_arg(rew, torch.float32, self.n, "rew"); tensor_arg(reset, torch.long, self.n, "reset"); tensor_arg(time_outs, torch.long, self.n, "time_outs")
+        check(lib().mpc_episode_add(self._handle, rew.data_ptr(), reset.data_ptr(), time_outs.data_ptr(), _lib.stream(self.device)), "mpc_episode_add")
 
     def restart(self):
         """Zeroes the in-flight accumulators: the episodes under way are dropped, the window and the totals stay."""
-        check(lib().mpc_episode_restart(self._handle, _stream(self.device)), "mpc_episode_restart")
+        check(lib().mpc_episode_restart(self._handle, _lib.stream(self.device)), "mpc_episode_restart")
 
     def clear(self):
         """Zeroes everything."""
-        check(lib().mpc_episode_clear(self._handle, _stream(self.device)), "mpc_episode_clear")
+        check(lib().mpc_episode_clear(self._handle, _lib.stream(self.device)), "mpc_episode_clear")
 
     @property
     def summary(self):
@@ -157,7 +122,7 @@ class EpisodeStats:
         brings the tensor up to date (the means are float64 sums over the window's slots divided by the count, 0.0 for an empty window) and returns
         the SAME tensor, which the next access rewrites: ``clone()`` a value that has to outlive it.  No host synchronisation.  The summary is not
         refreshed per tick because the means need the window after the tick's last launch; the trainer asks once per iteration."""
-        check(lib().mpc_episode_summary(self._handle, _stream(self.device)), "mpc_episode_summary")
+        check(lib().mpc_episode_summary(self._handle, _lib.stream(self.device)), "mpc_episode_summary")
         return self._summary
 
     @staticmethod

@@ -23,8 +23,7 @@ class BatchedLocomotion:
         iterations_between_mpc: the second constructor argument of ConvexMPCLocomotion (ConvexMPCLocomotion.py:58); None = what
         RobotRunnerMin passes, int(27 / (1000 controller_dt)) (RobotRunnerMin.py:21-22: 2 at the reference's controller_dt = 0.01)."""
         import torch
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("BatchedLocomotion needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        _lib.need_gpu("BatchedLocomotion")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         torch.cuda.set_device(self.device)
         rt = np.ascontiguousarray(robot_type, dtype=np.int32)
@@ -44,11 +43,7 @@ class BatchedLocomotion:
         _lib.check(_lib.lib().mpc_ctrl_set_solver(self._handle, 1 if solver == "exact" else 0), "mpc_ctrl_set_solver")
         self.torques = torch.zeros((self.n, 12), dtype=torch.float32, device=self.device)
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib is not None and _lib._LIB is not None:
-            _lib._LIB.mpc_ctrl_destroy(h)
-            self._handle = None
+    __del__ = _lib.finalizer("mpc_ctrl_destroy")
 
     def step(self, dof_states, est, commands, torques=None):
         """dof_states [N,12,2] (or [N*12,2]), est [N,18], commands [N,16]: contiguous cuda float32.
@@ -56,10 +51,9 @@ class BatchedLocomotion:
         import torch
         commands = self._full_commands(commands)
         for name, t, numel in (("dof_states", dof_states, self.n * 24), ("est", est, self.n * 18), ("commands", commands, self.n * 16)):
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-                raise ValueError(f"{name} must be a contiguous cuda float32 tensor with {numel} elements")
+            _lib.tensor_arg(t, torch.float32, numel, name)
         torques = self.torques if torques is None else torques
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         _lib.check(_lib.lib().mpc_ctrl_step(self._handle, dof_states.data_ptr(), est.data_ptr(), commands.data_ptr(),
                                             torques.data_ptr(), stream), "mpc_ctrl_step")
         return torques
@@ -74,10 +68,9 @@ class BatchedLocomotion:
         dof_states, body_states, commands = self._inputs(dof_states, body_states, commands)
         commands = self._full_commands(commands)
         for name, t, numel in (("dof_states", dof_states, self.n * 24), ("body_states", body_states, self.n * 13), ("commands", commands, self.n * 16)):
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-                raise ValueError(f"{name} must be a contiguous cuda float32 tensor with {numel} elements")
+            _lib.tensor_arg(t, torch.float32, numel, name)
         torques = self.torques if torques is None else torques
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         _lib.check(_lib.lib().mpc_ctrl_run(self._handle, dof_states.data_ptr(), body_states.data_ptr(), commands.data_ptr(),
                                            torques.data_ptr(), stream), "mpc_ctrl_run")
         return torques
@@ -109,7 +102,7 @@ class BatchedLocomotion:
 
     def reset(self, env_ids=None):
         import torch
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         if env_ids is None:
             _lib.check(_lib.lib().mpc_ctrl_reset(self._handle, None, 0, stream), "mpc_ctrl_reset")
             return
@@ -126,10 +119,9 @@ class BatchedLocomotion:
         the swing trajectories carry over.  A cuda int32 tensor [n] is taken as it is, stream-ordered (no host round trip, no synchronisation:
         BASELINE configs[2] cycles Trot / Walk / Bound every 50 steps); a host array is validated, copied and waited for."""
         import torch
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         if hasattr(gait_id, "is_cuda") and gait_id.is_cuda:
-            if gait_id.dtype != torch.int32 or not gait_id.is_contiguous() or gait_id.numel() != self.n:
-                raise ValueError("gait_id on the device must be a contiguous int32 tensor with one entry per robot")
+            _lib.tensor_arg(gait_id, torch.int32, self.n, "gait_id on the device")
             _lib.check(_lib.lib().mpc_ctrl_set_gait_device(self._handle, gait_id.data_ptr(), stream), "mpc_ctrl_set_gait_device")
             return
         gi = np.ascontiguousarray(gait_id.cpu().numpy() if hasattr(gait_id, "cpu") else gait_id, dtype=np.int32)
@@ -144,11 +136,10 @@ class BatchedLocomotion:
     def fsm_init(self, control_mode, operating_mode=1, check_safety=True):
         """``RobotRunnerFSM.init`` for every robot: fresh controller objects and ``ControlFSM.initialize`` into
         ``control_mode[r]`` (per-robot ``Parameters.control_mode``); operating_mode 0 TEST / 1 NORMAL."""
-        import torch
         cm = np.ascontiguousarray(control_mode, dtype=np.int32)
         if len(cm) != self.n:
             raise ValueError("control_mode must have one entry per robot")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         _lib.check(_lib.lib().mpc_ctrl_fsm_init(self._handle, cm.ctypes.data, int(operating_mode), int(bool(check_safety)), stream), "mpc_ctrl_fsm_init")
 
     def run_fsm(self, dof_states, body_states, commands, request, torques=None, estimated=False):
@@ -159,12 +150,10 @@ class BatchedLocomotion:
         dof_states, body_states, commands = self._inputs(dof_states, body_states, commands)
         commands = self._full_commands(commands)
         for name, t, numel in (("dof_states", dof_states, self.n * 24), ("body_states", body_states, self.n * 13), ("commands", commands, self.n * 16)):
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-                raise ValueError(f"{name} must be a contiguous cuda float32 tensor with {numel} elements")
-        if request.dtype != torch.int32 or not request.is_cuda or not request.is_contiguous() or request.numel() != self.n:
-            raise ValueError("request must be a contiguous cuda int32 tensor with one entry per robot")
+            _lib.tensor_arg(t, torch.float32, numel, name)
+        _lib.tensor_arg(request, torch.int32, self.n, "request")
         torques = self.torques if torques is None else torques
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         fn = _lib.lib().mpc_ctrl_run_fsm_estimated if estimated else _lib.lib().mpc_ctrl_run_fsm
         _lib.check(fn(self._handle, dof_states.data_ptr(), body_states.data_ptr(), commands.data_ptr(), request.data_ptr(), torques.data_ptr(), stream), "mpc_ctrl_run_fsm")
         return torques
@@ -172,7 +161,7 @@ class BatchedLocomotion:
     def fsm_reset(self, env_ids=None, control_mode=None):
         """``RobotRunnerFSM.reset`` (= ``ControlFSM.initialize``) for the given robots (all if None)."""
         import torch
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         cm = None if control_mode is None else np.ascontiguousarray(control_mode, dtype=np.int32)
         if cm is not None and cm.shape != (self.n,):
             raise ValueError(f"fsm_reset: control_mode must have one entry per robot ({self.n}), got shape {cm.shape}")
@@ -198,12 +187,11 @@ class BatchedLocomotion:
         ``compute_observations(dof, result, commands, self.weights)``), then the control FSM with those weights.
         ``policy`` is a ``weight_policy.WeightPolicy``; returns (torques [N,12], weights [N,12])."""
         import torch
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         dof_states, body_states, commands3 = self._inputs(dof_states, body_states, commands3)
         if prev_weights is not None and not hasattr(prev_weights, "is_cuda"):
             prev_weights = torch.from_numpy(np.ascontiguousarray(prev_weights, dtype=np.float32)).to(self.device)
-        if body_states.dtype != torch.float32 or not body_states.is_cuda or not body_states.is_contiguous() or body_states.numel() != self.n * 13:
-            raise ValueError("body_states must be a contiguous cuda float32 tensor with %d elements" % (self.n * 13))
+        _lib.tensor_arg(body_states, torch.float32, self.n * 13, "body_states")
         _lib.check(_lib.lib().mpc_ctrl_update_estimate(self._handle, body_states.data_ptr(), stream), "mpc_ctrl_update_estimate")
         # the observations straight from the controller's estimate and ground_normal_yaw (no copies), and the FSM tick without a second StateEstimator.update
         obs = policy.observations_from(self, dof_states, commands3, prev_weights)
@@ -216,7 +204,7 @@ class BatchedLocomotion:
         import torch
         est = torch.empty((self.n, 18), dtype=torch.float32, device=self.device)
         nrm = torch.empty((self.n, 3), dtype=torch.float32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         _lib.check(_lib.lib().mpc_ctrl_estimate(self._handle, est.data_ptr(), nrm.data_ptr(), stream), "mpc_ctrl_estimate")
         return est, nrm
 
@@ -234,11 +222,10 @@ class BatchedLocomotion:
 
     def set_iteration(self, iteration):
         """``cMPC.iterationCounter = iteration[r]`` for every robot (ConvexMPCLocomotion.py:62): gait phase and MPC cadence follow from it."""
-        import torch
         it = np.ascontiguousarray(iteration, dtype=np.int32)
         if it.shape != (self.n,):
             raise ValueError("iteration must have one entry per robot")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _lib.stream(self.device)
         _lib.check(_lib.lib().mpc_ctrl_set_iteration(self._handle, it.ctypes.data, stream), "mpc_ctrl_set_iteration")
 
     def enable_timing(self):

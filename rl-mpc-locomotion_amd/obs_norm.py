@@ -23,41 +23,26 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import ci, ll, need_gpu, pvp, text, vp
 
 # the entry points of include/mpc_obs_norm.h (bound here, not in any other module's list)
-SYMBOLS = ["mpc_obsnorm_create", "mpc_obsnorm_destroy", "mpc_obsnorm_bind", "mpc_obsnorm_apply", "mpc_obsnorm_clear", "mpc_obsnorm_last_error"]
-_BOUND = None
+DECLS = {
+    "mpc_obsnorm_create": (ci, [pvp, ci, C.c_float, ll]),
+    "mpc_obsnorm_destroy": (None, [vp]),
+    "mpc_obsnorm_bind": (ci, [vp, vp]),
+    "mpc_obsnorm_apply": (ci, [vp, vp, vp, ll, ci, vp]),
+    "mpc_obsnorm_clear": (ci, [vp, vp]),
+    "mpc_obsnorm_last_error": (text, []),
+}
+SYMBOLS = list(DECLS)
+lib = _lib.binder(DECLS)             # libmpc_batch.so with the normaliser's entry points bound
+check = _lib.checker(lib, "mpc_obsnorm_last_error")
 
 MAX_OBS, BLOCK_ROWS = 256, 32
 
 
 class _Buffers(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("state", "count", "mean", "var", "std")]
-
-
-def lib():
-    """libmpc_batch.so with the normaliser's entry points bound."""
-    global _BOUND
-    L = _lib.lib()
-    if _BOUND is not L:
-        vp, ci, ll = C.c_void_p, C.c_int, C.c_longlong
-        L.mpc_obsnorm_create.argtypes = [C.POINTER(vp), ci, C.c_float, ll]; L.mpc_obsnorm_create.restype = ci
-        L.mpc_obsnorm_destroy.argtypes = [vp]; L.mpc_obsnorm_destroy.restype = None
-        L.mpc_obsnorm_bind.argtypes = [vp, vp]; L.mpc_obsnorm_bind.restype = ci
-        L.mpc_obsnorm_apply.argtypes = [vp, vp, vp, ll, ci, vp]; L.mpc_obsnorm_apply.restype = ci
-        L.mpc_obsnorm_clear.argtypes = [vp, vp]; L.mpc_obsnorm_clear.restype = ci
-        L.mpc_obsnorm_last_error.argtypes = []; L.mpc_obsnorm_last_error.restype = C.c_char_p
-        _BOUND = L
-    return L
-
-
-def check(rc, what):
-    if rc != _lib.MPC_OK:
-        raise _lib.MpcLibraryError(f"{what} failed ({rc}): {lib().mpc_obsnorm_last_error().decode()}")
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 class ObsNormalizer:
@@ -67,8 +52,7 @@ class ObsNormalizer:
     [2, num_obs] float64.  ``guard`` (for tests) puts that many spare elements on either side of every one of them."""
 
     def __init__(self, num_obs, eps=1e-2, until=None, device=None, guard=0):
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("ObsNormalizer needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        need_gpu("ObsNormalizer")
         self.num_obs, self.eps, self.until = int(num_obs), float(eps), None if until is None else int(until)
         if self.until is not None and self.until < 0:
             raise ValueError("until must be None or a row count >= 0")
@@ -91,34 +75,27 @@ class ObsNormalizer:
             check(lib().mpc_obsnorm_bind(self._handle, C.addressof(b)), "mpc_obsnorm_bind")
         self.clear()
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib is not None and _lib._LIB is not None:
-            _lib._LIB.mpc_obsnorm_destroy(h)
-            self._handle = None
+    __del__ = _lib.finalizer("mpc_obsnorm_destroy")
 
     def __call__(self, obs, out=None, update=True):
         """``update``: the batch is first merged into the running state (rsl_rl's ``forward`` in training: update, then normalise), so the
         statistics include the rows they normalise.  ``out``: ``obs`` itself (in place) or any other contiguous [n, num_obs] float32 cuda tensor
         that does not otherwise overlap ``obs``; a fresh tensor when None.  Stream-ordered, no host synchronisation -- except that the first batch with
         more rows than any before it allocates the workspace of partials."""
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("ObsNormalizer needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
-        if not obs.is_cuda:
-            raise _lib.MpcLibraryError(f"ObsNormalizer runs on the device: a tensor on {obs.device} was given; no CPU fallback")
+        need_gpu("ObsNormalizer", obs)
         if obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[1] != self.num_obs or obs.shape[0] < 1 or not obs.is_contiguous() or obs.device != self.device:
             raise ValueError(f"obs must be a contiguous float32 [n >= 1, {self.num_obs}] tensor on {self.device}")
         if out is None:
             out = torch.empty_like(obs)
         elif out.dtype != torch.float32 or out.shape != obs.shape or not out.is_contiguous() or out.device != self.device:
             raise ValueError(f"out must be a contiguous float32 {tuple(obs.shape)} tensor on {self.device}")
-        check(lib().mpc_obsnorm_apply(self._handle, obs.data_ptr(), out.data_ptr(), obs.shape[0], 1 if update else 0, _stream(self.device)),
+        check(lib().mpc_obsnorm_apply(self._handle, obs.data_ptr(), out.data_ptr(), obs.shape[0], 1 if update else 0, _lib.stream(self.device)),
               "mpc_obsnorm_apply")
         return out
 
     def clear(self):
         """Back to the fresh state: count 0, mean 0, var 1 (and the float32 buffers with them)."""
-        check(lib().mpc_obsnorm_clear(self._handle, _stream(self.device)), "mpc_obsnorm_clear")
+        check(lib().mpc_obsnorm_clear(self._handle, _lib.stream(self.device)), "mpc_obsnorm_clear")
 
     def state_dict(self):
         """rsl_rl's four keys (``_mean``, ``_var``, ``_std`` float32 [1, D], ``count`` int64) and ``state64`` (float64 [2, D]: with it a resumed run

@@ -34,86 +34,40 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._lib import cd, ci, ll, need_gpu, pvp, tensor_arg, text, vp
 from .episode import S_EPISODES, S_MEAN_LENGTH, S_MEAN_RETURN, S_WINDOW_COUNT, S_WINDOW_TIMEOUTS, EpisodeStats, random_progress
 from .obs_norm import ObsNormalizer
 
 NUM_ACTIONS = 12
 
 # the entry points of include/mpc_ppo.h (bound here, not in _lib.SYMBOLS, which lists include/mpc_batch.h)
-SYMBOLS = ["mpc_ac_create", "mpc_ac_destroy", "mpc_ac_bind", "mpc_ac_act", "mpc_ac_evaluate", "mpc_ac_act_inference", "mpc_rollout_add",
-           "mpc_rollout_returns", "mpc_ppo_last_error"]
-_BOUND = None
-
-
-def lib():
-    """libmpc_batch.so with the PPO entry points bound."""
-    global _BOUND
-    L = _lib.lib()
-    if _BOUND is not L:
-        vp, ci, cd = C.c_void_p, C.c_int, C.c_double
-        L.mpc_ac_create.argtypes = [C.POINTER(vp), ci, vp, ci, vp]; L.mpc_ac_create.restype = ci
-        L.mpc_ac_destroy.argtypes = [vp]; L.mpc_ac_destroy.restype = None
-        L.mpc_ac_bind.argtypes = [vp, vp, vp, vp, vp, vp]; L.mpc_ac_bind.restype = ci
-        L.mpc_ac_act.argtypes = [vp, ci, vp, C.c_ulonglong, C.c_uint, vp, vp, vp, vp, vp, vp, vp]; L.mpc_ac_act.restype = ci
-        L.mpc_ac_evaluate.argtypes = [vp, ci, vp, vp, vp]; L.mpc_ac_evaluate.restype = ci
-        L.mpc_ac_act_inference.argtypes = [vp, ci, vp, vp, vp]; L.mpc_ac_act_inference.restype = ci
-        L.mpc_rollout_add.argtypes = [ci, cd, vp, vp, vp, vp, vp, vp, vp]; L.mpc_rollout_add.restype = ci
-        L.mpc_rollout_returns.argtypes = [ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp]; L.mpc_rollout_returns.restype = ci
-        L.mpc_ppo_last_error.argtypes = []; L.mpc_ppo_last_error.restype = C.c_char_p
-        _BOUND = L
-    return L
-
+DECLS = {
+    "mpc_ac_create": (ci, [pvp, ci, vp, ci, vp]),
+    "mpc_ac_destroy": (None, [vp]),
+    "mpc_ac_bind": (ci, [vp, vp, vp, vp, vp, vp]),
+    "mpc_ac_act": (ci, [vp, ci, vp, C.c_ulonglong, C.c_uint, vp, vp, vp, vp, vp, vp, vp]),
+    "mpc_ac_evaluate": (ci, [vp, ci, vp, vp, vp]),
+    "mpc_ac_act_inference": (ci, [vp, ci, vp, vp, vp]),
+    "mpc_rollout_add": (ci, [ci, cd, vp, vp, vp, vp, vp, vp, vp]),
+    "mpc_rollout_returns": (ci, [ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp]),
+    "mpc_ppo_last_error": (text, []),
+}
+SYMBOLS = list(DECLS)
+lib = _lib.binder(DECLS)                           # libmpc_batch.so with the PPO entry points bound
+check = _lib.checker(lib, "mpc_ppo_last_error")
 
 # the entry points of include/mpc_ppo_update.h, with a binding of their own
-UPDATE_SYMBOLS = ["mpc_ppo_update_create", "mpc_ppo_update_destroy", "mpc_ppo_update_tensors", "mpc_ppo_update_bind", "mpc_ppo_update_set_storage",
-                  "mpc_ppo_update_grads", "mpc_ppo_update_apply"]
-_UPDATE_BOUND = None
-
-
-def update_lib():
-    """libmpc_batch.so with the entry points of the device update bound (and those of ``lib()``)."""
-    global _UPDATE_BOUND
-    L = lib()
-    if _UPDATE_BOUND is not L:
-        vp, ci, cd, ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-        L.mpc_ppo_update_create.argtypes = [C.POINTER(vp), vp, ci]; L.mpc_ppo_update_create.restype = ci
-        L.mpc_ppo_update_destroy.argtypes = [vp]; L.mpc_ppo_update_destroy.restype = None
-        L.mpc_ppo_update_tensors.argtypes = [vp]; L.mpc_ppo_update_tensors.restype = ci
-        L.mpc_ppo_update_bind.argtypes = [vp, vp, vp, vp]; L.mpc_ppo_update_bind.restype = ci
-        L.mpc_ppo_update_set_storage.argtypes = [vp, ll] + [vp] * 8; L.mpc_ppo_update_set_storage.restype = ci
-        L.mpc_ppo_update_grads.argtypes = [vp, ci, vp, cd, cd, cd, ci, ci, cd, vp, vp, vp]; L.mpc_ppo_update_grads.restype = ci
-        L.mpc_ppo_update_apply.argtypes = [vp, cd, cd, cd, cd, ci, vp, vp]; L.mpc_ppo_update_apply.restype = ci
-        _UPDATE_BOUND = L
-    return L
-
-
-def check(rc, what):
-    if rc != _lib.MPC_OK:
-        raise _lib.MpcLibraryError(f"{what} failed ({rc}): {lib().mpc_ppo_last_error().decode()}")
-
-
-def _need_gpu(what, *tensors):
-    if not torch.cuda.is_available():
-        raise _lib.MpcLibraryError(f"{what} needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
-    for t in tensors:
-        if not t.is_cuda:
-            raise _lib.MpcLibraryError(f"{what} runs on the device: a tensor on {t.device} was given; no CPU fallback")
-
-
-def _f32(t, numel, name):
-    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-        raise ValueError(f"{name} must be a contiguous cuda float32 tensor with {numel} elements")
-    return t
-
-
-def _i64(t, numel, name):
-    if t.dtype != torch.long or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-        raise ValueError(f"{name} must be a contiguous cuda int64 tensor with {numel} elements")
-    return t
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
+UPDATE_DECLS = {
+    "mpc_ppo_update_create": (ci, [pvp, vp, ci]),
+    "mpc_ppo_update_destroy": (None, [vp]),
+    "mpc_ppo_update_tensors": (ci, [vp]),
+    "mpc_ppo_update_bind": (ci, [vp, vp, vp, vp]),
+    "mpc_ppo_update_set_storage": (ci, [vp, ll] + [vp] * 8),
+    "mpc_ppo_update_grads": (ci, [vp, ci, vp, cd, cd, cd, ci, ci, cd, vp, vp, vp]),
+    "mpc_ppo_update_apply": (ci, [vp, cd, cd, cd, cd, ci, vp, vp]),
+}
+UPDATE_SYMBOLS = list(UPDATE_DECLS)
+update_lib = _lib.binder(UPDATE_DECLS, base=lib)   # ... with the entry points of the device update bound (and those of ``lib()``)
 
 
 @dataclass
@@ -171,11 +125,7 @@ class ActorCritic(nn.Module):
         self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
         self._handle, self._bound_ptrs = None, None
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib is not None and _lib._LIB is not None:
-            _lib._LIB.mpc_ac_destroy(h)
-            self._handle = None
+    __del__ = _lib.finalizer("mpc_ac_destroy")
 
     # ---- the device path -----------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -185,7 +135,7 @@ class ActorCritic(nn.Module):
     def _ready(self, what, obs):
         """The handle, bound to the parameters' current device addresses (checked on every call: ``.to()`` moves them, an optimiser step
         or ``load_state_dict`` does not)."""
-        _need_gpu(what, obs, self.std)
+        need_gpu(what, obs, self.std)
         la, lc = self._linears(self.actor), self._linears(self.critic)
         params = [m.weight for m in la] + [m.bias for m in la] + [m.weight for m in lc] + [m.bias for m in lc] + [self.std]
         ptrs = tuple(p.data_ptr() for p in params)
@@ -207,7 +157,7 @@ class ActorCritic(nn.Module):
                                         arr(ptrs[2 * na + nc:2 * na + 2 * nc]), ptrs[-1]), "mpc_ac_bind")
             self._bound_ptrs = ptrs
         n = obs.shape[0]
-        _f32(obs, n * self.num_obs, "obs")
+        tensor_arg(obs, torch.float32, n * self.num_obs, "obs")
         return n
 
     def bind_order(self):
@@ -226,11 +176,11 @@ class ActorCritic(nn.Module):
             out = dict(actions=e(12), actions_log_prob=e(1), values=e(1), mu=e(12), sigma=e(12))
         else:
             for k, w in (("actions", 12), ("actions_log_prob", 1), ("values", 1), ("mu", 12), ("sigma", 12)):
-                _f32(out[k], n * w, k)
+                tensor_arg(out[k], torch.float32, n * w, k)
         eps = torch.empty((n, 12), dtype=torch.float32, device=dev) if return_eps else None
         check(lib().mpc_ac_act(self._handle, n, obs.data_ptr(), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, out["actions"].data_ptr(),
                                out["actions_log_prob"].data_ptr(), out["values"].data_ptr(), out["mu"].data_ptr(), out["sigma"].data_ptr(),
-                               eps.data_ptr() if return_eps else None, _stream(dev)), "mpc_ac_act")
+                               eps.data_ptr() if return_eps else None, _lib.stream(dev)), "mpc_ac_act")
         if return_eps:
             out = dict(out, eps=eps)
         return out
@@ -238,15 +188,15 @@ class ActorCritic(nn.Module):
     def evaluate(self, obs, out=None):
         """The critic alone: obs [n, num_obs] -> values [n, 1]."""
         n = self._ready("ActorCritic.evaluate", obs)
-        values = torch.empty((n, 1), dtype=torch.float32, device=obs.device) if out is None else _f32(out, n, "out")
-        check(lib().mpc_ac_evaluate(self._handle, n, obs.data_ptr(), values.data_ptr(), _stream(obs.device)), "mpc_ac_evaluate")
+        values = torch.empty((n, 1), dtype=torch.float32, device=obs.device) if out is None else tensor_arg(out, torch.float32, n, "out")
+        check(lib().mpc_ac_evaluate(self._handle, n, obs.data_ptr(), values.data_ptr(), _lib.stream(obs.device)), "mpc_ac_evaluate")
         return values
 
     def act_inference(self, obs):
         """The actor's mean: obs [n, num_obs] -> [n, 12], bit for bit the raw action of ``WeightPolicy.step`` on the same weights."""
         n = self._ready("ActorCritic.act_inference", obs)
         mean = torch.empty((n, 12), dtype=torch.float32, device=obs.device)
-        check(lib().mpc_ac_act_inference(self._handle, n, obs.data_ptr(), mean.data_ptr(), _stream(obs.device)), "mpc_ac_act_inference")
+        check(lib().mpc_ac_act_inference(self._handle, n, obs.data_ptr(), mean.data_ptr(), _lib.stream(obs.device)), "mpc_ac_act_inference")
         return mean
 
     # ---- the differentiable path of the update ---------------------------------------------------------------------------------------------
@@ -279,24 +229,24 @@ class RolloutStorage:
         """``PPO.process_env_step`` + ``add_transitions`` for the slot ``act`` has just written (``self.step``, then advanced): rewards[t] = rew +
         gamma * (values[t] * time_outs), dones[t] = reset, read from the task's own buffers (rew float32, reset and time_outs int64) before its next
         step rewrites them; ``obs``, the observations ``act`` was given, are copied into observations[t]."""
-        _need_gpu("RolloutStorage.add", rew, self.rewards)
+        need_gpu("RolloutStorage.add", rew, self.rewards)
         t = self.step
         if t >= self.T:
             raise RuntimeError("rollout storage overflow: clear() after compute_returns")
-        _f32(rew, self.n, "rew"); _i64(reset, self.n, "reset"); _i64(time_outs, self.n, "time_outs")
+        tensor_arg(rew, torch.float32, self.n, "rew"); tensor_arg(reset, torch.long, self.n, "reset"); tensor_arg(time_outs, torch.long, self.n, "time_outs")
         if obs is not None:
             self.observations[t].copy_(obs)
         check(lib().mpc_rollout_add(self.n, float(gamma), rew.data_ptr(), reset.data_ptr(), time_outs.data_ptr(), self.values[t].data_ptr(),
-                                    self.rewards[t].data_ptr(), self.dones[t].data_ptr(), _stream(self.device)), "mpc_rollout_add")
+                                    self.rewards[t].data_ptr(), self.dones[t].data_ptr(), _lib.stream(self.device)), "mpc_rollout_add")
         self.step += 1
 
     def compute_returns(self, last_values, gamma, lam):
         """``RolloutStorage.compute_returns``: GAE over the T slots into ``returns``, then ``advantages`` = returns - values normalised over all
         T N values."""
-        _need_gpu("RolloutStorage.compute_returns", last_values, self.rewards)
-        _f32(last_values, self.n, "last_values")
+        need_gpu("RolloutStorage.compute_returns", last_values, self.rewards)
+        tensor_arg(last_values, torch.float32, self.n, "last_values")
         check(lib().mpc_rollout_returns(self.n, self.T, float(gamma), float(lam), self.rewards.data_ptr(), self.dones.data_ptr(), self.values.data_ptr(),
-                                        last_values.data_ptr(), self.returns.data_ptr(), self.advantages.data_ptr(), _stream(self.device)),
+                                        last_values.data_ptr(), self.returns.data_ptr(), self.advantages.data_ptr(), _lib.stream(self.device)),
               "mpc_rollout_returns")
 
     def mini_batch_generator(self, num_mini_batches, num_epochs=8):
@@ -334,18 +284,14 @@ class PPO:
         self._handle, self._max_rows, self._bound, self._storage_ptrs, self._ac_ptrs = None, 0, None, None, None
         self.lr_device, self.record_lr, self.lr_trace = None, False, None       # record_lr (for tests): keep the rate after every decision in lr_trace
         if backend == "hip":
-            _need_gpu('PPO(backend="hip")', actor_critic.std)
+            need_gpu('PPO(backend="hip")', actor_critic.std)
             group = self.optimizer.param_groups[0]
             if group["amsgrad"] or group["weight_decay"] != 0 or group["maximize"]:
                 raise ValueError("the device update restates plain Adam: no amsgrad, weight decay or maximize")
             update_lib()
             self.lr_device = torch.full((1,), self.learning_rate, dtype=torch.float64, device=actor_critic.std.device)
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib is not None and _lib._LIB is not None:
-            _lib._LIB.mpc_ppo_update_destroy(h)
-            self._handle = None
+    __del__ = _lib.finalizer("mpc_ppo_update_destroy")
 
     def adapt_learning_rate(self, kl_mean):
         """The adaptive schedule: lr / 1.5 (not below 1e-5) if kl > 2 desired_kl, lr * 1.5 (not above 1e-2) if 0 < kl < desired_kl / 2."""
@@ -435,7 +381,7 @@ class PPO:
     def _update_hip(self, storage, indices=None):
         c = self.cfg
         dev = self.actor_critic.std.device
-        _need_gpu("PPO.update", storage.observations, self.actor_critic.std)
+        need_gpu("PPO.update", storage.observations, self.actor_critic.std)
         if storage.device != dev:
             raise _lib.MpcLibraryError("PPO.update: the storage and the parameters live on different devices")
         total = storage.n * storage.T
@@ -444,12 +390,12 @@ class PPO:
             raise ValueError("fewer rows than mini-batches")
         if indices is None:
             indices = torch.randperm(c.num_mini_batches * size, device=dev)
-        _i64(indices, c.num_mini_batches * size, "indices")
+        tensor_arg(indices, torch.long, c.num_mini_batches * size, "indices")
         step = self._device_state(size)
         L = update_lib()
         flat = (storage.observations, storage.actions, storage.values, storage.advantages, storage.returns, storage.actions_log_prob, storage.mu, storage.sigma)
         widths = (self.actor_critic.num_obs, NUM_ACTIONS, 1, 1, 1, 1, NUM_ACTIONS, NUM_ACTIONS)
-        ptrs = tuple(_f32(t, total * w, "storage").data_ptr() for t, w in zip(flat, widths))
+        ptrs = tuple(tensor_arg(t, torch.float32, total * w, "storage").data_ptr() for t, w in zip(flat, widths))
         if ptrs != self._storage_ptrs:
             check(L.mpc_ppo_update_set_storage(self._handle, total, *ptrs), "mpc_ppo_update_set_storage")
             self._storage_ptrs = ptrs
@@ -460,7 +406,7 @@ class PPO:
         terms = torch.empty((k, 4), dtype=torch.float32, device=dev)
         if self.record_lr:
             self.lr_trace = torch.empty(k, dtype=torch.float64, device=dev)
-        stream = _stream(dev)
+        stream = _lib.stream(dev)
         params = self.actor_critic.bind_order()
         with torch.cuda.device(dev):
             for e in range(c.num_learning_epochs):
@@ -520,8 +466,7 @@ class PPOTrainer:
     tensor; ``self.obs`` is then the normalised observation.  ``evaluate`` and ``get_inference_policy`` normalise without updating."""
 
     def __init__(self, env, cfg=None, seed=1, device=None, update="torch", normalize_obs=False, obs_norm_eps=1e-2, obs_norm_until=None):
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("PPOTrainer needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        need_gpu("PPOTrainer")
         self.cfg = cfg if cfg is not None else PPOConfig()
         self.env, self.seed = env, int(seed)
         self.device = torch.device(device if device is not None else getattr(env, "device", f"cuda:{torch.cuda.current_device()}"))

@@ -32,14 +32,24 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
+from ._lib import ci, pvp, text, vp
 
 NUM_OBS = 48
 # the order of the sum at aliengo.py:398
 REWARD_TERMS = ("lin_vel_xy", "lin_vel_z", "ang_vel_xy", "ang_vel_z", "torque", "collision")
 
 # the entry points of include/mpc_task.h (bound here, not in _lib.SYMBOLS, which lists include/mpc_batch.h)
-SYMBOLS = ["mpc_task_create", "mpc_task_destroy", "mpc_task_buffers", "mpc_task_begin", "mpc_task_finish", "mpc_task_last_error"]
-_BOUND = None
+DECLS = {
+    "mpc_task_create": (ci, [pvp, ci, vp]),
+    "mpc_task_destroy": (None, [vp]),
+    "mpc_task_buffers": (ci, [vp, vp]),
+    "mpc_task_begin": (ci, [vp, vp]),
+    "mpc_task_finish": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]),
+    "mpc_task_last_error": (text, []),
+}
+SYMBOLS = list(DECLS)
+lib = _lib.binder(DECLS)               # libmpc_batch.so with the task entry points bound
+check = _lib.checker(lib, "mpc_task_last_error")
 
 
 class _Config(C.Structure):            # mpc_task_config
@@ -50,27 +60,6 @@ class _Config(C.Structure):            # mpc_task_config
 
 class _BufferSet(C.Structure):         # mpc_task_buffer_set
     _fields_ = [(name, C.c_void_p) for name in ("d_progress", "d_reset", "d_timeout", "d_reset_ids", "d_commands", "d_obs", "d_rew")]
-
-
-def lib():
-    """libmpc_batch.so with the task entry points bound."""
-    global _BOUND
-    L = _lib.lib()
-    if _BOUND is not L:
-        vp, ci = C.c_void_p, C.c_int
-        L.mpc_task_create.argtypes = [C.POINTER(vp), ci, vp]; L.mpc_task_create.restype = ci
-        L.mpc_task_destroy.argtypes = [vp]; L.mpc_task_destroy.restype = None
-        L.mpc_task_buffers.argtypes = [vp, vp]; L.mpc_task_buffers.restype = ci
-        L.mpc_task_begin.argtypes = [vp, vp]; L.mpc_task_begin.restype = ci
-        L.mpc_task_finish.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]; L.mpc_task_finish.restype = ci
-        L.mpc_task_last_error.argtypes = []; L.mpc_task_last_error.restype = C.c_char_p
-        _BOUND = L
-    return L
-
-
-def check(rc, what):
-    if rc != _lib.MPC_OK:
-        raise _lib.MpcLibraryError(f"{what} failed ({rc}): {lib().mpc_task_last_error().decode()}")
 
 
 @dataclass
@@ -129,13 +118,6 @@ class TaskConfig:
         return c
 
 
-def _f32(t, numel, name):
-    import torch
-    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-        raise ValueError(f"{name} must be a contiguous cuda float32 tensor with {numel} elements")
-    return t
-
-
 class TaskPostPhysics:
     """The task's buffers and the two kernels, for N environments.  ``commands`` [N,3], ``progress_buf``, ``reset_buf``, ``timeout_buf`` [N]
     (int64, as the reference's), ``obs_buf`` [N,48] and ``rew_buf`` [N] are public cuda tensors; a caller may overwrite ``commands``.
@@ -143,8 +125,7 @@ class TaskPostPhysics:
 
     def __init__(self, n, cfg=None, device=None):
         import torch
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("TaskPostPhysics needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        _lib.need_gpu("TaskPostPhysics")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         torch.cuda.set_device(self.device)
         self.cfg = cfg if cfg is not None else TaskConfig()
@@ -162,21 +143,13 @@ class TaskPostPhysics:
                         self.commands.data_ptr(), self.obs_buf.data_ptr(), self.rew_buf.data_ptr())
         check(lib().mpc_task_buffers(self._handle, C.addressof(bs)), "mpc_task_buffers")
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib is not None and _lib._LIB is not None:
-            _lib._LIB.mpc_task_destroy(h)
-            self._handle = None
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self.device).cuda_stream
+    __del__ = _lib.finalizer("mpc_task_destroy")
 
     def begin(self):
         """vec_task.py:326 and aliengo.py:274-278, :344-349: ``timeout_buf``, ``progress_buf += 1``, and for the environments whose ``reset_buf``
         is set fresh ``commands`` and ``progress_buf = 0``.  Returns ``reset_ids`` [N] int32 (r where environment r is being reset, -1 elsewhere)
         for the device reset entry points; stream-ordered, no host synchronisation."""
-        check(lib().mpc_task_begin(self._handle, self._stream()), "mpc_task_begin")
+        check(lib().mpc_task_begin(self._handle, _lib.stream(self.device)), "mpc_task_begin")
         return self.reset_ids
 
     def finish(self, root_states, dof_state, actions, torques, contact_forces=None, base_index=0, knee_indices=None, hip_indices=None, fell=None):
@@ -185,13 +158,14 @@ class TaskPostPhysics:
         is Isaac Gym's net contact force tensor; fell [N] (bool / uint8) is the toy plant's flag, taken as base contact."""
         import torch
         n = self.n
-        _f32(root_states, n * 13, "root_states"); _f32(dof_state, n * 24, "dof_state"); _f32(actions, n * 12, "actions"); _f32(torques, n * 12, "torques")
+        for name, t, numel in (("root_states", root_states, n * 13), ("dof_state", dof_state, n * 24), ("actions", actions, n * 12), ("torques", torques, n * 12)):
+            _lib.tensor_arg(t, torch.float32, numel, name)
         cf_ptr, bodies, knee, hip = None, 0, None, None
         if contact_forces is not None:
             if contact_forces.dim() != 3 or contact_forces.shape[0] != n or contact_forces.shape[2] != 3:
                 raise ValueError("contact_forces: [N, bodies, 3] expected")
             bodies = int(contact_forces.shape[1])
-            _f32(contact_forces, n * bodies * 3, "contact_forces")
+            _lib.tensor_arg(contact_forces, torch.float32, n * bodies * 3, "contact_forces")
             if knee_indices is None or hip_indices is None:
                 raise ValueError("contact_forces need knee_indices and hip_indices")
             knee = np.ascontiguousarray(knee_indices.cpu().numpy() if hasattr(knee_indices, "cpu") else knee_indices, dtype=np.int32).reshape(-1)
@@ -206,7 +180,7 @@ class TaskPostPhysics:
             fell_ptr = fell.data_ptr()
         check(lib().mpc_task_finish(self._handle, root_states.data_ptr(), dof_state.data_ptr(), actions.data_ptr(), torques.data_ptr(), cf_ptr, bodies,
                                     int(base_index), None if knee is None else knee.ctypes.data, None if hip is None else hip.ctypes.data, fell_ptr,
-                                    self._stream()), "mpc_task_finish")
+                                    _lib.stream(self.device)), "mpc_task_finish")
         return self.obs_buf, self.rew_buf, self.reset_buf
 
 
@@ -218,8 +192,7 @@ class BatchedRLTask:
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
                  **bridge_args):
         import torch
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("BatchedRLTask needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        _lib.need_gpu("BatchedRLTask")
         from .env_bridge import MpcEnvBridge
         from .toy_sim import BatchedToySim
         self.cfg = cfg if cfg is not None else TaskConfig()

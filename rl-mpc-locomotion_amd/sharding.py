@@ -7,6 +7,7 @@ per-robot torques ([n_local, 12] float32 per rank) when one consumer wants the w
 device.  ``torch.distributed`` with backend "nccl" is RCCL on ROCm; the CPU tests run the same code over
 "gloo".
 """
+from . import _lib
 
 
 def shard_bounds(n_total: int, rank: int, world: int):
@@ -61,7 +62,6 @@ class PeerExchange:
         import ctypes as C
         import torch
         import torch.distributed as dist
-        from . import _lib
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -84,39 +84,25 @@ class PeerExchange:
         if self.world > 1:
             dist.barrier(group=group)      # every rank has opened every region before anybody writes
 
-    @staticmethod
-    def _check(rc, what):
-        from . import _lib
-        if rc != 0:
-            raise _lib.MpcLibraryError(f"{what} failed ({rc}): {_lib.lib().mpc_peer_last_error().decode()}")
+    _check = staticmethod(_lib.checker(_lib.lib, "mpc_peer_last_error"))
+    __del__ = _lib.finalizer("mpc_peer_destroy", "_h")
 
     def put(self, local):
         import torch
-        from . import _lib
-        if local.dtype != torch.float32 or not local.is_cuda or not local.is_contiguous() or local.numel() != self.n_local * self.width:
-            raise ValueError("PeerExchange.put: a contiguous cuda float32 [n_local, width] tensor")
-        self._check(_lib.lib().mpc_peer_put(self._h, local.data_ptr(), self.lo, self.n_local, torch.cuda.current_stream(self.device).cuda_stream), "mpc_peer_put")
+        _lib.tensor_arg(local, torch.float32, self.n_local * self.width, "PeerExchange.put: local")
+        self._check(_lib.lib().mpc_peer_put(self._h, local.data_ptr(), self.lo, self.n_local, _lib.stream(self.device)), "mpc_peer_put")
 
     def wait(self):
         import torch
-        from . import _lib
         out = torch.empty((self.n_total, self.width), dtype=torch.float32, device=self.device)
-        self._check(_lib.lib().mpc_peer_wait(self._h, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream), "mpc_peer_wait")
+        self._check(_lib.lib().mpc_peer_wait(self._h, out.data_ptr(), _lib.stream(self.device)), "mpc_peer_wait")
         return out
 
     def timeouts(self):
         import ctypes as C
-        from . import _lib
         n = C.c_int(0)
         self._check(_lib.lib().mpc_peer_timeouts(self._h, C.addressof(n)), "mpc_peer_timeouts")
         return n.value
-
-    def __del__(self):
-        from . import _lib
-        h = getattr(self, "_h", None)
-        if h and _lib is not None and _lib._LIB is not None:
-            _lib._LIB.mpc_peer_destroy(h)
-            self._h = None
 
 
 class ShardedLocomotion:

@@ -22,8 +22,15 @@ construction, not in the draws (``numpy.random.default_rng(seed)``, not the glob
 """
 import numpy as np
 
+from ._lib import cd, ci, text, vp
+
 # the entry points of include/mpc_terrain.h (bound by toy_sim.lib(), whose handle they act on; not in _lib.SYMBOLS, which lists include/mpc_batch.h)
-SYMBOLS = ["mpc_terrain_attach", "mpc_terrain_query", "mpc_terrain_last_error"]
+DECLS = {
+    "mpc_terrain_attach": (ci, [vp, ci, ci, vp, cd, cd, cd, cd, vp]),
+    "mpc_terrain_query": (ci, [vp, vp, ci, vp, vp, vp]),
+    "mpc_terrain_last_error": (text, []),
+}
+SYMBOLS = list(DECLS)
 
 
 class Terrain:

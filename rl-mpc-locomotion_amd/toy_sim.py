@@ -21,49 +21,32 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import cd, ci, pvp, text, vp
 from .quadruped import ROBOT_TABLE64
+from .terrain import DECLS as TERRAIN_DECLS
 
 F64_LEN = 49      # per-robot state record: pos3 quat4 (xyzw) v3 w3 q12 qd12 anchor12
 I32_LEN = 9       # contact4 lift4 fell
 
 # the entry points of include/mpc_sim.h (bound here, not in _lib.SYMBOLS, which lists include/mpc_batch.h)
-SYMBOLS = ["mpc_sim_create", "mpc_sim_destroy", "mpc_sim_size", "mpc_sim_step", "mpc_sim_observe", "mpc_sim_reset_device", "mpc_sim_get_state",
-           "mpc_sim_set_state", "mpc_sim_flags", "mpc_sim_last_error"]
-# (include/mpc_terrain.h's are listed in terrain.SYMBOLS and bound here as well: they act on the same handle)
-_BOUND = None
-
-
-def lib():
-    """libmpc_batch.so with the toy-plant entry points bound."""
-    global _BOUND
-    L = _lib.lib()
-    if _BOUND is not L:
-        vp, ci, cd = C.c_void_p, C.c_int, C.c_double
-        L.mpc_terrain_attach.argtypes = [vp, ci, ci, vp, cd, cd, cd, cd, vp]; L.mpc_terrain_attach.restype = ci
-        L.mpc_terrain_query.argtypes = [vp, vp, ci, vp, vp, vp]; L.mpc_terrain_query.restype = ci
-        L.mpc_terrain_last_error.argtypes = []; L.mpc_terrain_last_error.restype = C.c_char_p
-        L.mpc_sim_create.argtypes = [C.POINTER(vp), ci, vp, ci, vp, vp, vp, cd]; L.mpc_sim_create.restype = ci
-        L.mpc_sim_destroy.argtypes = [vp]; L.mpc_sim_destroy.restype = None
-        L.mpc_sim_size.argtypes = [vp]; L.mpc_sim_size.restype = ci
-        L.mpc_sim_step.argtypes = [vp, vp, vp, vp, vp]; L.mpc_sim_step.restype = ci
-        L.mpc_sim_observe.argtypes = [vp, vp, vp, vp]; L.mpc_sim_observe.restype = ci
-        L.mpc_sim_reset_device.argtypes = [vp, vp, ci, vp]; L.mpc_sim_reset_device.restype = ci
-        L.mpc_sim_get_state.argtypes = [vp, vp, vp]; L.mpc_sim_get_state.restype = ci
-        L.mpc_sim_set_state.argtypes = [vp, vp, vp]; L.mpc_sim_set_state.restype = ci
-        L.mpc_sim_flags.argtypes = [vp, vp, vp, vp]; L.mpc_sim_flags.restype = ci
-        L.mpc_sim_last_error.argtypes = []; L.mpc_sim_last_error.restype = C.c_char_p
-        _BOUND = L
-    return L
-
-
-def check(rc, what):
-    if rc != _lib.MPC_OK:
-        raise _lib.MpcLibraryError(f"{what} failed ({rc}): {lib().mpc_sim_last_error().decode()}")
-
-
-def check_terrain(rc, what):
-    if rc != _lib.MPC_OK:
-        raise _lib.MpcLibraryError(f"{what} failed ({rc}): {lib().mpc_terrain_last_error().decode()}")
+DECLS = {
+    "mpc_sim_create": (ci, [pvp, ci, vp, ci, vp, vp, vp, cd]),
+    "mpc_sim_destroy": (None, [vp]),
+    "mpc_sim_size": (ci, [vp]),
+    "mpc_sim_step": (ci, [vp, vp, vp, vp, vp]),
+    "mpc_sim_observe": (ci, [vp, vp, vp, vp]),
+    "mpc_sim_reset_device": (ci, [vp, vp, ci, vp]),
+    "mpc_sim_get_state": (ci, [vp, vp, vp]),
+    "mpc_sim_set_state": (ci, [vp, vp, vp]),
+    "mpc_sim_flags": (ci, [vp, vp, vp, vp]),
+    "mpc_sim_last_error": (text, []),
+}
+SYMBOLS = list(DECLS)
+# libmpc_batch.so with the toy-plant entry points bound (include/mpc_terrain.h's are listed in terrain.SYMBOLS and bound here as well: they act on
+# the same handle)
+lib = _lib.binder({**DECLS, **TERRAIN_DECLS})
+check = _lib.checker(lib, "mpc_sim_last_error")
+check_terrain = _lib.checker(lib, "mpc_terrain_last_error")
 
 
 class BatchedToySim:
@@ -77,8 +60,7 @@ class BatchedToySim:
             raise ValueError("terrain and a non-zero slope exclude each other: the terrain replaces the plane")
         if terrain is None and origin is not None:
             raise ValueError("origin needs a terrain")
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("BatchedToySim needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        _lib.need_gpu("BatchedToySim")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         torch.cuda.set_device(self.device)
         rt = np.ascontiguousarray(robot_type, dtype=np.int32).reshape(-1)
@@ -101,26 +83,17 @@ class BatchedToySim:
                                                    float(terrain.x0), float(terrain.y0), self.origin.ctypes.data), "mpc_terrain_attach")
         self._observe()
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib is not None and _lib._LIB is not None:
-            _lib._LIB.mpc_sim_destroy(h)
-            self._handle = None
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self.device).cuda_stream
+    __del__ = _lib.finalizer("mpc_sim_destroy")
 
     def _observe(self):
-        check(lib().mpc_sim_observe(self._handle, self.dof_state.data_ptr(), self.root_states.data_ptr(), self._stream()), "mpc_sim_observe")
+        check(lib().mpc_sim_observe(self._handle, self.dof_state.data_ptr(), self.root_states.data_ptr(), _lib.stream(self.device)), "mpc_sim_observe")
 
     def step(self, torques):
         """One tick of every robot that has not fallen, torques [N,12] contiguous cuda float32 (FL FR RL RR x hip, thigh, calf).
         Updates dof_state and root_states in place and returns them; stream-ordered, no host synchronisation."""
         import torch
-        if torques.dtype != torch.float32 or not torques.is_cuda or not torques.is_contiguous() or torques.numel() != self.n * 12:
-            raise ValueError(f"torques must be a contiguous cuda float32 tensor with {self.n * 12} elements")
-        check(lib().mpc_sim_step(self._handle, torques.data_ptr(), self.dof_state.data_ptr(), self.root_states.data_ptr(), self._stream()), "mpc_sim_step")
+        _lib.tensor_arg(torques, torch.float32, self.n * 12, "torques")
+        check(lib().mpc_sim_step(self._handle, torques.data_ptr(), self.dof_state.data_ptr(), self.root_states.data_ptr(), _lib.stream(self.device)), "mpc_sim_step")
         return self.dof_state, self.root_states
 
     def reset_idx(self, env_ids):
@@ -136,7 +109,7 @@ class BatchedToySim:
             d_ids = torch.from_numpy(ids).to(self.device)
         if d_ids.numel() == 0:
             return
-        check(lib().mpc_sim_reset_device(self._handle, d_ids.data_ptr(), d_ids.numel(), self._stream()), "mpc_sim_reset_device")
+        check(lib().mpc_sim_reset_device(self._handle, d_ids.data_ptr(), d_ids.numel(), _lib.stream(self.device)), "mpc_sim_reset_device")
         self._observe()
 
     def terrain_query(self, xy, normals=True):
@@ -148,13 +121,13 @@ class BatchedToySim:
         k = int(xy.shape[0])
         z = torch.zeros((k,), dtype=torch.float64, device=self.device)
         nrm = torch.zeros((k, 3), dtype=torch.float64, device=self.device) if normals else None
-        check_terrain(lib().mpc_terrain_query(self._handle, xy.data_ptr(), k, z.data_ptr(), None if nrm is None else nrm.data_ptr(), self._stream()),
+        check_terrain(lib().mpc_terrain_query(self._handle, xy.data_ptr(), k, z.data_ptr(), None if nrm is None else nrm.data_ptr(), _lib.stream(self.device)),
                       "mpc_terrain_query")
         return z, nrm
 
     def flags(self):
         """(contact [N,4] bool, fell [N] bool) cuda tensors of the current state (the same two tensors on every call)."""
-        check(lib().mpc_sim_flags(self._handle, self._contact.data_ptr(), self._fell.data_ptr(), self._stream()), "mpc_sim_flags")
+        check(lib().mpc_sim_flags(self._handle, self._contact.data_ptr(), self._fell.data_ptr(), _lib.stream(self.device)), "mpc_sim_flags")
         return self._contact, self._fell
 
     def get_state(self):

@@ -20,8 +20,7 @@ class WeightPolicy:
         """layers: [(weight [out, in], bias [out]), ...] float32 (torch Linear layout).
         obs_scales = (linearVelocityScale, angularVelocityScale, dofPositionScale, dofVelocityScale), cfg/task/*.yaml."""
         import torch
-        if not torch.cuda.is_available():
-            raise _lib.MpcLibraryError("WeightPolicy needs a GPU (torch.cuda.is_available() is False); no CPU fallback")
+        _lib.need_gpu("WeightPolicy")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         torch.cuda.set_device(self.device)
         ws = [np.ascontiguousarray(w, dtype=np.float32) for w, _ in layers]
@@ -53,31 +52,17 @@ class WeightPolicy:
             layers.append((w.detach().cpu().numpy() if hasattr(w, "detach") else w, b.detach().cpu().numpy() if hasattr(b, "detach") else b))
         return cls(layers, **kw)
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib is not None and _lib._LIB is not None:
-            _lib._LIB.mpc_policy_destroy(h)
-            self._handle = None
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    @staticmethod
-    def _chk(name, t, numel):
-        import torch
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-            raise ValueError(f"{name} must be a contiguous cuda float32 tensor with {numel} elements")
+    __del__ = _lib.finalizer("mpc_policy_destroy")
 
     def step(self, obs, return_actions=False):
         """obs [n, 48] -> MPC weights [n, 12] (and the raw actor output if asked)."""
         import torch
         n = obs.shape[0]
-        self._chk("obs", obs, n * self.num_obs)
+        _lib.tensor_arg(obs, torch.float32, n * self.num_obs, "obs")
         weights = torch.empty((n, self.num_actions), dtype=torch.float32, device=self.device)
         actions = torch.empty_like(weights) if return_actions else None
         _lib.check(_lib.lib().mpc_policy_step(self._handle, n, obs.data_ptr(), actions.data_ptr() if return_actions else None,
-                                              weights.data_ptr(), self._stream()), "mpc_policy_step")
+                                              weights.data_ptr(), _lib.stream(self.device)), "mpc_policy_step")
         return (weights, actions) if return_actions else weights
 
     def compute_observations(self, dof_states, est, ground_normal_yaw, commands, actions):
@@ -87,10 +72,10 @@ class WeightPolicy:
         n = commands.shape[0]
         for name, t, k in (("dof_states", dof_states, 24), ("est", est, 18), ("ground_normal_yaw", ground_normal_yaw, 3),
                            ("commands", commands, 3), ("actions", actions, 12)):
-            self._chk(name, t, n * k)
+            _lib.tensor_arg(t, torch.float32, n * k, name)
         obs = torch.empty((n, 48), dtype=torch.float32, device=self.device)
         _lib.check(_lib.lib().mpc_policy_observations(n, dof_states.data_ptr(), est.data_ptr(), ground_normal_yaw.data_ptr(), commands.data_ptr(),
-                                                      actions.data_ptr(), self._scales.ctypes.data, obs.data_ptr(), self._stream()),
+                                                      actions.data_ptr(), self._scales.ctypes.data, obs.data_ptr(), _lib.stream(self.device)),
                    "mpc_policy_observations")
         return obs
 
@@ -101,17 +86,17 @@ class WeightPolicy:
         import torch
         n = ctl.n
         for name, t, k in (("dof_states", dof_states, 24), ("commands", commands, 3), ("actions", actions, 12)):
-            self._chk(name, t, n * k)
+            _lib.tensor_arg(t, torch.float32, n * k, name)
         obs = torch.empty((n, 48), dtype=torch.float32, device=self.device)
         _lib.check(_lib.lib().mpc_ctrl_policy_observations(ctl._handle, dof_states.data_ptr(), commands.data_ptr(), actions.data_ptr(), self._scales.ctypes.data,
-                                                           obs.data_ptr(), self._stream()), "mpc_ctrl_policy_observations")
+                                                           obs.data_ptr(), _lib.stream(self.device)), "mpc_ctrl_policy_observations")
         return obs
 
     def pack_commands(self, commands, weights):
         """[n,3] velocity commands + [n,12] MPC weights -> the [n,16] command record of BatchedLocomotion.run/step."""
         import torch
         n = commands.shape[0]
-        self._chk("commands", commands, n * 3); self._chk("weights", weights, n * 12)
+        _lib.tensor_arg(commands, torch.float32, n * 3, "commands"); _lib.tensor_arg(weights, torch.float32, n * 12, "weights")
         out = torch.empty((n, 16), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().mpc_pack_commands(n, commands.data_ptr(), weights.data_ptr(), out.data_ptr(), self._stream()), "mpc_pack_commands")
+        _lib.check(_lib.lib().mpc_pack_commands(n, commands.data_ptr(), weights.data_ptr(), out.data_ptr(), _lib.stream(self.device)), "mpc_pack_commands")
         return out

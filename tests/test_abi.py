@@ -10,10 +10,13 @@ from rl_mpc_locomotion_amd import _lib
 from tests.helpers import ROOT
 
 
-def _declared():
-    src = open(os.path.join(ROOT, "include", "mpc_batch.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(mpc_[a-z0-9_]+)\s*\(", src)))
+def _source(header):
+    """include/<header> without its comments."""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+
+
+def _declared(header="mpc_batch.h"):
+    return sorted(set(re.findall(r"\b(mpc_[a-z0-9_]+)\s*\(", _source(header))))
 
 
 def test_header_symbols_are_exported():
@@ -25,6 +28,38 @@ def test_header_symbols_are_exported():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/mpc_batch.h but not exported"
     assert sorted(_lib.SYMBOLS) == names
+
+
+# every header under include/ and the lib() that binds its entry points
+BINDERS = {"mpc_batch.h": ("_lib", "lib"), "mpc_sim.h": ("toy_sim", "lib"), "mpc_terrain.h": ("toy_sim", "lib"), "mpc_task.h": ("rl_task", "lib"),
+           "mpc_ppo.h": ("ppo", "lib"), "mpc_ppo_update.h": ("ppo", "update_lib"), "mpc_episode.h": ("episode", "lib"),
+           "mpc_obs_norm.h": ("obs_norm", "lib")}
+
+
+def _prototypes(header):
+    """[(name, return type, parameter count)] of the mpc_* prototypes of include/<header>."""
+    out = []
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(mpc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _source(header)):
+        params = params.strip()
+        out.append((name, " ".join(ret.split()), 0 if params in ("", "void") else params.count(",") + 1))
+    return out
+
+
+@pytest.mark.parametrize("header", sorted(os.listdir(os.path.join(ROOT, "include"))))
+def test_bindings_match_the_prototypes(header, monkeypatch):
+    """Every prototype of every header has a ctypes binding once its module's lib() alone has run on a freshly loaded library object: argtypes
+    set, as many of them as the prototype has parameters, and no restype exactly where the prototype returns void."""
+    import importlib
+    module, fn = BINDERS[header]
+    protos = _prototypes(header)
+    assert sorted(p[0] for p in protos) == _declared(header), "a declaration that the prototype pattern does not parse"
+    monkeypatch.setattr(_lib, "_LIB", None)          # (a new CDLL object: nothing that another module or test bound carries over)
+    L = getattr(importlib.import_module("rl_mpc_locomotion_amd." + module), fn)()
+    for name, ret, count in protos:
+        f = getattr(L, name)
+        assert f.argtypes is not None, f"{name} is declared in include/{header} but {module}.{fn}() does not bind it"
+        assert len(f.argtypes) == count, f"{name}: {len(f.argtypes)} argtypes, the prototype has {count} parameters"
+        assert (f.restype is None) == (ret == "void"), f"{name}: restype {f.restype}, the prototype returns {ret}"
 
 
 def test_input_len_and_horizons():
