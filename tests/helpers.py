@@ -16,6 +16,27 @@ GRF_RTOL = 1e-5
 GRF_RTOL_STRESS = 2e-4
 
 
+# The derived bound of the float32 kernel tests (tests/test_ppo_gemm_gpu.py, tests/test_policy_layer_gpu.py): a float32 sum of n terms, in any order and
+# fused or not, lies within gamma(n) * sum |terms| of the exact sum (Higham, Accuracy and Stability of Numerical Algorithms, section 3.1).
+U = 2.0 ** -24
+
+
+def gamma(n):
+    return n * U / (1.0 - n * U)
+
+
+def ulp32(x):
+    """The float32 spacing of the binade that holds |x| (float64 in), at least the smallest subnormal."""
+    _, e = np.frexp(np.abs(np.asarray(x, np.float64)))
+    return np.maximum(np.ldexp(1.0, e - 24), 2.0 ** -149)
+
+
+def draw(rng, shape, scale, lo=0.5, hi=2.0):
+    """float32 values of either sign whose magnitudes are log-uniform in [lo, hi] * scale: no term of a product sum is small beside the others."""
+    mag = np.exp(rng.uniform(np.log(lo), np.log(hi), shape))
+    return (rng.choice([-1.0, 1.0], shape) * mag * scale).astype(np.float32)
+
+
 def grf_rtol(name):
     return GRF_RTOL_STRESS if name.endswith("stress") else GRF_RTOL
 

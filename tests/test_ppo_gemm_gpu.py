@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import ROOT
+from tests.helpers import ROOT, U, draw as _draw, gamma, ulp32  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -35,7 +35,6 @@ HIPCC = "/opt/rocm/bin/hipcc"
 FORWARD, BACKWARD_DATA, BACKWARD_WEIGHT = 0, 1, 2                 # pgemm::Kind
 KIND_NAMES = ("forward", "backward data", "backward weight")
 TILES = {"narrow": 0, "wide": 1}                                  # gemm_kernel<KIND, 2, 1>, gemm_kernel<KIND, 2, 2>
-U = 2.0 ** -24
 SENTINEL = 0x7FA5C3E1                                             # a NaN with a payload: no kernel result has these bits
 
 # Two problems per launch, so one problem's workgroups leave early; the second slot of the last case is empty (tiles_m = 0).  pad: the leading
@@ -92,21 +91,6 @@ def harness(tmp_path_factory):
 
 
 # ------------------------------------------------------------------ inputs and float64 references (host only; shared by the two tiles)
-
-def gamma(n):
-    return n * U / (1.0 - n * U)
-
-
-def ulp32(x):
-    """The float32 spacing of the binade that holds |x| (float64 in), at least the smallest subnormal."""
-    _, e = np.frexp(np.abs(np.asarray(x, np.float64)))
-    return np.maximum(np.ldexp(1.0, e - 24), 2.0 ** -149)
-
-
-def _draw(rng, shape, scale):
-    mag = np.exp(rng.uniform(np.log(0.5), np.log(2.0), shape))
-    return (rng.choice([-1.0, 1.0], shape) * mag * scale).astype(np.float32)
-
 
 def _index(rng, rows, limit):
     """An int64 row index with repeats, unsorted, with values below 0 and at or above limit (the kernel clamps to [0, limit))."""

@@ -100,9 +100,9 @@ def test_parameters_are_read_in_place():
     assert not torch.equal(after["sigma"], before["sigma"])
 
 
-@pytest.mark.parametrize("n", (1, 63, 65))
-def test_add_and_compute_returns_match_the_torch_loop(n):
-    T = 5
+def _add_and_compute_returns(n, T):
+    """T adds and compute_returns on a storage of n environments against the torch loop (check_returns), and a rerun.  Returns what the device read and
+    wrote as [T, n] numpy arrays: (returns - values, normalised advantages)."""
     rew, reset, time_outs, values, last = ppo_ref.rollout(T, n, seed=30 + n)
     st = P.RolloutStorage(n, T, DEV)
     st.values.copy_(values)
@@ -117,10 +117,33 @@ def test_add_and_compute_returns_match_the_torch_loop(n):
         st.add(d_rew[0], d_reset[0], d_to[0], GAMMA)
     st.compute_returns(last.to(DEV), GAMMA, LAM)
     h = lambda x: x[..., 0].cpu().numpy()
-    check_returns(h(st.rewards), h(st.returns), h(st.returns) - h(st.values), h(st.advantages), rew, reset, time_outs, values, last, f"device n = {n}")
+    raw = h(st.returns) - h(st.values)
+    check_returns(h(st.rewards), h(st.returns), raw, h(st.advantages), rew, reset, time_outs, values, last, f"device n = {n}, T = {T}")
     first = st.advantages.clone()
     st.compute_returns(last.to(DEV), GAMMA, LAM)                                 # fixed-order float64 sums: a rerun is bit-identical
     assert torch.equal(first, st.advantages)
+    return raw, h(first)
+
+
+@pytest.mark.parametrize("n", (1, 63, 65))
+def test_add_and_compute_returns_match_the_torch_loop(n):
+    _add_and_compute_returns(n, 5)
+
+
+# normalise_kernel is one workgroup of 1024 lanes, each walking i += 1024: m = n T around one trip (1023, 1024, 1025), two trips and one element
+# (2049), and PPOConfig's own 4096 x 24 = 98 304 (96 trips, every lane of the tree loaded)
+@pytest.mark.parametrize("n, T", ((341, 3), (1024, 1), (205, 5), (683, 3), (4096, 24)))
+def test_compute_returns_normalises_beyond_one_trip(n, T):
+    """On top of check_returns: the kernel's moments are float64 and differ from the sequential ones in summation order only, so the float32 rounding
+    of (a - mean) / (std + 1e-8) may flip against that of ppo_ref.normalise in float64 but cannot move further: one float32 ulp, everywhere."""
+    from tests.helpers import ulp32
+    assert n * T in (1023, 1024, 1025, 2049, 98304)
+    raw, adv = _add_and_compute_returns(n, T)
+    want = ppo_ref.normalise(torch.from_numpy(raw).double()).float().numpy()
+    assert np.isfinite(adv).all() and adv.shape == want.shape == (T, n)
+    off = np.abs(adv.astype(np.float64) - want.astype(np.float64)) / ulp32(want)
+    print(f"device n = {n}, T = {T}: normalised advantages within {off.max():.2f} ulp of the rounded float64 evaluation, {int((off > 0).sum())} of {off.size} differ")
+    assert (off <= 1.0).all(), f"n = {n}, T = {T}: {int((off > 1.0).sum())} normalised advantages more than one ulp off, worst {off.max():.2f}"
 
 
 def test_sampler_on_the_device():
