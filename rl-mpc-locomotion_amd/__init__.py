@@ -9,8 +9,9 @@ from .rl_task import BatchedRLTask, TaskConfig, TaskPostPhysics  # noqa: E402,F4
 _PPO = ("ActorCritic", "RolloutStorage", "PPO", "PPOConfig", "PPOTrainer")
 _EPISODE = ("EpisodeStats",)
 _OBS_NORM = ("ObsNormalizer", "fold_normalizer")
+_CURRICULUM = ("TerrainCurriculum",)
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM]
 
 
 def __getattr__(name):
@@ -24,4 +25,7 @@ def __getattr__(name):
     if name in _OBS_NORM:
         from . import obs_norm
         return getattr(obs_norm, name)
+    if name in _CURRICULUM:
+        from . import curriculum
+        return getattr(curriculum, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

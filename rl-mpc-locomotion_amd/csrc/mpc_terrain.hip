@@ -1,5 +1,5 @@
 // mpc_terrain.hip -- the C ABI of include/mpc_terrain.h: toy_sim.h's HeightField instantiations of toy_init / toy_step on the device, one lane
-// per robot as in mpc_sim.hip, and a point query of the surface.  The field is int16 in HBM, read with plain 2-byte loads (four per lookup): a
+// per robot as in mpc_sim.hip, a point query of the surface, and the accessors of the origin array (mpc_curriculum.h).  The field is int16 in HBM, read with plain 2-byte loads (four per lookup): a
 // 500 x 500 field is 500 KB and stays in the caches.  mpc_sim.hip owns the handle (mpc_sim_internal.h) and launches these through
 // simint::terrain_launch_* once a terrain is attached.
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mpc_terrain.h"
+#include "mpc_curriculum.h"
 #include "mpc_host.h"
 #include "mpc_sim_internal.h"
 #include "toy_sim.h"
@@ -167,6 +168,25 @@ int mpc_terrain_query(mpc_sim *s, const double *d_xy, int k, double *d_z, double
   DeviceGuard guard_(s->device);
   hipLaunchKernelGGL(terrain_query_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), terrain_args(s), d_xy, k, d_z, d_normal);
   HIP_TRY(hipGetLastError());
+  return MPC_OK;
+}
+
+// (declared in mpc_curriculum.h) the origin array of a sim with a terrain: its device address, and its contents on the host
+int mpc_terrain_origins(mpc_sim *s, double **d_origin) {
+  if (!d_origin) return fail(MPC_E_ARG, "mpc_terrain_origins: null result pointer");
+  if (!s) return fail(MPC_E_ARG, "mpc_terrain_origins: null sim handle");
+  if (!s->d_origin) return fail(MPC_E_ARG, "mpc_terrain_origins: the sim has no terrain attached");
+  *d_origin = s->d_origin;
+  return MPC_OK;
+}
+
+int mpc_terrain_get_origins(mpc_sim *s, double *h_origin) {
+  if (!h_origin) return fail(MPC_E_ARG, "mpc_terrain_get_origins: null result pointer");
+  if (!s) return fail(MPC_E_ARG, "mpc_terrain_get_origins: null sim handle");
+  if (!s->d_origin) return fail(MPC_E_ARG, "mpc_terrain_get_origins: the sim has no terrain attached");
+  DeviceGuard guard_(s->device);
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h_origin, s->d_origin, sizeof(double) * 2 * (size_t)s->n, hipMemcpyDeviceToHost));
   return MPC_OK;
 }
 

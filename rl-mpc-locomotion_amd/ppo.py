@@ -516,7 +516,8 @@ class PPOTrainer:
         """``num_iterations`` of collection + update.  Appends one record per iteration to ``infos`` (read from the device once, after the
         update) and returns the list.  Besides the losses a record carries rsl_rl's episode statistics: ``mean_episode_return`` and
         ``mean_episode_length`` over the last 100 finished episodes (0.0 while there are none), ``episodes_in_window``, ``timeouts_in_window`` and
-        the cumulative ``episodes_finished``.  ``init_at_random_ep_len``: before the first collection ``env.progress_buf`` is set to integers
+        the cumulative ``episodes_finished``; on an environment with a terrain ``curriculum`` also ``mean_terrain_level`` and ``terrain_level_by_type``
+        as they stand after the iteration.  ``init_at_random_ep_len``: before the first collection ``env.progress_buf`` is set to integers
         uniform on [0, ``env.cfg.max_episode_length``), drawn from the trainer's seed, so that the environments do not time out on one tick.  As in
         rsl_rl's ``learn``, this happens at the start of EVERY call that sets the flag (the same draw each time: it moves episodes that are under way),
         so set it on the first call only."""
@@ -533,18 +534,22 @@ class PPOTrainer:
             value_loss, surrogate = self.alg.update(self.storage)
             stats = torch.stack((mean_reward, done_rate, value_loss, surrogate, self.actor_critic.std.detach().mean())).double()
             episodes = self.episode_stats.summary                                # float64, on the device: rides along in the one read
+            curriculum = getattr(self.env, "curriculum", None)
+            tail = (episodes,) if curriculum is None else (episodes, curriculum.summary())      # (a terrain curriculum's levels ride along too)
             if self.alg.backend == "hip":                                        # and so does the device's learning rate
-                stats = torch.cat((stats, self.alg.lr_device, episodes)).tolist()
+                stats = torch.cat((stats, self.alg.lr_device, *tail)).tolist()
                 self.alg.sync_learning_rate(stats[5])
                 ep = stats[6:]
             else:
-                stats = torch.cat((stats, episodes)).tolist()
+                stats = torch.cat((stats, *tail)).tolist()
                 ep = stats[5:]
             self.iteration += 1
             self.infos.append(dict(iter=self.iteration, mean_reward=stats[0], done_rate=stats[1], value_loss=stats[2], surrogate_loss=stats[3],
                                    mean_noise_std=stats[4], learning_rate=self.alg.learning_rate, mean_episode_return=ep[S_MEAN_RETURN],
                                    mean_episode_length=ep[S_MEAN_LENGTH], episodes_in_window=int(ep[S_WINDOW_COUNT]),
                                    episodes_finished=int(ep[S_EPISODES]), timeouts_in_window=int(ep[S_WINDOW_TIMEOUTS])))
+            if curriculum is not None:
+                self.infos[-1].update(curriculum.record(ep[episodes.numel():], curriculum.num_types))
         return self.infos
 
     def evaluate(self, num_ticks, groups=None, num_groups=1):

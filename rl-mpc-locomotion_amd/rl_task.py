@@ -186,12 +186,19 @@ class TaskPostPhysics:
 
 class BatchedRLTask:
     """``VecTask.step`` / ``reset`` for N robots on the toy plant: MpcEnvBridge (actions -> torques), BatchedToySim (the simulator), and
-    the two task kernels.  ``terrain`` / ``origin`` put the robots on a height field (BatchedToySim).  See the module text for what the toy
-    cannot do."""
+    the two task kernels.  ``terrain`` / ``origin`` put the robots on a height field (BatchedToySim).  ``curriculum`` (a
+    ``curriculum.TerrainCurriculum`` for as many environments; not together with ``terrain`` or ``origin``): the terrain and the initial origins are
+    the curriculum's, and every reset moves the robot to the tile its new level names.  See the module text for what the toy cannot do."""
 
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
-                 **bridge_args):
+                 curriculum=None, **bridge_args):
         import torch
+        if curriculum is not None:
+            if terrain is not None or origin is not None:
+                raise ValueError("curriculum brings its own terrain and origins: terrain= / origin= exclude it")
+            if curriculum.n != len(np.asarray(robot_type).reshape(-1)):
+                raise ValueError(f"the curriculum holds {curriculum.n} environments, robot_type {len(np.asarray(robot_type).reshape(-1))}")
+            terrain, origin = curriculum.terrain, curriculum.origins0
         _lib.need_gpu("BatchedRLTask")
         from .env_bridge import MpcEnvBridge
         from .toy_sim import BatchedToySim
@@ -200,6 +207,9 @@ class BatchedRLTask:
         self.device, self.n = self.bridge.device, self.bridge.n
         self.num_envs, self.num_obs, self.num_actions = self.n, NUM_OBS, 12
         self.sim = BatchedToySim(robot_type, slope=slope, yaw0=yaw0, dt=self.cfg.dt, device=self.device, terrain=terrain, origin=origin)
+        self.curriculum = curriculum
+        if curriculum is not None:
+            curriculum.bind(self.sim)
         self.task = TaskPostPhysics(self.n, self.cfg, device=self.device)
         t = self.task
         self.commands, self.progress_buf, self.reset_buf, self.timeout_buf = t.commands, t.progress_buf, t.reset_buf, t.timeout_buf
@@ -216,6 +226,8 @@ class BatchedRLTask:
         torch.clamp(actions.to(self.device, torch.float32).reshape(self.n, 12), -self.cfg.clip_actions, self.cfg.clip_actions, out=self.actions)    # :312
         self.torques = self.bridge.pre_physics_step(self.actions, sim.dof_state, sim.root_states, self.commands)                # aliengo.py:227-263
         sim.step(self.torques)                                                                                                  # gym.simulate
+        if self.curriculum is not None:    # the flags begin is about to consume, the finished episode's commands, the root states before the reset
+            self.curriculum.update(self.reset_buf, sim.root_states, self.commands)
         ids = t.begin()                                                                                                         # :326, aliengo.py:274-278
         self.bridge.ctl.reset(ids)                                                                                              # aliengo.py:330-334
         sim.reset_idx(ids)                                                                                                      # aliengo.py:336-342

@@ -5,6 +5,11 @@ tools/closed_loop_rate.py (controller + toy plant alone) and against the same ha
 blocks of ticks that end in a synchronise (median of the blocks, the three loops alternating): robot-ticks / s.  The shader clock is recorded as
 bench.py --full records it (device_state).
     python tools/rl_task_rate.py [--ticks 100] [--blocks 7] [--out profiles/r08_rl_task.json]
+--curriculum times the terrain curriculum instead (rl_mpc_locomotion_amd.curriculum) on legged_gym's 10 x 20 grid of 8 m tiles, in one process: the
+`update` kernel alone and the `begin` kernel alone from HIP events inside the running loop (median, p10, p90 over the ticks), and BatchedRLTask.step
+with the curriculum against the same task on the same field and origins without one, in alternating blocks; with --learn K also what K iterations of
+PPO from level 0 do to the levels, and PPOTrainer.evaluate's falls per terrain type before and after.
+    python tools/rl_task_rate.py --curriculum [--learn 30] [--out profiles/r14_curriculum.json]
 The kernel-trace stats of the same step: rocprofv3 --kernel-trace --stats ... -- python tools/rl_task_rate.py --ticks 50 --quick"""
 import argparse
 import json
@@ -119,16 +124,119 @@ def med(x):
     return float(np.median(x))
 
 
+def spread(x):
+    return {"median_ms": med(x), "p10_ms": float(np.percentile(x, 10)), "p90_ms": float(np.percentile(x, 90))}
+
+
+def tick_curriculum(task, actions, ev):
+    """BatchedRLTask.step's statements with a curriculum, with events around `update` and around `begin`"""
+    sim, t = task.sim, task.task
+    tau = task.bridge.pre_physics_step(actions, sim.dof_state, sim.root_states, task.commands)
+    sim.step(tau)
+    ev[0].record()
+    task.curriculum.update(task.reset_buf, sim.root_states, task.commands)
+    ev[1].record()
+    ids = t.begin()
+    ev[2].record()
+    task.bridge.ctl.reset(ids)
+    sim.reset_idx(ids)
+    _, fell = sim.flags()
+    t.finish(sim.root_states, sim.dof_state, actions, tau, fell=fell)
+
+
+def curriculum_report(args, dev, n, actions):
+    from bench import device_state
+    from rl_mpc_locomotion_amd.curriculum import TerrainCurriculum
+    from rl_mpc_locomotion_amd.terrain import TerrainGrid
+    grid = TerrainGrid(num_levels=10, num_types=20, tile_length=8.0, tile_width=8.0, seed=0)
+    cfg = TaskConfig(**CFG)
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "ticks_per_block": args.ticks, "blocks": args.blocks,
+           "grid": {"levels": grid.num_levels, "types": grid.num_types, "tile_m": grid.tile_length, "nodes": [grid.terrain.rows, grid.terrain.cols]},
+           "max_init_level": args.max_init_level, "device_state": {"before": device_state(0)}}
+
+    def make_pair():
+        cur = TerrainCurriculum(grid, n, max_init_level=args.max_init_level, seed=0, device=dev, episode_length_s=cfg.episode_length_s)
+        with_c = BatchedRLTask([0] * n, [TROT] * n, cfg=cfg, horizon=10, yaw0=yaw, flat_ground=True, device=dev, curriculum=cur)
+        without = BatchedRLTask([0] * n, [TROT] * n, cfg=cfg, horizon=10, yaw0=yaw, flat_ground=True, device=dev, terrain=grid.terrain, origin=cur.origins0)
+        return cur, with_c, without
+    cur, with_c, without = make_pair()
+    loops = {"step_with_curriculum": with_c, "step_without": without}
+    for task in loops.values():
+        task.reset()
+        for _ in range(20):
+            task.step(actions)
+    torch.cuda.synchronize()
+    wall = {k: [] for k in loops}
+    for _ in range(args.blocks):          # the two loops alternate, block by block
+        for name, task in loops.items():
+            t0 = time.perf_counter()
+            for _ in range(args.ticks):
+                task.step(actions)
+            torch.cuda.synchronize()
+            wall[name].append(time.perf_counter() - t0)
+    for name, w in wall.items():
+        res[name] = {"ms_per_tick_median": med(w) / args.ticks * 1e3, "ms_per_tick_min": min(w) / args.ticks * 1e3, "ms_per_tick_max": max(w) / args.ticks * 1e3,
+                     "robot_ticks_per_s": n * args.ticks / med(w)}
+    res["with_over_without_ms_per_tick"] = res["step_with_curriculum"]["ms_per_tick_median"] / res["step_without"]["ms_per_tick_median"]
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.ticks * 2)]
+    for e in ev:
+        tick_curriculum(with_c, actions, e)
+    torch.cuda.synchronize()
+    upd, beg = np.array([e[0].elapsed_time(e[1]) for e in ev]), np.array([e[1].elapsed_time(e[2]) for e in ev])
+    res["update_kernel"], res["begin_kernel"], res["events"] = spread(upd), spread(beg), len(ev)
+    res["update_over_begin_median"] = med(upd) / med(beg)
+    res["condition_update_at_most_twice_begin"] = bool(med(upd) <= 2.0 * med(beg))
+    s = cur.summary().tolist()
+    res["after_timing"] = {"fallen_fraction": {k: float(t.sim.flags()[1].float().mean().item()) for k, t in loops.items()},
+                           "resets_seen_per_env_mean": float(cur.counts.float().mean().item()), **TerrainCurriculum.record(s, grid.num_types)}
+    res["device_state"]["mid"] = device_state(0, smi=False)
+    if args.learn > 0:                    # a finding, not a condition: does the toy's policy climb?
+        from rl_mpc_locomotion_amd.ppo import PPOConfig, PPOTrainer
+        res["learn"] = {}
+        for normalize in (False, True):
+            cur = TerrainCurriculum(grid, n, max_init_level=0, seed=0, device=dev, episode_length_s=TaskConfig().episode_length_s)
+            task = BatchedRLTask([0] * n, [TROT] * n, cfg=TaskConfig(), horizon=10, yaw0=yaw, flat_ground=True, device=dev, curriculum=cur)
+            trainer = PPOTrainer(task, PPOConfig(), seed=1, update="hip", normalize_obs=normalize)
+            keys = ("episodes", "time_outs", "terminations", "mean_length")
+            ev0 = trainer.evaluate(args.eval_ticks, groups=cur.types, num_groups=grid.num_types)
+            lv0 = TerrainCurriculum.record(cur.summary().tolist(), grid.num_types)
+            infos = trainer.learn(args.learn, init_at_random_ep_len=True)[-args.learn:]
+            ev1 = trainer.evaluate(args.eval_ticks, groups=cur.types, num_groups=grid.num_types)
+            lv1 = TerrainCurriculum.record(cur.summary().tolist(), grid.num_types)
+            brief = lambda e: {"overall": {k: e[k] for k in keys}, "terminations_by_type": [g["terminations"] for g in e["groups"]],
+                               "episodes_by_type": [g["episodes"] for g in e["groups"]]}
+            res["learn"]["normalize_obs_" + str(normalize).lower()] = {
+                "iterations": args.learn, "eval_ticks": args.eval_ticks, "tile_kind_of_type": list(grid.kind),
+                "mean_terrain_level_per_iteration": [i["mean_terrain_level"] for i in infos], "mean_reward_per_iteration": [i["mean_reward"] for i in infos],
+                "mean_episode_length_per_iteration": [i["mean_episode_length"] for i in infos],
+                "terrain_level_by_type_last": infos[-1]["terrain_level_by_type"], "levels_after_first_evaluate": lv0, "levels_after_last_evaluate": lv1,
+                "evaluate_before": brief(ev0), "evaluate_after": brief(ev1)}
+    res["device_state"]["after"] = device_state(0, smi=False)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--ticks", type=int, default=100, help="ticks per block")
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--robots", type=int, default=4096)
     ap.add_argument("--quick", action="store_true", help="one block of BatchedRLTask.step only (for a kernel trace)")
+    ap.add_argument("--curriculum", action="store_true", help="time the terrain curriculum (see the head of this file)")
+    ap.add_argument("--max-init-level", type=int, default=9, help="--curriculum: initial levels uniform in 0 .. this")
+    ap.add_argument("--learn", type=int, default=0, help="--curriculum: also K PPO iterations from level 0, with evaluate() before and after")
+    ap.add_argument("--eval-ticks", type=int, default=500)
     ap.add_argument("--out")
     args = ap.parse_args()
     dev, n = "cuda:0", args.robots
     actions = torch.zeros((n, 12), dtype=torch.float32, device=dev)
+    if args.curriculum:
+        res = curriculum_report(args, dev, n, actions)
+        print(json.dumps(res, indent=1))
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        sys.exit(0)
     if args.quick:
         task = make(n, dev)
         for _ in range(args.ticks):
