@@ -10,8 +10,9 @@ _PPO = ("ActorCritic", "RolloutStorage", "PPO", "PPOConfig", "PPOTrainer")
 _EPISODE = ("EpisodeStats",)
 _OBS_NORM = ("ObsNormalizer", "fold_normalizer")
 _CURRICULUM = ("TerrainCurriculum",)
+_HEIGHT_SCAN = ("HeightScan",)
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN]
 
 
 def __getattr__(name):
@@ -28,4 +29,7 @@ def __getattr__(name):
     if name in _CURRICULUM:
         from . import curriculum
         return getattr(curriculum, name)
+    if name in _HEIGHT_SCAN:
+        from . import height_scan
+        return getattr(height_scan, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

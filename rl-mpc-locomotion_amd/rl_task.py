@@ -188,11 +188,22 @@ class BatchedRLTask:
     """``VecTask.step`` / ``reset`` for N robots on the toy plant: MpcEnvBridge (actions -> torques), BatchedToySim (the simulator), and
     the two task kernels.  ``terrain`` / ``origin`` put the robots on a height field (BatchedToySim).  ``curriculum`` (a
     ``curriculum.TerrainCurriculum`` for as many environments; not together with ``terrain`` or ``origin``): the terrain and the initial origins are
-    the curriculum's, and every reset moves the robot to the tile its new level names.  See the module text for what the toy cannot do."""
+    the curriculum's, and every reset moves the robot to the tile its new level names.  ``height_scan`` (a ``height_scan.HeightScan`` for as many
+    environments; needs ``terrain`` or ``curriculum``): ``obs_buf`` becomes the task's own wide buffer [N, ``height_scan.width(48)``] -- the 48
+    columns, the scan of the terrain around the base, a zero pad -- ``num_obs`` its width, and ``measured_heights`` [N, P] the heights in metres.
+    See the module text for what the toy cannot do."""
 
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
-                 curriculum=None, **bridge_args):
+                 curriculum=None, height_scan=None, **bridge_args):
         import torch
+        if height_scan is not None:
+            if terrain is None and curriculum is None:
+                raise ValueError("height_scan measures a terrain: give terrain= or curriculum=")
+            if height_scan.n != len(np.asarray(robot_type).reshape(-1)):
+                raise ValueError(f"the height scan holds {height_scan.n} environments, robot_type {len(np.asarray(robot_type).reshape(-1))}")
+            clip_obs = (cfg if cfg is not None else TaskConfig()).clip_observations
+            if np.float32(height_scan.obs_clip) != np.float32(clip_obs):
+                raise ValueError(f"the height scan clips its columns to {height_scan.obs_clip}, the task's clip_observations is {clip_obs}")
         if curriculum is not None:
             if terrain is not None or origin is not None:
                 raise ValueError("curriculum brings its own terrain and origins: terrain= / origin= exclude it")
@@ -217,6 +228,12 @@ class BatchedRLTask:
         self.actions = torch.zeros((self.n, 12), dtype=torch.float32, device=self.device)
         self.torques = self.bridge.ctl.torques
         self.extras = {}
+        self.height_scan = height_scan
+        if height_scan is not None:
+            height_scan.bind(self.sim)
+            self.num_obs = height_scan.width(NUM_OBS)
+            self.obs_buf = torch.zeros((self.n, self.num_obs), dtype=torch.float32, device=self.device)
+            self.measured_heights = torch.zeros((self.n, height_scan.num_points), dtype=torch.float32, device=self.device)
 
     def step(self, actions):
         """``VecTask.step`` (vec_task.py:298-339): actions [N,12] -> (obs_buf, rew_buf, reset_buf, {"time_outs": timeout_buf}).  The returned
@@ -233,6 +250,8 @@ class BatchedRLTask:
         sim.reset_idx(ids)                                                                                                      # aliengo.py:336-342
         _, fell = sim.flags()              # after the reset: a robot that has just been put back standing is not flagged a second time
         t.finish(sim.root_states, sim.dof_state, self.actions, self.torques, fell=fell)                                         # aliengo.py:280-281, :337
+        if self.height_scan is not None:   # the same post-reset root states, and the origins the curriculum has just written
+            self.height_scan.measure(sim.root_states, t.obs_buf, out=self.obs_buf, heights=self.measured_heights)
         self.extras["time_outs"] = self.timeout_buf
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
 

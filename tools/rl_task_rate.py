@@ -10,6 +10,11 @@ bench.py --full records it (device_state).
 with the curriculum against the same task on the same field and origins without one, in alternating blocks; with --learn K also what K iterations of
 PPO from level 0 do to the levels, and PPOTrainer.evaluate's falls per terrain type before and after.
     python tools/rl_task_rate.py --curriculum [--learn 30] [--out profiles/r14_curriculum.json]
+--heights times the terrain height scan (rl_mpc_locomotion_amd.height_scan) on the same grid, with or without --curriculum: the scan kernel against
+the `finish` kernel from HIP events inside the running loop (p10, median, p90 and the ratio), the bytes the kernel moves per second against what the
+wide rows' writes alone come to, BatchedRLTask.step with and without the scan in alternating blocks, one PPOTrainer.learn iteration at 240 columns
+against 48 for both update backends, and with --curriculum --learn K what K iterations do to the levels with and without the scan.
+    python tools/rl_task_rate.py --heights [--curriculum --learn 30] [--out profiles/r15_height_scan.json]
 The kernel-trace stats of the same step: rocprofv3 --kernel-trace --stats ... -- python tools/rl_task_rate.py --ticks 50 --quick"""
 import argparse
 import json
@@ -216,6 +221,118 @@ def curriculum_report(args, dev, n, actions):
     return res
 
 
+def tick_heights(task, actions, ev):
+    """BatchedRLTask.step's statements with a height scan, with events around `finish` and around the scan"""
+    sim, t = task.sim, task.task
+    tau = task.bridge.pre_physics_step(actions, sim.dof_state, sim.root_states, task.commands)
+    sim.step(tau)
+    if task.curriculum is not None:
+        task.curriculum.update(task.reset_buf, sim.root_states, task.commands)
+    ids = t.begin()
+    task.bridge.ctl.reset(ids)
+    sim.reset_idx(ids)
+    _, fell = sim.flags()
+    ev[0].record()
+    t.finish(sim.root_states, sim.dof_state, actions, tau, fell=fell)
+    ev[1].record()
+    task.height_scan.measure(sim.root_states, t.obs_buf, out=task.obs_buf, heights=task.measured_heights)
+    ev[2].record()
+
+
+HBM_PEAK_BYTES_PER_S = 8.0e12           # MI355X, HBM3E spec
+
+
+def heights_report(args, dev, n, actions):
+    from bench import device_state
+    from rl_mpc_locomotion_amd.curriculum import TerrainCurriculum
+    from rl_mpc_locomotion_amd.height_scan import HeightScan
+    from rl_mpc_locomotion_amd.terrain import TerrainGrid
+    grid = TerrainGrid(num_levels=10, num_types=20, tile_length=8.0, tile_width=8.0, seed=0)
+    cfg = TaskConfig(**CFG)
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "ticks_per_block": args.ticks, "blocks": args.blocks,
+           "grid": {"levels": grid.num_levels, "types": grid.num_types, "tile_m": grid.tile_length, "nodes": [grid.terrain.rows, grid.terrain.cols]},
+           "curriculum": bool(args.curriculum), "max_init_level": args.max_init_level, "device_state": {"before": device_state(0)}}
+
+    def make_task(with_scan, task_cfg=cfg, max_init_level=args.max_init_level):
+        cur = TerrainCurriculum(grid, n, max_init_level=max_init_level, seed=0, device=dev, episode_length_s=task_cfg.episode_length_s)
+        where = dict(curriculum=cur) if args.curriculum else dict(terrain=grid.terrain, origin=cur.origins0)
+        return BatchedRLTask([0] * n, [TROT] * n, cfg=task_cfg, horizon=10, yaw0=yaw, flat_ground=True, device=dev,
+                             height_scan=HeightScan(n, device=dev) if with_scan else None, **where)
+    loops = {"step_with_scan": make_task(True), "step_without": make_task(False)}
+    for task in loops.values():
+        task.reset()
+        for _ in range(20):
+            task.step(actions)
+    torch.cuda.synchronize()
+    wall = {k: [] for k in loops}
+    for _ in range(args.blocks):          # the two loops alternate, block by block
+        for name, task in loops.items():
+            t0 = time.perf_counter()
+            for _ in range(args.ticks):
+                task.step(actions)
+            torch.cuda.synchronize()
+            wall[name].append(time.perf_counter() - t0)
+    for name, w in wall.items():
+        res[name] = {"ms_per_tick_median": med(w) / args.ticks * 1e3, "ms_per_tick_min": min(w) / args.ticks * 1e3, "ms_per_tick_max": max(w) / args.ticks * 1e3,
+                     "robot_ticks_per_s": n * args.ticks / med(w)}
+    res["with_over_without_ms_per_tick"] = res["step_with_scan"]["ms_per_tick_median"] / res["step_without"]["ms_per_tick_median"]
+    task = loops["step_with_scan"]
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.ticks * 2)]
+    for e in ev:
+        tick_heights(task, actions, e)
+    torch.cuda.synchronize()
+    fin, scn = np.array([e[0].elapsed_time(e[1]) for e in ev]), np.array([e[1].elapsed_time(e[2]) for e in ev])
+    res["finish_kernel"], res["scan_kernel"], res["events"] = spread(fin), spread(scn), len(ev)
+    res["scan_over_finish_median"] = med(scn) / med(fin)
+    # the bytes the algorithm needs, from the shapes: what it reads (root states, origins, the narrow rows, the points once, three int16 per point) and
+    # what it writes (the wide rows, the heights)
+    P, w = task.height_scan.num_points, task.num_obs
+    rows = n * w * 4
+    moved = rows + n * P * 4 + n * 48 * 4 + n * 13 * 4 + n * 2 * 8 + P * 2 * 4 + n * P * 3 * 2
+    t_s = med(scn) * 1e-3
+    res["scan_bytes"] = {"wide_row_writes": rows, "all_reads_and_writes": moved, "achieved_bytes_per_s": moved / t_s, "row_writes_bytes_per_s": rows / t_s,
+                         "row_writes_alone_at_hbm_peak_ms": rows / HBM_PEAK_BYTES_PER_S * 1e3, "hbm_peak_bytes_per_s": HBM_PEAK_BYTES_PER_S,
+                         "share_of_hbm_peak": moved / t_s / HBM_PEAK_BYTES_PER_S}
+    cols = task.obs_buf[:, 48:48 + P]
+    res["after_timing"] = {"fallen_fraction": {k: float(t.sim.flags()[1].float().mean().item()) for k, t in loops.items()},
+                           "scan_columns": {"min": float(cols.min().item()), "max": float(cols.max().item()), "distinct": int(len(torch.unique(cols)))}}
+    res["device_state"]["mid"] = device_state(0, smi=False)
+    del loops, task
+    # one learn iteration, 240 columns against 48, both update backends: alternating, after a warm-up iteration each
+    from rl_mpc_locomotion_amd.ppo import PPOConfig, PPOTrainer
+    res["learn_iteration"] = {}
+    for backend in ("torch", "hip"):
+        trainers = {"columns_240": PPOTrainer(make_task(True), PPOConfig(), seed=1, update=backend),
+                    "columns_48": PPOTrainer(make_task(False), PPOConfig(), seed=1, update=backend)}
+        for tr in trainers.values():
+            tr.learn(1)
+        torch.cuda.synchronize()
+        wall = {k: [] for k in trainers}
+        for _ in range(args.learn_blocks):
+            for name, tr in trainers.items():
+                t0 = time.perf_counter()
+                tr.learn(1)
+                torch.cuda.synchronize()
+                wall[name].append(time.perf_counter() - t0)
+        out = {k: {"s_median": med(w), "s_min": min(w), "s_max": max(w)} for k, w in wall.items()}
+        out["wide_over_narrow_median"] = out["columns_240"]["s_median"] / out["columns_48"]["s_median"]
+        res["learn_iteration"][backend] = out
+        del trainers
+    if args.learn > 0 and args.curriculum:      # a finding, not a condition: does sight make the toy's policy climb?
+        res["learn"] = {}
+        for with_scan in (False, True):
+            task = make_task(with_scan, task_cfg=TaskConfig(), max_init_level=0)
+            trainer = PPOTrainer(task, PPOConfig(), seed=1, update="hip")
+            infos = trainer.learn(args.learn, init_at_random_ep_len=True)[-args.learn:]
+            res["learn"]["with_scan" if with_scan else "without_scan"] = {
+                "iterations": args.learn, "num_obs": task.num_obs, "mean_terrain_level_per_iteration": [i["mean_terrain_level"] for i in infos],
+                "mean_reward_per_iteration": [i["mean_reward"] for i in infos], "mean_episode_length_per_iteration": [i["mean_episode_length"] for i in infos],
+                "terrain_level_by_type_last": infos[-1]["terrain_level_by_type"]}
+    res["device_state"]["after"] = device_state(0, smi=False)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--ticks", type=int, default=100, help="ticks per block")
@@ -226,12 +343,14 @@ if __name__ == "__main__":
     ap.add_argument("--max-init-level", type=int, default=9, help="--curriculum: initial levels uniform in 0 .. this")
     ap.add_argument("--learn", type=int, default=0, help="--curriculum: also K PPO iterations from level 0, with evaluate() before and after")
     ap.add_argument("--eval-ticks", type=int, default=500)
+    ap.add_argument("--heights", action="store_true", help="time the terrain height scan (see the head of this file); with or without --curriculum")
+    ap.add_argument("--learn-blocks", type=int, default=3, help="--heights: timed learn iterations per trainer")
     ap.add_argument("--out")
     args = ap.parse_args()
     dev, n = "cuda:0", args.robots
     actions = torch.zeros((n, 12), dtype=torch.float32, device=dev)
-    if args.curriculum:
-        res = curriculum_report(args, dev, n, actions)
+    if args.heights or args.curriculum:
+        res = (heights_report if args.heights else curriculum_report)(args, dev, n, actions)
         print(json.dumps(res, indent=1))
         if args.out:
             with open(args.out, "w") as fh:
