@@ -11,8 +11,9 @@ _EPISODE = ("EpisodeStats",)
 _OBS_NORM = ("ObsNormalizer", "fold_normalizer")
 _CURRICULUM = ("TerrainCurriculum",)
 _HEIGHT_SCAN = ("HeightScan",)
+_DOMAIN_RAND = ("DomainRand", "NoiseSpec", "PushSpec")
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND]
 
 
 def __getattr__(name):
@@ -32,4 +33,7 @@ def __getattr__(name):
     if name in _HEIGHT_SCAN:
         from . import height_scan
         return getattr(height_scan, name)
+    if name in _DOMAIN_RAND:
+        from . import domain_rand
+        return getattr(domain_rand, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

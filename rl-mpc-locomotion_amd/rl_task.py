@@ -191,11 +191,17 @@ class BatchedRLTask:
     the curriculum's, and every reset moves the robot to the tile its new level names.  ``height_scan`` (a ``height_scan.HeightScan`` for as many
     environments; needs ``terrain`` or ``curriculum``): ``obs_buf`` becomes the task's own wide buffer [N, ``height_scan.width(48)``] -- the 48
     columns, the scan of the terrain around the base, a zero pad -- ``num_obs`` its width, and ``measured_heights`` [N, P] the heights in metres.
+    ``domain_rand`` (a ``domain_rand.DomainRand`` for as many environments): while its ``enabled`` is true, noise on the actions in place of the
+    clamp at the head of ``step``, a push of the base after the plant's step on push ticks, and noise on ``obs_buf``'s columns last.
     See the module text for what the toy cannot do."""
 
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
-                 curriculum=None, height_scan=None, **bridge_args):
+                 curriculum=None, height_scan=None, domain_rand=None, **bridge_args):
         import torch
+        if domain_rand is not None:        # everything that can be refused before the device is touched
+            n_envs = len(np.asarray(robot_type).reshape(-1))
+            width = NUM_OBS if height_scan is None else height_scan.width(NUM_OBS)
+            domain_rand.validate(n=n_envs, num_obs=width, dt=(cfg if cfg is not None else TaskConfig()).dt)
         if height_scan is not None:
             if terrain is None and curriculum is None:
                 raise ValueError("height_scan measures a terrain: give terrain= or curriculum=")
@@ -234,15 +240,28 @@ class BatchedRLTask:
             self.num_obs = height_scan.width(NUM_OBS)
             self.obs_buf = torch.zeros((self.n, self.num_obs), dtype=torch.float32, device=self.device)
             self.measured_heights = torch.zeros((self.n, height_scan.num_points), dtype=torch.float32, device=self.device)
+        self.domain_rand = domain_rand
+        if domain_rand is not None:
+            domain_rand.bind(self.sim, dt=self.cfg.dt)
+            self.num_active_obs = NUM_OBS + (height_scan.num_points if height_scan is not None else 0)      # what is not the scan's zero pad
 
     def step(self, actions):
         """``VecTask.step`` (vec_task.py:298-339): actions [N,12] -> (obs_buf, rew_buf, reset_buf, {"time_outs": timeout_buf}).  The returned
         tensors are the task's own buffers, rewritten by the next step.  Nothing is copied to the host and nothing waits for the device."""
         import torch
         sim, t = self.sim, self.task
-        torch.clamp(actions.to(self.device, torch.float32).reshape(self.n, 12), -self.cfg.clip_actions, self.cfg.clip_actions, out=self.actions)    # :312
+        dr = self.domain_rand if self.domain_rand is not None and self.domain_rand.enabled else None
+        if dr is None or dr.specs["actions"] is None:
+            torch.clamp(actions.to(self.device, torch.float32).reshape(self.n, 12), -self.cfg.clip_actions, self.cfg.clip_actions, out=self.actions)    # :312
+        if dr is not None:
+            dr.begin_step()
+            if dr.specs["actions"] is not None:                                                                                # :308-312, one launch
+                dr.noise("actions", actions.to(self.device, torch.float32).reshape(self.n, 12).contiguous(), out=self.actions, clip=self.cfg.clip_actions,
+                         tick=dr.tick)
         self.torques = self.bridge.pre_physics_step(self.actions, sim.dof_state, sim.root_states, self.commands)                # aliengo.py:227-263
         sim.step(self.torques)                                                                                                  # gym.simulate
+        if dr is not None:                 # legged_gym's _post_physics_step_callback: termination, reward and observations see the pushed velocity
+            dr.after_physics(sim.root_states)
         if self.curriculum is not None:    # the flags begin is about to consume, the finished episode's commands, the root states before the reset
             self.curriculum.update(self.reset_buf, sim.root_states, self.commands)
         ids = t.begin()                                                                                                         # :326, aliengo.py:274-278
@@ -252,6 +271,8 @@ class BatchedRLTask:
         t.finish(sim.root_states, sim.dof_state, self.actions, self.torques, fell=fell)                                         # aliengo.py:280-281, :337
         if self.height_scan is not None:   # the same post-reset root states, and the origins the curriculum has just written
             self.height_scan.measure(sim.root_states, t.obs_buf, out=self.obs_buf, heights=self.measured_heights)
+        if dr is not None and dr.specs["observations"] is not None:                                                             # :331-337, in place
+            dr.noise("observations", self.obs_buf, active=self.num_active_obs, clip=self.cfg.clip_observations, tick=dr.tick)
         self.extras["time_outs"] = self.timeout_buf
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
 

@@ -15,6 +15,12 @@ the `finish` kernel from HIP events inside the running loop (p10, median, p90 an
 wide rows' writes alone come to, BatchedRLTask.step with and without the scan in alternating blocks, one PPOTrainer.learn iteration at 240 columns
 against 48 for both update backends, and with --curriculum --learn K what K iterations do to the levels with and without the scan.
     python tools/rl_task_rate.py --heights [--curriculum --learn 30] [--out profiles/r15_height_scan.json]
+--domain-rand times the opt-in domain randomisation (rl_mpc_locomotion_amd.domain_rand) at its widest, 240 columns with the height scan on the same grid:
+the three launches alone from HIP events inside the running loop (the action-noise kernel, the push kernel -- launched on every tick for the timing --
+and the observation-noise kernel, beside the `finish` kernel and the scan; p10, median, p90), the bytes the observation kernel moves, and
+BatchedRLTask.step with the option (legged_gym's observation noise, gaussian action noise, a push every 1500 ticks) against the same task without it in
+alternating blocks, with their p10 - p90 and the share of the tick the option adds.
+    python tools/rl_task_rate.py --domain-rand [--out profiles/r16_domain_rand.json]
 The kernel-trace stats of the same step: rocprofv3 --kernel-trace --stats ... -- python tools/rl_task_rate.py --ticks 50 --quick"""
 import argparse
 import json
@@ -333,6 +339,100 @@ def heights_report(args, dev, n, actions):
     return res
 
 
+def tick_domain_rand(task, raw_actions, ev):
+    """BatchedRLTask.step's statements with the domain randomisation, with events around its three launches, `finish` and the scan (the push is
+    launched on every tick here, for the timing; max_vel 0 would freeze the robots, so it pushes as configured)"""
+    sim, t, dr = task.sim, task.task, task.domain_rand
+    dr.begin_step()
+    ev[0].record()
+    dr.noise("actions", raw_actions, out=task.actions, clip=task.cfg.clip_actions, tick=dr.tick)
+    ev[1].record()
+    tau = task.bridge.pre_physics_step(task.actions, sim.dof_state, sim.root_states, task.commands)
+    sim.step(tau)
+    dr.common_step_counter += 1
+    ev[2].record()
+    dr.push_robots(sim.root_states, dr.common_step_counter)
+    ev[3].record()
+    ids = t.begin()
+    task.bridge.ctl.reset(ids)
+    sim.reset_idx(ids)
+    _, fell = sim.flags()
+    ev[4].record()
+    t.finish(sim.root_states, sim.dof_state, task.actions, tau, fell=fell)
+    ev[5].record()
+    task.height_scan.measure(sim.root_states, t.obs_buf, out=task.obs_buf, heights=task.measured_heights)
+    ev[6].record()
+    dr.noise("observations", task.obs_buf, active=task.num_active_obs, clip=task.cfg.clip_observations, tick=dr.tick)
+    ev[7].record()
+
+
+def domain_rand_report(args, dev, n, actions):
+    from bench import device_state
+    from rl_mpc_locomotion_amd.curriculum import TerrainCurriculum
+    from rl_mpc_locomotion_amd.domain_rand import DomainRand, NoiseSpec, PushSpec
+    from rl_mpc_locomotion_amd.height_scan import HeightScan
+    from rl_mpc_locomotion_amd.terrain import TerrainGrid
+    grid = TerrainGrid(num_levels=10, num_types=20, tile_length=8.0, tile_width=8.0, seed=0)
+    cfg = TaskConfig(**CFG)
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    origins = TerrainCurriculum(grid, n, max_init_level=args.max_init_level, seed=0, device=dev, episode_length_s=cfg.episode_length_s).origins0
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "ticks_per_block": args.ticks, "blocks": args.blocks,
+           "grid": {"levels": grid.num_levels, "types": grid.num_types, "tile_m": grid.tile_length, "nodes": [grid.terrain.rows, grid.terrain.cols]},
+           "device_state": {"before": device_state(0)}}
+
+    def make_task(with_dr):
+        scan = HeightScan(n, device=dev)
+        dr = DomainRand(n, observations=NoiseSpec.legged_gym(cfg, height_scan=scan), actions=NoiseSpec("gaussian", "additive", (0.0, 0.02)),
+                        push=PushSpec(), seed=1, device=dev) if with_dr else None
+        return BatchedRLTask([0] * n, [TROT] * n, cfg=cfg, horizon=10, yaw0=yaw, flat_ground=True, device=dev, terrain=grid.terrain, origin=origins,
+                             height_scan=scan, domain_rand=dr)
+    loops = {"step_with_domain_rand": make_task(True), "step_without": make_task(False)}
+    for task in loops.values():
+        task.reset()
+        for _ in range(20):
+            task.step(actions)
+    torch.cuda.synchronize()
+    wall = {k: [] for k in loops}
+    for _ in range(args.blocks):          # the two loops alternate, block by block
+        for name, task in loops.items():
+            t0 = time.perf_counter()
+            for _ in range(args.ticks):
+                task.step(actions)
+            torch.cuda.synchronize()
+            wall[name].append(time.perf_counter() - t0)
+    for name, w in wall.items():
+        per = np.array(w) / args.ticks * 1e3
+        res[name] = {"ms_per_tick_median": med(per), "ms_per_tick_p10": float(np.percentile(per, 10)), "ms_per_tick_p90": float(np.percentile(per, 90)),
+                     "ms_per_tick_min": float(per.min()), "ms_per_tick_max": float(per.max()), "robot_ticks_per_s": n * args.ticks / med(w)}
+    res["with_over_without_ms_per_tick"] = res["step_with_domain_rand"]["ms_per_tick_median"] / res["step_without"]["ms_per_tick_median"]
+    task = loops["step_with_domain_rand"]
+    res["launches_in_the_timed_blocks"] = dict(task.domain_rand.launches)
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(8)] for _ in range(args.ticks * 2)]
+    for e in ev:
+        tick_domain_rand(task, actions, e)
+    torch.cuda.synchronize()
+    span = lambda i: np.array([e[i].elapsed_time(e[i + 1]) for e in ev])
+    parts = {"action_noise_kernel": span(0), "push_kernel": span(2), "finish_kernel": span(4), "scan_kernel": span(5), "observation_noise_kernel": span(6)}
+    for k, v in parts.items():
+        res[k] = spread(v)
+    res["events"] = len(ev)
+    three = med(parts["action_noise_kernel"]) + med(parts["observation_noise_kernel"])
+    tick_ms = res["step_without"]["ms_per_tick_median"]
+    res["share_of_the_tick"] = {"two_noise_launches_medians_ms": three, "push_launch_median_ms": med(parts["push_kernel"]),
+                                "noise_launches_over_step_without": three / tick_ms,
+                                "all_three_over_step_without": (three + med(parts["push_kernel"])) / tick_ms,
+                                "measured_step_difference_over_step_without": res["with_over_without_ms_per_tick"] - 1.0}
+    w = task.num_obs
+    rows = 2 * n * w * 4 + w * 4          # the rows read and written, the column scales
+    t_s = med(parts["observation_noise_kernel"]) * 1e-3
+    res["observation_noise_bytes"] = {"rows_read_and_written": rows, "achieved_bytes_per_s": rows / t_s, "at_hbm_peak_ms": rows / HBM_PEAK_BYTES_PER_S * 1e3,
+                                      "hbm_peak_bytes_per_s": HBM_PEAK_BYTES_PER_S, "share_of_hbm_peak": rows / t_s / HBM_PEAK_BYTES_PER_S}
+    res["observation_noise_over_scan_median"] = med(parts["observation_noise_kernel"]) / med(parts["scan_kernel"])
+    res["after_timing"] = {"fallen_fraction": {k: float(t.sim.flags()[1].float().mean().item()) for k, t in loops.items()}}
+    res["device_state"]["after"] = device_state(0, smi=False)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--ticks", type=int, default=100, help="ticks per block")
@@ -345,12 +445,13 @@ if __name__ == "__main__":
     ap.add_argument("--eval-ticks", type=int, default=500)
     ap.add_argument("--heights", action="store_true", help="time the terrain height scan (see the head of this file); with or without --curriculum")
     ap.add_argument("--learn-blocks", type=int, default=3, help="--heights: timed learn iterations per trainer")
+    ap.add_argument("--domain-rand", action="store_true", help="time the domain randomisation's three launches and the step with and without it")
     ap.add_argument("--out")
     args = ap.parse_args()
     dev, n = "cuda:0", args.robots
     actions = torch.zeros((n, 12), dtype=torch.float32, device=dev)
-    if args.heights or args.curriculum:
-        res = (heights_report if args.heights else curriculum_report)(args, dev, n, actions)
+    if args.domain_rand or args.heights or args.curriculum:
+        res = (domain_rand_report if args.domain_rand else heights_report if args.heights else curriculum_report)(args, dev, n, actions)
         print(json.dumps(res, indent=1))
         if args.out:
             with open(args.out, "w") as fh:
