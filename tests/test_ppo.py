@@ -189,13 +189,16 @@ def test_sampler(shim):
     assert len(np.unique(eps)) > 0.99 * eps.size
 
 
-def _filled_storage(ac, n, T, seed):
-    """A CPU storage as a collection would leave it, from a slightly different (older) policy."""
+def _filled_storage(ac, n, T, seed, zero_pad=0):
+    """A CPU storage as a collection would leave it, from a slightly different (older) policy.  zero_pad: the last so many observation columns are
+    exactly 0.0 in every row (the height scan's pad columns), and the policy's outputs are those of such rows."""
     g = torch.Generator().manual_seed(seed)
     st = P.RolloutStorage(n, T, "cpu", num_obs=ac.num_obs)
     r = lambda *shape: torch.randn(shape, generator=g)
     with torch.no_grad():
         st.observations.copy_(r(T, n, ac.num_obs))
+        if zero_pad:
+            st.observations[..., ac.num_obs - zero_pad:] = 0.0
         st.mu.copy_(ac.actor(st.observations) + 0.05 * r(T, n, 12))
         st.sigma.copy_((ac.std * (1.0 + 0.1 * torch.rand(12, generator=g))).expand(T, n, 12))
         st.actions.copy_(st.mu + st.sigma * r(T, n, 12))

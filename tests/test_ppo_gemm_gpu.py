@@ -2,7 +2,9 @@
 
 tests/device/ppo_gemm_harness.hip is compiled once per run with hipcc and loaded through ctypes; the test fills the pgemm::Launch and names the
 kind and the tile (narrow = gemm_kernel<KIND, 2, 1>, wide = gemm_kernel<KIND, 2, 2>) itself, so the launch plan (csrc/ppo_gemm_plan.h) is not involved
-and the 128 x 128 tile and the 512- and 1024-row chunks run at shapes far below those at which the plan picks them.
+and the 128 x 128 tile and the 512- and 1024-row chunks run at shapes far below those at which the plan picks them.  The axis sets stand at the two
+shape tables; they include what the 240-column observation rows of training with a height scan add: K = 240 through the row index, N = 240, and a
+weight gradient of nin = 240 with ldb = 240 in 1024- and in 256-row chunks.
 
 The tolerance is derived, not measured.  A float32 sum of n products, in any order and fused or not, lies within gamma_n * sum |a_k b_k| of the exact
 sum, gamma_n = n u / (1 - n u), u = 2^-24 (Higham, Accuracy and Stability of Numerical Algorithms, section 3.1).  Hence, per element,
@@ -37,10 +39,10 @@ KIND_NAMES = ("forward", "backward data", "backward weight")
 TILES = {"narrow": 0, "wide": 1}                                  # gemm_kernel<KIND, 2, 1>, gemm_kernel<KIND, 2, 2>
 SENTINEL = 0x7FA5C3E1                                             # a NaN with a payload: no kernel result has these bits
 
-# Two problems per launch, so one problem's workgroups leave early; the second slot of the last case is empty (tiles_m = 0).  pad: the leading
+# Two problems per launch, so one problem's workgroups leave early; the second slot of one case is empty (tiles_m = 0).  pad: the leading
 # dimensions are round4(width) + 4 instead of round4(width).  idx (forward): the rows of X are read through an int64 index.
-# Forward and backward data, (M, N, K).  Over the cases: M in {1, 31, 33, 127, 128, 129, 257}, N in {1, 12, 16, 63, 65, 127, 128, 129, 144},
-# K in {1, 2, 3, 4, 5, 31, 32, 33, 48, 63, 65, 100}, each with every kind and tile (tests/test_ppo_gemm_plan.py checks that of this table).
+# Forward and backward data, (M, N, K).  Over the cases: M in {1, 31, 33, 127, 128, 129, 257}, N in {1, 12, 16, 63, 65, 127, 128, 129, 144, 240},
+# K in {1, 2, 3, 4, 5, 16, 31, 32, 33, 48, 63, 65, 100, 240}, each with every kind and tile (tests/test_ppo_gemm_plan.py checks that of this table).
 FB_CASES = (
     dict(shapes=((1, 12, 1), (257, 144, 100)), pad=False, idx=(True, False)),
     dict(shapes=((31, 1, 2), (129, 129, 65)), pad=True, idx=(False, True)),
@@ -49,8 +51,12 @@ FB_CASES = (
     dict(shapes=((128, 127, 5), (33, 12, 33)), pad=False, idx=(False, False)),
     dict(shapes=((129, 16, 31), (1, 144, 32)), pad=True, idx=(False, True)),
     dict(shapes=((129, 65, 33), None), pad=True, idx=(True, False)),
+    # the wide observation rows (240 columns with the default height scan): the first layer's reduction, 7 1/2 trips of 32 through the index with
+    # lda = 240 as the update passes it, and 240 output columns (the narrow tile's fourth column tile holds 48, the wide tile's second 112)
+    dict(shapes=((129, 65, 240), (33, 128, 16)), pad=False, idx=(True, False)),
+    dict(shapes=((257, 240, 48), (31, 12, 240)), pad=True, idx=(False, True)),
 )
-# Backward weight, (nout, nin, rows, chunk_rows).  nout in {1, 12, 16, 127, 129}, nin in {16, 48, 65, 128, 144}, rows in {1, 31, 33, 255, 256, 257, 1023,
+# Backward weight, (nout, nin, rows, chunk_rows).  nout in {1, 12, 16, 127, 129}, nin in {16, 48, 65, 128, 144, 240}, rows in {1, 31, 33, 255, 256, 257, 1023,
 # 1025, 2049} and 512, 1024; every chunk length with a row count that leaves a last chunk of one row (257 / 256, 1025 / 512, 2049 / 1024) and with one
 # that fills the last chunk (256 / 256, 512 / 512, 1024 / 1024).  idx: the rows of X are read through the index.  db: the dbias partials are asked for.
 BW_CASES = (
@@ -61,6 +67,10 @@ BW_CASES = (
     dict(shapes=((129, 144, 1023, 1024), (16, 48, 1024, 1024)), pad=False, idx=(True, False), db=(True, True)),
     dict(shapes=((1, 128, 512, 512), (127, 16, 1024, 512)), pad=True, idx=(False, False), db=(True, True)),
     dict(shapes=((12, 144, 2049, 256), None), pad=True, idx=(True, False), db=(True, True)),
+    # the first layer's weight gradient on the wide rows: nin = 240 read through the index with ldb = 240 (pad=False) in 1024-row chunks, the last of
+    # one row, as mpc_ppo_update_grads plans it from 15 361 rows on; and nin = 240 in 256-row chunks, as it plans it below that
+    dict(shapes=((129, 240, 2049, 1024), (12, 16, 33, 256)), pad=False, idx=(True, False), db=(True, True)),
+    dict(shapes=((127, 240, 1025, 256), (1, 48, 31, 512)), pad=True, idx=(False, True), db=(True, True)),
 )
 
 WORST = {}                                                        # (kind, tile) -> largest error / bound seen, printed as evidence

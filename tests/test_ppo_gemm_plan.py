@@ -4,7 +4,9 @@ header (no HIP in it) is compiled with g++ into a small shim and driven through 
   * that the (kind, tile, chunk length) combinations of the training workload (PPOConfig()'s nets, 4096 robots x 24 steps / 4 mini-batches) are among
     those the GPU tests' own shape tables plan, so a change of the plan that moves the workload onto kernels no test runs fails here, without a GPU;
   * that the workspace of mpc_ppo_update_create (ceil(max_rows / 256) chunk partials per layer) holds every planned launch;
-  * that the shape tables of tests/test_ppo_gemm_gpu.py cover the tile and vector edges they name, with every chunk length."""
+  * that the shape tables of tests/test_ppo_gemm_gpu.py cover the tile and vector edges they name, with every chunk length;
+  * the same for the workload on the wide observation rows of a height scan (240 columns by default, and 256): the width moves one launch, the first
+    layer's weight gradient, onto 1024-row chunks (and at 256 onto the 128 x 128 tile), and the GPU tests' wide tables plan and run that."""
 import ctypes as C
 import subprocess
 
@@ -54,12 +56,12 @@ def plan(tmp_path_factory):
     return run
 
 
-def launches(nets, rows):
-    """mpc_ppo_update_grads' GEMM launches for a net pair (hidden layers of actor and critic) at `rows` rows, in its order: (kind, actor's (M, N, K) or None,
+def launches(nets, rows, num_obs=48):
+    """mpc_ppo_update_grads' GEMM launches for a net pair (hidden layers of actor and critic) at `rows` rows of `num_obs` columns, in its order: (kind, actor's (M, N, K) or None,
     critic's): layer l of both nets side by side forward; backward from each net's last layer down, backward weight, then backward data into the
     layer below.  The sequence is copied by hand from csrc/mpc_ppo_update.hip (which says so at its forward and backward loops): a launch added or
     reshaped there has to be restated here."""
-    dims = [[48, *nets[0], 12], [48, *nets[1], 1]]
+    dims = [[num_obs, *nets[0], 12], [num_obs, *nets[1], 1]]
     nl = [len(d) - 1 for d in dims]
     out = []
     for l in range(max(nl)):
@@ -76,17 +78,17 @@ def launches(nets, rows):
     return out
 
 
-def planned(plan, nets, rows):
+def planned(plan, nets, rows, num_obs=48):
     """Per launch (kind, tile, chunk_rows, chunks of the two problems)."""
     out = []
-    for kind, a, b in launches(nets, rows):
+    for kind, a, b in launches(nets, rows, num_obs):
         p = plan(kind, a, b)
         out.append((kind, p["tile"], p["chunk_rows"], (p["problems"][0][2], p["problems"][1][2])))
     return out
 
 
-def combos(plan, nets, rows):
-    return {(kind, tile, chunk_rows) for kind, tile, chunk_rows, _ in planned(plan, nets, rows)}
+def combos(plan, nets, rows, num_obs=48):
+    return {(kind, tile, chunk_rows) for kind, tile, chunk_rows, _ in planned(plan, nets, rows, num_obs)}
 
 
 def _rows(case):
@@ -152,30 +154,88 @@ def test_the_training_workload_runs_only_kernels_the_gpu_tests_run(plan):
     assert production <= direct and tested <= direct, (production - direct, tested - direct)
 
 
+def _height_scan_row():
+    """(width, live columns) of the observation row with HeightScan's default points: the task's columns and the scan, padded with zeros."""
+    from rl_mpc_locomotion_amd import height_scan, rl_task
+    points = len(height_scan.POINTS_X) * len(height_scan.POINTS_Y)
+    return height_scan.padded_width(rl_task.NUM_OBS, points), rl_task.NUM_OBS + points
+
+
+def test_the_wide_training_workload_runs_only_kernels_the_gpu_tests_run(plan):
+    """The workload with the default height scan, and one of 256 columns, launch by launch: the plan is the 48-wide one except in the last launch, the
+    first layer's weight gradient (the only backward-weight launch that reads X through the index), which takes 1024-row chunks (24) -- on the
+    128 x 64 tile at 240 columns, on the 128 x 128 tile at 256.  Its combinations are among those that the wide tables of
+    tests/test_ppo_update_gpu.py plan, and that launch itself is planned there with 17 chunks, the last of one row."""
+    cfg = P.PPOConfig()
+    nets = (cfg.actor_hidden_dims, cfg.critic_hidden_dims)
+    rows = 4096 * cfg.num_steps_per_env // cfg.num_mini_batches
+    assert rows == 24576 and nets == U.NETS["reference"]
+    scan, live = _height_scan_row()
+    assert scan in U.WIDTHS and scan in U.BIG_WIDTHS and U.ZERO_PAD == {scan: scan - live}      # the GPU tests' wide row is this one, zeros included
+    assert U.BIG_WIDTHS == (scan, 256) and (scan, scan - live) == (240, 5)
+    at48 = planned(plan, nets, rows)
+    assert at48 == [
+        (FORWARD, WIDE, 0, (1, 1)), (FORWARD, WIDE, 0, (1, 1)), (FORWARD, WIDE, 0, (1, 1)), (FORWARD, NARROW, 0, (1, 1)),
+        (BACKWARD_WEIGHT, NARROW, 256, (96, 96)), (BACKWARD_DATA, WIDE, 0, (1, 1)),
+        (BACKWARD_WEIGHT, WIDE, 256, (96, 96)), (BACKWARD_DATA, WIDE, 0, (1, 1)),
+        (BACKWARD_WEIGHT, WIDE, 1024, (24, 24)), (BACKWARD_DATA, WIDE, 0, (1, 1)),
+        (BACKWARD_WEIGHT, NARROW, 256, (96, 96))]
+    direct = {(kind, tile, 0) for kind in (FORWARD, BACKWARD_DATA) for tile in G.TILES}
+    direct |= {(BACKWARD_WEIGHT, tile, s[3]) for tile in G.TILES for case in G.BW_CASES for s in case["shapes"] if s}
+    for num_obs, tile in ((scan, NARROW), (256, WIDE)):
+        assert launches(nets, rows, num_obs)[-1] == (BACKWARD_WEIGHT, (512, num_obs, rows), (512, num_obs, rows))
+        got = planned(plan, nets, rows, num_obs)
+        assert got == at48[:-1] + [(BACKWARD_WEIGHT, tile, 1024, (24, 24))] and got != at48, (num_obs, got)
+        # end to end: the wide tables alone
+        tested = set()
+        for name in U.WIDE_NETS:
+            for case in U.WIDE_ROWS:
+                for width in U.WIDTHS:
+                    tested |= combos(plan, U.NETS[name], _rows(U.ROWS[case]), width)
+        assert all(tile == NARROW and chunk_rows in (0, 256) for _, tile, chunk_rows in tested)      # (the small cases: the index, the widths, the edges)
+        big = _rows(U.BIG_ROWS["production"])
+        assert planned(plan, nets, big, num_obs)[-1] == (BACKWARD_WEIGHT, tile, 1024, (17, 17)) and big - 16 * 1024 == 1
+        tested |= combos(plan, nets, big, num_obs)
+        production = combos(plan, nets, rows, num_obs)
+        assert (BACKWARD_WEIGHT, tile, 1024) in production
+        assert production <= tested, production - tested
+        assert production <= direct and tested <= direct, (production - direct, tested - direct)
+    # 15 361 rows is where (512, 240, rows) first plans 1024-row chunks (2 x 4 x 4 x ceil(rows / 1024) >= 512; 512-row chunks below that)
+    assert planned(plan, nets, 15360, scan)[-1][2] == 512 and planned(plan, nets, 15361, scan)[-1][2] == 1024
+
+
 def test_the_workspace_holds_every_planned_launch(plan):
     """mpc_ppo_update_create allocates ceil(max_rows / kMinChunk) chunk partials per layer; a launch at rows <= max_rows never plans more."""
     all_nets = list(U.ALL_NETS.values()) + [((512, 256, 128), (64,)), ((16,), (512, 512))]
     for nets in all_nets:
-        for rows in (1, 97, 255, 256, 257, 1023, 1024, 1025, 1040, 4095, 4097, 16385, 24576, 98304):
-            for kind, _, chunk_rows, chunks in planned(plan, nets, rows):
-                assert max(chunks) <= -(-rows // 256), (nets, rows, chunks)
-                if kind == BACKWARD_WEIGHT:
-                    assert chunk_rows in (256, 512, 1024) and all(c in (1, -(-rows // chunk_rows)) for c in chunks)
-                else:
-                    assert chunk_rows == 0 and chunks == (1, 1)
+        for num_obs in (48, 16, 240, 256):
+            for rows in (1, 97, 255, 256, 257, 1023, 1024, 1025, 1040, 4095, 4097, 16385, 24576, 98304):
+                for kind, _, chunk_rows, chunks in planned(plan, nets, rows, num_obs):
+                    assert max(chunks) <= -(-rows // 256), (nets, num_obs, rows, chunks)
+                    if kind == BACKWARD_WEIGHT:
+                        assert chunk_rows in (256, 512, 1024) and all(c in (1, -(-rows // chunk_rows)) for c in chunks)
+                    else:
+                        assert chunk_rows == 0 and chunks == (1, 1)
 
 
 def test_the_direct_tests_shape_tables_cover_the_edges():
     """tests/test_ppo_gemm_gpu.py: every axis value with every kind (every case runs with both tiles), two problems per launch and one empty second
-    slot, padded leading dimensions, an index in forward and in backward weight, every chunk length with a one-row and with a full last chunk."""
+    slot, padded leading dimensions, an index in forward and in backward weight, every chunk length with a one-row and with a full last chunk, and
+    the 240-column rows as the update reads them."""
     assert sorted(G.TILES) == ["narrow", "wide"] and G.TILES["narrow"] == 0 and G.TILES["wide"] == 1
     fb = [s for case in G.FB_CASES for s in case["shapes"] if s]
     assert {s[0] for s in fb} >= {1, 31, 33, 127, 128, 129, 257}
-    assert {s[1] for s in fb} >= {1, 12, 16, 63, 65, 127, 128, 129, 144}
-    assert {s[2] for s in fb} >= {1, 2, 3, 4, 5, 31, 32, 33, 48, 63, 65, 100}
+    assert {s[1] for s in fb} >= {1, 12, 16, 63, 65, 127, 128, 129, 144, 240}
+    assert {s[2] for s in fb} >= {1, 2, 3, 4, 5, 16, 31, 32, 33, 48, 63, 65, 100, 240}
+    # the wide rows' first layer: K = 240 through the index on unpadded rows (lda = 240)
+    assert any(s and s[2] == 240 and case["idx"][k] and not case["pad"] for case in G.FB_CASES for k, s in enumerate(case["shapes"]))
     bw = [s for case in G.BW_CASES for s in case["shapes"] if s]
     assert {s[0] for s in bw} >= {1, 12, 16, 127, 129}
-    assert {s[1] for s in bw} >= {16, 48, 65, 128, 144}
+    assert {s[1] for s in bw} >= {16, 48, 65, 128, 144, 240}
+    # the wide rows' first layer: nin = 240 through the index with ldb = 240, in 1024-row chunks with a last chunk of one row; and in 256-row chunks
+    assert any(s and s[1] == 240 and s[3] == 1024 and s[2] % 1024 == 1 and s[2] > 1024 and case["idx"][k] and not case["pad"]
+               for case in G.BW_CASES for k, s in enumerate(case["shapes"]))
+    assert any(s[1] == 240 and s[3] == 256 and s[2] > 256 for s in bw)
     assert {s[2] for s in bw} >= {1, 31, 33, 255, 256, 257, 1023, 1025, 2049}
     for chunk_rows in (256, 512, 1024):
         last = {s[2] - (-(-s[2] // chunk_rows) - 1) * chunk_rows for s in bw if s[3] == chunk_rows and s[2] > chunk_rows}

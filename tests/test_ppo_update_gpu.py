@@ -8,7 +8,13 @@ scalar terms as tests/test_ppo_update.py pools them, over the same cases.  Large
 
 Those row counts all plan the 128 x 64 tile and 256-row weight-gradient chunks (csrc/ppo_gemm_plan.h).  BIG_ROWS x BIG_NETS are the cases that reach what
 the training workload runs -- the 128 x 128 tile in all three kinds and chunks of 1024 and 512 rows -- with a pool of their own, so the cases above keep
-their gaps; tests/test_ppo_gemm_plan.py pins which kernel each of this module's shapes reaches."""
+their gaps; tests/test_ppo_gemm_plan.py pins which kernel each of this module's shapes reaches.
+
+All of those rows are 48 columns wide.  WIDTHS x WIDE_NETS x WIDE_ROWS and BIG_WIDTHS are the same comparisons at other widths, each (net pair, width)
+with a pool of its own: 16 (the narrowest row mpc_ac_create takes, half a reduction trip of the GEMM), 240 (the training row with the default height
+scan: 48 task columns, 187 scan values and five pad columns that are exactly 0.0 in every row, as here) and 256 (where the first layer's weight
+gradient takes the 128 x 128 tile).  At 16 385 rows a 240-wide first layer plans 1024-row chunks on the 128 x 64 tile with ldb = 240, which nothing else
+does.  The gradient of a weight column whose input column is exactly zero is exactly zero, and Adam leaves such a column bit for bit where it was."""
 import numpy as np
 import pytest
 import torch
@@ -26,28 +32,41 @@ NETS = {"reference": ((512, 256, 128), (512, 256, 128)), "uneven": ((32, 16), (6
 ROWS = {"single": (1, 1, 1), "ragged": (65, 6, 4), "chunked": (65, 16, 1)}        # n, T, mini-batches: 1 row; 4 x 97 rows, 2 left out; 1040 rows
 BIG_NETS = {"reference": NETS["reference"], "square": ((256, 256), (256, 256))}
 BIG_ROWS = {"production": (3277, 5, 1)}                                           # 16 385 rows in one mini-batch: 17 chunks of 1024, 33 of 512, the last of 1 row
-ALL_NETS, ALL_ROWS = {**NETS, **BIG_NETS}, {**ROWS, **BIG_ROWS}
+# Net pairs for mpc_ppo_update_apply alone, by the number of float64 partials norm_kernel joins (tensors x ceil(largest numel / 4096)); its 1024 lanes
+# take partials i, i + 1024, ..., and every pair above stays inside the first trip (the reference nets have the most: 17 x 32 = 544).
+#   "second trip"  11 tensors x 128 blocks (the 512 x 1024 layer) = 1408: block 0 of both critic biases and of std lie at 1024, 1152 and 1280
+#   "first past"   33 tensors (the most the ABI takes) x 32 blocks (512 x 256) = 1056: std's block 0 is partial 1024 itself, the first one of the second
+#                  trip.  No pair has fewer partials with a live one past 1023: the last tensor's block 0 sits at (tensors - 1) x blocks, tensors is odd
+#                  and at most 33, so blocks >= 32; 31 tensors would need 35 blocks (1085).
+NORM_NETS = {"second trip": ((1024, 512), (64,)), "first past": ((512, 256, 16, 16, 16, 16, 16), (16,) * 7)}
+NORM_PARTIALS = {"second trip": 1408, "first past": 1056}
+ALL_NETS, ALL_ROWS = {**NETS, **BIG_NETS, **NORM_NETS}, {**ROWS, **BIG_ROWS}
 DESIRED_KL = (0.01, 0.06, 1.0)                                                    # first-step kl 0.048 .. 0.076: down, unchanged, up
+# Other widths than 48.  ZERO_PAD: width -> trailing columns that are exactly 0.0 in every row, as the height scan pads 48 + 187 to 240.
+WIDTHS, WIDE_NETS, WIDE_ROWS = (16, 240), ("odd", "uneven"), ("chunked", "ragged")
+BIG_WIDTHS = (240, 256)                                                            # on the reference nets at BIG_ROWS["production"]
+ZERO_PAD = {240: 5}
 
 
-def _cfg(nets, mini_batches=1, **kw):
+def _cfg(nets, mini_batches=1, num_obs=48, **kw):
+    """(PPOConfig carries no width: the nets take it from the task, here from _fixture's actor-critic; num_obs is accepted so a call names its case.)"""
     return P.PPOConfig(actor_hidden_dims=ALL_NETS[nets][0], critic_hidden_dims=ALL_NETS[nets][1], init_noise_std=0.7, num_mini_batches=mini_batches, **kw)
 
 
-def _fixture(nets, rows):
-    """(CPU actor-critic, CPU storage, injected permutation) as tests/test_ppo.py builds them."""
+def _fixture(nets, rows, num_obs=48):
+    """(CPU actor-critic, CPU storage, injected permutation) as tests/test_ppo.py builds them; the last ZERO_PAD[num_obs] observation columns zero."""
     n, T, mb = ALL_ROWS[rows]
     torch.manual_seed(5)
-    ac = P.ActorCritic(48, 12, *ALL_NETS[nets], init_noise_std=0.7)
-    st = _filled_storage(ac, n=n, T=T, seed=6)
+    ac = P.ActorCritic(num_obs, 12, *ALL_NETS[nets], init_noise_std=0.7)
+    st = _filled_storage(ac, n=n, T=T, seed=6, zero_pad=ZERO_PAD.get(num_obs, 0))
     size = n * T // mb
     perm = torch.randperm(n * T, generator=torch.Generator().manual_seed(7))[:mb * size].contiguous()
     return ac, st, perm
 
 
-def _to_device(ac, st):
+def _to_device(ac, st, num_obs=None):
     dev = ref.clone(ac, torch.float32).to(DEV)
-    out = P.RolloutStorage(st.n, st.T, DEV)
+    out = P.RolloutStorage(st.n, st.T, DEV, num_obs=ac.num_obs if num_obs is None else num_obs)
     for f in ref.FIELDS:
         getattr(out, f).copy_(getattr(st, f))
     out.step = out.T
@@ -67,21 +86,23 @@ def _pooled(errs_and_gaps, what):
 
 @pytest.fixture(scope="module")
 def grads_reference():
-    """Per net pair: float64 and float32 gradients and terms of every mini-batch of every row-count case, computed once."""
+    """Per net pair: float64 and float32 gradients and terms of every mini-batch of every row-count case, computed once.  At another width, over
+    other row-count cases or with other settings of PPOConfig it is a pool of its own."""
     cache = {}
 
-    def get(nets):
-        if nets not in cache:
+    def get(nets, num_obs=48, row_cases=tuple(ROWS), **cfg_kw):
+        key = (nets, num_obs, row_cases, tuple(sorted(cfg_kw.items())))
+        if key not in cache:
             cases = {}
-            for rows in ROWS:
-                ac, st, perm = _fixture(nets, rows)
+            for rows in row_cases:
+                ac, st, perm = _fixture(nets, rows, num_obs)
                 mb = ROWS[rows][2]
                 size = len(perm) // mb
-                cfg = _cfg(nets, mb)
+                cfg = _cfg(nets, mb, num_obs, **cfg_kw)
                 cases[rows] = [(ref.grads_of(ac, cfg, st, perm[i * size:(i + 1) * size], torch.float64),
                                 ref.grads_of(ac, cfg, st, perm[i * size:(i + 1) * size], torch.float32)) for i in range(mb)]
-            cache[nets] = cases
-        return cache[nets]
+            cache[key] = cases
+        return cache[key]
     return get
 
 
@@ -144,38 +165,50 @@ def big_reference():
     """Per net pair and BIG_ROWS case: the fixture and the float64 and float32 gradients and terms of its one mini-batch, computed once."""
     cache = {}
 
-    def get(nets):
-        if nets not in cache:
+    def get(nets, num_obs=48):
+        if (nets, num_obs) not in cache:
             cases = {}
             for rows in BIG_ROWS:
                 assert BIG_ROWS[rows][2] == 1
-                ac, st, perm = _fixture(nets, rows)
-                cfg = _cfg(nets, 1, desired_kl=0.06)
+                ac, st, perm = _fixture(nets, rows, num_obs)
+                cfg = _cfg(nets, 1, num_obs, desired_kl=0.06)
                 cases[rows] = (ac, st, perm, ref.grads_of(ac, cfg, st, perm, torch.float64), ref.grads_of(ac, cfg, st, perm, torch.float32))
-            cache[nets] = cases
-        return cache[nets]
+            cache[(nets, num_obs)] = cases
+        return cache[(nets, num_obs)]
     return get
 
 
-def _device_grads(alg, dst, perm, size):
-    """One mpc_ppo_update_grads over the first `size` rows of perm on alg's handle: (gradients, terms, learning rate) on the host."""
+def _device_grads(alg, dst, perm, size, first=0):
+    """One mpc_ppo_update_grads over rows first .. first + size of perm on alg's handle: (gradients, terms, learning rate) on the host."""
     L = P.update_lib()
     P.check(L.mpc_ppo_update_set_storage(alg._handle, dst.n * dst.T, *[getattr(dst, f).data_ptr() for f in ref.FIELDS]), "set_storage")
     idx = perm.to(DEV)
     terms = torch.zeros(4, device=DEV)
     alg.lr_device.fill_(1e-3)
     c = alg.cfg
-    P.check(L.mpc_ppo_update_grads(alg._handle, size, idx.data_ptr(), c.clip_param, c.value_loss_coef, c.entropy_coef, 1, 1, c.desired_kl,
-                                   alg.lr_device.data_ptr(), terms.data_ptr(), None), "grads")
+    P.check(L.mpc_ppo_update_grads(alg._handle, size, idx.data_ptr() + 8 * first, c.clip_param, c.value_loss_coef, c.entropy_coef, int(c.use_clipped_value_loss), 1,
+                                   c.desired_kl, alg.lr_device.data_ptr(), terms.data_ptr(), None), "grads")
     return [p.grad.cpu().clone() for p in alg.actor_critic.bind_order()], terms.cpu().clone(), float(alg.lr_device)
 
 
-@pytest.mark.parametrize("rows", sorted(BIG_ROWS))
-@pytest.mark.parametrize("nets", sorted(BIG_NETS))
-def test_grads_on_the_production_plan_match_float64_autograd(big_reference, nets, rows):
-    """test_grads_match_float64_autograd's rule (desired_kl = 0.06) at a row count that plans the wide tile and the long chunks; the float32 gap is
-    pooled over the BIG_ROWS cases of this net pair only."""
-    cases = big_reference(nets)
+def _first_layer_weights(ac):
+    names = _names(ac)
+    return names.index("actor W0"), names.index("critic W0")
+
+
+def _zero_pad_columns_are_exactly_zero(ac, grads, what):
+    """The first-layer weight gradients of both nets: +0.0 or -0.0 bit for bit in the columns whose input is zero in every row, and some non-zero
+    element in every other column."""
+    live = ac.num_obs - ZERO_PAD[ac.num_obs]
+    for k in _first_layer_weights(ac):
+        g = grads[k]
+        assert g.shape[1] == ac.num_obs and g.dtype == torch.float32
+        assert bool(((g[:, live:].contiguous().view(torch.int32) & 0x7FFFFFFF) == 0).all()), f"{what}: {_names(ac)[k]} has a non-zero gradient in a column whose input is zero"
+        assert bool((g[:, :live] != 0).any(0).all()), f"{what}: {_names(ac)[k]} has a live column without a gradient"
+
+
+def _check_production(cases, nets, rows, what):
+    """test_grads_match_float64_autograd's rule (desired_kl = 0.06) on one BIG_ROWS case of big_reference, the gaps pooled over `cases`."""
     gap = max(ref.rel_l2(g32, g64) for _, _, _, (g64s, _, _), (g32s, _, _) in cases.values() for g32, g64 in zip(g32s, g64s))
     rel = lambda x, r: abs(x - r) / abs(r)
     pool3 = max(rel(b[1][q], a[1][q]) for _, _, _, a, b in cases.values() for q in range(3))
@@ -183,19 +216,122 @@ def test_grads_on_the_production_plan_match_float64_autograd(big_reference, nets
     ac, st, perm, (g64s, t64, frac), _ = cases[rows]
     assert 0.05 < frac[0] < 0.95 and 0.05 < frac[1] < 0.95, frac
     dev, dst = _to_device(ac, st)
-    alg = P.PPO(dev, _cfg(nets, 1, desired_kl=0.06), backend="hip")
+    alg = P.PPO(dev, _cfg(nets, 1, ac.num_obs, desired_kl=0.06), backend="hip")
     alg._device_state(len(perm))
     got, terms, lr = _device_grads(alg, dst, perm, len(perm))
     assert lr == ref.adapt(1e-3, t64[3], alg.cfg), t64[3]
     for q, name in enumerate(("surrogate", "value loss", "entropy", "kl")):
         g = pool_kl if q == 3 else pool3
         err = rel(float(terms[q]), t64[q])
-        print(f"{nets} {rows}: {name} off by {err:.3e} (bound {4 * g:.3e}, ratio {err / g:.3f})")
+        print(f"{what}: {name} off by {err:.3e} (bound {4 * g:.3e}, ratio {err / g:.3f})")
         assert g > 0 and err <= 4 * g, (name, err, g)
     names = _names(ac)
     for k in range(len(names)):
-        print(f"{nets} {rows}: {names[k]} off by {ref.rel_l2(got[k], g64s[k]):.3e}, its own float32 gap {ref.rel_l2(cases[rows][4][0][k], g64s[k]):.3e}")
-    _pooled([(names[k], ref.rel_l2(got[k], g64s[k]), gap) for k in range(len(names))], f"{nets} {rows}: gradients")
+        print(f"{what}: {names[k]} off by {ref.rel_l2(got[k], g64s[k]):.3e}, its own float32 gap {ref.rel_l2(cases[rows][4][0][k], g64s[k]):.3e}")
+    _pooled([(names[k], ref.rel_l2(got[k], g64s[k]), gap) for k in range(len(names))], f"{what}: gradients")
+    return got
+
+
+@pytest.mark.parametrize("rows", sorted(BIG_ROWS))
+@pytest.mark.parametrize("nets", sorted(BIG_NETS))
+def test_grads_on_the_production_plan_match_float64_autograd(big_reference, nets, rows):
+    """test_grads_match_float64_autograd's rule (desired_kl = 0.06) at a row count that plans the wide tile and the long chunks; the float32 gap is
+    pooled over the BIG_ROWS cases of this net pair only."""
+    _check_production(big_reference(nets), nets, rows, f"{nets} {rows}")
+
+
+@pytest.mark.parametrize("rows", sorted(BIG_ROWS))
+@pytest.mark.parametrize("num_obs", BIG_WIDTHS)
+def test_grads_on_the_production_plan_of_the_wide_rows_match_float64_autograd(big_reference, num_obs, rows):
+    """The same at the widths training reaches with a height scan, on the reference nets, each width with a pool of its own.  At 240 columns and
+    16 385 rows the first layer's weight gradient is the one launch that runs the 128 x 64 tile over 1024-row chunks (17, the last of one row), reads
+    its rows through the index with ldb = 240 and ends in a column tile of 48 live columns; at 256 it takes the 128 x 128 tile
+    (tests/test_ppo_gemm_plan.py pins both plans).  Measured error / gap: DESIGN.md section 8.3."""
+    cases = big_reference("reference", num_obs)
+    got = _check_production(cases, "reference", rows, f"reference {rows} at {num_obs} columns")
+    if num_obs in ZERO_PAD:
+        _zero_pad_columns_are_exactly_zero(cases[rows][0], got, f"reference {rows} at {num_obs} columns")
+
+
+def _check_small(cases, nets, rows, num_obs=48, **cfg_kw):
+    """test_grads_match_float64_autograd's rule on every mini-batch of one case of grads_reference, the gaps pooled over `cases`, under
+    _cfg(nets, mini-batches, **cfg_kw); returns per mini-batch (device gradients, device terms, float64 terms, the bounds of the three loss terms and
+    of the gradients)."""
+    gap = max(ref.rel_l2(g32, g64) for case in cases.values() for (g64s, _, _), (g32s, _, _) in case for g32, g64 in zip(g32s, g64s))
+    rel = lambda x, r: abs(x - r) / abs(r)
+    pool3 = max(rel(b[1][q], a[1][q]) for case in cases.values() for a, b in case for q in range(3))
+    pool_kl = max(rel(b[1][3], a[1][3]) for case in cases.values() for a, b in case)
+    ac, st, perm = _fixture(nets, rows, num_obs)
+    mb = ROWS[rows][2]
+    size = len(perm) // mb
+    dev, dst = _to_device(ac, st)
+    alg = P.PPO(dev, _cfg(nets, mb, num_obs, **cfg_kw), backend="hip")
+    alg._device_state(size)
+    names, out = _names(ac), []
+    for i in range(mb):
+        what = f"{nets} {rows} at {num_obs} columns{''.join(f', {k} = {v}' for k, v in cfg_kw.items())}, mini-batch {i}"
+        (g64s, t64, frac), _ = cases[rows][i]
+        assert 0.05 < frac[0] < 0.95 and 0.05 < frac[1] < 0.95, frac
+        got, terms, lr = _device_grads(alg, dst, perm, size, first=i * size)
+        assert lr == ref.adapt(1e-3, t64[3], alg.cfg), t64[3]
+        for q, name in enumerate(("surrogate", "value loss", "entropy", "kl")):
+            g = pool_kl if q == 3 else pool3
+            err = rel(float(terms[q]), t64[q])
+            print(f"{what}: {name} off by {err:.3e} (bound {4 * g:.3e}, ratio {err / g:.3f})")
+            assert g > 0 and err <= 4 * g, (name, err, g)
+        _pooled([(names[k], ref.rel_l2(got[k], g64s[k]), gap) for k in range(len(names))], f"{what}: gradients")
+        if num_obs in ZERO_PAD:
+            _zero_pad_columns_are_exactly_zero(ac, got, what)
+        out.append((got, terms, t64, 4 * pool3, 4 * gap))
+    return out
+
+
+@pytest.mark.parametrize("rows", WIDE_ROWS)
+@pytest.mark.parametrize("num_obs", WIDTHS)
+@pytest.mark.parametrize("nets", WIDE_NETS)
+def test_grads_match_float64_autograd_at_other_widths(grads_reference, nets, num_obs, rows):
+    """Every gradient tensor, the four terms and the learning-rate decision of every mini-batch at 16 and 240 columns, the float32 gap pooled over
+    WIDE_ROWS of this net pair and width only."""
+    _check_small(grads_reference(nets, num_obs, WIDE_ROWS), nets, rows, num_obs)
+
+
+def test_the_unclipped_value_loss_matches_float64_autograd(grads_reference):
+    """use_clipped_value_loss = 0 reaches head_row on the device: terms and gradients of the four ragged mini-batches against autograd under
+    PPOConfig(use_clipped_value_loss=False), with a pool of their own; and the value loss is not the clipped run's, by more than the bound."""
+    plain = _check_small(grads_reference("uneven", 48, ("ragged",), use_clipped_value_loss=False), "uneven", "ragged", use_clipped_value_loss=False)
+    clipped = grads_reference("uneven")["ragged"]
+    critic_w0 = _first_layer_weights(_fixture("uneven", "ragged")[0])[1]
+    for i, (got, terms, t64, bound, grad_bound) in enumerate(plain):
+        (c64s, c64, _), _ = clipped[i]
+        assert all(abs(t64[q] - c64[q]) <= 1e-12 * abs(c64[q]) for q in (0, 2, 3))   # the flag moves the value loss alone
+        away = abs(float(terms[1]) - c64[1]) / abs(c64[1])
+        print(f"uneven ragged mini-batch {i}: value loss {float(terms[1]):.9g}, float64 unclipped {t64[1]:.9g}, float64 clipped {c64[1]:.9g}: {away:.3e} away (bound {bound:.3e})")
+        assert away > bound and c64[1] > t64[1]
+        assert ref.rel_l2(got[critic_w0], c64s[critic_w0]) > grad_bound                   # and the critic's gradient is not the clipped run's
+
+
+def test_adam_leaves_the_weights_of_the_zero_columns_where_they_were():
+    """One mpc_ppo_update_apply behind the 240-wide gradients: the first-layer weights that multiply the five zero columns are bit for bit what they
+    were and their moments are zero; every tensor, and every other column of the two first-layer weights, moved."""
+    nets, rows, num_obs = "uneven", "chunked", 240
+    ac, st, perm = _fixture(nets, rows, num_obs)
+    live = num_obs - ZERO_PAD[num_obs]
+    dev, dst = _to_device(ac, st)
+    alg = P.PPO(dev, _cfg(nets, 1, num_obs), backend="hip")
+    alg._device_state(len(perm))
+    grads, _, _ = _device_grads(alg, dst, perm, len(perm))
+    _zero_pad_columns_are_exactly_zero(ac, grads, "before the step")
+    params = dev.bind_order()
+    before = [p.detach().cpu().clone() for p in params]
+    P.check(P.update_lib().mpc_ppo_update_apply(alg._handle, alg.cfg.max_grad_norm, 0.9, 0.999, 1e-8, 1, alg.lr_device.data_ptr(), None), "apply")
+    after = [p.detach().cpu() for p in params]
+    assert all(not torch.equal(a, b) for a, b in zip(after, before))
+    for k in _first_layer_weights(ac):
+        assert torch.equal(after[k][:, live:].contiguous().view(torch.int32), before[k][:, live:].contiguous().view(torch.int32))
+        assert bool((after[k][:, :live] != before[k][:, :live]).any(0).all())
+        for key in ("exp_avg", "exp_avg_sq"):
+            m = alg.optimizer.state[params[k]][key].cpu()
+            assert bool((m[:, live:] == 0).all()) and bool((m[:, :live] != 0).any(0).all()), key
 
 
 @pytest.mark.parametrize("nets", sorted(BIG_NETS))
@@ -244,6 +380,12 @@ def apply_reference(grads_reference):
 def test_apply_matches_clip_and_adam(apply_reference, nets, max_norm):
     ac, grads, norms, runs = apply_reference(nets)
     assert all(0.25 < x < 1e3 for x in norms), norms                               # 0.25 always clips, 1e3 never
+    _check_apply(ac, grads, runs, nets, max_norm)
+
+
+def _check_apply(ac, grads, runs, nets, max_norm):
+    """mpc_ppo_update_apply over the float32 gradients `grads` (one list per step) from ac's parameters: parameter changes and both moments after
+    every step within 4 x the gap of runs[(m, float32)] from runs[(m, float64)] (ref.apply_steps), pooled over the steps, tensors and every m."""
     p0 = [p.detach().clone() for p in ac.bind_order()]
     names = _names(ac)
     gaps = {}
@@ -277,6 +419,28 @@ def test_apply_matches_clip_and_adam(apply_reference, nets, max_norm):
                     a, b = a - p0[k].double(), b - p0[k].double()
                 errs.append((names[k], ref.rel_l2(a, b), gaps[kind]))
             _pooled(errs, f"{nets} max_norm {max_norm} step {s + 1}: {what}")
+
+
+@pytest.mark.parametrize("nets", sorted(NORM_NETS))
+def test_apply_joins_more_norm_partials_than_one_trip_of_its_lanes(nets):
+    """test_apply_matches_clip_and_adam's rule where norm_kernel's 1024 lanes walk their i += 1024 loop a second time (NORM_NETS).  The gradients are
+    synthetic: normal draws scaled so that every tensor holds the same share of the squared norm, three different sets for the three steps, so the
+    partials past 1023 (small tensors: biases and std) carry 3 / 11 and 1 / 33 of it and the clip at 0.25 depends on them."""
+    torch.manual_seed(5)
+    ac = P.ActorCritic(48, 12, *NORM_NETS[nets], init_noise_std=0.7)
+    params = ac.bind_order()
+    blocks = -(-max(p.numel() for p in params) // 4096)
+    assert len(params) * blocks == NORM_PARTIALS[nets] > 1024                       # what mpc_ppo_update_apply hands to norm_kernel
+    assert (len(params) - 1) * blocks >= 1024 and params[-1] is ac.std             # the last tensor's only live partial lies in the second trip
+    g = torch.Generator().manual_seed(11)
+    grads = [[torch.randn(p.shape, generator=g) / p.numel() ** 0.5 for p in params] for _ in range(3)]
+    norms = [float(torch.cat([x.flatten() for x in gs]).double().norm()) for gs in grads]
+    # tensor k's block b is partial k * blocks + b: what the second trip reads of it starts at block 1024 - k * blocks
+    tail = [float(torch.cat([x.flatten()[4096 * max(0, 1024 - k * blocks):] for k, x in enumerate(gs)]).double().norm()) for gs in grads]
+    print(f"{nets}: {len(params)} tensors x {blocks} blocks, norms {norms}, of which past partial 1023 {tail}")
+    assert all(x > 1.0 for x in norms) and all(t > 0.1 * x for t, x in zip(tail, norms)), (norms, tail)      # 0.25 clips; the second trip is a tenth or more
+    runs = {(0.25, dt): ref.apply_steps(ac, grads, 0.25, 1e-3 / 1.5, dt) for dt in (torch.float32, torch.float64)}
+    _check_apply(ac, grads, runs, nets, 0.25)
 
 
 @pytest.fixture(scope="module")
