@@ -55,7 +55,11 @@ typedef double mpc_double2 __attribute__((ext_vector_type(2)));
 // L2 write-back / invalidate -- the jobs of one solve may run on different XCDs, each with its own L2.
 #define MPC_GST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define MPC_GLD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+// One wait for every global load issued so far (s_waitcnt vmcnt(0), gfx9 encoding: expcnt and lgkmcnt not waited for).  After a batch of
+// independent loads into registers: what follows uses them without a wait per load (mpc_wrench.h Solver::load_batched)
+#define MPC_WAIT_LOADS() __builtin_amdgcn_s_waitcnt(0x0F70)
 #else
+#define MPC_WAIT_LOADS() ((void)0)
 #define MPC_GST(p, v) (*(p) = (v))
 #define MPC_GLD(p) (*(p))
 #define MPC_LDS_LOAD128(p, lo, hi) do { (lo) = (p)[0]; (hi) = (p)[1]; } while (0)
@@ -186,6 +190,8 @@ struct Cfg {
     const int pos = kAsPos[k];
     return (qp[QP_CONE + pos] * sc[SC_E + 5 * f + pos / 3]) * sc[SC_D + 3 * f + pos % 3];
   }
+  // ... from values already in registers: the cone block's entry, E of its row, D of its column (the same two roundings)
+  static MPC_HD double scaled_cone_entry(double a, double e, double d) { return (a * e) * d; }
   // The same two records as mpc_batch_get_qp / mpc_batch_get_scale hand them out (include/mpc_batch.h: every bound, the dense cone
   // block): q[N] l[M] u[M] cone[15] pad | B6 th1 th2 pad2   and   D[N] E[M] q_s[N] A_s[15 NF] l_s[M] u_s[M] c 1/c | job[2]
   static constexpr int XQP_L = N, XQP_U = N + M, XQP_CONE = N + 2 * M, XQP_LEN = XQP_CONE + 16 + 72 + 36 + 8;

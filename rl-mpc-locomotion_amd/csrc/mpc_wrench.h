@@ -249,8 +249,10 @@ struct Solver {
   long long tlast = 0;
 #ifndef MPC_SECTION_PROFILE
   MPC_HD void lap(int) {}
+  static constexpr bool kSectionLaps = MPC_PROFILE_SUB != 0;      // whether tc[] holds anything but the totals (slots 0 of the polish job, 15)
 #else
   MPC_HD void lap(int k) { const long long now = MPC_CLOCK(); tc[k] += now - tlast; tlast = now; }
+  static constexpr bool kSectionLaps = true;
 #endif
 
   static MPC_HD double fast_recip(double d) {
@@ -505,7 +507,99 @@ struct Solver {
   // ends of a job); a foot lane fetching its own 3 + 5 + 5 values straight from HBM touched every line of the record several times.)
   static constexpr int SL = 2 * N + 2 * M + 2;   // state record: x[N] z[M] y[M] q_old[N] rho flag
   static_assert(SL + N <= Sh::PARTLEN, "the state / force stage must fit Shared::part");
+  // (JOB: the polish job's load, which also fetches what the ADMM job left for it -- the two residuals in jobrec, info[4])
+  template <bool JOB = false>
   MPC_HD void load() {
+    if constexpr (T <= 64) load_batched<JOB>();
+    else load_phased();
+    ex.par([&](Th &t) {
+      if (t.foot) {
+        const int f = t.fid;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t.x[c] = s.part[3 * f + c];      // scaled iterates of the previous call; zeros on the first call
+#pragma unroll
+        for (int r = 0; r < 5; ++r) { t.z[r] = s.part[N + 5 * f + r]; t.y[r] = s.part[N + M + 5 * f + r]; }
+        if (t.tyb >> 10) s.bad = 1;
+      }
+      if (t.tid == 0) {
+        const bool first = s.part[2 * N + 2 * M + 1] == 0.0;
+        s.first = first;
+        s.rho = first ? kRho0 : s.part[2 * N + 2 * M];
+      }
+    });
+    ex.par([](Th &) {});      // (the stage is read before anything else writes s.part)
+    lap(0);
+  }
+  // The first phase of load() in a single-wavefront workgroup.  The wave is alone on its SIMD, so every memory round trip it waits for
+  // is fully exposed, and nothing here depends on anything but the robot: every load of the phase is issued first -- the state record
+  // with lane-contiguous addresses (one MPC_GLD per lane and 64 values), the wrench description, the foot's values of the QP and scale
+  // records -- then ONE wait, then the LDS stage and the per-foot constants.  (Every address is the lane's base plus a constant, as in
+  // load_phased: offsets of their own per array would stay in registers for the whole kernel, which has none to spare.)
+  template <bool JOB>
+  MPC_HD void load_batched() {
+    constexpr int NS = (N + 2 * M + T - 1) / T, NB = (72 + T - 1) / T;
+    ex.par([&](Th &t) {
+      const int f = t.fid;
+      double sv[NS], rf = 0, b6[NB], t1 = 0, t2 = 0, q[3] = {0, 0, 0}, d[3] = {0, 0, 0}, e[5] = {0, 0, 0, 0, 0}, bnd[3] = {0, 0, 0}, cone[9], cc[2], jr[2] = {0, 0};
+      int nf = 0;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {      // x, z, y (the previous q in between is the prep kernel's business)
+        sv[k] = 0;
+        if ((k + 1) * T <= N + 2 * M || t.tid + k * T < N + 2 * M) sv[k] = MPC_GLD(state + t.tid + k * T);
+      }
+      if (t.tid < 2) rf = MPC_GLD(state + 2 * N + 2 * M + t.tid);      // rho, flag
+      if constexpr (JOB) { jr[0] = MPC_GLD(jobrec); jr[1] = MPC_GLD(jobrec + 1); nf = MPC_GLD(info + 4); }
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        b6[k] = 0;
+        if ((k + 1) * T <= 72 || t.tid + k * T < 72) b6[k] = qp[C::QP_B6 + t.tid + k * T];
+      }
+      if (t.tid < 36) t1 = qp[C::QP_TH1 + t.tid];
+      if (t.tid < 6) t2 = qp[C::QP_TH2 + t.tid];
+      if (t.foot) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { q[c] = sc[C::SC_QS + 3 * f + c]; d[c] = sc[C::SC_D + 3 * f + c]; bnd[c] = qp[C::QP_BND + 3 * f + c]; }
+#pragma unroll
+        for (int r = 0; r < 5; ++r) e[r] = sc[C::SC_E + 5 * f + r];
+      }
+#pragma unroll
+      for (int k = 0; k < 9; ++k) cone[k] = qp[C::QP_CONE + kAsPos[k]];
+      cc[0] = sc[C::SC_C]; cc[1] = sc[C::SC_C + 1];
+      const double alpha = mdl.alpha;
+      MPC_WAIT_LOADS();
+#pragma unroll
+      for (int k = 0; k < NS; ++k) if ((k + 1) * T <= N + 2 * M || t.tid + k * T < N + 2 * M) s.part[t.tid + k * T] = sv[k];
+      if (t.tid < 2) s.part[2 * N + 2 * M + t.tid] = rf;
+#pragma unroll
+      for (int k = 0; k < NB; ++k) if ((k + 1) * T <= 72 || t.tid + k * T < 72) s.B6[t.tid + k * T] = b6[k];
+      if (t.tid < 36) s.th1[t.tid] = t1;
+      if (t.tid < 6) s.th2[t.tid] = t2;
+      if (t.foot) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t.q[c] = q[c];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s.fa[pidx(k, f)] = C::scaled_cone_entry(cone[k], e[kAsPos[k] / 3], d[kAsPos[k] % 3]);
+        s.fa[pidx(15, f)] = 0.0;
+        int tyb = 0;
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {      // (see load_phased)
+          const double lo = e[r] * (r < 4 ? 0.0 : bnd[0]), hi = e[r] * (r < 4 ? bnd[1] : bnd[2]);
+          s.fa[pidx(10 + r, f)] = hi;
+          if (r == 4) s.fa[pidx(9, f)] = lo;
+          const int ty = (lo < -kInfty * kMinScaling && hi > kInfty * kMinScaling) ? 0 : (hi - lo < kRhoTol ? 2 : 1);
+          tyb |= ty << (2 * r);
+          if (lo > hi) tyb |= 1 << 10;
+        }
+        t.tyb = tyb;
+      }
+      if (t.tid == 0) {
+        s.c = cc[0]; s.cinv = cc[1]; s.calpha = cc[0] * alpha;
+        s.status = JOB ? kStSolved : kStUnsolved; s.status_polish = 0; s.rho_updates = 0; s.nfact = nf; s.iter = 0; s.done = 0; s.bad = 0; s.pol_ok = 0; s.sig_changed = 0; s.loose_ok = 0;
+        if constexpr (JOB) { s.pri_res = jr[0]; s.dua_res = jr[1]; }
+      }
+    });
+  }
+  MPC_HD void load_phased() {
     ex.par([&](Th &t) {
       for (int i = t.tid; i < N + 2 * M; i += T) s.part[i] = MPC_GLD(state + i);      // x, z, y (the previous q in between is the prep kernel's business)
       if (t.tid < 2) s.part[2 * N + 2 * M + t.tid] = MPC_GLD(state + 2 * N + 2 * M + t.tid);      // rho, flag
@@ -540,23 +634,6 @@ struct Solver {
         s.status = kStUnsolved; s.status_polish = 0; s.rho_updates = 0; s.nfact = 0; s.iter = 0; s.done = 0; s.bad = 0; s.pol_ok = 0; s.sig_changed = 0; s.loose_ok = 0;
       }
     });
-    ex.par([&](Th &t) {
-      if (t.foot) {
-        const int f = t.fid;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) t.x[c] = s.part[3 * f + c];      // scaled iterates of the previous call; zeros on the first call
-#pragma unroll
-        for (int r = 0; r < 5; ++r) { t.z[r] = s.part[N + 5 * f + r]; t.y[r] = s.part[N + M + 5 * f + r]; }
-        if (t.tyb >> 10) s.bad = 1;
-      }
-      if (t.tid == 0) {
-        const bool first = s.part[2 * N + 2 * M + 1] == 0.0;
-        s.first = first;
-        s.rho = first ? kRho0 : s.part[2 * N + 2 * M];
-      }
-    });
-    ex.par([](Th &) {});      // (the stage is read before anything else writes s.part)
-    lap(0);
   }
   // my foot's constants, fetched where they are used (volatile 64-bit LDS loads: the compiler neither hoists them out of the
   // iteration loop nor keeps them in registers across it -- 30 VGPRs the loop does not have)
@@ -2776,10 +2853,13 @@ struct Solver {
   MPC_HD void polish_job() {
     const long long t0 = MPC_CLOCK();
     tlast = t0; if (MPC_PROFILE_SUB == 8) t_start = t0;
-    load();          // (x, z, y of the state record are the ADMM part's result)
-    ex.par([&](Th &t) {
-      if (t.tid == 0) { s.pri_res = MPC_GLD(jobrec); s.dua_res = MPC_GLD(jobrec + 1); s.status = kStSolved; s.nfact = MPC_GLD(info + 4); }
-    });
+    if constexpr (T <= 64) load<true>();      // (x, z, y of the state record are the ADMM part's result; its residuals and info[4] in the same batch)
+    else {
+      load();
+      ex.par([&](Th &t) {
+        if (t.tid == 0) { s.pri_res = MPC_GLD(jobrec); s.dua_res = MPC_GLD(jobrec + 1); s.status = kStSolved; s.nfact = MPC_GLD(info + 4); }
+      });
+    }
     lap(9);
     polish();
     lap(14);
@@ -2800,8 +2880,11 @@ struct Solver {
       if (t.tid == 0) {
         MPC_GST(info + 2, s.status_polish); MPC_GST(info + 4, s.nfact);
         if (prof) {   // (slot 0: the polish job as a whole; the sections add to the ADMM job's under MPC_SECTION_PROFILE)
-          for (int k = 6; k < 15; ++k) if (k != 8 && k != 10) MPC_GST(prof + k, MPC_GLD(prof + k) + tc[k]);
-          MPC_GST(prof, MPC_GLD(prof) + (MPC_CLOCK() - t0));
+          if constexpr (T <= 64 && !kSectionLaps) MPC_GST(prof, MPC_CLOCK() - t0);      // (no laps: the sections would add zero, and the ADMM job's store() left 0 in slot 0)
+          else {
+            for (int k = 6; k < 15; ++k) if (k != 8 && k != 10) MPC_GST(prof + k, MPC_GLD(prof + k) + tc[k]);
+            MPC_GST(prof, MPC_GLD(prof) + (MPC_CLOCK() - t0));
+          }
         }
       }
     });
