@@ -12,8 +12,9 @@ _OBS_NORM = ("ObsNormalizer", "fold_normalizer")
 _CURRICULUM = ("TerrainCurriculum",)
 _HEIGHT_SCAN = ("HeightScan",)
 _DOMAIN_RAND = ("DomainRand", "NoiseSpec", "PushSpec")
+_EPISODE_TERMS = ("EpisodeTerms", "CommandCurriculumSpec")
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS]
 
 
 def __getattr__(name):
@@ -36,4 +37,7 @@ def __getattr__(name):
     if name in _DOMAIN_RAND:
         from . import domain_rand
         return getattr(domain_rand, name)
+    if name in _EPISODE_TERMS:
+        from . import episode_terms
+        return getattr(episode_terms, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -517,7 +517,8 @@ class PPOTrainer:
         update) and returns the list.  Besides the losses a record carries rsl_rl's episode statistics: ``mean_episode_return`` and
         ``mean_episode_length`` over the last 100 finished episodes (0.0 while there are none), ``episodes_in_window``, ``timeouts_in_window`` and
         the cumulative ``episodes_finished``; on an environment with a terrain ``curriculum`` also ``mean_terrain_level`` and ``terrain_level_by_type``
-        as they stand after the iteration.  ``init_at_random_ep_len``: before the first collection ``env.progress_buf`` is set to integers
+        as they stand after the iteration; on one with ``episode_terms`` also ``episode_terms``: ``rew_<term>`` over the episodes closed during the
+        iteration, ``max_command_x``, ``min_command_x`` and ``command_widenings`` (``EpisodeTerms.record``).  ``init_at_random_ep_len``: before the first collection ``env.progress_buf`` is set to integers
         uniform on [0, ``env.cfg.max_episode_length``), drawn from the trainer's seed, so that the environments do not time out on one tick.  As in
         rsl_rl's ``learn``, this happens at the start of EVERY call that sets the flag (the same draw each time: it moves episodes that are under way),
         so set it on the first call only."""
@@ -536,6 +537,10 @@ class PPOTrainer:
             episodes = self.episode_stats.summary                                # float64, on the device: rides along in the one read
             curriculum = getattr(self.env, "curriculum", None)
             tail = (episodes,) if curriculum is None else (episodes, curriculum.summary())      # (a terrain curriculum's levels ride along too)
+            terms = getattr(self.env, "episode_terms", None)
+            if terms is not None:                                                # (and the per-term episode sums of the iteration's closed episodes)
+                terms_summary = terms.summary()
+                tail = tail + (terms_summary,)
             if self.alg.backend == "hip":                                        # and so does the device's learning rate
                 stats = torch.cat((stats, self.alg.lr_device, *tail)).tolist()
                 self.alg.sync_learning_rate(stats[5])
@@ -550,6 +555,9 @@ class PPOTrainer:
                                    episodes_finished=int(ep[S_EPISODES]), timeouts_in_window=int(ep[S_WINDOW_TIMEOUTS])))
             if curriculum is not None:
                 self.infos[-1].update(curriculum.record(ep[episodes.numel():], curriculum.num_types))
+            if terms is not None:
+                self.infos[-1]["episode_terms"] = terms.record(ep[len(ep) - terms_summary.numel():])
+                terms.new_window()                                               # the next record covers the next iteration's episodes
         return self.infos
 
     def evaluate(self, num_ticks, groups=None, num_groups=1):
@@ -557,17 +565,26 @@ class PPOTrainer:
         with no storage write and no update, counted by a fresh ``EpisodeStats`` (``groups`` / ``num_groups``: e.g. the robot type of each
         environment); one host read at the end.  Returns the overall totals -- ``episodes``, ``time_outs``, ``terminations`` (episodes minus
         time-outs: on the toy plant, falls), ``mean_return``, ``mean_length`` -- and the same per group under ``groups``.  ``tick`` and the noise
-        sequence are untouched; the training statistics drop the episodes under way (``restart``), which the evaluation has cut in two."""
+        sequence are untouched; the training statistics drop the episodes under way (``restart``), which the evaluation has cut in two.  An environment's
+        ``episode_terms`` has ``curriculum_enabled`` cleared for the loop: the command ranges stay where training left them."""
         stats = EpisodeStats(self.env.num_envs, groups=groups, num_groups=num_groups, device=self.device)
         if self.obs is None:
             self.obs = self._first_obs()
         norm = self.obs_norm
-        with torch.no_grad():
-            for _ in range(int(num_ticks)):
-                self.obs, rew, reset, extras = self.env.step(self.actor_critic.act_inference(self.obs))
-                if norm is not None:                                             # the statistics stay as training left them
-                    self.obs = norm(self.obs, out=self._obs_held, update=False)
-                stats.add(rew, reset, extras["time_outs"])
+        terms = getattr(self.env, "episode_terms", None)
+        enabled = terms.curriculum_enabled if terms is not None else None
+        if terms is not None:                                                    # an evaluation does not move the command ranges
+            terms.curriculum_enabled = False
+        try:
+            with torch.no_grad():
+                for _ in range(int(num_ticks)):
+                    self.obs, rew, reset, extras = self.env.step(self.actor_critic.act_inference(self.obs))
+                    if norm is not None:                                         # the statistics stay as training left them
+                        self.obs = norm(self.obs, out=self._obs_held, update=False)
+                    stats.add(rew, reset, extras["time_outs"])
+        finally:
+            if terms is not None:
+                terms.curriculum_enabled = enabled
         out = stats.read()
         self.episode_stats.restart()
         keys = ("episodes", "time_outs", "terminations", "mean_return", "mean_length")
@@ -578,11 +595,15 @@ class PPOTrainer:
     def save(self, path):
         """The checkpoint as rsl_rl writes it; ``WeightPolicy.from_state_dict(torch.load(path)["model_state_dict"])`` loads its actor.  With
         normalisation on it also carries ``obs_norm_state_dict`` (rsl_rl 2.x's key), and the actor expects normalised observations:
-        ``obs_norm.fold_normalizer(ck["model_state_dict"], ck["obs_norm_state_dict"])`` gives the state dict for raw ones."""
+        ``obs_norm.fold_normalizer(ck["model_state_dict"], ck["obs_norm_state_dict"])`` gives the state dict for raw ones.  On an environment with
+        ``episode_terms`` it carries ``episode_terms_state_dict`` (the x command range, the widenings, the tick), which ``load`` restores when present."""
         ck = {"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(), "iter": self.iteration,
               "infos": self.infos}
         if self.obs_norm is not None:
             ck["obs_norm_state_dict"] = self.obs_norm.state_dict()
+        terms = getattr(self.env, "episode_terms", None)
+        if terms is not None:                                                    # the command range the policy was trained up to
+            ck["episode_terms_state_dict"] = terms.state_dict()
         torch.save(ck, path)
 
     def load(self, path, load_optimizer=True):
@@ -593,6 +614,11 @@ class PPOTrainer:
         if self.obs_norm is not None:
             self.obs_norm.load_state_dict(ck["obs_norm_state_dict"])
             self.obs = None                                                      # (normalised with the statistics before the load)
+        terms = getattr(self.env, "episode_terms", None)
+        if terms is not None and "episode_terms_state_dict" in ck:
+            terms.load_state_dict(ck["episode_terms_state_dict"])
+            if hasattr(self.env, "common_step_counter"):
+                self.env.common_step_counter = terms.tick
         self.actor_critic.load_state_dict(ck["model_state_dict"])      # (in place: the kernels keep reading the same addresses)
         if load_optimizer:
             self.alg.optimizer.load_state_dict(ck["optimizer_state_dict"])

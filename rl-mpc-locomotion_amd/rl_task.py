@@ -193,11 +193,16 @@ class BatchedRLTask:
     columns, the scan of the terrain around the base, a zero pad -- ``num_obs`` its width, and ``measured_heights`` [N, P] the heights in metres.
     ``domain_rand`` (a ``domain_rand.DomainRand`` for as many environments): while its ``enabled`` is true, noise on the actions in place of the
     clamp at the head of ``step``, a push of the base after the plant's step on push ticks, and noise on ``obs_buf``'s columns last.
+    ``episode_terms`` (an ``episode_terms.EpisodeTerms`` for as many environments): the per-term episode sums are closed straight after ``begin``
+    -- with a command curriculum the environments being reset also get commands from the curriculum's ranges in place of those ``begin`` drew --
+    and fed after ``finish``; ``common_step_counter`` counts the task's ticks on the host and is the tick the curriculum sees.
     See the module text for what the toy cannot do."""
 
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
-                 curriculum=None, height_scan=None, domain_rand=None, **bridge_args):
+                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, **bridge_args):
         import torch
+        if episode_terms is not None and episode_terms.n != len(np.asarray(robot_type).reshape(-1)):      # refused before the device is touched
+            raise ValueError(f"the episode terms hold {episode_terms.n} environments, robot_type {len(np.asarray(robot_type).reshape(-1))}")
         if domain_rand is not None:        # everything that can be refused before the device is touched
             n_envs = len(np.asarray(robot_type).reshape(-1))
             width = NUM_OBS if height_scan is None else height_scan.width(NUM_OBS)
@@ -244,6 +249,8 @@ class BatchedRLTask:
         if domain_rand is not None:
             domain_rand.bind(self.sim, dt=self.cfg.dt)
             self.num_active_obs = NUM_OBS + (height_scan.num_points if height_scan is not None else 0)      # what is not the scan's zero pad
+        self.episode_terms = episode_terms
+        self.common_step_counter = 0       # the ticks this task has stepped, counted on the host: the command curriculum's clock
 
     def step(self, actions):
         """``VecTask.step`` (vec_task.py:298-339): actions [N,12] -> (obs_buf, rew_buf, reset_buf, {"time_outs": timeout_buf}).  The returned
@@ -265,10 +272,16 @@ class BatchedRLTask:
         if self.curriculum is not None:    # the flags begin is about to consume, the finished episode's commands, the root states before the reset
             self.curriculum.update(self.reset_buf, sim.root_states, self.commands)
         ids = t.begin()                                                                                                         # :326, aliengo.py:274-278
+        et = self.episode_terms
+        if et is not None:                 # close the marked episodes, decide, and put the curriculum's commands in place before finish reads them
+            self.common_step_counter += 1
+            et.close_and_resample(ids, self.commands, self.common_step_counter)
         self.bridge.ctl.reset(ids)                                                                                              # aliengo.py:330-334
         sim.reset_idx(ids)                                                                                                      # aliengo.py:336-342
         _, fell = sim.flags()              # after the reset: a robot that has just been put back standing is not flagged a second time
         t.finish(sim.root_states, sim.dof_state, self.actions, self.torques, fell=fell)                                         # aliengo.py:280-281, :337
+        if et is not None:                 # the tensors finish has just read, the same base contact
+            et.accumulate(sim.root_states, self.commands, self.torques, fell)
         if self.height_scan is not None:   # the same post-reset root states, and the origins the curriculum has just written
             self.height_scan.measure(sim.root_states, t.obs_buf, out=self.obs_buf, heights=self.measured_heights)
         if dr is not None and dr.specs["observations"] is not None:                                                             # :331-337, in place

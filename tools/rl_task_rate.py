@@ -21,6 +21,12 @@ and the observation-noise kernel, beside the `finish` kernel and the scan; p10, 
 BatchedRLTask.step with the option (legged_gym's observation noise, gaussian action noise, a push every 1500 ticks) against the same task without it in
 alternating blocks, with their p10 - p90 and the share of the tick the option adds.
     python tools/rl_task_rate.py --domain-rand [--out profiles/r16_domain_rand.json]
+--terms times the per-term episode sums (rl_mpc_locomotion_amd.episode_terms), with --command-curriculum also the command curriculum they drive, on
+the flat plane: the unit's two calls alone from HIP events inside the running loop (close_and_resample: two launches, three with the curriculum;
+accumulate: one; beside the `begin` and `finish` kernels; p10, median, p90), and BatchedRLTask.step with the unit against the same task without it --
+the step as it is without the option -- in alternating blocks, with the share of the tick the unit adds; with --learn K also what K PPO iterations
+do with the curriculum and with the fixed default range (one seed: a finding, not a claim).
+    python tools/rl_task_rate.py --terms [--command-curriculum] [--learn 20] [--out profiles/episode_terms_rate.json]
 The kernel-trace stats of the same step: rocprofv3 --kernel-trace --stats ... -- python tools/rl_task_rate.py --ticks 50 --quick"""
 import argparse
 import json
@@ -433,6 +439,94 @@ def domain_rand_report(args, dev, n, actions):
     return res
 
 
+def tick_terms(task, actions, ev):
+    """BatchedRLTask.step's statements with the episode terms, with events around `begin`, the unit's two calls and `finish`"""
+    sim, t, et = task.sim, task.task, task.episode_terms
+    tau = task.bridge.pre_physics_step(actions, sim.dof_state, sim.root_states, task.commands)
+    sim.step(tau)
+    ev[0].record()
+    ids = t.begin()
+    ev[1].record()
+    task.common_step_counter += 1
+    et.close_and_resample(ids, task.commands, task.common_step_counter)
+    ev[2].record()
+    task.bridge.ctl.reset(ids)
+    sim.reset_idx(ids)
+    _, fell = sim.flags()
+    ev[3].record()
+    t.finish(sim.root_states, sim.dof_state, actions, tau, fell=fell)
+    ev[4].record()
+    et.accumulate(sim.root_states, task.commands, tau, fell)
+    ev[5].record()
+
+
+def terms_report(args, dev, n, actions):
+    from bench import device_state
+    from rl_mpc_locomotion_amd.episode_terms import CommandCurriculumSpec, EpisodeTerms
+    cfg = TaskConfig(episode_length_s=args.episode_s)                          # the default command ranges: the curriculum starts inside them
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    spec = CommandCurriculumSpec(max_curriculum=2.5, x_range0=(-1.0, 1.0)) if args.command_curriculum else None
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "ticks_per_block": args.ticks, "blocks": args.blocks,
+           "command_curriculum": bool(args.command_curriculum), "episode_length_s": cfg.episode_length_s,
+           "launches_per_tick": {"close_and_resample": 3 if spec is not None else 2, "accumulate": 1}, "device_state": {"before": device_state(0)}}
+
+    def make_task(with_terms, task_cfg=cfg, task_spec=spec):
+        et = EpisodeTerms(n, task_cfg, command_curriculum=task_spec, device=dev) if with_terms else None
+        return BatchedRLTask([0] * n, [TROT] * n, cfg=task_cfg, horizon=10, yaw0=yaw, flat_ground=True, device=dev, episode_terms=et)
+    loops = {"step_with_terms": make_task(True), "step_without": make_task(False)}
+    for task in loops.values():
+        task.reset()
+        for _ in range(20):
+            task.step(actions)
+    torch.cuda.synchronize()
+    wall = {k: [] for k in loops}
+    for _ in range(args.blocks):          # the two loops alternate, block by block
+        for name, task in loops.items():
+            t0 = time.perf_counter()
+            for _ in range(args.ticks):
+                task.step(actions)
+            torch.cuda.synchronize()
+            wall[name].append(time.perf_counter() - t0)
+    for name, w in wall.items():
+        per = np.array(w) / args.ticks * 1e3
+        res[name] = {"ms_per_tick_median": med(per), "ms_per_tick_p10": float(np.percentile(per, 10)), "ms_per_tick_p90": float(np.percentile(per, 90)),
+                     "ms_per_tick_min": float(per.min()), "ms_per_tick_max": float(per.max()), "robot_ticks_per_s": n * args.ticks / med(w)}
+    res["with_over_without_ms_per_tick"] = res["step_with_terms"]["ms_per_tick_median"] / res["step_without"]["ms_per_tick_median"]
+    task = loops["step_with_terms"]
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(6)] for _ in range(args.ticks * 2)]
+    for e in ev:
+        tick_terms(task, actions, e)
+    torch.cuda.synchronize()
+    span = lambda i: np.array([e[i].elapsed_time(e[i + 1]) for e in ev])
+    parts = {"begin_kernel": span(0), "close_and_resample": span(1), "finish_kernel": span(3), "accumulate_kernel": span(4)}
+    for k, v in parts.items():
+        res[k] = spread(v)
+    res["events"] = len(ev)
+    unit = med(parts["close_and_resample"]) + med(parts["accumulate_kernel"])
+    tick_ms = res["step_without"]["ms_per_tick_median"]
+    res["share_of_the_tick"] = {"unit_launches_medians_us": unit * 1e3, "unit_over_step_without": unit / tick_ms,
+                                "unit_over_begin_plus_finish": unit / (med(parts["begin_kernel"]) + med(parts["finish_kernel"])),
+                                "measured_step_difference_over_step_without": res["with_over_without_ms_per_tick"] - 1.0}
+    et = task.episode_terms
+    res["after_timing"] = {"fallen_fraction": {k: float(t.sim.flags()[1].float().mean().item()) for k, t in loops.items()},
+                           "resamples_seen_per_env_mean": float(et.counts.float().mean().item()), "record": EpisodeTerms.record(et.summary().tolist())}
+    res["device_state"]["mid"] = device_state(0, smi=False)
+    del loops, task
+    if args.learn > 0:                    # a finding, not a condition, and one seed: what the curriculum does to a short training run
+        from rl_mpc_locomotion_amd.ppo import PPOConfig, PPOTrainer
+        res["learn"] = {"seeds": 1, "iterations": args.learn}
+        learn_cfg = TaskConfig()
+        for name, learn_spec in (("command_curriculum", CommandCurriculumSpec(max_curriculum=2.5, x_range0=(-1.0, 1.0))), ("fixed_default_range", None)):
+            trainer = PPOTrainer(make_task(True, learn_cfg, learn_spec), PPOConfig(), seed=1, update="hip")
+            infos = trainer.learn(args.learn, init_at_random_ep_len=True)[-args.learn:]
+            res["learn"][name] = {"mean_reward_per_iteration": [i["mean_reward"] for i in infos],
+                                  "mean_episode_length_per_iteration": [i["mean_episode_length"] for i in infos],
+                                  "rew_lin_vel_xy_per_iteration": [i["episode_terms"]["rew_lin_vel_xy"] for i in infos],
+                                  "max_command_x_per_iteration": [i["episode_terms"]["max_command_x"] for i in infos], "last_record": infos[-1]["episode_terms"]}
+    res["device_state"]["after"] = device_state(0, smi=False)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--ticks", type=int, default=100, help="ticks per block")
@@ -441,17 +535,20 @@ if __name__ == "__main__":
     ap.add_argument("--quick", action="store_true", help="one block of BatchedRLTask.step only (for a kernel trace)")
     ap.add_argument("--curriculum", action="store_true", help="time the terrain curriculum (see the head of this file)")
     ap.add_argument("--max-init-level", type=int, default=9, help="--curriculum: initial levels uniform in 0 .. this")
-    ap.add_argument("--learn", type=int, default=0, help="--curriculum: also K PPO iterations from level 0, with evaluate() before and after")
+    ap.add_argument("--learn", type=int, default=0, help="--curriculum: also K PPO iterations from level 0, with evaluate() before and after; --terms: K iterations with and without the command curriculum")
     ap.add_argument("--eval-ticks", type=int, default=500)
     ap.add_argument("--heights", action="store_true", help="time the terrain height scan (see the head of this file); with or without --curriculum")
     ap.add_argument("--learn-blocks", type=int, default=3, help="--heights: timed learn iterations per trainer")
     ap.add_argument("--domain-rand", action="store_true", help="time the domain randomisation's three launches and the step with and without it")
+    ap.add_argument("--terms", action="store_true", help="time the per-term episode sums' launches and the step with and without them")
+    ap.add_argument("--command-curriculum", action="store_true", help="--terms: with the command curriculum (one more launch per tick)")
+    ap.add_argument("--episode-s", type=float, default=20.0, help="--terms: the episode length of the timed tasks, in seconds")
     ap.add_argument("--out")
     args = ap.parse_args()
     dev, n = "cuda:0", args.robots
     actions = torch.zeros((n, 12), dtype=torch.float32, device=dev)
-    if args.domain_rand or args.heights or args.curriculum:
-        res = (domain_rand_report if args.domain_rand else heights_report if args.heights else curriculum_report)(args, dev, n, actions)
+    if args.terms or args.domain_rand or args.heights or args.curriculum:
+        res = (terms_report if args.terms else domain_rand_report if args.domain_rand else heights_report if args.heights else curriculum_report)(args, dev, n, actions)
         print(json.dumps(res, indent=1))
         if args.out:
             with open(args.out, "w") as fh:
