@@ -5,6 +5,7 @@
  *
  *   mpc_ac_act            ActorCritic.act + evaluate: actor and critic MLPs in ONE launch, the actor half ending in the sampling / log-prob
  *                         epilogue.  Every output pointer is the caller's and may point straight into slot t of its rollout storage.
+ *   mpc_ac_act_asymmetric the same launch for an asymmetric actor-critic: the critic reads privileged rows of its own width
  *   mpc_ac_evaluate       the critic alone (the iteration's last_values)
  *   mpc_ac_act_inference  the actor's mean alone (ActorCritic.act_inference)
  *   mpc_rollout_add       PPO.process_env_step: the time-out bootstrap r' = r + gamma (v to) and the done flag into slot t, read from the task's own
@@ -40,6 +41,11 @@ enum { MPC_AC_MAX_LAYERS = 8, MPC_AC_ACTIONS = 12 };
  * differ otherwise.  Limits of mpc_policy_create: 1 .. 8 layers, every layer input width a positive multiple of 16, at most 16 outputs.  Host-only:
  * no device is needed until mpc_ac_bind. */
 int mpc_ac_create(mpc_ac **out, int n_actor_layers, const int *actor_dims, int n_critic_layers, const int *critic_dims);
+/* The asymmetric actor-critic (rsl_rl's num_critic_obs): the same two stacks with the same limits per stack, but the critic reads rows of its own,
+ * so actor_dims[0] and critic_dims[0] are independent (the LDS limit holds for the wider of the two nets).  On such a handle the critic's
+ * observations are an argument of their own (mpc_ac_act_asymmetric), mpc_ac_evaluate reads rows of width critic_dims[0] and mpc_ac_act_inference
+ * rows of width actor_dims[0]; the plain mpc_ac_act is refused with MPC_E_ARG, before the device is touched, when the two widths differ. */
+int mpc_ac_create_asymmetric(mpc_ac **out, int n_actor_layers, const int *actor_dims, int n_critic_layers, const int *critic_dims);
 void mpc_ac_destroy(mpc_ac *ac);
 /* The parameters, on the current HIP device: per layer a DEVICE pointer to its weight [out][in] row-major (torch Linear.weight) and to its bias [out],
  * given as host arrays of n_actor_layers / n_critic_layers pointers, and d_std [12].  Every pointer must be non-null and 16-byte aligned.  Kept, not
@@ -50,6 +56,11 @@ int mpc_ac_bind(mpc_ac *ac, const float *const *d_actor_weights, const float *co
  * rsl_rl's action_sigma) and, unless NULL, d_eps [n][12] (the noise, for tests).  eps of environment r is a function of (seed, r, step) alone. */
 int mpc_ac_act(mpc_ac *ac, int n, const float *d_obs, unsigned long long seed, unsigned int step, float *d_actions, float *d_log_prob, float *d_values,
                float *d_mean, float *d_sigma, float *d_eps, void *stream);
+/* The same single launch with the critic's rows given apart: d_obs [n][actor_dims[0]] feeds the actor, d_critic_obs [n][critic_dims[0]] (non-null)
+ * the critic.  The actor's outputs are bit for bit those of the plain call on the same actor and d_obs; d_values those of mpc_ac_evaluate on
+ * d_critic_obs. */
+int mpc_ac_act_asymmetric(mpc_ac *ac, int n, const float *d_obs, const float *d_critic_obs, unsigned long long seed, unsigned int step, float *d_actions,
+                          float *d_log_prob, float *d_values, float *d_mean, float *d_sigma, float *d_eps, void *stream);
 int mpc_ac_evaluate(mpc_ac *ac, int n, const float *d_obs, float *d_values, void *stream);
 int mpc_ac_act_inference(mpc_ac *ac, int n, const float *d_obs, float *d_mean, void *stream);
 /* d_rew [n] float32, d_reset [n] and d_timeout [n] int64 (0 / 1; the task's buffers as they are), d_values_t [n] (slot t, as written by mpc_ac_act)

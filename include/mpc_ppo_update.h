@@ -44,6 +44,10 @@ int mpc_ppo_update_bind(mpc_ppo_update *u, float *const *d_grads, float *const *
  * d_log_prob [.]. */
 int mpc_ppo_update_set_storage(mpc_ppo_update *u, long long total_rows, const float *d_obs, const float *d_actions, const float *d_values,
                                const float *d_advantages, const float *d_returns, const float *d_log_prob, const float *d_mu, const float *d_sigma);
+/* The critic's rows of an asymmetric actor-critic (mpc_ac_create_asymmetric): d_critic_obs [total_rows][critic_dims[0]], 16-byte aligned, indexed by
+ * the same d_idx as the rest of the storage; the critic's first layer reads it, forward and backward, in place of d_obs.  NULL clears it.  An
+ * asymmetric mpc_ac without it is refused by mpc_ppo_update_grads with MPC_E_ARG. */
+int mpc_ppo_update_set_critic_storage(mpc_ppo_update *u, const float *d_critic_obs);
 /* One mini-batch: rows 1 .. max_rows, d_idx [rows] int64 row numbers into the storage (values outside [0, total_rows) are clamped into it).  Writes the
  * bound gradients, d_terms [4] = (surrogate, value loss, mean entropy, mean kl) as float32, and, if adaptive != 0, *d_lr (float64) by
  * PPO.adapt_learning_rate's rule with desired_kl > 0.  clip_param > 0. */

@@ -13,8 +13,9 @@ _CURRICULUM = ("TerrainCurriculum",)
 _HEIGHT_SCAN = ("HeightScan",)
 _DOMAIN_RAND = ("DomainRand", "NoiseSpec", "PushSpec")
 _EPISODE_TERMS = ("EpisodeTerms", "CommandCurriculumSpec")
+_PRIVILEGED_OBS = ("PrivilegedObs",)
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS, "privileged_obs", *_PRIVILEGED_OBS]
 
 
 def __getattr__(name):
@@ -40,4 +41,7 @@ def __getattr__(name):
     if name in _EPISODE_TERMS:
         from . import episode_terms
         return getattr(episode_terms, name)
+    if name in _PRIVILEGED_OBS:
+        from . import privileged_obs
+        return getattr(privileged_obs, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

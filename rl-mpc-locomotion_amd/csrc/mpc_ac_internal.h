@@ -14,6 +14,7 @@ struct mpc_ac_view {
   const float *std;                      // [12]
   int device;
   bool bound;
+  bool asymmetric;                       // made by mpc_ac_create_asymmetric: the critic's rows are not the actor's (dims[1][0] may differ from dims[0][0])
 };
 
 // false for a null handle

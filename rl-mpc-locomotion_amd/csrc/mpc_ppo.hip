@@ -45,11 +45,14 @@ struct ActOut {
 };
 
 // grid (ceil(n / 16), nets); net = first_net + blockIdx.y.  sample: the actor's epilogue draws actions (mpc_ac_act); otherwise it writes the mean alone.
-__global__ __launch_bounds__(policy::kThreads) void ac_kernel(Nets nets, int first_net, int sample, int n, const float *__restrict__ obs,
-                                                             unsigned long long seed, unsigned int step, ActOut out) {
+// actor_obs [n][actor dims[0]] and critic_obs [n][critic dims[0]]: each net's workgroups stage their own rows at their own width (the same pointer
+// twice where both nets read the same observations); the pointer of a net that the launch does not run is never read.
+__global__ __launch_bounds__(policy::kThreads) void ac_kernel(Nets nets, int first_net, int sample, int n, const float *__restrict__ actor_obs,
+                                                             const float *__restrict__ critic_obs, unsigned long long seed, unsigned int step, ActOut out) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int which = first_net + (int)blockIdx.y;
   const policy::Net &net = nets.net[which];
+  const float *__restrict__ obs = which == kCritic ? critic_obs : actor_obs;
   int wmax_even = 0, wmax_odd = 0;     // widest activation held by buffer 0 (layers 0, 2, ...) / buffer 1, as policy::mlp_kernel lays them out
   for (int l = 0; l <= net.n_layers; ++l) {
     int &m = (l & 1) ? wmax_odd : wmax_even;
@@ -167,6 +170,7 @@ struct mpc_ac {
   size_t lds = 0;
   int device = -1;
   bool bound = false;
+  bool asymmetric = false;             // made by mpc_ac_create_asymmetric: the critic reads rows of its own
 };
 
 // mpc_ac_internal.h: the handle as the update unit (mpc_ppo_update.hip) sees it
@@ -184,6 +188,7 @@ bool mpc_ac_get_view(const mpc_ac *ac, mpc_ac_view *out) {
   out->std = ac->nets.std;
   out->device = ac->device;
   out->bound = ac->bound;
+  out->asymmetric = ac->asymmetric;
   return true;
 }
 
@@ -195,12 +200,16 @@ const char *mpc_ppo_last_error(void) { return g_err.c_str(); }
 
 void mpc_ac_destroy(mpc_ac *ac) { delete ac; }      // owns no device memory: the parameters are the caller's
 
-int mpc_ac_create(mpc_ac **out, int n_actor_layers, const int *actor_dims, int n_critic_layers, const int *critic_dims) {
-  if (!out) return fail(MPC_E_ARG, "mpc_ac_create: bad argument");
-  if (const char *why = check_stack(n_actor_layers, actor_dims, MPC_AC_ACTIONS)) return fail(MPC_E_ARG, std::string("mpc_ac_create: actor: ") + why);
-  if (const char *why = check_stack(n_critic_layers, critic_dims, 1)) return fail(MPC_E_ARG, std::string("mpc_ac_create: critic: ") + why);
-  if (actor_dims[0] != critic_dims[0]) return fail(MPC_E_ARG, "mpc_ac_create: actor and critic read the same observations (equal input widths)");
+// mpc_ac_create and mpc_ac_create_asymmetric: the same limits per stack, the LDS limit on the wider of the two
+static int ac_create(const char *who, bool asymmetric, mpc_ac **out, int n_actor_layers, const int *actor_dims, int n_critic_layers, const int *critic_dims) {
+  const std::string name(who);
+  if (!out) return fail(MPC_E_ARG, name + ": bad argument");
+  if (const char *why = check_stack(n_actor_layers, actor_dims, MPC_AC_ACTIONS)) return fail(MPC_E_ARG, name + ": actor: " + why);
+  if (const char *why = check_stack(n_critic_layers, critic_dims, 1)) return fail(MPC_E_ARG, name + ": critic: " + why);
+  if (!asymmetric && actor_dims[0] != critic_dims[0])
+    return fail(MPC_E_ARG, name + ": actor and critic read the same observations (equal input widths)");
   mpc_ac *ac = new mpc_ac();
+  ac->asymmetric = asymmetric;
   const int nl[2] = {n_actor_layers, n_critic_layers};
   const int *dims[2] = {actor_dims, critic_dims};
   for (int k = 0; k < 2; ++k) {
@@ -209,9 +218,17 @@ int mpc_ac_create(mpc_ac **out, int n_actor_layers, const int *actor_dims, int n
     const size_t b = policy::lds_bytes(ac->nets.net[k]);
     ac->lds = b > ac->lds ? b : ac->lds;
   }
-  if (ac->lds > 160 * 1024) { delete ac; return fail(MPC_E_ARG, "mpc_ac_create: layers too wide for one CU's LDS"); }
+  if (ac->lds > 160 * 1024) { delete ac; return fail(MPC_E_ARG, name + ": layers too wide for one CU's LDS"); }
   *out = ac;
   return MPC_OK;
+}
+
+int mpc_ac_create(mpc_ac **out, int n_actor_layers, const int *actor_dims, int n_critic_layers, const int *critic_dims) {
+  return ac_create("mpc_ac_create", false, out, n_actor_layers, actor_dims, n_critic_layers, critic_dims);
+}
+
+int mpc_ac_create_asymmetric(mpc_ac **out, int n_actor_layers, const int *actor_dims, int n_critic_layers, const int *critic_dims) {
+  return ac_create("mpc_ac_create_asymmetric", true, out, n_actor_layers, actor_dims, n_critic_layers, critic_dims);
 }
 
 int mpc_ac_bind(mpc_ac *ac, const float *const *d_actor_weights, const float *const *d_actor_biases, const float *const *d_critic_weights,
@@ -238,12 +255,12 @@ int mpc_ac_bind(mpc_ac *ac, const float *const *d_actor_weights, const float *co
   return MPC_OK;
 }
 
-static int ac_launch(mpc_ac *ac, int n, const float *d_obs, int first_net, int nets, int sample, unsigned long long seed, unsigned int step,
-                     const ActOut &o, void *stream) {
+static int ac_launch(mpc_ac *ac, int n, const float *d_obs, const float *d_critic_obs, int first_net, int nets, int sample, unsigned long long seed,
+                     unsigned int step, const ActOut &o, void *stream) {
   DeviceGuard guard_(ac->device);
   const dim3 grid((unsigned)((n + policy::kRows - 1) / policy::kRows), (unsigned)nets);
-  hipLaunchKernelGGL(ac_kernel, grid, dim3(policy::kThreads), ac->lds, reinterpret_cast<hipStream_t>(stream), ac->nets, first_net, sample, n, d_obs, seed,
-                     step, o);
+  hipLaunchKernelGGL(ac_kernel, grid, dim3(policy::kThreads), ac->lds, reinterpret_cast<hipStream_t>(stream), ac->nets, first_net, sample, n, d_obs, d_critic_obs,
+                     seed, step, o);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
@@ -254,20 +271,32 @@ int mpc_ac_act(mpc_ac *ac, int n, const float *d_obs, unsigned long long seed, u
   // (rows of twelve floats are written as 8-byte pairs)
   if ((reinterpret_cast<uintptr_t>(d_actions) | reinterpret_cast<uintptr_t>(d_mean) | reinterpret_cast<uintptr_t>(d_sigma) | reinterpret_cast<uintptr_t>(d_eps)) & 7u)
     return fail(MPC_E_ARG, "mpc_ac_act: d_actions, d_mean, d_sigma and d_eps must be 8-byte aligned");
+  if (ac->nets.net[kActor].dims[0] != ac->nets.net[kCritic].dims[0])
+    return fail(MPC_E_ARG, "mpc_ac_act: the critic of this asymmetric handle reads rows of another width: use mpc_ac_act_asymmetric");
   if (!ac->bound) return fail(MPC_E_ARG, "mpc_ac_act: no parameters bound (mpc_ac_bind)");
-  return ac_launch(ac, n, d_obs, kActor, 2, 1, seed, step, ActOut{d_actions, d_log_prob, d_values, d_mean, d_sigma, d_eps}, stream);
+  return ac_launch(ac, n, d_obs, d_obs, kActor, 2, 1, seed, step, ActOut{d_actions, d_log_prob, d_values, d_mean, d_sigma, d_eps}, stream);
+}
+
+int mpc_ac_act_asymmetric(mpc_ac *ac, int n, const float *d_obs, const float *d_critic_obs, unsigned long long seed, unsigned int step, float *d_actions,
+                          float *d_log_prob, float *d_values, float *d_mean, float *d_sigma, float *d_eps, void *stream) {
+  if (!ac || n <= 0 || !d_obs || !d_actions || !d_log_prob || !d_values || !d_mean || !d_sigma) return fail(MPC_E_ARG, "mpc_ac_act_asymmetric: bad argument");
+  if (!d_critic_obs) return fail(MPC_E_ARG, "mpc_ac_act_asymmetric: d_critic_obs is null");
+  if ((reinterpret_cast<uintptr_t>(d_actions) | reinterpret_cast<uintptr_t>(d_mean) | reinterpret_cast<uintptr_t>(d_sigma) | reinterpret_cast<uintptr_t>(d_eps)) & 7u)
+    return fail(MPC_E_ARG, "mpc_ac_act_asymmetric: d_actions, d_mean, d_sigma and d_eps must be 8-byte aligned");
+  if (!ac->bound) return fail(MPC_E_ARG, "mpc_ac_act_asymmetric: no parameters bound (mpc_ac_bind)");
+  return ac_launch(ac, n, d_obs, d_critic_obs, kActor, 2, 1, seed, step, ActOut{d_actions, d_log_prob, d_values, d_mean, d_sigma, d_eps}, stream);
 }
 
 int mpc_ac_evaluate(mpc_ac *ac, int n, const float *d_obs, float *d_values, void *stream) {
   if (!ac || n <= 0 || !d_obs || !d_values) return fail(MPC_E_ARG, "mpc_ac_evaluate: bad argument");
   if (!ac->bound) return fail(MPC_E_ARG, "mpc_ac_evaluate: no parameters bound (mpc_ac_bind)");
-  return ac_launch(ac, n, d_obs, kCritic, 1, 0, 0, 0, ActOut{nullptr, nullptr, d_values, nullptr, nullptr, nullptr}, stream);
+  return ac_launch(ac, n, nullptr, d_obs, kCritic, 1, 0, 0, 0, ActOut{nullptr, nullptr, d_values, nullptr, nullptr, nullptr}, stream);
 }
 
 int mpc_ac_act_inference(mpc_ac *ac, int n, const float *d_obs, float *d_mean, void *stream) {
   if (!ac || n <= 0 || !d_obs || !d_mean || (reinterpret_cast<uintptr_t>(d_mean) & 7u)) return fail(MPC_E_ARG, "mpc_ac_act_inference: bad argument");
   if (!ac->bound) return fail(MPC_E_ARG, "mpc_ac_act_inference: no parameters bound (mpc_ac_bind)");
-  return ac_launch(ac, n, d_obs, kActor, 1, 0, 0, 0, ActOut{nullptr, nullptr, nullptr, d_mean, nullptr, nullptr}, stream);
+  return ac_launch(ac, n, d_obs, nullptr, kActor, 1, 0, 0, 0, ActOut{nullptr, nullptr, nullptr, d_mean, nullptr, nullptr}, stream);
 }
 
 int mpc_rollout_add(int n, double gamma, const float *d_rew, const long long *d_reset, const long long *d_timeout, const float *d_values_t,

@@ -216,7 +216,10 @@ struct mpc_ppo_update {
   float *grad[kMaxTensors] = {}, *exp_avg[kMaxTensors] = {}, *exp_avg_sq[kMaxTensors] = {};
   bool grads_bound = false, moments_bound = false, storage_set = false;
   Storage st{};
+  const float *critic_obs = nullptr;            // [total_rows][dims[kCritic][0]] (mpc_ppo_update_set_critic_storage), or null: the critic reads st.obs
 
+  // the rows layer 0 of net k reads through the index
+  const float *rows0(int k) const { return k == kCritic && critic_obs ? critic_obs : st.obs; }
   int ld(int k, int l) const { return l + 1 == nl[k] ? kOutLd : dims[k][l + 1]; }
   // mpc_ac_bind's order: actor weights, actor biases, critic weights, critic biases, std
   int w_index(int k, int l) const { return (k == kActor ? 0 : 2 * nl[0]) + l; }
@@ -315,6 +318,14 @@ int mpc_ppo_update_set_storage(mpc_ppo_update *u, long long total_rows, const fl
   return MPC_OK;
 }
 
+int mpc_ppo_update_set_critic_storage(mpc_ppo_update *u, const float *d_critic_obs) {
+  if (d_critic_obs && (reinterpret_cast<uintptr_t>(d_critic_obs) & 15u))
+    return fail(MPC_E_ARG, "mpc_ppo_update_set_critic_storage: d_critic_obs must be 16-byte aligned");
+  if (!u) return fail(MPC_E_ARG, "mpc_ppo_update_set_critic_storage: bad argument");
+  u->critic_obs = d_critic_obs;                 // (null: back to the actor's rows)
+  return MPC_OK;
+}
+
 int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, double clip_param, double value_loss_coef, double entropy_coef,
                          int use_clipped_value_loss, int adaptive, double desired_kl, double *d_lr, float *d_terms, void *stream) {
   if (!u || !d_idx || !d_terms) return fail(MPC_E_ARG, "mpc_ppo_update_grads: bad argument");
@@ -327,6 +338,8 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
   if (!u->storage_set) return fail(MPC_E_ARG, "mpc_ppo_update_grads: no storage set (mpc_ppo_update_set_storage)");
   mpc_ac_view v;
   if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return fail(MPC_E_ARG, "mpc_ppo_update_grads: the mpc_ac has no parameters bound");
+  if (v.asymmetric && !u->critic_obs)
+    return fail(MPC_E_ARG, "mpc_ppo_update_grads: an asymmetric mpc_ac needs the critic's rows (mpc_ppo_update_set_critic_storage)");
   DeviceGuard guard_(u->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int maxl = u->nl[0] > u->nl[1] ? u->nl[0] : u->nl[1];
@@ -338,7 +351,7 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
     for (int k = 0; k < 2; ++k) {
       if (l >= u->nl[k]) continue;
       pgemm::Problem &p = L.p[k];
-      p.A = l == 0 ? u->st.obs : u->Y[k][l - 1];
+      p.A = l == 0 ? u->rows0(k) : u->Y[k][l - 1];
       p.idx = l == 0 ? d_idx : nullptr;
       p.idx_limit = u->st.total_rows;
       p.B = v.w[k][l];
@@ -373,7 +386,7 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
       const int nout = u->dims[k][l + 1], nin = u->dims[k][l];
       pgemm::Problem &p = W.p[k];
       p.A = u->dY[k][l]; p.lda = u->ld(k, l);
-      p.B = l == 0 ? u->st.obs : u->Y[k][l - 1];
+      p.B = l == 0 ? u->rows0(k) : u->Y[k][l - 1];
       p.ldb = l == 0 ? nin : u->ld(k, l - 1);
       p.idx = l == 0 ? d_idx : nullptr;
       p.idx_limit = u->st.total_rows;

@@ -121,22 +121,24 @@ class ObsNormalizer:
             self.state64[1].copy_(sd["_var"][0].to(torch.float64))
 
 
-def fold_normalizer(model_state_dict, obs_norm_state_dict, eps=1e-2):
+def fold_normalizer(model_state_dict, obs_norm_state_dict, eps=1e-2, critic_obs_norm_state_dict=None):
     """A ``model_state_dict`` whose actor and critic take RAW observations: the normaliser folded into layer 0,
     ``W'[:, c] = W[:, c] / (std_c + eps)`` and ``b' = b - W' mean``, computed in float64 from the float32 buffers (``std_c + eps`` as the float32 sum
     normalisation uses) and rounded once; every other key passes through untouched.  ``eps`` is the normaliser's.  ``WeightPolicy.from_state_dict``
-    and the reference's loader then run a policy trained with normalisation unchanged.
+    and the reference's loader then run a policy trained with normalisation unchanged.  ``critic_obs_norm_state_dict``: the statistics of the critic's
+    own rows (a checkpoint of an asymmetric run carries them), folded into the critic in place of the actor's.
 
     The limit: where ``|mean_c| >> std_c`` the folded layer computes ``W' x - W' mean`` in float32 and the two cancel; a caller who needs better
     runs ``ObsNormalizer(...)(obs, update=False)`` in front of ``WeightPolicy.step`` instead."""
-    mean = obs_norm_state_dict["_mean"].reshape(-1)
-    std = obs_norm_state_dict["_std"].reshape(-1).to(torch.float32)
-    scale = (std + torch.tensor(eps, dtype=torch.float32, device=std.device)).to(torch.float64)
     out = dict(model_state_dict)
     for net in ("actor", "critic"):
         wk, bk = f"{net}.0.weight", f"{net}.0.bias"
         if wk not in out:
             continue
+        sd = critic_obs_norm_state_dict if net == "critic" and critic_obs_norm_state_dict is not None else obs_norm_state_dict
+        mean = sd["_mean"].reshape(-1)
+        std = sd["_std"].reshape(-1).to(torch.float32)
+        scale = (std + torch.tensor(eps, dtype=torch.float32, device=std.device)).to(torch.float64)
         W, b = out[wk], out[bk]
         if W.shape[1] != mean.numel():
             raise ValueError(f"{wk} takes {W.shape[1]} observations, the normaliser has {mean.numel()}")

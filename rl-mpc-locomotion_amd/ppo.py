@@ -22,7 +22,9 @@ RL_Environment/tasks/legged_config_ppo.py); rsl_rl itself is an empty submodule 
 Not rsl_rl's: the exploration noise is a counter-based generator keyed by (seed, environment, step, action pair), not torch's, so parity
 with ``Normal.sample`` is in distribution only, and |eps| <= 5.768 (ppo_rollout.h).  Observation normalisation (rsl_rl 2.x's
 ``EmpiricalNormalization``) is opt-in: ``PPOTrainer(..., normalize_obs=True)`` puts ``obs_norm.ObsNormalizer`` between the environment and everything
-that reads an observation.  Not built: recurrent policies, privileged critic observations (the reference uses none), logging beyond ``infos``.  The runner's episode statistics (mean return and
+that reads an observation.  Privileged critic observations (rsl_rl's ``num_critic_obs`` / ``privileged_observations``; the reference uses none) are opt-in too: an
+environment with ``num_privileged_obs`` (``BatchedRLTask(privileged_obs=...)``) gets an asymmetric actor-critic whose critic reads ``env.privileged_obs_buf``,
+in the collection (``mpc_ac_act_asymmetric``), the storage and both update backends.  Not built: recurrent policies, logging beyond ``infos``.  The runner's episode statistics (mean return and
 length over the last 100 finished episodes) are kept on the device by ``episode.EpisodeStats``; ``PPOTrainer.evaluate`` is the reference's ``cfg.test`` loop.
 
 The device entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
@@ -43,9 +45,11 @@ NUM_ACTIONS = 12
 # the entry points of include/mpc_ppo.h (bound here, not in _lib.SYMBOLS, which lists include/mpc_batch.h)
 DECLS = {
     "mpc_ac_create": (ci, [pvp, ci, vp, ci, vp]),
+    "mpc_ac_create_asymmetric": (ci, [pvp, ci, vp, ci, vp]),
     "mpc_ac_destroy": (None, [vp]),
     "mpc_ac_bind": (ci, [vp, vp, vp, vp, vp, vp]),
     "mpc_ac_act": (ci, [vp, ci, vp, C.c_ulonglong, C.c_uint, vp, vp, vp, vp, vp, vp, vp]),
+    "mpc_ac_act_asymmetric": (ci, [vp, ci, vp, vp, C.c_ulonglong, C.c_uint, vp, vp, vp, vp, vp, vp, vp]),
     "mpc_ac_evaluate": (ci, [vp, ci, vp, vp, vp]),
     "mpc_ac_act_inference": (ci, [vp, ci, vp, vp, vp]),
     "mpc_rollout_add": (ci, [ci, cd, vp, vp, vp, vp, vp, vp, vp]),
@@ -63,6 +67,7 @@ UPDATE_DECLS = {
     "mpc_ppo_update_tensors": (ci, [vp]),
     "mpc_ppo_update_bind": (ci, [vp, vp, vp, vp]),
     "mpc_ppo_update_set_storage": (ci, [vp, ll] + [vp] * 8),
+    "mpc_ppo_update_set_critic_storage": (ci, [vp, vp]),
     "mpc_ppo_update_grads": (ci, [vp, ci, vp, cd, cd, cd, ci, ci, cd, vp, vp, vp]),
     "mpc_ppo_update_apply": (ci, [vp, cd, cd, cd, cd, ci, vp, vp]),
 }
@@ -113,15 +118,22 @@ class ActorCritic(nn.Module):
     ``critic.{0,2,..}.{weight,bias}``) and loads through ``WeightPolicy.from_state_dict``.
 
     ``act``, ``evaluate`` and ``act_inference`` run the device kernels on the parameters where they are (no gradient flows through
-    them); ``log_prob_entropy_value`` is the differentiable torch path of the update."""
+    them); ``log_prob_entropy_value`` is the differentiable torch path of the update.
 
-    def __init__(self, num_obs=48, num_actions=NUM_ACTIONS, actor_hidden_dims=(512, 256, 128), critic_hidden_dims=(512, 256, 128), init_noise_std=1.0):
+    ``num_critic_obs`` (rsl_rl's; None: the critic reads the actor's rows, as before): the critic's first ``Linear`` has that width and the critic's
+    rows are an argument of their own -- ``act(obs, ..., critic_obs=)``, ``evaluate(critic_obs)``, ``log_prob_entropy_value(obs, actions, critic_obs)``
+    -- through the asymmetric entry points (``mpc_ac_create_asymmetric``, ``mpc_ac_act_asymmetric``).  The state dict has the same keys either way."""
+
+    def __init__(self, num_obs=48, num_actions=NUM_ACTIONS, actor_hidden_dims=(512, 256, 128), critic_hidden_dims=(512, 256, 128), init_noise_std=1.0,
+                 num_critic_obs=None):
         super().__init__()
         if num_actions != NUM_ACTIONS:
             raise ValueError("the sampling kernel draws six Box-Muller pairs: twelve actions (the MPC weights)")
         self.num_obs, self.num_actions = int(num_obs), int(num_actions)
+        self.num_critic_obs = None if num_critic_obs is None else int(num_critic_obs)
+        self.critic_width = self.num_obs if num_critic_obs is None else self.num_critic_obs      # what the critic's first layer reads
         self.actor = mlp(num_obs, actor_hidden_dims, num_actions)
-        self.critic = mlp(num_obs, critic_hidden_dims, 1)
+        self.critic = mlp(self.critic_width, critic_hidden_dims, 1)
         self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
         self._handle, self._bound_ptrs = None, None
 
@@ -132,10 +144,12 @@ class ActorCritic(nn.Module):
     def _linears(seq):
         return [m for m in seq if isinstance(m, nn.Linear)]
 
-    def _ready(self, what, obs):
+    def _ready(self, what, obs, width=None, critic_obs=None):
         """The handle, bound to the parameters' current device addresses (checked on every call: ``.to()`` moves them, an optimiser step
-        or ``load_state_dict`` does not)."""
+        or ``load_state_dict`` does not).  ``obs`` has ``width`` columns (None: ``num_obs``); ``critic_obs``, when given, ``critic_width``."""
         need_gpu(what, obs, self.std)
+        if critic_obs is not None:
+            need_gpu(what, critic_obs)
         la, lc = self._linears(self.actor), self._linears(self.critic)
         params = [m.weight for m in la] + [m.bias for m in la] + [m.weight for m in lc] + [m.bias for m in lc] + [self.std]
         ptrs = tuple(p.data_ptr() for p in params)
@@ -143,8 +157,9 @@ class ActorCritic(nn.Module):
             dims = lambda ls: [ls[0].in_features] + [m.out_features for m in ls]
             da, dc = dims(la), dims(lc)
             h = C.c_void_p()
-            check(lib().mpc_ac_create(C.byref(h), len(la), C.cast((C.c_int * len(da))(*da), C.c_void_p), len(lc),
-                                      C.cast((C.c_int * len(dc))(*dc), C.c_void_p)), "mpc_ac_create")
+            create = "mpc_ac_create" if self.num_critic_obs is None else "mpc_ac_create_asymmetric"
+            check(getattr(lib(), create)(C.byref(h), len(la), C.cast((C.c_int * len(da))(*da), C.c_void_p), len(lc),
+                                         C.cast((C.c_int * len(dc))(*dc), C.c_void_p)), create)
             self._handle = h
         if ptrs != self._bound_ptrs:
             for p in params:
@@ -157,7 +172,9 @@ class ActorCritic(nn.Module):
                                         arr(ptrs[2 * na + nc:2 * na + 2 * nc]), ptrs[-1]), "mpc_ac_bind")
             self._bound_ptrs = ptrs
         n = obs.shape[0]
-        tensor_arg(obs, torch.float32, n * self.num_obs, "obs")
+        tensor_arg(obs, torch.float32, n * (self.num_obs if width is None else width), "obs")
+        if critic_obs is not None:
+            tensor_arg(critic_obs, torch.float32, n * self.critic_width, "critic_obs")
         return n
 
     def bind_order(self):
@@ -165,11 +182,14 @@ class ActorCritic(nn.Module):
         la, lc = self._linears(self.actor), self._linears(self.critic)
         return [m.weight for m in la] + [m.bias for m in la] + [m.weight for m in lc] + [m.bias for m in lc] + [self.std]
 
-    def act(self, obs, seed, step, out=None, return_eps=False):
+    def act(self, obs, seed, step, out=None, return_eps=False, critic_obs=None):
         """``ActorCritic.act`` + ``evaluate`` in one launch: obs [n, num_obs] -> a dict of ``actions`` [n,12], ``actions_log_prob`` [n,1],
         ``values`` [n,1], ``mu`` [n,12], ``sigma`` [n,12] (and ``eps`` [n,12] if asked).  ``out``: the same dict of caller's tensors to write
-        into (slot t of a RolloutStorage: ``storage.slot(t)``).  The noise of environment r is a function of (seed, r, step) alone."""
-        n = self._ready("ActorCritic.act", obs)
+        into (slot t of a RolloutStorage: ``storage.slot(t)``).  The noise of environment r is a function of (seed, r, step) alone.
+        ``critic_obs`` [n, critic_width]: the rows the critic reads (required when ``num_critic_obs`` was given); still one launch."""
+        if critic_obs is None and self.num_critic_obs is not None:
+            raise ValueError("this actor-critic was made with num_critic_obs: act needs critic_obs")
+        n = self._ready("ActorCritic.act", obs, critic_obs=critic_obs)
         dev = obs.device
         if out is None:
             e = lambda k: torch.empty((n, k), dtype=torch.float32, device=dev)
@@ -178,16 +198,19 @@ class ActorCritic(nn.Module):
             for k, w in (("actions", 12), ("actions_log_prob", 1), ("values", 1), ("mu", 12), ("sigma", 12)):
                 tensor_arg(out[k], torch.float32, n * w, k)
         eps = torch.empty((n, 12), dtype=torch.float32, device=dev) if return_eps else None
-        check(lib().mpc_ac_act(self._handle, n, obs.data_ptr(), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, out["actions"].data_ptr(),
-                               out["actions_log_prob"].data_ptr(), out["values"].data_ptr(), out["mu"].data_ptr(), out["sigma"].data_ptr(),
-                               eps.data_ptr() if return_eps else None, _lib.stream(dev)), "mpc_ac_act")
+        tail = (int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, out["actions"].data_ptr(), out["actions_log_prob"].data_ptr(), out["values"].data_ptr(),
+                out["mu"].data_ptr(), out["sigma"].data_ptr(), eps.data_ptr() if return_eps else None, _lib.stream(dev))
+        if critic_obs is None:
+            check(lib().mpc_ac_act(self._handle, n, obs.data_ptr(), *tail), "mpc_ac_act")
+        else:
+            check(lib().mpc_ac_act_asymmetric(self._handle, n, obs.data_ptr(), critic_obs.data_ptr(), *tail), "mpc_ac_act_asymmetric")
         if return_eps:
             out = dict(out, eps=eps)
         return out
 
     def evaluate(self, obs, out=None):
-        """The critic alone: obs [n, num_obs] -> values [n, 1]."""
-        n = self._ready("ActorCritic.evaluate", obs)
+        """The critic alone: obs [n, critic_width] (the critic's own rows when ``num_critic_obs`` was given) -> values [n, 1]."""
+        n = self._ready("ActorCritic.evaluate", obs, width=self.critic_width)
         values = torch.empty((n, 1), dtype=torch.float32, device=obs.device) if out is None else tensor_arg(out, torch.float32, n, "out")
         check(lib().mpc_ac_evaluate(self._handle, n, obs.data_ptr(), values.data_ptr(), _lib.stream(obs.device)), "mpc_ac_evaluate")
         return values
@@ -200,25 +223,28 @@ class ActorCritic(nn.Module):
         return mean
 
     # ---- the differentiable path of the update ---------------------------------------------------------------------------------------------
-    def log_prob_entropy_value(self, obs, actions):
+    def log_prob_entropy_value(self, obs, actions, critic_obs=None):
         """(log-prob [B], entropy [B], value [B,1], mu [B,12], sigma [B,12]) of ``actions`` under the current parameters, in plain torch with
-        autograd: ``Normal(actor(obs), std)`` as rsl_rl's ``update_distribution`` builds it."""
+        autograd: ``Normal(actor(obs), std)`` as rsl_rl's ``update_distribution`` builds it; the value is the critic's of ``critic_obs`` (None: of
+        ``obs``, rsl_rl's ``critic_obs = privileged_obs if privileged_obs is not None else obs``)."""
         mu = self.actor(obs)
         dist = torch.distributions.Normal(mu, mu * 0. + self.std)
-        return dist.log_prob(actions).sum(dim=-1), dist.entropy().sum(dim=-1), self.critic(obs), mu, dist.stddev
+        return dist.log_prob(actions).sum(dim=-1), dist.entropy().sum(dim=-1), self.critic(obs if critic_obs is None else critic_obs), mu, dist.stddev
 
 
 class RolloutStorage:
     """rsl_rl's ``RolloutStorage`` without its staging: [T, N, ...] float32 tensors ``observations`` [T,N,num_obs], ``actions``, ``mu``,
     ``sigma`` [T,N,12], ``values``, ``rewards``, ``dones``, ``actions_log_prob``, ``returns``, ``advantages`` [T,N,1].  ``ActorCritic.act``
     writes into ``slot(t)``; ``add`` and ``compute_returns`` are device kernels (a storage on the CPU can be filled by hand and read by
-    ``PPO.update``, which is plain torch)."""
+    ``PPO.update``, which is plain torch).  ``num_privileged_obs`` (rsl_rl's; None: no such tensor): ``privileged_observations`` [T,N,Wp], the
+    critic's rows, which the mini-batch generator then yields last."""
 
-    def __init__(self, n, T, device, num_obs=48, num_actions=NUM_ACTIONS):
+    def __init__(self, n, T, device, num_obs=48, num_actions=NUM_ACTIONS, num_privileged_obs=None):
         self.n, self.T, self.device = int(n), int(T), torch.device(device)
         z = lambda k: torch.zeros((self.T, self.n, k), dtype=torch.float32, device=self.device)
         self.observations, self.actions, self.mu, self.sigma = z(num_obs), z(num_actions), z(num_actions), z(num_actions)
         self.values, self.rewards, self.dones, self.actions_log_prob, self.returns, self.advantages = z(1), z(1), z(1), z(1), z(1), z(1)
+        self.privileged_observations = None if num_privileged_obs is None else z(int(num_privileged_obs))
         self.step = 0
 
     def slot(self, t):
@@ -251,12 +277,14 @@ class RolloutStorage:
 
     def mini_batch_generator(self, num_mini_batches, num_epochs=8):
         """rsl_rl's: one ``torch.randperm`` over T N for all epochs, mini-batch size T N // num_mini_batches.  Yields (obs, actions, values,
-        advantages, returns, old log-prob, old mu, old sigma)."""
+        advantages, returns, old log-prob, old mu, old sigma) and, with ``privileged_observations``, the critic's rows as a ninth element."""
         batch = self.n * self.T
         size = batch // num_mini_batches
         idx = torch.randperm(num_mini_batches * size, device=self.device)
         flat = [x.flatten(0, 1) for x in (self.observations, self.actions, self.values, self.advantages, self.returns, self.actions_log_prob, self.mu,
                                           self.sigma)]
+        if self.privileged_observations is not None:
+            flat.append(self.privileged_observations.flatten(0, 1))
         for _ in range(num_epochs):
             for i in range(num_mini_batches):
                 b = idx[i * size:(i + 1) * size]
@@ -306,8 +334,11 @@ class PPO:
     def losses(self, batch):
         """(surrogate, value loss, mean entropy, mean kl) of one mini-batch of ``RolloutStorage.mini_batch_generator``; kl carries no gradient."""
         c = self.cfg
-        obs, actions, old_values, adv, returns, old_logp, old_mu, old_sigma = batch
-        logp, entropy, value, mu, sigma = self.actor_critic.log_prob_entropy_value(obs, actions)
+        obs, actions, old_values, adv, returns, old_logp, old_mu, old_sigma = batch[:8]
+        critic_obs = batch[8] if len(batch) > 8 else None                        # the critic's rows, when the storage keeps them
+        if critic_obs is None and self.actor_critic.num_critic_obs is not None:
+            raise ValueError("the actor-critic was made with num_critic_obs and the batch carries no critic rows (RolloutStorage(num_privileged_obs=))")
+        logp, entropy, value, mu, sigma = self.actor_critic.log_prob_entropy_value(obs, actions, critic_obs)
         with torch.no_grad():
             kl = torch.sum(torch.log(sigma / old_sigma + 1.e-5) + (torch.square(old_sigma) + torch.square(old_mu - mu)) / (2.0 * torch.square(sigma)) - 0.5,
                            axis=-1).mean()
@@ -342,7 +373,7 @@ class PPO:
         torch creates them); returns the common step count."""
         ac = self.actor_critic
         dev = ac.std.device
-        ac._ready("PPO.update", torch.empty((1, ac.num_obs), dtype=torch.float32, device=dev))
+        ac._ready("PPO.update", torch.empty((1, ac.num_obs), dtype=torch.float32, device=dev))      # (the handle and its binding: nothing is launched)
         params = ac.bind_order()
         steps = set()
         for p in params:
@@ -396,8 +427,13 @@ class PPO:
         flat = (storage.observations, storage.actions, storage.values, storage.advantages, storage.returns, storage.actions_log_prob, storage.mu, storage.sigma)
         widths = (self.actor_critic.num_obs, NUM_ACTIONS, 1, 1, 1, 1, NUM_ACTIONS, NUM_ACTIONS)
         ptrs = tuple(tensor_arg(t, torch.float32, total * w, "storage").data_ptr() for t, w in zip(flat, widths))
+        critic_rows = storage.privileged_observations                            # None on a symmetric run: today's calls and no other
+        if critic_rows is not None:
+            ptrs += (tensor_arg(critic_rows, torch.float32, total * self.actor_critic.critic_width, "storage.privileged_observations").data_ptr(),)
         if ptrs != self._storage_ptrs:
-            check(L.mpc_ppo_update_set_storage(self._handle, total, *ptrs), "mpc_ppo_update_set_storage")
+            check(L.mpc_ppo_update_set_storage(self._handle, total, *ptrs[:8]), "mpc_ppo_update_set_storage")
+            if critic_rows is not None or (self._storage_ptrs is not None and len(self._storage_ptrs) > 8):      # set, or cleared after a storage that had them
+                check(L.mpc_ppo_update_set_critic_storage(self._handle, ptrs[8] if critic_rows is not None else None), "mpc_ppo_update_set_critic_storage")
             self._storage_ptrs = ptrs
         adaptive = c.desired_kl is not None and c.schedule == "adaptive"
         group = self.optimizer.param_groups[0]
@@ -463,7 +499,15 @@ class PPOTrainer:
     ``normalize_obs=True`` (off by default): every observation the environment returns goes once through an ``ObsNormalizer`` (``obs_norm``; ``obs_norm_eps``,
     ``obs_norm_until`` are its ``eps`` and ``until``) -- counted once, normalised once with the statistics that include it, written by the normalising
     launch where the tick's ``copy_`` would have written -- and ``act``, the storage, ``evaluate`` and both update backends see the normalised
-    tensor; ``self.obs`` is then the normalised observation.  ``evaluate`` and ``get_inference_policy`` normalise without updating."""
+    tensor; ``self.obs`` is then the normalised observation.  ``evaluate`` and ``get_inference_policy`` normalise without updating.
+
+    An environment with ``num_privileged_obs`` (``BatchedRLTask(privileged_obs=...)``; read with ``getattr``, None otherwise) trains an asymmetric
+    actor-critic: the critic's first layer is that wide, each tick's ``env.privileged_obs_buf`` is kept in ``storage.privileged_observations[t]``
+    beside the actor's observation (the rows the action was computed from), ``last_values`` is the critic's of the last privileged row, and both
+    update backends feed the critic those rows.  With ``normalize_obs`` the critic's rows go through a second normaliser, ``critic_obs_norm``, under
+    the same discipline (update, then normalise, once per row); a constant column of theirs -- the zero pad, a contact flag that never changes --
+    has zero variance and normalises to 0 / eps = 0.  The checkpoint then carries ``critic_obs_norm_state_dict`` as well.  Without
+    ``num_privileged_obs`` nothing changes: the same launches through the same entry points."""
 
     def __init__(self, env, cfg=None, seed=1, device=None, update="torch", normalize_obs=False, obs_norm_eps=1e-2, obs_norm_until=None):
         need_gpu("PPOTrainer")
@@ -472,20 +516,29 @@ class PPOTrainer:
         self.device = torch.device(device if device is not None else getattr(env, "device", f"cuda:{torch.cuda.current_device()}"))
         torch.manual_seed(self.seed)
         c = self.cfg
-        self.actor_critic = ActorCritic(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std).to(self.device)
+        self.num_privileged_obs = getattr(env, "num_privileged_obs", None)
+        priv = self.num_privileged_obs
+        self.actor_critic = ActorCritic(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std, num_critic_obs=priv).to(self.device)
         self.alg = PPO(self.actor_critic, c, backend=update)
-        self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions)
+        self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions, num_privileged_obs=priv)
         self.episode_stats = EpisodeStats(env.num_envs, device=self.device)      # rsl_rl's rewbuffer / lenbuffer (deque(maxlen=100)), on the device
         self.iteration, self.tick, self.obs = 0, 0, None
+        self.critic_obs = None                                                   # the critic's rows that go with self.obs (None without privileged observations)
         self.infos = []
-        self.obs_norm = None
+        self.obs_norm, self.critic_obs_norm = None, None
         if normalize_obs:
             self.obs_norm = ObsNormalizer(env.num_obs, eps=obs_norm_eps, until=obs_norm_until, device=self.device)
             self._obs_held = torch.zeros((env.num_envs, env.num_obs), dtype=torch.float32, device=self.device)      # the normalised observation between collections
+            if priv is not None:
+                self.critic_obs_norm = ObsNormalizer(priv, eps=obs_norm_eps, until=obs_norm_until, device=self.device)
+                self._critic_held = torch.zeros((env.num_envs, priv), dtype=torch.float32, device=self.device)
 
     def _first_obs(self):
-        """``env.reset()``'s observation, normalised (and counted) when normalisation is on."""
+        """``env.reset()``'s observation, normalised (and counted) when normalisation is on; ``critic_obs`` follows it."""
         obs = self.env.reset()
+        if self.num_privileged_obs is not None:
+            rows = self.env.privileged_obs_buf
+            self.critic_obs = rows if self.critic_obs_norm is None else self.critic_obs_norm(rows, out=self._critic_held)
         return obs if self.obs_norm is None else self.obs_norm(obs, out=self._obs_held)
 
     def collect(self, record_eps=None):
@@ -494,22 +547,28 @@ class PPOTrainer:
         if self.obs is None:
             self.obs = self._first_obs()
         st.clear()
-        norm = self.obs_norm
+        norm, cnorm, priv = self.obs_norm, self.critic_obs_norm, self.num_privileged_obs is not None
         with torch.no_grad():
             for t in range(st.T):
-                obs = self.obs
-                out = self.actor_critic.act(obs, self.seed, self.tick, out=st.slot(t), return_eps=record_eps is not None)
+                obs, critic_obs = self.obs, self.critic_obs
+                out = self.actor_critic.act(obs, self.seed, self.tick, out=st.slot(t), return_eps=record_eps is not None, critic_obs=critic_obs)
                 if record_eps is not None:
                     record_eps.append(out["eps"])
                 if norm is None or t == 0:
                     st.observations[t].copy_(obs)
+                if priv and (cnorm is None or t == 0):                           # the critic's rows the values of slot t were computed from
+                    st.privileged_observations[t].copy_(critic_obs)
                 self.obs, rew, reset, extras = self.env.step(st.actions[t])
                 if norm is not None:                                             # update, then normalise, into the slot the next tick reads
                     self.obs = norm(self.obs, out=st.observations[t + 1] if t + 1 < st.T else self._obs_held)
+                if priv:                                                         # the task's own buffer, rewritten by its next step; or its normalised copy
+                    self.critic_obs = self.env.privileged_obs_buf
+                    if cnorm is not None:
+                        self.critic_obs = cnorm(self.critic_obs, out=st.privileged_observations[t + 1] if t + 1 < st.T else self._critic_held)
                 st.add(rew, reset, extras["time_outs"], c.gamma)
                 self.episode_stats.add(rew, reset, extras["time_outs"])
                 self.tick += 1
-            self.last_values = self.actor_critic.evaluate(self.obs)
+            self.last_values = self.actor_critic.evaluate(self.critic_obs if priv else self.obs)
             st.compute_returns(self.last_values, c.gamma, c.lam)
 
     def learn(self, num_iterations, init_at_random_ep_len=False):
@@ -582,6 +641,9 @@ class PPOTrainer:
                     if norm is not None:                                         # the statistics stay as training left them
                         self.obs = norm(self.obs, out=self._obs_held, update=False)
                     stats.add(rew, reset, extras["time_outs"])
+                if self.num_privileged_obs is not None:                          # the critic's rows that go with self.obs, for the next collection
+                    rows = self.env.privileged_obs_buf
+                    self.critic_obs = rows if self.critic_obs_norm is None else self.critic_obs_norm(rows, out=self._critic_held, update=False)
         finally:
             if terms is not None:
                 terms.curriculum_enabled = enabled
@@ -595,12 +657,15 @@ class PPOTrainer:
     def save(self, path):
         """The checkpoint as rsl_rl writes it; ``WeightPolicy.from_state_dict(torch.load(path)["model_state_dict"])`` loads its actor.  With
         normalisation on it also carries ``obs_norm_state_dict`` (rsl_rl 2.x's key), and the actor expects normalised observations:
-        ``obs_norm.fold_normalizer(ck["model_state_dict"], ck["obs_norm_state_dict"])`` gives the state dict for raw ones.  On an environment with
+        ``obs_norm.fold_normalizer(ck["model_state_dict"], ck["obs_norm_state_dict"])`` gives the state dict for raw ones.  With privileged observations as well it carries ``critic_obs_norm_state_dict``, the statistics of the critic's
+        rows (``fold_normalizer(..., critic_obs_norm_state_dict=)``); ``load`` refuses a checkpoint whose critic reads rows of another width.  On an environment with
         ``episode_terms`` it carries ``episode_terms_state_dict`` (the x command range, the widenings, the tick), which ``load`` restores when present."""
         ck = {"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(), "iter": self.iteration,
               "infos": self.infos}
         if self.obs_norm is not None:
             ck["obs_norm_state_dict"] = self.obs_norm.state_dict()
+        if self.critic_obs_norm is not None:                                     # the critic's rows have statistics of their own
+            ck["critic_obs_norm_state_dict"] = self.critic_obs_norm.state_dict()
         terms = getattr(self.env, "episode_terms", None)
         if terms is not None:                                                    # the command range the policy was trained up to
             ck["episode_terms_state_dict"] = terms.state_dict()
@@ -608,12 +673,19 @@ class PPOTrainer:
 
     def load(self, path, load_optimizer=True):
         ck = torch.load(path, map_location=self.device)
+        width = int(ck["model_state_dict"]["critic.0.weight"].shape[1])
+        if width != self.actor_critic.critic_width:
+            raise ValueError(f"the checkpoint's critic reads rows of {width} columns, this trainer's critic rows of {self.actor_critic.critic_width}")
         if ("obs_norm_state_dict" in ck) != (self.obs_norm is not None):
             raise ValueError("the checkpoint was written with observation normalisation and this trainer has none" if self.obs_norm is None else
                              "this trainer normalises observations and the checkpoint carries no obs_norm_state_dict")
         if self.obs_norm is not None:
             self.obs_norm.load_state_dict(ck["obs_norm_state_dict"])
             self.obs = None                                                      # (normalised with the statistics before the load)
+        if self.critic_obs_norm is not None:
+            if "critic_obs_norm_state_dict" not in ck:
+                raise ValueError("this trainer normalises the critic's rows and the checkpoint carries no critic_obs_norm_state_dict")
+            self.critic_obs_norm.load_state_dict(ck["critic_obs_norm_state_dict"])
         terms = getattr(self.env, "episode_terms", None)
         if terms is not None and "episode_terms_state_dict" in ck:
             terms.load_state_dict(ck["episode_terms_state_dict"])

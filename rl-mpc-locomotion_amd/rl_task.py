@@ -196,11 +196,16 @@ class BatchedRLTask:
     ``episode_terms`` (an ``episode_terms.EpisodeTerms`` for as many environments): the per-term episode sums are closed straight after ``begin``
     -- with a command curriculum the environments being reset also get commands from the curriculum's ranges in place of those ``begin`` drew --
     and fed after ``finish``; ``common_step_counter`` counts the task's ticks on the host and is the tick the curriculum sees.
+    ``privileged_obs`` (a ``privileged_obs.PrivilegedObs`` for as many environments): one more launch per tick, after the height scan and BEFORE the
+    observation noise, writes ``privileged_obs_buf`` [N, ``num_privileged_obs``] -- the noise-free row, the foot contacts, the episode phase, a zero
+    pad -- which ``get_privileged_observations()`` returns; without it the three are None, as in rsl_rl.
     See the module text for what the toy cannot do."""
 
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
-                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, **bridge_args):
+                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, **bridge_args):
         import torch
+        if privileged_obs is not None and privileged_obs.n != len(np.asarray(robot_type).reshape(-1)):      # refused before the device is touched
+            raise ValueError(f"the privileged observations hold {privileged_obs.n} environments, robot_type {len(np.asarray(robot_type).reshape(-1))}")
         if episode_terms is not None and episode_terms.n != len(np.asarray(robot_type).reshape(-1)):      # refused before the device is touched
             raise ValueError(f"the episode terms hold {episode_terms.n} environments, robot_type {len(np.asarray(robot_type).reshape(-1))}")
         if domain_rand is not None:        # everything that can be refused before the device is touched
@@ -250,6 +255,14 @@ class BatchedRLTask:
             domain_rand.bind(self.sim, dt=self.cfg.dt)
             self.num_active_obs = NUM_OBS + (height_scan.num_points if height_scan is not None else 0)      # what is not the scan's zero pad
         self.episode_terms = episode_terms
+        self.privileged_obs, self.privileged_obs_buf, self.num_privileged_obs = privileged_obs, None, None
+        if privileged_obs is not None:
+            from .privileged_obs import inverse_length, privileged_width
+            privileged_obs.bind(self.sim)
+            self._num_scan = height_scan.num_points if height_scan is not None else 0
+            self._inv_len = inverse_length(self.cfg.max_episode_length)
+            self.num_privileged_obs = privileged_width(self._num_scan)
+            self.privileged_obs_buf = torch.zeros((self.n, self.num_privileged_obs), dtype=torch.float32, device=self.device)
         self.common_step_counter = 0       # the ticks this task has stepped, counted on the host: the command curriculum's clock
 
     def step(self, actions):
@@ -284,10 +297,16 @@ class BatchedRLTask:
             et.accumulate(sim.root_states, self.commands, self.torques, fell)
         if self.height_scan is not None:   # the same post-reset root states, and the origins the curriculum has just written
             self.height_scan.measure(sim.root_states, t.obs_buf, out=self.obs_buf, heights=self.measured_heights)
+        if self.privileged_obs is not None:                                    # the clean copy exists because this launch comes before the noise
+            self.privileged_obs.assemble(self.obs_buf, self.progress_buf, self._inv_len, num_scan=self._num_scan, out=self.privileged_obs_buf)
         if dr is not None and dr.specs["observations"] is not None:                                                             # :331-337, in place
             dr.noise("observations", self.obs_buf, active=self.num_active_obs, clip=self.cfg.clip_observations, tick=dr.tick)
         self.extras["time_outs"] = self.timeout_buf
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
+
+    def get_privileged_observations(self):
+        """rsl_rl's ``VecEnv.get_privileged_observations``: ``privileged_obs_buf`` (rewritten by every step), or None without ``privileged_obs``."""
+        return self.privileged_obs_buf
 
     def reset(self):
         """``VecTask.reset`` (vec_task.py:351-363): one step with zero actions; returns obs_buf."""

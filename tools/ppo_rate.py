@@ -6,6 +6,11 @@ backends alternating repeat by repeat on the same actor-critic and storage.  In 
 nn.Sequential, Normal(...).sample / log_prob, the storage copies, the time-out bootstrap and rsl_rl's GAE loop.  The shader clock is recorded as
 bench.py --full records it (device_state).
     python tools/ppo_rate.py [--repeats 7] [--out profiles/r10_ppo_update.json]
+--privileged times one iteration (collection, update, both) of the asymmetric actor-critic on a task with privileged observations against the symmetric
+one on the same task without them, the two trainers alternating repeat by repeat in one process, with the device update: on the flat plane (48 actor
+columns; 48 against 64 critic columns) or with --heights on the terrain grid (240 columns everywhere: the asymmetric path at equal widths).
+--baseline times the symmetric trainer alone (it runs on a tree without the option, for a measurement of the parent commit in the same session).
+    python tools/ppo_rate.py --privileged [--heights] [--baseline] [--out results/privileged_iteration.json]
 The kernel-trace stats: rocprofv3 --kernel-trace --stats ... -- python tools/ppo_rate.py --quick   (3 collections and one update per backend)"""
 import argparse
 import json
@@ -77,16 +82,84 @@ def stats(x):
             "p90_ms": float(np.percentile(x, 90)), "samples": int(x.size)}
 
 
+def privileged_report(args, dev, n):
+    from bench import device_state
+    cfg = PPOConfig()
+    T = cfg.num_steps_per_env
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    where = {}
+    if args.heights:
+        from rl_mpc_locomotion_amd.curriculum import TerrainCurriculum
+        from rl_mpc_locomotion_amd.height_scan import HeightScan
+        from rl_mpc_locomotion_amd.terrain import TerrainGrid
+        grid = TerrainGrid(num_levels=10, num_types=20, tile_length=8.0, tile_width=8.0, seed=0)
+        origins = TerrainCurriculum(grid, n, max_init_level=9, seed=0, device=dev, episode_length_s=TaskConfig().episode_length_s).origins0
+        where = dict(terrain=grid.terrain, origin=origins)
+
+    def make_task(with_privileged):
+        opts = dict(where)
+        if args.heights:
+            opts["height_scan"] = HeightScan(n, device=dev)
+        if with_privileged:
+            from rl_mpc_locomotion_amd.privileged_obs import PrivilegedObs
+            opts["privileged_obs"] = PrivilegedObs(n, device=dev)
+        return BatchedRLTask([0] * n, [TROT] * n, cfg=TaskConfig(), horizon=10, yaw0=yaw, flat_ground=True, device=dev, **opts)
+    trainers = {"symmetric": PPOTrainer(make_task(False), cfg, seed=1, update="hip")}
+    if not args.baseline:
+        trainers["asymmetric"] = PPOTrainer(make_task(True), cfg, seed=1, update="hip")
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "num_steps_per_env": T, "repeats": args.repeats, "update": "hip",
+           "heights": bool(args.heights), "baseline_only": bool(args.baseline), "mini_batches_per_update": cfg.num_learning_epochs * cfg.num_mini_batches,
+           "columns": {k: {"actor": tr.actor_critic.actor[0].in_features, "critic": tr.actor_critic.critic[0].in_features} for k, tr in trainers.items()},
+           "device_state": {"before": device_state(0)}}
+    for tr in trainers.values():          # warm-up: cold solves, code objects, Adam's state, the update's workspace
+        tr.learn(2)
+    torch.cuda.synchronize()
+    times = {k: {"collect": [], "update": [], "full": []} for k in trainers}
+    names = list(trainers)
+    for rep in range(args.repeats):       # which one goes first alternates
+        for name in (names if rep % 2 == 0 else names[::-1]):
+            tr = trainers[name]
+            a, b, c = ev(), ev(), ev()
+            a.record()
+            tr.collect()
+            b.record()
+            tr.alg.update(tr.storage)
+            c.record()
+            torch.cuda.synchronize()
+            tb = times[name]
+            tb["collect"].append(a.elapsed_time(b)); tb["update"].append(b.elapsed_time(c)); tb["full"].append(a.elapsed_time(c))
+    for name, tb in times.items():
+        res[name] = {k: stats(v) for k, v in tb.items()}
+        res[name]["robot_ticks_per_s_training"] = n * T / (float(np.median(tb["full"])) * 1e-3)
+    if not args.baseline:
+        res["asymmetric_over_symmetric_median"] = {k: res["asymmetric"][k]["median_ms"] / res["symmetric"][k]["median_ms"] for k in ("collect", "update", "full")}
+        res["asymmetric_inside_symmetric_p10_p90"] = {k: bool(res["symmetric"][k]["p10_ms"] <= res["asymmetric"][k]["median_ms"] <= res["symmetric"][k]["p90_ms"])
+                                                      for k in ("collect", "update", "full")}
+    res["device_state"]["after"] = device_state(0, smi=False)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--robots", type=int, default=4096)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--quick", action="store_true", help="3 collections and one update only (for a kernel trace)")
+    ap.add_argument("--privileged", action="store_true", help="one iteration of the asymmetric actor-critic against the symmetric one (see the head of this file)")
+    ap.add_argument("--heights", action="store_true", help="--privileged: on the terrain grid with the height scan (240 columns)")
+    ap.add_argument("--baseline", action="store_true", help="--privileged: the symmetric trainer alone (runs on a tree without the option)")
     ap.add_argument("--out")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("ppo_rate.py measures on the GPU; none is visible")
     dev, n = "cuda:0", args.robots
+    if args.privileged:
+        res = privileged_report(args, dev, n)
+        print(json.dumps(res, indent=1))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        sys.exit(0)
     cfg = PPOConfig()
     T = cfg.num_steps_per_env
     env = make_env(n, dev)

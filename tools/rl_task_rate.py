@@ -27,6 +27,12 @@ accumulate: one; beside the `begin` and `finish` kernels; p10, median, p90), and
 the step as it is without the option -- in alternating blocks, with the share of the tick the unit adds; with --learn K also what K PPO iterations
 do with the curriculum and with the fixed default range (one seed: a finding, not a claim).
     python tools/rl_task_rate.py --terms [--command-curriculum] [--learn 20] [--out profiles/episode_terms_rate.json]
+--privileged times the critic's privileged observation row (rl_mpc_locomotion_amd.privileged_obs), on the flat plane (48 actor columns, 64 privileged)
+or with --heights on the terrain grid (240 and 240): the assembly kernel alone from HIP events inside the running loop, beside the `finish` kernel and
+the scan (p10, median, p90), the bytes it moves, and BatchedRLTask.step with the option against the same task without it in alternating blocks, with
+the share of the tick the launch adds.  --baseline times only the task without the option (it runs on a tree that has no such unit, for a
+measurement of the parent commit in the same session).
+    python tools/rl_task_rate.py --privileged [--heights] [--baseline] [--out results/privileged_step.json]
 The kernel-trace stats of the same step: rocprofv3 --kernel-trace --stats ... -- python tools/rl_task_rate.py --ticks 50 --quick"""
 import argparse
 import json
@@ -527,6 +533,99 @@ def terms_report(args, dev, n, actions):
     return res
 
 
+def tick_privileged(task, actions, ev):
+    """BatchedRLTask.step's statements with the privileged row, with events around `finish`, the scan (when there is one) and the assembly kernel"""
+    sim, t = task.sim, task.task
+    tau = task.bridge.pre_physics_step(actions, sim.dof_state, sim.root_states, task.commands)
+    sim.step(tau)
+    ids = t.begin()
+    task.bridge.ctl.reset(ids)
+    sim.reset_idx(ids)
+    _, fell = sim.flags()
+    ev[0].record()
+    t.finish(sim.root_states, sim.dof_state, actions, tau, fell=fell)
+    ev[1].record()
+    if task.height_scan is not None:
+        task.height_scan.measure(sim.root_states, t.obs_buf, out=task.obs_buf, heights=task.measured_heights)
+    ev[2].record()
+    task.privileged_obs.assemble(task.obs_buf, task.progress_buf, task._inv_len, num_scan=task._num_scan, out=task.privileged_obs_buf)
+    ev[3].record()
+
+
+def privileged_report(args, dev, n, actions):
+    from bench import device_state
+    cfg = TaskConfig(**CFG)
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "ticks_per_block": args.ticks, "blocks": args.blocks,
+           "heights": bool(args.heights), "baseline_only": bool(args.baseline), "device_state": {"before": device_state(0)}}
+    where = {}
+    if args.heights:
+        from rl_mpc_locomotion_amd.curriculum import TerrainCurriculum
+        from rl_mpc_locomotion_amd.height_scan import HeightScan
+        from rl_mpc_locomotion_amd.terrain import TerrainGrid
+        grid = TerrainGrid(num_levels=10, num_types=20, tile_length=8.0, tile_width=8.0, seed=0)
+        origins = TerrainCurriculum(grid, n, max_init_level=args.max_init_level, seed=0, device=dev, episode_length_s=cfg.episode_length_s).origins0
+        where = dict(terrain=grid.terrain, origin=origins)
+
+    def make_task(with_privileged):
+        opts = dict(where)
+        if args.heights:
+            opts["height_scan"] = HeightScan(n, device=dev)
+        if with_privileged:
+            from rl_mpc_locomotion_amd.privileged_obs import PrivilegedObs
+            opts["privileged_obs"] = PrivilegedObs(n, device=dev)
+        return BatchedRLTask([0] * n, [TROT] * n, cfg=cfg, horizon=10, yaw0=yaw, flat_ground=True, device=dev, **opts)
+    loops = {"step_without": make_task(False)} if args.baseline else {"step_with_privileged": make_task(True), "step_without": make_task(False)}
+    for task in loops.values():
+        task.reset()
+        for _ in range(20):
+            task.step(actions)
+    torch.cuda.synchronize()
+    wall = {k: [] for k in loops}
+    for _ in range(args.blocks):          # the loops alternate, block by block
+        for name, task in loops.items():
+            t0 = time.perf_counter()
+            for _ in range(args.ticks):
+                task.step(actions)
+            torch.cuda.synchronize()
+            wall[name].append(time.perf_counter() - t0)
+    for name, w in wall.items():
+        per = np.array(w) / args.ticks * 1e3
+        res[name] = {"ms_per_tick_median": med(per), "ms_per_tick_p10": float(np.percentile(per, 10)), "ms_per_tick_p90": float(np.percentile(per, 90)),
+                     "ms_per_tick_min": float(per.min()), "ms_per_tick_max": float(per.max()), "robot_ticks_per_s": n * args.ticks / med(w)}
+    res["after_timing"] = {"fallen_fraction": {k: float(t.sim.flags()[1].float().mean().item()) for k, t in loops.items()}}
+    if not args.baseline:
+        res["with_over_without_ms_per_tick"] = res["step_with_privileged"]["ms_per_tick_median"] / res["step_without"]["ms_per_tick_median"]
+        task = loops["step_with_privileged"]
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.ticks * 2)]
+        for e in ev:
+            tick_privileged(task, actions, e)
+        torch.cuda.synchronize()
+        span = lambda i: np.array([e[i].elapsed_time(e[i + 1]) for e in ev])
+        parts = {"finish_kernel": span(0), "assembly_kernel": span(2)}
+        if args.heights:
+            parts["scan_kernel"] = span(1)
+        for k, v in parts.items():
+            res[k] = spread(v)
+        res["events"] = len(ev)
+        tick_ms = res["step_without"]["ms_per_tick_median"]
+        res["share_of_the_tick"] = {"assembly_kernel_median_us": med(parts["assembly_kernel"]) * 1e3, "assembly_over_step_without": med(parts["assembly_kernel"]) / tick_ms,
+                                    "assembly_over_finish_median": med(parts["assembly_kernel"]) / med(parts["finish_kernel"]),
+                                    "measured_step_difference_over_step_without": res["with_over_without_ms_per_tick"] - 1.0}
+        # the bytes the algorithm needs, from the shapes: the live columns read, four contact words and one counter per environment, the whole row written
+        wp, live = task.num_privileged_obs, 48 + task._num_scan
+        moved = n * live * 4 + n * 4 * 4 + n * 8 + n * wp * 4
+        t_s = med(parts["assembly_kernel"]) * 1e-3
+        res["assembly_bytes"] = {"actor_columns": task.num_obs, "privileged_columns": wp, "row_writes": n * wp * 4, "all_reads_and_writes": moved,
+                                 "achieved_bytes_per_s": moved / t_s, "at_hbm_peak_ms": moved / HBM_PEAK_BYTES_PER_S * 1e3,
+                                 "hbm_peak_bytes_per_s": HBM_PEAK_BYTES_PER_S, "share_of_hbm_peak": moved / t_s / HBM_PEAK_BYTES_PER_S}
+        rows = task.privileged_obs_buf
+        res["after_timing"]["privileged_row"] = {"contact_mean": float(rows[:, live:live + 4].mean().item()), "phase_max": float(rows[:, live + 4].max().item()),
+                                                  "equals_the_actor_row_in_the_live_columns": bool(torch.equal(rows[:, :live], task.obs_buf[:, :live]))}
+    res["device_state"]["after"] = device_state(0, smi=False)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--ticks", type=int, default=100, help="ticks per block")
@@ -543,14 +642,17 @@ if __name__ == "__main__":
     ap.add_argument("--terms", action="store_true", help="time the per-term episode sums' launches and the step with and without them")
     ap.add_argument("--command-curriculum", action="store_true", help="--terms: with the command curriculum (one more launch per tick)")
     ap.add_argument("--episode-s", type=float, default=20.0, help="--terms: the episode length of the timed tasks, in seconds")
+    ap.add_argument("--privileged", action="store_true", help="time the privileged row's assembly kernel and the step with and without it; with or without --heights")
+    ap.add_argument("--baseline", action="store_true", help="--privileged: only the task without the option (runs on a tree without the unit)")
     ap.add_argument("--out")
     args = ap.parse_args()
     dev, n = "cuda:0", args.robots
     actions = torch.zeros((n, 12), dtype=torch.float32, device=dev)
-    if args.terms or args.domain_rand or args.heights or args.curriculum:
-        res = (terms_report if args.terms else domain_rand_report if args.domain_rand else heights_report if args.heights else curriculum_report)(args, dev, n, actions)
+    if args.privileged or args.terms or args.domain_rand or args.heights or args.curriculum:
+        res = (privileged_report if args.privileged else terms_report if args.terms else domain_rand_report if args.domain_rand else heights_report if args.heights else curriculum_report)(args, dev, n, actions)
         print(json.dumps(res, indent=1))
         if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as fh:
                 json.dump(res, fh, indent=1)
         sys.exit(0)
