@@ -37,6 +37,9 @@ from ._lib import ci, pvp, text, vp
 NUM_OBS = 48
 # the order of the sum at aliengo.py:398
 REWARD_TERMS = ("lin_vel_xy", "lin_vel_z", "ang_vel_xy", "ang_vel_z", "torque", "collision")
+# the parts of BatchedRLTask.step, in the order it runs them (its docstring says what each one is)
+STAGES = ("actions", "controller", "plant", "push", "terrain_curriculum", "begin", "episode_close", "resets", "finish", "episode_accumulate", "height_scan",
+          "privileged_obs", "observation_noise")
 
 # the entry points of include/mpc_task.h (bound here, not in _lib.SYMBOLS, which lists include/mpc_batch.h)
 DECLS = {
@@ -204,32 +207,30 @@ class BatchedRLTask:
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
                  curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, **bridge_args):
         import torch
-        if privileged_obs is not None and privileged_obs.n != len(np.asarray(robot_type).reshape(-1)):      # refused before the device is touched
-            raise ValueError(f"the privileged observations hold {privileged_obs.n} environments, robot_type {len(np.asarray(robot_type).reshape(-1))}")
-        if episode_terms is not None and episode_terms.n != len(np.asarray(robot_type).reshape(-1)):      # refused before the device is touched
-            raise ValueError(f"the episode terms hold {episode_terms.n} environments, robot_type {len(np.asarray(robot_type).reshape(-1))}")
-        if domain_rand is not None:        # everything that can be refused before the device is touched
-            n_envs = len(np.asarray(robot_type).reshape(-1))
-            width = NUM_OBS if height_scan is None else height_scan.width(NUM_OBS)
-            domain_rand.validate(n=n_envs, num_obs=width, dt=(cfg if cfg is not None else TaskConfig()).dt)
-        if height_scan is not None:
-            if terrain is None and curriculum is None:
+        n_envs = len(np.asarray(robot_type).reshape(-1))
+        cfg = cfg if cfg is not None else TaskConfig()
+        # everything that can be refused is refused here, before the device is touched: one pass over the options, the first fault raises
+        for unit, holds in ((privileged_obs, "the privileged observations hold"), (episode_terms, "the episode terms hold"), (domain_rand, None),
+                            (height_scan, "the height scan holds"), (curriculum, "the curriculum holds")):
+            if unit is None:
+                continue
+            if unit is domain_rand:        # counts its environments itself, with its specs against the row's width and its push against the tick
+                unit.validate(n=n_envs, num_obs=NUM_OBS if height_scan is None else height_scan.width(NUM_OBS), dt=cfg.dt)
+                continue
+            if unit is height_scan and terrain is None and curriculum is None:
                 raise ValueError("height_scan measures a terrain: give terrain= or curriculum=")
-            if height_scan.n != len(np.asarray(robot_type).reshape(-1)):
-                raise ValueError(f"the height scan holds {height_scan.n} environments, robot_type {len(np.asarray(robot_type).reshape(-1))}")
-            clip_obs = (cfg if cfg is not None else TaskConfig()).clip_observations
-            if np.float32(height_scan.obs_clip) != np.float32(clip_obs):
-                raise ValueError(f"the height scan clips its columns to {height_scan.obs_clip}, the task's clip_observations is {clip_obs}")
-        if curriculum is not None:
-            if terrain is not None or origin is not None:
+            if unit is curriculum and (terrain is not None or origin is not None):
                 raise ValueError("curriculum brings its own terrain and origins: terrain= / origin= exclude it")
-            if curriculum.n != len(np.asarray(robot_type).reshape(-1)):
-                raise ValueError(f"the curriculum holds {curriculum.n} environments, robot_type {len(np.asarray(robot_type).reshape(-1))}")
+            if unit.n != n_envs:
+                raise ValueError(f"{holds} {unit.n} environments, robot_type {n_envs}")
+            if unit is height_scan and np.float32(unit.obs_clip) != np.float32(cfg.clip_observations):
+                raise ValueError(f"the height scan clips its columns to {unit.obs_clip}, the task's clip_observations is {cfg.clip_observations}")
+        if curriculum is not None:
             terrain, origin = curriculum.terrain, curriculum.origins0
         _lib.need_gpu("BatchedRLTask")
         from .env_bridge import MpcEnvBridge
         from .toy_sim import BatchedToySim
-        self.cfg = cfg if cfg is not None else TaskConfig()
+        self.cfg = cfg
         self.bridge = MpcEnvBridge(robot_type, gait_id, horizon=horizon, controller_dt=self.cfg.dt, flat_ground=flat_ground, device=device, **bridge_args)
         self.device, self.n = self.bridge.device, self.bridge.n
         self.num_envs, self.num_obs, self.num_actions = self.n, NUM_OBS, 12
@@ -265,9 +266,27 @@ class BatchedRLTask:
             self.privileged_obs_buf = torch.zeros((self.n, self.num_privileged_obs), dtype=torch.float32, device=self.device)
         self.common_step_counter = 0       # the ticks this task has stepped, counted on the host: the command curriculum's clock
 
-    def step(self, actions):
+    def step(self, actions, mark=None):
         """``VecTask.step`` (vec_task.py:298-339): actions [N,12] -> (obs_buf, rew_buf, reset_buf, {"time_outs": timeout_buf}).  The returned
-        tensors are the task's own buffers, rewritten by the next step.  Nothing is copied to the host and nothing waits for the device."""
+        tensors are the task's own buffers, rewritten by the next step.  Nothing is copied to the host and nothing waits for the device.
+
+        The tick's parts are named by ``STAGES``, in the order they run:
+            actions             the clamp, or with action noise ``begin_step`` and the noise launch in its place
+            controller          ``bridge.pre_physics_step``
+            plant               ``sim.step``
+            push                ``domain_rand.after_physics``              only while a DomainRand is enabled (it launches on push ticks)
+            terrain_curriculum  ``curriculum.update``                      only with a curriculum
+            begin               ``task.begin``
+            episode_close       ``episode_terms.close_and_resample``       only with episode_terms
+            resets              ``ctl.reset``, ``sim.reset_idx``, ``sim.flags``
+            finish              ``task.finish``
+            episode_accumulate  ``episode_terms.accumulate``               only with episode_terms
+            height_scan         ``height_scan.measure``                    only with a height scan
+            privileged_obs      ``privileged_obs.assemble``                only with privileged_obs
+            observation_noise   the observation-noise launch               only while a DomainRand is enabled and has observation noise
+        ``mark``, when given, is called as ``mark(name)`` on the host right after each stage that ran on this tick has been launched, and not for a
+        stage whose option is absent; a caller that records an event on the current stream in it times the stages (tools/rl_task_rate.py).  It must
+        not synchronise, copy or launch anything itself, and it changes nothing in what the step computes or launches."""
         import torch
         sim, t = self.sim, self.task
         dr = self.domain_rand if self.domain_rand is not None and self.domain_rand.enabled else None
@@ -278,29 +297,55 @@ class BatchedRLTask:
             if dr.specs["actions"] is not None:                                                                                # :308-312, one launch
                 dr.noise("actions", actions.to(self.device, torch.float32).reshape(self.n, 12).contiguous(), out=self.actions, clip=self.cfg.clip_actions,
                          tick=dr.tick)
+        if mark is not None:
+            mark("actions")
         self.torques = self.bridge.pre_physics_step(self.actions, sim.dof_state, sim.root_states, self.commands)                # aliengo.py:227-263
+        if mark is not None:
+            mark("controller")
         sim.step(self.torques)                                                                                                  # gym.simulate
+        if mark is not None:
+            mark("plant")
         if dr is not None:                 # legged_gym's _post_physics_step_callback: termination, reward and observations see the pushed velocity
             dr.after_physics(sim.root_states)
+            if mark is not None:
+                mark("push")
         if self.curriculum is not None:    # the flags begin is about to consume, the finished episode's commands, the root states before the reset
             self.curriculum.update(self.reset_buf, sim.root_states, self.commands)
+            if mark is not None:
+                mark("terrain_curriculum")
         ids = t.begin()                                                                                                         # :326, aliengo.py:274-278
+        if mark is not None:
+            mark("begin")
         et = self.episode_terms
         if et is not None:                 # close the marked episodes, decide, and put the curriculum's commands in place before finish reads them
             self.common_step_counter += 1
             et.close_and_resample(ids, self.commands, self.common_step_counter)
+            if mark is not None:
+                mark("episode_close")
         self.bridge.ctl.reset(ids)                                                                                              # aliengo.py:330-334
         sim.reset_idx(ids)                                                                                                      # aliengo.py:336-342
         _, fell = sim.flags()              # after the reset: a robot that has just been put back standing is not flagged a second time
+        if mark is not None:
+            mark("resets")
         t.finish(sim.root_states, sim.dof_state, self.actions, self.torques, fell=fell)                                         # aliengo.py:280-281, :337
+        if mark is not None:
+            mark("finish")
         if et is not None:                 # the tensors finish has just read, the same base contact
             et.accumulate(sim.root_states, self.commands, self.torques, fell)
+            if mark is not None:
+                mark("episode_accumulate")
         if self.height_scan is not None:   # the same post-reset root states, and the origins the curriculum has just written
             self.height_scan.measure(sim.root_states, t.obs_buf, out=self.obs_buf, heights=self.measured_heights)
+            if mark is not None:
+                mark("height_scan")
         if self.privileged_obs is not None:                                    # the clean copy exists because this launch comes before the noise
             self.privileged_obs.assemble(self.obs_buf, self.progress_buf, self._inv_len, num_scan=self._num_scan, out=self.privileged_obs_buf)
+            if mark is not None:
+                mark("privileged_obs")
         if dr is not None and dr.specs["observations"] is not None:                                                             # :331-337, in place
             dr.noise("observations", self.obs_buf, active=self.num_active_obs, clip=self.cfg.clip_observations, tick=dr.tick)
+            if mark is not None:
+                mark("observation_noise")
         self.extras["time_outs"] = self.timeout_buf
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
 

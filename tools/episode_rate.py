@@ -21,6 +21,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rl_mpc_locomotion_amd  # noqa: E402,F401
+from _rate import ev, stats  # noqa: E402
 from rl_mpc_locomotion_amd import _lib, episode as E  # noqa: E402
 from rl_mpc_locomotion_amd.ppo import PPOConfig, PPOTrainer  # noqa: E402
 from rl_mpc_locomotion_amd.rl_task import BatchedRLTask, TaskConfig  # noqa: E402
@@ -46,16 +47,6 @@ class TorchRunner:
         self.lenbuffer.extend(self.cur_episode_length[new_ids][:, 0].cpu().numpy().tolist())
         self.cur_reward_sum[new_ids] = 0
         self.cur_episode_length[new_ids] = 0
-
-
-def ev():
-    return torch.cuda.Event(enable_timing=True)
-
-
-def stats(x):
-    x = np.asarray(x, dtype=np.float64)
-    return {"median_ms": float(np.median(x)), "min_ms": float(x.min()), "max_ms": float(x.max()), "p10_ms": float(np.percentile(x, 10)),
-            "p90_ms": float(np.percentile(x, 90)), "samples": int(x.size)}
 
 
 def timing(args, dev):

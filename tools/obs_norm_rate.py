@@ -21,6 +21,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rl_mpc_locomotion_amd  # noqa: E402,F401
+from _rate import ev, stats  # noqa: E402
 from rl_mpc_locomotion_amd import _lib  # noqa: E402
 from rl_mpc_locomotion_amd.obs_norm import ObsNormalizer  # noqa: E402
 from rl_mpc_locomotion_amd.ppo import PPOConfig, PPOTrainer  # noqa: E402
@@ -50,16 +51,6 @@ class TorchNormalizer:
         self._var += rate * (var_x - self._var + delta_mean * (mean_x - self._mean))
         self._std = torch.sqrt(self._var)
         return torch.div(x - self._mean, self._std + self.eps, out=out)
-
-
-def ev():
-    return torch.cuda.Event(enable_timing=True)
-
-
-def stats(x):
-    x = np.asarray(x, dtype=np.float64)
-    return {"median_ms": float(np.median(x)), "min_ms": float(x.min()), "max_ms": float(x.max()), "p10_ms": float(np.percentile(x, 10)),
-            "p90_ms": float(np.percentile(x, 90)), "samples": int(x.size)}
 
 
 def make_env(n, robot_type, terrain, dev):

@@ -23,6 +23,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rl_mpc_locomotion_amd  # noqa: E402,F401
+from _rate import ev, stats  # noqa: E402
 from rl_mpc_locomotion_amd import _lib  # noqa: E402
 from rl_mpc_locomotion_amd.ppo import PPO, PPOConfig, PPOTrainer, RolloutStorage  # noqa: E402
 from rl_mpc_locomotion_amd.rl_task import BatchedRLTask, TaskConfig  # noqa: E402
@@ -70,16 +71,6 @@ def torch_returns(ac, st, obs, gamma, lam):
             st.returns[step] = advantage + st.values[step]
         adv = st.returns - st.values
         st.advantages = (adv - adv.mean()) / (adv.std() + 1e-8)
-
-
-def ev():
-    return torch.cuda.Event(enable_timing=True)
-
-
-def stats(x):
-    x = np.asarray(x, dtype=np.float64)
-    return {"median_ms": float(np.median(x)), "min_ms": float(x.min()), "max_ms": float(x.max()), "p10_ms": float(np.percentile(x, 10)),
-            "p90_ms": float(np.percentile(x, 90)), "samples": int(x.size)}
 
 
 def privileged_report(args, dev, n):
