@@ -155,9 +155,31 @@ def need_gpu(what, *tensors):
 
 
 def tensor_arg(t, dtype, numel, name):
-    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
-        raise ValueError(f"{name} must be a contiguous cuda {str(dtype).replace('torch.', '')} tensor with {numel} elements")
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    if t.dtype not in dtypes or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name} must be a contiguous cuda {' / '.join(str(d).replace('torch.', '') for d in dtypes)} tensor with {numel} elements")
     return t
+
+
+def flag_arg(t, n, name):
+    """tensor_arg for a flag array, which may be bool or uint8 (one byte either way)."""
+    import torch
+    return tensor_arg(t, (torch.bool, torch.uint8), n, name)
+
+
+def device_of(device):
+    """The torch.device a wrapper lives on: ``device``, or torch's current cuda device for None."""
+    import torch
+    return torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+
+
+def device_view(ptr, shape, typestr, device):
+    """A cuda tensor of ``shape`` over the device memory at ``ptr``; the memory is a handle's, so the view is valid while its owner lives."""
+    import torch
+
+    class _Array:
+        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
+    return torch.as_tensor(_Array(), device=device)
 
 
 def stream(device):

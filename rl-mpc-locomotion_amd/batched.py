@@ -23,7 +23,7 @@ class BatchedConvexMpc:
         solver: "osqp" = the reference's OSQP branch (BASELINE's comparator), "exact" = its qpOASES branch (the QP's optimum, cold every call)."""
         import torch
         _lib.need_gpu("BatchedConvexMpc")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         torch.cuda.set_device(self.device)
         mass = np.ascontiguousarray(mass, dtype=np.float64).reshape(-1)
         inertia9 = np.ascontiguousarray(inertia9, dtype=np.float64).reshape(len(mass), 9)

@@ -11,7 +11,7 @@
 //                                              lin_vel_x[1] = clip(lin_vel_x[1] + 0.5, 0., max_curriculum)
 //                                            called when common_step_counter % max_episode_length == 0
 //   rsl_rl      the runner's ep_infos        the mean of the "rew_<term>" entries over an iteration
-// The six terms are those of rltask::reward_reset (rl_task.h), in its order; "tracking_lin_vel" is its lin_vel_xy.
+// The six terms are rltask::reward_terms (rl_task.h), the function reward_reset itself sums; "tracking_lin_vel" is its lin_vel_xy.
 //
 // Compile with -ffp-contract=off.  The per-environment sums are float32, everything across environments is float64.
 //
@@ -27,8 +27,6 @@
 //     legged_gym's same-tick reset_idx.  Its sums hold every tick of the episode either way;
 //   * the command draws are rl_task.h's counter-based generator keyed by (seed, env, count, 4 + axis), `count` being this unit's own count of the
 //     environment's resamples: parity with torch_rand_float is in distribution only (uniform in the current ranges);
-//   * the terms are the unclipped products.  The reward itself is their sum clipped at 0, so the terms of a tick add up to less than the reward
-//     where the clip bit;
 //   * only the x range moves.  The y and yaw ranges stay the configured ones;
 //   * an episode whose sums are not all finite is zeroed and resampled like any other but closes nothing: it is neither counted nor added.  A
 //     plant state that has blown up gives NaN terms (the reward hides them: fmaxf(NaN, 0) is 0), and torch's mean over such an episode would be
@@ -54,30 +52,9 @@ enum { kGlobRanges = 0, kGlobWindow = 6, kGlobWidenings = 6 + 1 + kTerms, kGlobL
 // what `summary` writes: closed in window, six window term sums, x lo, x hi, widenings, max_episode_length_s
 enum { kSumClosed = 0, kSumTerms = 1, kSumLo = 1 + kTerms, kSumHi = 2 + kTerms, kSumWidenings = 3 + kTerms, kSumEpisodeS = 4 + kTerms, kSummaryLen = 5 + kTerms };
 
-// The six products of rltask::reward_reset in REWARD_TERMS order, the same operations in the same order:
-// fmaxf(((((t0 + t1) + t2) + t3) + t4) + t5, 0.0f) is bit for bit what reward_reset returns.
-MPC_HD void reward_terms(const rltask::Config &c, const float *root, const float *commands, const float *torques, const rltask::Contacts &k,
-                         float *terms) {
-  using namespace rltask;
-  float lin[3], ang[3];
-  quat_rotate_inverse(root + 3, root + 7, lin);
-  quat_rotate_inverse(root + 3, root + 10, ang);
-  const float ex = commands[0] - lin[0], ey = commands[1] - lin[1], ez = commands[2] - ang[2];
-  const float lin_vel_error = ex * ex + ey * ey;
-  const float ang_vel_error = ez * ez;
-  terms[kRewLinVelXY] = expf(-lin_vel_error / 0.25f) * c.rew[kRewLinVelXY];
-  terms[kRewAngVelZ] = expf(-ang_vel_error / 0.25f) * c.rew[kRewAngVelZ];
-  terms[kRewLinVelZ] = (lin[2] * lin[2]) * c.rew[kRewLinVelZ];
-  terms[kRewAngVelXY] = (ang[0] * ang[0] + ang[1] * ang[1]) * c.rew[kRewAngVelXY];
-  terms[kRewCollision] = (float)k.knees * c.rew[kRewCollision];
-  float t2 = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) t2 = t2 + torques[i] * torques[i];
-  terms[kRewTorque] = t2 * c.rew[kRewTorque];
-}
-
-// the reward from its terms: the left-to-right sum, clipped at 0
-MPC_HD float reward_from_terms(const float *t) { return fmaxf(((((t[0] + t[1]) + t[2]) + t[3]) + t[4]) + t[5], 0.0f); }
+// the six products of a tick and their clipped sum are the task's own (rl_task.h), so the sums of an episode add up to its reward by construction
+using rltask::reward_from_terms;
+using rltask::reward_terms;
 
 // one tick of one environment: episode_sums += rew, and the tick is counted
 MPC_HD void accumulate_env(const float *terms, float *sums, int &ticks) {

@@ -18,6 +18,7 @@
 #include "policy_mlp.h"
 
 using namespace mpc;
+using mpchost::DeviceArray;
 using mpchost::DeviceGuard;
 
 #define MPC_DECL_OPS(HH) extern "C" const mpc::HorizonOps *mpc_horizon_ops_##HH(void);
@@ -56,29 +57,33 @@ struct mpc_batch {
   int n = 0, h = 0;
   const HorizonOps *ops = nullptr;   // the kernel set of this planning horizon (mpc_horizon.h)
   int state_len = 0;
-  RobotModel *d_models = nullptr;
-  double *d_state = nullptr, *d_qp = nullptr, *d_sc = nullptr;   // warm start, QP record (q, l, u, cone, wrench form of P), scale record
-  int *d_info = nullptr;   // used when the caller passes no info buffer
-  long long *d_prof = nullptr;   // per-robot section cycle counts of the last solve
-  int *d_order = nullptr;        // job list of the solve kernel: the launch's active robots, longest expected solve first (order_block, written by the prep launch)
-  int *d_sched = nullptr;        // [kSchedLen] job counters of the launch; d_ready [n]: polish entries (mpc_solve_jobs_kernel)
-  int *d_ready = nullptr;
-  int *d_seed = nullptr;         // [n, 4 h] exact mode: the working set each robot's previous call ended on (seeds the active-set method; MPC_EXACT_WARM=0: never)
+  DeviceArray<RobotModel> d_models;
+  DeviceArray<double> d_state, d_qp, d_sc;   // warm start, QP record (q, l, u, cone, wrench form of P), scale record
+  DeviceArray<int> d_info;       // used when the caller passes no info buffer
+  DeviceArray<long long> d_prof; // per-robot section cycle counts of the last solve
+  DeviceArray<int> d_order;      // job list of the solve kernel: the launch's active robots, longest expected solve first (order_block, written by the prep launch)
+  DeviceArray<int> d_sched;      // [kSchedLen] job counters of the launch; d_ready [n]: polish entries (mpc_solve_jobs_kernel)
+  DeviceArray<int> d_ready;
+  DeviceArray<int> d_seed;       // [n, 4 h] exact mode: the working set each robot's previous call ended on (seeds the active-set method; MPC_EXACT_WARM=0: never)
   bool warm_sets = true;
   bool f32_seed = false;         // MPC_EXACT_F32_SEED=1 (tuning hook, default off): the exact mode's seed comes from the float32 search of the call (mpc_exact32.h)
   int job_slots = 0;             // wave slots of the device for the persistent job kernel (0: one workgroup per robot)
   bool timing = false;           // mpc_batch_enable_timing: HIP events around the two kernels of each launch
   hipEvent_t ev[kTimingRing][3];
   long long launches = 0;
-  float *d_host_in = nullptr;    // staging for mpc_batch_solve_host
-  double *d_host_in64 = nullptr; // ... and mpc_batch_solve_host_f64
-  double *d_host_f = nullptr;
-  unsigned char *d_hist = nullptr;   // [n][kOrderHistory] cycles / 16384 of the last solves (order_block's sort key is their maximum)
+  DeviceArray<float> d_host_in;      // staging for mpc_batch_solve_host, allocated on its first call
+  DeviceArray<double> d_host_in64;   // ... and mpc_batch_solve_host_f64
+  DeviceArray<double> d_host_f;
+  DeviceArray<unsigned char> d_hist; // [n][kOrderHistory] cycles / 16384 of the last solves (order_block's sort key is their maximum)
   unsigned long long order_launches = 0;
   int device = 0;                // the HIP device the handle was created on: every entry point runs under a DeviceGuard for it
   int exact = 0;                 // mpc_batch_set_solver: 1 = the QP's exact optimum (the reference's qpOASES branch), cold on every call
   int max_iter = kMaxIter;       // mpc_batch_set_max_iter: OSQP's max_iter setting (OSQP mode)
   long long bytes = 0;
+
+  ~mpc_batch() {
+    if (timing) for (auto &e3 : ev) for (auto &e : e3) (void)hipEventDestroy(e);
+  }
 };
 
 
@@ -128,10 +133,10 @@ int mpc_batch_create(mpc_batch **out, int n, int horizon, double timestep, doubl
   if (!out || n <= 0 || !mass || !inertia9) return fail(MPC_E_ARG, "mpc_batch_create: bad argument");
   const HorizonOps *ops = horizon_ops(horizon);
   if (!ops) return fail(MPC_E_HORIZON, "mpc_batch_create: planning horizon outside the built range (mpc_supported_horizons: 2 .. 20 in the shipped library)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_batch_create: no HIP device");
+  const int device = mpchost::current_device();
+  if (device < 0) return fail(MPC_E_NODEVICE, "mpc_batch_create: no HIP device");
   mpc_batch *b = new mpc_batch();
-  (void)hipGetDevice(&b->device);
+  b->device = device;
   b->n = n;
   b->h = horizon;
   b->ops = ops;
@@ -139,25 +144,15 @@ int mpc_batch_create(mpc_batch **out, int n, int horizon, double timestep, doubl
   b->state_len = (int)(64 * horizon + 2);
   std::vector<RobotModel> models(n);
   for (int i = 0; i < n; ++i) models[i] = make_model(mass[i], inertia9 + 9 * (size_t)i, timestep, alpha);
-  auto cleanup = [&]() { mpc_batch_destroy(b); };
+  const size_t N = (size_t)n;
   hipError_t e;
-  if ((e = hipMalloc(&b->d_models, sizeof(RobotModel) * n)) != hipSuccess ||
-      (e = hipMalloc(&b->d_state, sizeof(double) * (size_t)n * b->state_len)) != hipSuccess ||
-      (e = hipMalloc(&b->d_qp, sizeof(double) * (size_t)n * qp_len)) != hipSuccess ||
-      (e = hipMalloc(&b->d_sc, sizeof(double) * (size_t)n * sc_len)) != hipSuccess ||
-      (e = hipMalloc(&b->d_info, sizeof(int) * (size_t)n * kInfoLen)) != hipSuccess ||
-      (e = hipMalloc(&b->d_prof, sizeof(long long) * (size_t)n * kProfLen)) != hipSuccess ||
-      (e = hipMalloc(&b->d_order, sizeof(int) * (size_t)n)) != hipSuccess ||
-      (e = hipMalloc(&b->d_hist, (size_t)n * kOrderHistory)) != hipSuccess ||
-      (e = hipMalloc(&b->d_sched, sizeof(int) * kSchedLen)) != hipSuccess ||
-      (e = hipMalloc(&b->d_ready, sizeof(int) * (size_t)n)) != hipSuccess ||
-      (e = hipMalloc(&b->d_seed, sizeof(int) * (size_t)n * 4 * horizon)) != hipSuccess ||
-      (e = hipMemset(b->d_seed, 0, sizeof(int) * (size_t)n * 4 * horizon)) != hipSuccess ||
-      (e = hipMemset(b->d_prof, 0, sizeof(long long) * (size_t)n * kProfLen)) != hipSuccess ||
-      (e = hipMemcpy(b->d_models, models.data(), sizeof(RobotModel) * n, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemset(b->d_hist, 0, (size_t)n * kOrderHistory)) != hipSuccess ||
-      (e = hipMemset(b->d_state, 0, sizeof(double) * (size_t)n * b->state_len)) != hipSuccess) {
-    cleanup();
+  if ((e = b->d_models.alloc_copy(models.data(), N)) != hipSuccess || (e = b->d_state.alloc_zero(N * b->state_len)) != hipSuccess ||
+      (e = b->d_qp.alloc(N * qp_len)) != hipSuccess || (e = b->d_sc.alloc(N * sc_len)) != hipSuccess ||
+      (e = b->d_info.alloc(N * kInfoLen)) != hipSuccess || (e = b->d_prof.alloc_zero(N * kProfLen)) != hipSuccess ||
+      (e = b->d_order.alloc(N)) != hipSuccess || (e = b->d_hist.alloc_zero(N * kOrderHistory)) != hipSuccess ||
+      (e = b->d_sched.alloc(kSchedLen)) != hipSuccess || (e = b->d_ready.alloc(N)) != hipSuccess ||
+      (e = b->d_seed.alloc_zero(N * 4 * horizon)) != hipSuccess) {
+    mpc_batch_destroy(b);
     return fail(MPC_E_HIP, std::string("mpc_batch_create: ") + hipGetErrorString(e));
   }
   {   // the persistent job kernel runs one workgroup per wave slot: four single-wave workgroups per CU (one per SIMD, full register budget)
@@ -177,25 +172,7 @@ int mpc_batch_create(mpc_batch **out, int n, int horizon, double timestep, doubl
   return MPC_OK;
 }
 
-void mpc_batch_destroy(mpc_batch *b) {
-  if (!b) return;
-  if (b->d_models) (void)hipFree(b->d_models);
-  if (b->d_state) (void)hipFree(b->d_state);
-  if (b->d_qp) (void)hipFree(b->d_qp);
-  if (b->d_sc) (void)hipFree(b->d_sc);
-  if (b->d_info) (void)hipFree(b->d_info);
-  if (b->d_prof) (void)hipFree(b->d_prof);
-  if (b->d_order) (void)hipFree(b->d_order);
-  if (b->d_hist) (void)hipFree(b->d_hist);
-  if (b->d_sched) (void)hipFree(b->d_sched);
-  if (b->d_ready) (void)hipFree(b->d_ready);
-  if (b->d_seed) (void)hipFree(b->d_seed);
-  if (b->timing) for (auto &e3 : b->ev) for (auto &e : e3) (void)hipEventDestroy(e);
-  if (b->d_host_in) (void)hipFree(b->d_host_in);
-  if (b->d_host_in64) (void)hipFree(b->d_host_in64);
-  if (b->d_host_f) (void)hipFree(b->d_host_f);
-  delete b;
-}
+void mpc_batch_destroy(mpc_batch *b) { mpchost::destroy_handle(b); }
 
 int mpc_batch_solve(mpc_batch *b, const float *d_in, double *d_forces, int *d_info, void *stream) {
   if (!b || !d_in || !d_forces) return fail(MPC_E_ARG, "mpc_batch_solve: bad argument");
@@ -267,8 +244,8 @@ int mpc_batch_solve_host(mpc_batch *b, const float *h_in, double *h_forces, int 
   DeviceGuard guard_(b->device);
   const size_t inlen = 56 + 4 * (size_t)b->h, N = 12 * (size_t)b->h;
   if (!b->d_host_in) {   // staging buffers of the host-pointer entry point, kept for the life of the handle
-    HIP_TRY(hipMalloc(&b->d_host_in, sizeof(float) * b->n * inlen));
-    if (!b->d_host_f) HIP_TRY(hipMalloc(&b->d_host_f, sizeof(double) * b->n * N));
+    HIP_TRY(b->d_host_in.alloc(b->n * inlen));
+    if (!b->d_host_f) HIP_TRY(b->d_host_f.alloc(b->n * N));
   }
   HIP_TRY(hipMemcpy(b->d_host_in, h_in, sizeof(float) * b->n * inlen, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_host_f, h_forces, sizeof(double) * b->n * N, hipMemcpyHostToDevice));   // rows of unsolved robots stay as passed in
@@ -284,8 +261,8 @@ int mpc_batch_solve_host_f64(mpc_batch *b, const double *h_in, double *h_forces,
   DeviceGuard guard_(b->device);
   const size_t inlen = 56 + 4 * (size_t)b->h, N = 12 * (size_t)b->h;
   if (!b->d_host_in64) {
-    HIP_TRY(hipMalloc(&b->d_host_in64, sizeof(double) * b->n * inlen));
-    if (!b->d_host_f) HIP_TRY(hipMalloc(&b->d_host_f, sizeof(double) * b->n * N));
+    HIP_TRY(b->d_host_in64.alloc(b->n * inlen));
+    if (!b->d_host_f) HIP_TRY(b->d_host_f.alloc(b->n * N));
   }
   HIP_TRY(hipMemcpy(b->d_host_in64, h_in, sizeof(double) * b->n * inlen, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_host_f, h_forces, sizeof(double) * b->n * N, hipMemcpyHostToDevice));   // rows of unsolved robots stay as passed in
@@ -631,31 +608,28 @@ __global__ __launch_bounds__(kCtrlThreads) void ctrl_post_kernel(int n, CtrlStat
 
 struct mpc_ctrl {
   int n = 0;
-  mpc_batch *solver = nullptr;
-  CtrlState *d_state = nullptr;
-  RobotConst *d_rc = nullptr;
-  int *d_robot_type = nullptr, *d_gait = nullptr, *d_active = nullptr, *d_info = nullptr;
-  float *d_rec = nullptr, *d_est = nullptr;
-  double *d_forces = nullptr;
+  int device = 0;                 // the solver's
+  mpc_batch *solver = nullptr;    // owned: destroyed with the controller
+  DeviceArray<CtrlState> d_state;
+  DeviceArray<RobotConst> d_rc;
+  DeviceArray<int> d_robot_type, d_gait, d_active, d_info;
+  DeviceArray<float> d_rec, d_est;
+  DeviceArray<double> d_forces;
   GaitTable gt;
   CtrlParams cp;
   std::vector<int> h_iter;        // host mirror of every robot's iterationCounter (deterministic outside the FSM): lets a tick
   bool mirror_valid = true;       // on which no robot is due for an MPC update skip the solver launches
-  FsmState *d_fsm = nullptr;      // control FSM (allocated by mpc_ctrl_fsm_init)
-  int *d_fsm_mode = nullptr;      // per-robot control mode of the last (re)initialisation
+  DeviceArray<FsmState> d_fsm;    // control FSM (allocated by mpc_ctrl_fsm_init)
+  DeviceArray<int> d_fsm_mode;    // per-robot control mode of the last (re)initialisation
   FsmParams fp{};
   int fsm_op_mode = kOpNormal;
+
+  ~mpc_ctrl() { mpc_batch_destroy(solver); }
 };
 
 extern "C" {
 
-void mpc_ctrl_destroy(mpc_ctrl *c) {
-  if (!c) return;
-  mpc_batch_destroy(c->solver);
-  void *ptrs[] = {c->d_state, c->d_rc, c->d_robot_type, c->d_gait, c->d_active, c->d_info, c->d_rec, c->d_est, c->d_forces, c->d_fsm, c->d_fsm_mode};
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  delete c;
-}
+void mpc_ctrl_destroy(mpc_ctrl *c) { mpchost::destroy_handle(c); }
 
 int mpc_ctrl_create(mpc_ctrl **out, int n, int horizon, double controller_dt, int iters_between_mpc, double alpha, int flat_ground,
                     const int *robot_type, const int *gait_id, int n_types, const double *robot_table, const int *gait_off,
@@ -674,6 +648,7 @@ int mpc_ctrl_create(mpc_ctrl **out, int n, int horizon, double controller_dt, in
   const double dt_mpc = controller_dt * iters_between_mpc;
   int rc0 = mpc_batch_create(&c->solver, n, horizon, dt_mpc, alpha, mass.data(), inertia.data());
   if (rc0 != MPC_OK) { delete c; return rc0; }
+  c->device = c->solver->device;
   c->cp = CtrlParams{controller_dt, iters_between_mpc, dt_mpc, horizon, flat_ground};
   c->gt.n_seg = horizon;
   for (int g = 0; g < kNumGaitIds; ++g)
@@ -686,18 +661,13 @@ int mpc_ctrl_create(mpc_ctrl **out, int n, int horizon, double controller_dt, in
     rcs[t].body_height = row[10]; rcs[t].mu = (float)row[11];
     for (int k = 0; k < 13; ++k) rcs[t].weights[k] = (float)row[12 + k];
   }
-  const size_t inlen = 56 + 4 * (size_t)horizon;
+  const size_t N = (size_t)n, inlen = 56 + 4 * (size_t)horizon;
   hipError_t e;
-  if ((e = hipMalloc(&c->d_state, sizeof(CtrlState) * n)) != hipSuccess || (e = hipMalloc(&c->d_rc, sizeof(RobotConst) * n_types)) != hipSuccess ||
-      (e = hipMalloc(&c->d_robot_type, sizeof(int) * n)) != hipSuccess || (e = hipMalloc(&c->d_gait, sizeof(int) * n)) != hipSuccess ||
-      (e = hipMalloc(&c->d_active, sizeof(int) * n)) != hipSuccess || (e = hipMalloc(&c->d_info, sizeof(int) * (size_t)n * kInfoLen)) != hipSuccess ||
-      (e = hipMalloc(&c->d_rec, sizeof(float) * n * inlen)) != hipSuccess || (e = hipMalloc(&c->d_est, sizeof(float) * (size_t)n * kEstLen)) != hipSuccess || (e = hipMalloc(&c->d_forces, sizeof(double) * (size_t)n * 12 * horizon)) != hipSuccess ||
-      (e = hipMemcpy(c->d_rc, rcs.data(), sizeof(RobotConst) * n_types, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(c->d_robot_type, robot_type, sizeof(int) * n, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(c->d_gait, gait_id, sizeof(int) * n, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemset(c->d_info, 0, sizeof(int) * (size_t)n * kInfoLen)) != hipSuccess ||
-      (e = hipMemset(c->d_rec, 0, sizeof(float) * n * inlen)) != hipSuccess ||
-      (e = hipMemset(c->d_forces, 0, sizeof(double) * (size_t)n * 12 * horizon)) != hipSuccess) {
+  if ((e = c->d_state.alloc(N)) != hipSuccess || (e = c->d_rc.alloc_copy(rcs.data(), (size_t)n_types)) != hipSuccess ||
+      (e = c->d_robot_type.alloc_copy(robot_type, N)) != hipSuccess || (e = c->d_gait.alloc_copy(gait_id, N)) != hipSuccess ||
+      (e = c->d_active.alloc(N)) != hipSuccess || (e = c->d_info.alloc_zero(N * kInfoLen)) != hipSuccess ||
+      (e = c->d_rec.alloc_zero(N * inlen)) != hipSuccess || (e = c->d_est.alloc(N * kEstLen)) != hipSuccess ||
+      (e = c->d_forces.alloc_zero(N * 12 * horizon)) != hipSuccess) {
     mpc_ctrl_destroy(c);
     return fail(MPC_E_HIP, std::string("mpc_ctrl_create: ") + hipGetErrorString(e));
   }
@@ -879,8 +849,8 @@ int mpc_ctrl_fsm_init(mpc_ctrl *c, const int *control_mode, int operating_mode, 
       return fail(MPC_E_ARG, "mpc_ctrl_fsm_init: control mode must be 0 (PASSIVE), 4 (LOCOMOTION) or 6 (RECOVERY_STAND)");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!c->d_fsm) {
-    HIP_TRY(hipMalloc(&c->d_fsm, sizeof(FsmState) * c->n));
-    HIP_TRY(hipMalloc(&c->d_fsm_mode, sizeof(int) * c->n));
+    HIP_TRY(c->d_fsm.alloc((size_t)c->n));
+    HIP_TRY(c->d_fsm_mode.alloc((size_t)c->n));
   }
   c->mirror_valid = false;       // from here on the device decides which robots run the locomotion controller
   c->fp = fsm_params(c->cp.dt, check_safety);
@@ -984,8 +954,9 @@ int mpc_ctrl_solver_info(mpc_ctrl *c, int *h_info) {
 
 // ---- weight policy (RL_Environment/WeightPolicy.py) ------------------------------------------------------
 struct mpc_policy {
+  int device = 0;
   policy::Net net{};
-  float *d_params = nullptr;   // all weights and biases, one allocation
+  DeviceArray<float> d_params; // all weights and biases, one allocation
   size_t lds = 0;
 };
 
@@ -998,11 +969,7 @@ __global__ void ctrl_estimate_kernel(int n, const CtrlState *st, const float *es
 }
 }  // namespace
 
-void mpc_policy_destroy(mpc_policy *p) {
-  if (!p) return;
-  if (p->d_params) (void)hipFree(p->d_params);
-  delete p;
-}
+void mpc_policy_destroy(mpc_policy *p) { mpchost::destroy_handle(p); }
 
 int mpc_policy_create(mpc_policy **out, int n_layers, const int *dims, const float *const *weights, const float *const *biases,
                       const float *act_scale, const float *act_const) {
@@ -1015,13 +982,14 @@ int mpc_policy_create(mpc_policy **out, int n_layers, const int *dims, const flo
     total += (size_t)dims[l] * dims[l + 1] + (((size_t)dims[l + 1] + 7) / 8) * 8;   // keeps every array 32-byte aligned
   }
   if (dims[n_layers] > 16) return fail(MPC_E_ARG, "mpc_policy_create: at most 16 outputs");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_policy_create: no HIP device");
+  const int device = mpchost::current_device();
+  if (device < 0) return fail(MPC_E_NODEVICE, "mpc_policy_create: no HIP device");
   mpc_policy *p = new mpc_policy();
+  p->device = device;
   p->net.n_layers = n_layers;
   for (int l = 0; l <= n_layers; ++l) p->net.dims[l] = dims[l];
   std::vector<float> host(total, 0.f);
-  if (hipMalloc(&p->d_params, sizeof(float) * total) != hipSuccess) { delete p; return fail(MPC_E_HIP, "mpc_policy_create: hipMalloc"); }
+  if (p->d_params.alloc(total) != hipSuccess) { delete p; return fail(MPC_E_HIP, "mpc_policy_create: hipMalloc"); }
   size_t off = 0;
   for (int l = 0; l < n_layers; ++l) {
     const size_t nw = (size_t)dims[l] * dims[l + 1], nb = (((size_t)dims[l + 1] + 7) / 8) * 8;

@@ -78,8 +78,8 @@ __global__ __launch_bounds__(kSummaryThreads) void curriculum_summary_kernel(int
 struct mpc_curriculum {
   int n = 0, device = 0;
   Config c{};
-  int *d_level = nullptr, *d_count = nullptr, *d_type = nullptr;       // [n] each
-  double *d_tiles = nullptr;                                           // [num_levels][num_types][2]
+  mpchost::DeviceArray<int> d_level, d_count, d_type;                  // [n] each
+  mpchost::DeviceArray<double> d_tiles;                                // [num_levels][num_types][2]
   double *d_origin = nullptr;                                          // the bound sim's own array [n][2]
 };
 
@@ -87,16 +87,7 @@ extern "C" {
 
 const char *mpc_curriculum_last_error(void) { return g_err.c_str(); }
 
-void mpc_curriculum_destroy(mpc_curriculum *c) {
-  if (!c) return;
-  DeviceGuard guard_(c->device);
-  (void)hipDeviceSynchronize();
-  if (c->d_level) (void)hipFree(c->d_level);
-  if (c->d_count) (void)hipFree(c->d_count);
-  if (c->d_type) (void)hipFree(c->d_type);
-  if (c->d_tiles) (void)hipFree(c->d_tiles);
-  delete c;
-}
+void mpc_curriculum_destroy(mpc_curriculum *c) { mpchost::destroy_handle(c); }
 
 int mpc_curriculum_create(mpc_curriculum **out, int n, int num_levels, int num_types, const double *h_tile_origins, const int *h_levels0,
                           const int *h_types, double env_length, double episode_length_s, unsigned long long seed) {
@@ -116,19 +107,15 @@ int mpc_curriculum_create(mpc_curriculum **out, int n, int num_levels, int num_t
     if (h_types[r] < 0 || h_types[r] >= num_types)
       return fail(MPC_E_ARG, "mpc_curriculum_create: type of environment " + std::to_string(r) + " outside [0, num_types)");
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_curriculum_create: no HIP device");
+  const int device = mpchost::current_device();
+  if (device < 0) return fail(MPC_E_NODEVICE, "mpc_curriculum_create: no HIP device");
   mpc_curriculum *c = new mpc_curriculum();
   c->n = n;
+  c->device = device;
   c->c = Config{num_levels, num_types, (float)(env_length / 2.0), (float)episode_length_s, seed};
-  if (hipGetDevice(&c->device) != hipSuccess) { delete c; return fail(MPC_E_NODEVICE, "mpc_curriculum_create: no HIP device"); }
-  const size_t ints = sizeof(int) * (size_t)n;
   hipError_t e;
-  if ((e = hipMalloc(&c->d_level, ints)) != hipSuccess || (e = hipMalloc(&c->d_count, ints)) != hipSuccess ||
-      (e = hipMalloc(&c->d_type, ints)) != hipSuccess || (e = hipMalloc(&c->d_tiles, sizeof(double) * 2 * tiles)) != hipSuccess ||
-      (e = hipMemcpy(c->d_level, h_levels0, ints, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemset(c->d_count, 0, ints)) != hipSuccess ||
-      (e = hipMemcpy(c->d_type, h_types, ints, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(c->d_tiles, h_tile_origins, sizeof(double) * 2 * tiles, hipMemcpyHostToDevice)) != hipSuccess ||
+  if ((e = c->d_level.alloc_copy(h_levels0, (size_t)n)) != hipSuccess || (e = c->d_count.alloc_zero((size_t)n)) != hipSuccess ||
+      (e = c->d_type.alloc_copy(h_types, (size_t)n)) != hipSuccess || (e = c->d_tiles.alloc_copy(h_tile_origins, 2 * tiles)) != hipSuccess ||
       (e = hipDeviceSynchronize()) != hipSuccess) {
     mpc_curriculum_destroy(c);
     return fail(MPC_E_HIP, std::string("mpc_curriculum_create: ") + hipGetErrorString(e));

@@ -72,12 +72,12 @@ void mpc_drand_destroy(mpc_drand *h) { delete h; }
 int mpc_drand_create(mpc_drand **out, int n, unsigned long long seed) {
   if (!out) return fail(MPC_E_ARG, "mpc_drand_create: null argument");
   if (n < 1) return fail(MPC_E_ARG, "mpc_drand_create: n must be at least 1");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_drand_create: no HIP device");
+  const int device = mpchost::current_device();
+  if (device < 0) return fail(MPC_E_NODEVICE, "mpc_drand_create: no HIP device");
   mpc_drand *h = new mpc_drand();
   h->n = n;
   h->seed = seed;
-  if (hipGetDevice(&h->device) != hipSuccess) { delete h; return fail(MPC_E_NODEVICE, "mpc_drand_create: no HIP device"); }
+  h->device = device;
   *out = h;
   return MPC_OK;
 }

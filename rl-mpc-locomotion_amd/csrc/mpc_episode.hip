@@ -207,7 +207,7 @@ __global__ __launch_bounds__(kGridThreads) void random_progress_kernel(long long
 struct mpc_episode {
   int n = 0, cap = 0, num_groups = 0;
   mpc_episode_buffers_t buf{};
-  void *workspace = nullptr;
+  mpchost::DeviceArray<char> workspace;        // one allocation, on `device`; the three below point into it
   Part *parts = nullptr;
   int *offsets = nullptr;
   long long *tick = nullptr;
@@ -230,31 +230,23 @@ int mpc_episode_create(mpc_episode **out, int n, int cap, int num_groups) {
   return MPC_OK;
 }
 
-void mpc_episode_destroy(mpc_episode *ep) {
-  if (!ep) return;
-  if (ep->workspace) {
-    DeviceGuard guard_(ep->device);
-    (void)hipFree(ep->workspace);
-  }
-  delete ep;
-}
+void mpc_episode_destroy(mpc_episode *ep) { mpchost::destroy_handle(ep); }
 
 int mpc_episode_bind(mpc_episode *ep, const mpc_episode_buffers_t *b) {
   if (!ep || !b) return fail(MPC_E_ARG, "mpc_episode_bind: bad argument");
   if (!b->d_cur_return || !b->d_cur_length || !b->d_win_return || !b->d_win_length || !b->d_win_timed_out || !b->d_counters || !b->d_sums || !b->d_summary)
     return fail(MPC_E_ARG, "mpc_episode_bind: every buffer but d_groups must be non-null");
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return fail(MPC_E_NODEVICE, "mpc_episode_bind: no HIP device");
+  const int dev = mpchost::current_device();
+  if (dev < 0) return fail(MPC_E_NODEVICE, "mpc_episode_bind: no HIP device");
   if (ep->workspace && ep->device != dev) {
     DeviceGuard guard_(ep->device);
-    (void)hipFree(ep->workspace);
-    ep->workspace = nullptr;
+    ep->workspace.reset();
   }
   if (!ep->workspace) {
     const size_t blocks = ((size_t)ep->n + kGridThreads - 1) / kGridThreads;
     const size_t parts = round16(blocks * (size_t)(ep->num_groups + 1) * sizeof(Part)), offsets = round16(blocks * sizeof(int));
-    HIP_TRY(hipMalloc(&ep->workspace, parts + offsets + 2 * sizeof(long long)));
-    char *w = static_cast<char *>(ep->workspace);
+    HIP_TRY(ep->workspace.alloc(parts + offsets + 2 * sizeof(long long)));
+    char *w = ep->workspace;
     ep->parts = reinterpret_cast<Part *>(w);
     ep->offsets = reinterpret_cast<int *>(w + parts);
     ep->tick = reinterpret_cast<long long *>(w + parts + offsets);

@@ -18,11 +18,13 @@
 #include "episode_terms.h"
 #include "mpc_episode_terms.h"
 #include "mpc_host.h"
+#include "mpc_task_config.h"
 
 using epterms::Curriculum;
 using epterms::kBlock;
 using epterms::kPartial;
 using epterms::kTerms;
+using mpchost::DeviceArray;
 using mpchost::DeviceGuard;
 
 static_assert(MPC_EPISODE_TERMS_SUMMARY == epterms::kSummaryLen && MPC_EPISODE_TERMS_STATE == epterms::kGlobLen && MPC_TASK_REW_TERMS == kTerms,
@@ -130,11 +132,6 @@ __global__ __launch_bounds__(64) void terms_summary_kernel(const double *__restr
     out[epterms::kSumEpisodeS] = episode_length_s;
   }
 }
-
-bool finite_all(const double *v, int k) {
-  for (int i = 0; i < k; ++i) if (!std::isfinite(v[i])) return false;
-  return true;
-}
 }  // namespace
 
 struct mpc_episode_terms {
@@ -143,10 +140,10 @@ struct mpc_episode_terms {
   bool curriculum = false;
   Curriculum k{};
   double episode_length_s = 0.0;
-  float *d_sums = nullptr;             // [n][6]
-  int *d_ticks = nullptr, *d_counts = nullptr;       // [n] each
-  double *d_partials = nullptr;        // [blocks][kPartial]
-  double *d_glob = nullptr;            // [kGlobLen]
+  DeviceArray<float> d_sums;           // [n][6]
+  DeviceArray<int> d_ticks, d_counts;  // [n] each
+  DeviceArray<double> d_partials;      // [blocks][kPartial]
+  DeviceArray<double> d_glob;          // [kGlobLen]
 };
 
 static dim3 env_grid(const mpc_episode_terms *h) { return dim3((unsigned)h->blocks); }
@@ -155,28 +152,18 @@ extern "C" {
 
 const char *mpc_episode_terms_last_error(void) { return g_err.c_str(); }
 
-void mpc_episode_terms_destroy(mpc_episode_terms *h) {
-  if (!h) return;
-  DeviceGuard guard_(h->device);
-  (void)hipDeviceSynchronize();
-  if (h->d_sums) (void)hipFree(h->d_sums);
-  if (h->d_ticks) (void)hipFree(h->d_ticks);
-  if (h->d_counts) (void)hipFree(h->d_counts);
-  if (h->d_partials) (void)hipFree(h->d_partials);
-  if (h->d_glob) (void)hipFree(h->d_glob);
-  delete h;
-}
+void mpc_episode_terms_destroy(mpc_episode_terms *h) { mpchost::destroy_handle(h); }
 
 int mpc_episode_terms_create(mpc_episode_terms **out, int n, const mpc_task_config *cfg, double episode_length_s, int curriculum, double x_lo0,
                              double x_hi0, double step, double threshold, double max_curriculum, long long update_every) {
   // everything is validated before the device is touched
   if (!out || !cfg) return fail(MPC_E_ARG, "mpc_episode_terms_create: null argument");
   if (n < 1) return fail(MPC_E_ARG, "mpc_episode_terms_create: n must be at least 1");
-  if (!finite_all(&cfg->lin_vel_scale, 4) || !finite_all(cfg->rew_scale, MPC_TASK_REW_TERMS) || !finite_all(&cfg->command_range[0][0], 6))
-    return fail(MPC_E_ARG, "mpc_episode_terms_create: a scale or a command range is not finite");
-  for (int a = 0; a < 3; ++a)
-    if (cfg->command_range[a][0] > cfg->command_range[a][1]) return fail(MPC_E_ARG, "mpc_episode_terms_create: command range with min > max");
-  if (cfg->max_episode_length < 1) return fail(MPC_E_ARG, "mpc_episode_terms_create: max_episode_length must be at least 1");
+  // (neither default_dof_pos nor clip_observations is checked: the terms read neither)
+  const taskcfg::Fault bad = taskcfg::check(*cfg);
+  if (bad == taskcfg::kNotFinite) return fail(MPC_E_ARG, "mpc_episode_terms_create: a scale or a command range is not finite");
+  if (bad == taskcfg::kRangeOrder) return fail(MPC_E_ARG, "mpc_episode_terms_create: command range with min > max");
+  if (bad == taskcfg::kEpisodeLength) return fail(MPC_E_ARG, "mpc_episode_terms_create: max_episode_length must be at least 1");
   if (!std::isfinite(episode_length_s) || !(episode_length_s > 0.0))
     return fail(MPC_E_ARG, "mpc_episode_terms_create: episode_length_s must be finite and > 0");
   if (curriculum) {
@@ -188,36 +175,24 @@ int mpc_episode_terms_create(mpc_episode_terms **out, int n, const mpc_task_conf
     if (!std::isfinite(threshold)) return fail(MPC_E_ARG, "mpc_episode_terms_create: threshold must be finite");
     if (update_every < 1) return fail(MPC_E_ARG, "mpc_episode_terms_create: update_every must be at least 1");
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_episode_terms_create: no HIP device");
+  const int device = mpchost::current_device();
+  if (device < 0) return fail(MPC_E_NODEVICE, "mpc_episode_terms_create: no HIP device");
   mpc_episode_terms *h = new mpc_episode_terms();
   h->n = n;
   h->blocks = (n + kBlock - 1) / kBlock;
-  rltask::Config &c = h->c;           // what the reward terms read, with mpc_task_create's roundings
-  c.lin_vel_scale = (float)cfg->lin_vel_scale; c.ang_vel_scale = (float)cfg->ang_vel_scale;
-  c.dof_pos_scale = (float)cfg->dof_pos_scale; c.dof_vel_scale = (float)cfg->dof_vel_scale;
-  for (int i = 0; i < kTerms; ++i) c.rew[i] = (float)cfg->rew_scale[i];
-  for (int a = 0; a < 3; ++a) { c.cmd_lo[a] = (float)cfg->command_range[a][0]; c.cmd_hi[a] = (float)cfg->command_range[a][1]; }
-  c.clip_obs = (float)cfg->clip_observations;
-  for (int i = 0; i < 12; ++i) c.default_dof_pos[i] = (float)cfg->default_dof_pos[i];
-  c.max_episode_length = cfg->max_episode_length;
-  c.seed = cfg->seed;
+  h->device = device;
+  h->c = taskcfg::to_device_config(*cfg);      // what the reward terms read
   h->curriculum = curriculum != 0;
   h->episode_length_s = episode_length_s;
-  h->k = Curriculum{0, 0, h->curriculum ? update_every : 1, (double)cfg->max_episode_length, threshold, (double)c.rew[rltask::kRewLinVelXY], step,
+  h->k = Curriculum{0, 0, h->curriculum ? update_every : 1, (double)cfg->max_episode_length, threshold, (double)h->c.rew[rltask::kRewLinVelXY], step,
                     max_curriculum};
   double glob[epterms::kGlobLen] = {};
   for (int a = 0; a < 3; ++a) { glob[2 * a] = cfg->command_range[a][0]; glob[2 * a + 1] = cfg->command_range[a][1]; }
   if (h->curriculum) { glob[0] = x_lo0; glob[1] = x_hi0; }
-  if (hipGetDevice(&h->device) != hipSuccess) { delete h; return fail(MPC_E_NODEVICE, "mpc_episode_terms_create: no HIP device"); }
-  const size_t ints = sizeof(int) * (size_t)n, floats = sizeof(float) * (size_t)n * kTerms, parts = sizeof(double) * (size_t)h->blocks * kPartial;
   hipError_t e;
-  if ((e = hipMalloc(&h->d_sums, floats)) != hipSuccess || (e = hipMalloc(&h->d_ticks, ints)) != hipSuccess ||
-      (e = hipMalloc(&h->d_counts, ints)) != hipSuccess || (e = hipMalloc(&h->d_partials, parts)) != hipSuccess ||
-      (e = hipMalloc(&h->d_glob, sizeof(glob))) != hipSuccess || (e = hipMemset(h->d_sums, 0, floats)) != hipSuccess ||
-      (e = hipMemset(h->d_ticks, 0, ints)) != hipSuccess || (e = hipMemset(h->d_counts, 0, ints)) != hipSuccess ||
-      (e = hipMemset(h->d_partials, 0, parts)) != hipSuccess || (e = hipMemcpy(h->d_glob, glob, sizeof(glob), hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipDeviceSynchronize()) != hipSuccess) {
+  if ((e = h->d_sums.alloc_zero((size_t)n * kTerms)) != hipSuccess || (e = h->d_ticks.alloc_zero((size_t)n)) != hipSuccess ||
+      (e = h->d_counts.alloc_zero((size_t)n)) != hipSuccess || (e = h->d_partials.alloc_zero((size_t)h->blocks * kPartial)) != hipSuccess ||
+      (e = h->d_glob.alloc_copy(glob, epterms::kGlobLen)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
     mpc_episode_terms_destroy(h);
     return fail(MPC_E_HIP, std::string("mpc_episode_terms_create: ") + hipGetErrorString(e));
   }

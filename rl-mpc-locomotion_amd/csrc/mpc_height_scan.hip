@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kThreads) void height_scan_kernel(Config c, Field f
 struct mpc_hscan {
   int n = 0, device = 0, P = 0;
   Config c{};
-  float *d_points = nullptr;           // [P][2]
+  mpchost::DeviceArray<float> d_points;        // [P][2]
   Field f{};                           // the bound sim's field (null until mpc_hscan_bind)
   const double *d_origin = nullptr;    // the bound sim's own array [n][2]
 };
@@ -78,13 +78,7 @@ int mpc_hscan_width(int in_width, int P) {
   return hscan::roundup16(in_width + P);
 }
 
-void mpc_hscan_destroy(mpc_hscan *h) {
-  if (!h) return;
-  DeviceGuard guard_(h->device);
-  (void)hipDeviceSynchronize();
-  if (h->d_points) (void)hipFree(h->d_points);
-  delete h;
-}
+void mpc_hscan_destroy(mpc_hscan *h) { mpchost::destroy_handle(h); }
 
 int mpc_hscan_create(mpc_hscan **out, int n, int P, const float *h_points, double offset, double clip, double scale, double obs_clip) {
   // everything is validated before the device is touched
@@ -97,17 +91,15 @@ int mpc_hscan_create(mpc_hscan **out, int n, int P, const float *h_points, doubl
   if (!std::isfinite(clip) || !(clip >= 0.0)) return fail(MPC_E_ARG, "mpc_hscan_create: clip must be finite and >= 0");
   if (!std::isfinite(scale)) return fail(MPC_E_ARG, "mpc_hscan_create: scale must be finite");
   if (!std::isfinite(obs_clip) || !(obs_clip >= 0.0)) return fail(MPC_E_ARG, "mpc_hscan_create: obs_clip must be finite and >= 0");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_hscan_create: no HIP device");
+  const int device = mpchost::current_device();
+  if (device < 0) return fail(MPC_E_NODEVICE, "mpc_hscan_create: no HIP device");
   mpc_hscan *h = new mpc_hscan();
   h->n = n;
+  h->device = device;
   h->P = P;
   h->c = Config{(float)offset, (float)clip, (float)scale, (float)obs_clip};
-  if (hipGetDevice(&h->device) != hipSuccess) { delete h; return fail(MPC_E_NODEVICE, "mpc_hscan_create: no HIP device"); }
-  const size_t bytes = sizeof(float) * 2 * (size_t)P;
   hipError_t e;
-  if ((e = hipMalloc(&h->d_points, bytes)) != hipSuccess || (e = hipMemcpy(h->d_points, h_points, bytes, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipDeviceSynchronize()) != hipSuccess) {
+  if ((e = h->d_points.alloc_copy(h_points, 2 * (size_t)P)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
     mpc_hscan_destroy(h);
     return fail(MPC_E_HIP, std::string("mpc_hscan_create: ") + hipGetErrorString(e));
   }

@@ -1,5 +1,12 @@
-// mpc_host.h -- the host-side scaffolding every C ABI unit (mpc_*.hip) shares: the device guard, the error slot, the HIP error check and a
-// byte rounding.  Host only, nothing in it reaches a kernel.  Not part of the C ABI.
+// mpc_host.h -- the host-side scaffolding every C ABI unit (mpc_*.hip) shares.  Host only, nothing in it reaches a kernel.  Not part of the C ABI.
+// What a unit gets from it:
+//   DeviceGuard        works on the handle's device and restores the caller's
+//   current_device     the device a `create` puts its handle on, or -1 for "no HIP device"
+//   destroy_handle     the body of every mpc_*_destroy: guard, synchronise, delete
+//   DeviceArray<T>     the owner of one hipMalloc'd array: a handle's `DeviceArray<T> d_x` is memory the handle owns and `delete` frees,
+//                      a plain `T *d_x` is memory of somebody else's
+//   ErrorSlot, HIP_TRY the text behind mpc_*_last_error and the check of a HIP call
+//   round16            a byte rounding
 //
 // A unit keeps its own slot, and with it its own mpc_*_last_error, and names the slot's setter `fail`:
 //   namespace {
@@ -22,12 +29,70 @@ struct DeviceGuard {
   int prev = -1;
   bool switched = false;
   explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+    if (dev >= 0 && hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
   }
   ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
   DeviceGuard(const DeviceGuard &) = delete;
   DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
+
+// The device a new handle lives on: the caller's current one.  -1 where there is no HIP device (the unit words its own MPC_E_NODEVICE message).
+inline int current_device() {
+  int ndev = 0, dev = -1;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return -1;
+  return dev;
+}
+
+// One hipMalloc'd array of T and its owner: freed by reset() and by the destructor, so a handle that holds its arrays as DeviceArray members
+// has no free list to keep.  Converts to T * so that launches and the other units read it as the pointer it is.  One hipMalloc / hipFree per
+// array, under the caller's device guard; an alloc* on an array that holds memory frees that first.
+template <typename T>
+class DeviceArray {
+ public:
+  DeviceArray() = default;
+  DeviceArray(const DeviceArray &) = delete;
+  DeviceArray &operator=(const DeviceArray &) = delete;
+  DeviceArray(DeviceArray &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DeviceArray &operator=(DeviceArray &&o) noexcept {
+    if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+    return *this;
+  }
+  ~DeviceArray() { reset(); }
+
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+  }
+  hipError_t alloc(size_t count) {
+    reset();
+    const hipError_t e = hipMalloc(&p_, sizeof(T) * count);
+    if (e != hipSuccess) p_ = nullptr;
+    return e;
+  }
+  hipError_t alloc_zero(size_t count) {
+    const hipError_t e = alloc(count);
+    return e != hipSuccess ? e : hipMemset(p_, 0, sizeof(T) * count);
+  }
+  hipError_t alloc_copy(const T *host, size_t count) {
+    const hipError_t e = alloc(count);
+    return e != hipSuccess ? e : hipMemcpy(p_, host, sizeof(T) * count, hipMemcpyHostToDevice);
+  }
+  T *get() const { return p_; }
+  operator T *() const { return p_; }
+
+ private:
+  T *p_ = nullptr;
+};
+
+// What every mpc_*_destroy is: wait, on the handle's device, for the launches that may still read its arrays, then delete (the DeviceArray
+// members free there, under the guard).  A handle that binds its device later and never did (device < 0) has nothing on any device.
+template <typename Handle>
+void destroy_handle(Handle *h) {
+  if (!h) return;
+  DeviceGuard guard_(h->device);
+  if (h->device >= 0) (void)hipDeviceSynchronize();
+  delete h;
+}
 
 // the text behind a unit's mpc_*_last_error: one thread_local instance per unit
 struct ErrorSlot : std::string {

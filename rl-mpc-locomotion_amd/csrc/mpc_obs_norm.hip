@@ -150,7 +150,7 @@ struct mpc_obsnorm {
   float eps = 0.0f;
   long long until = -1;
   mpc_obsnorm_buffers_t buf{};
-  void *workspace = nullptr;
+  mpchost::DeviceArray<char> workspace;        // on `device`
   long long capacity = 0;              // blocks the workspace holds
   int device = -1;
   bool bound = false;
@@ -170,24 +170,16 @@ int mpc_obsnorm_create(mpc_obsnorm **out, int num_obs, float eps, long long unti
   return MPC_OK;
 }
 
-void mpc_obsnorm_destroy(mpc_obsnorm *h) {
-  if (!h) return;
-  if (h->workspace) {
-    DeviceGuard guard_(h->device);
-    (void)hipFree(h->workspace);
-  }
-  delete h;
-}
+void mpc_obsnorm_destroy(mpc_obsnorm *h) { mpchost::destroy_handle(h); }
 
 int mpc_obsnorm_bind(mpc_obsnorm *h, const mpc_obsnorm_buffers_t *b) {
   if (!h || !b) return fail(MPC_E_ARG, "mpc_obsnorm_bind: bad argument");
   if (!b->d_state || !b->d_count || !b->d_mean || !b->d_var || !b->d_std) return fail(MPC_E_ARG, "mpc_obsnorm_bind: every buffer must be non-null");
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return fail(MPC_E_NODEVICE, "mpc_obsnorm_bind: no HIP device");
+  const int dev = mpchost::current_device();
+  if (dev < 0) return fail(MPC_E_NODEVICE, "mpc_obsnorm_bind: no HIP device");
   if (h->workspace && h->device != dev) {
     DeviceGuard guard_(h->device);
-    (void)hipFree(h->workspace);
-    h->workspace = nullptr;
+    h->workspace.reset();
     h->capacity = 0;
   }
   h->buf = *b;
@@ -206,14 +198,12 @@ int mpc_obsnorm_apply(mpc_obsnorm *h, const float *d_x, float *d_y, long long n,
   Call a{h->D, n, d_x, d_y, h->eps, h->until, h->buf, nullptr, nullptr, nullptr};
   if (update) {
     if (blocks > h->capacity) {        // (hipFree waits for the launches that still read the old one)
-      if (h->workspace) (void)hipFree(h->workspace);
-      h->workspace = nullptr;
       h->capacity = 0;
       const size_t counts = round16((size_t)blocks * sizeof(long long)), cols = round16((size_t)blocks * (size_t)h->D * sizeof(double));
-      HIP_TRY(hipMalloc(&h->workspace, counts + 2 * cols));
+      HIP_TRY(h->workspace.alloc(counts + 2 * cols));
       h->capacity = blocks;
     }
-    char *w = static_cast<char *>(h->workspace);
+    char *w = h->workspace;
     const size_t counts = round16((size_t)h->capacity * sizeof(long long)), cols = round16((size_t)h->capacity * (size_t)h->D * sizeof(double));
     a.part_n = reinterpret_cast<long long *>(w);
     a.part_mean = reinterpret_cast<double *>(w + counts);

@@ -240,8 +240,8 @@ int mpc_ac_bind(mpc_ac *ac, const float *const *d_actor_weights, const float *co
     for (int l = 0; l < ac->nets.net[k].n_layers; ++l)
       if (!aligned16(w[k][l]) || !aligned16(b[k][l])) return fail(MPC_E_ARG, "mpc_ac_bind: every weight and bias pointer must be non-null and 16-byte aligned");
   if (!aligned16(d_std)) return fail(MPC_E_ARG, "mpc_ac_bind: d_std must be non-null and 16-byte aligned");
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&dev) != hipSuccess) return fail(MPC_E_NODEVICE, "mpc_ac_bind: no HIP device");
+  const int dev = mpchost::current_device();
+  if (dev < 0) return fail(MPC_E_NODEVICE, "mpc_ac_bind: no HIP device");
   if (hipFuncSetAttribute(reinterpret_cast<const void *>(ac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ac->lds) != hipSuccess)
     return fail(MPC_E_HIP, "mpc_ac_bind: device set-up failed");
   for (int k = 0; k < 2; ++k)

@@ -204,7 +204,7 @@ struct mpc_ppo_update {
   int nl[2] = {0, 0};
   int dims[2][MPC_AC_MAX_LAYERS + 1] = {};
   int n_tensors = 0;
-  float *ws = nullptr;                          // one allocation
+  mpchost::DeviceArray<float> ws;               // one allocation; the pointers below, down to `norm`, point into it
   float *Y[2][MPC_AC_MAX_LAYERS] = {};          // [rows][ld(k, l)] activations after layer l
   float *dY[2][MPC_AC_MAX_LAYERS] = {};         // their gradients
   float *dWp[2][MPC_AC_MAX_LAYERS] = {};        // [chunks][out][in]
@@ -237,14 +237,7 @@ struct mpc_ppo_update {
 
 extern "C" {
 
-void mpc_ppo_update_destroy(mpc_ppo_update *u) {
-  if (!u) return;
-  if (u->ws) {
-    DeviceGuard guard_(u->device);
-    (void)hipFree(u->ws);
-  }
-  delete u;
-}
+void mpc_ppo_update_destroy(mpc_ppo_update *u) { mpchost::destroy_handle(u); }
 
 int mpc_ppo_update_tensors(const mpc_ppo_update *u) { return u ? u->n_tensors : -1; }
 
@@ -272,8 +265,7 @@ int mpc_ppo_update_create(mpc_ppo_update **out, mpc_ac *ac, int max_rows) {
   u->norm_blocks = (maxn + kNormPerBlock - 1) / kNormPerBlock;
   words += 2 * (size_t)u->head_blocks_max * kHeadStride + 2 * (size_t)round16(u->n_tensors * u->norm_blocks) + 16;
   DeviceGuard guard_(u->device);
-  if (hipMalloc(reinterpret_cast<void **>(&u->ws), words * sizeof(float)) != hipSuccess) {
-    u->ws = nullptr;
+  if (u->ws.alloc(words) != hipSuccess) {
     delete u;
     return fail(MPC_E_HIP, "mpc_ppo_update_create: the workspace could not be allocated");
   }

@@ -96,14 +96,7 @@ extern "C" {
 
 const char *mpc_sim_last_error(void) { return g_err.c_str(); }
 
-void mpc_sim_destroy(mpc_sim *s) {
-  if (!s) return;
-  DeviceGuard guard_(s->device);
-  (void)hipDeviceSynchronize();
-  void *ptrs[] = {s->d_f64, s->d_i32, s->d_type, s->d_slope, s->d_yaw, s->d_params, s->d_heights, s->d_origin};
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  delete s;
-}
+void mpc_sim_destroy(mpc_sim *s) { mpchost::destroy_handle(s); }
 
 int mpc_sim_create(mpc_sim **out, int n, const int *robot_type, int n_types, const double *table, const double *slope, const double *yaw0, double dt) {
   if (!out || n <= 0 || !robot_type || n_types <= 0 || !table || !(dt > 0.0)) return fail(MPC_E_ARG, "mpc_sim_create: bad argument");
@@ -119,20 +112,16 @@ int mpc_sim_create(mpc_sim **out, int n, const int *robot_type, int n_types, con
   std::vector<double> sl(2 * (size_t)n, 0.0), yaw(n, 0.0);
   if (slope) for (size_t i = 0; i < sl.size(); ++i) sl[i] = slope[i];
   if (yaw0) for (int r = 0; r < n; ++r) yaw[r] = yaw0[r];
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device");
+  const int device = mpchost::current_device();
+  if (device < 0) return fail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device");
   mpc_sim *s = new mpc_sim();
   s->n = n;
+  s->device = device;
   s->dt = dt;
-  if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(MPC_E_NODEVICE, "mpc_sim_create: no HIP device"); }
   hipError_t e;
-  if ((e = hipMalloc(&s->d_f64, sizeof(double) * kF64 * (size_t)n)) != hipSuccess || (e = hipMalloc(&s->d_i32, sizeof(int) * kI32 * (size_t)n)) != hipSuccess ||
-      (e = hipMalloc(&s->d_type, sizeof(int) * (size_t)n)) != hipSuccess || (e = hipMalloc(&s->d_slope, sizeof(double) * 2 * (size_t)n)) != hipSuccess ||
-      (e = hipMalloc(&s->d_yaw, sizeof(double) * (size_t)n)) != hipSuccess || (e = hipMalloc(&s->d_params, sizeof(Params) * n_types)) != hipSuccess ||
-      (e = hipMemcpy(s->d_type, robot_type, sizeof(int) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(s->d_slope, sl.data(), sizeof(double) * sl.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(s->d_yaw, yaw.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(s->d_params, params.data(), sizeof(Params) * n_types, hipMemcpyHostToDevice)) != hipSuccess) {
+  if ((e = s->d_f64.alloc(kF64 * (size_t)n)) != hipSuccess || (e = s->d_i32.alloc(kI32 * (size_t)n)) != hipSuccess ||
+      (e = s->d_type.alloc_copy(robot_type, (size_t)n)) != hipSuccess || (e = s->d_slope.alloc_copy(sl.data(), sl.size())) != hipSuccess ||
+      (e = s->d_yaw.alloc_copy(yaw.data(), (size_t)n)) != hipSuccess || (e = s->d_params.alloc_copy(params.data(), (size_t)n_types)) != hipSuccess) {
     mpc_sim_destroy(s);
     return fail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
   }

@@ -6,18 +6,19 @@
 
 #include <hip/hip_runtime.h>
 
+#include "mpc_host.h"
 #include "toy_sim.h"
 
 struct mpc_sim {
   int n = 0, device = 0;
   double dt = 0.0;
-  double *d_f64 = nullptr;             // [kF64][n]
-  int *d_i32 = nullptr, *d_type = nullptr;
-  double *d_slope = nullptr, *d_yaw = nullptr;
-  toysim::Params *d_params = nullptr;  // [n_types]
+  mpchost::DeviceArray<double> d_f64;  // [kF64][n]
+  mpchost::DeviceArray<int> d_i32, d_type;
+  mpchost::DeviceArray<double> d_slope, d_yaw;
+  mpchost::DeviceArray<toysim::Params> d_params;       // [n_types]
   // the terrain (null / 0 until mpc_terrain_attach): the sim's own copies
-  short *d_heights = nullptr;          // [rows][cols]
-  double *d_origin = nullptr;          // [n][2]
+  mpchost::DeviceArray<short> d_heights;               // [rows][cols]
+  mpchost::DeviceArray<double> d_origin;               // [n][2]
   int rows = 0, cols = 0;
   double hscale = 0.0, vscale = 0.0, x0 = 0.0, y0 = 0.0;
 };

@@ -5,11 +5,11 @@
 //                       the lanes of a store 192 bytes apart).  One wave per workgroup, so the one barrier between the two halves is a wave's.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <string>
 
 #include "../../include/mpc_task.h"
 #include "mpc_host.h"
+#include "mpc_task_config.h"
 #include "rl_task.h"
 
 using namespace rltask;
@@ -83,17 +83,12 @@ __global__ __launch_bounds__(kTaskThreads) void task_finish_kernel(Config c, int
     if (e < rows_here) out[f] = rows[e * kRowPad + (f - e * kObs)];
   }
 }
-
-bool finite_all(const double *v, int k) {
-  for (int i = 0; i < k; ++i) if (!std::isfinite(v[i])) return false;
-  return true;
-}
 }  // namespace
 
 struct mpc_task {
   int n = 0, device = 0;
   Config c{};
-  int *d_episode = nullptr;            // [n] how many times each environment has been reset: the generator's episode index
+  mpchost::DeviceArray<int> d_episode; // [n] how many times each environment has been reset: the generator's episode index
   mpc_task_buffer_set b{};
   bool bound = false;
 };
@@ -104,41 +99,24 @@ extern "C" {
 
 const char *mpc_task_last_error(void) { return g_err.c_str(); }
 
-void mpc_task_destroy(mpc_task *t) {
-  if (!t) return;
-  DeviceGuard guard_(t->device);
-  (void)hipDeviceSynchronize();
-  if (t->d_episode) (void)hipFree(t->d_episode);
-  delete t;
-}
+void mpc_task_destroy(mpc_task *t) { mpchost::destroy_handle(t); }
 
 int mpc_task_create(mpc_task **out, int n, const mpc_task_config *cfg) {
   if (!out || n <= 0 || !cfg) return fail(MPC_E_ARG, "mpc_task_create: bad argument");
-  if (!finite_all(&cfg->lin_vel_scale, 4) || !finite_all(cfg->rew_scale, MPC_TASK_REW_TERMS) || !finite_all(&cfg->command_range[0][0], 6) ||
-      !finite_all(cfg->default_dof_pos, 12))
+  const taskcfg::Fault bad = taskcfg::check(*cfg);
+  if (bad == taskcfg::kNotFinite || !taskcfg::finite_all(cfg->default_dof_pos, 12))
     return fail(MPC_E_ARG, "mpc_task_create: a scale, a command range or a default joint angle is not finite");
-  for (int a = 0; a < 3; ++a)
-    if (cfg->command_range[a][0] > cfg->command_range[a][1]) return fail(MPC_E_ARG, "mpc_task_create: command range with min > max");
+  if (bad == taskcfg::kRangeOrder) return fail(MPC_E_ARG, "mpc_task_create: command range with min > max");
   if (!(cfg->clip_observations > 0.0)) return fail(MPC_E_ARG, "mpc_task_create: clip_observations must be positive");
-  if (cfg->max_episode_length < 1) return fail(MPC_E_ARG, "mpc_task_create: max_episode_length must be at least 1");
-  Config c{};
-  c.lin_vel_scale = (float)cfg->lin_vel_scale; c.ang_vel_scale = (float)cfg->ang_vel_scale;
-  c.dof_pos_scale = (float)cfg->dof_pos_scale; c.dof_vel_scale = (float)cfg->dof_vel_scale;
-  for (int i = 0; i < kRewTerms; ++i) c.rew[i] = (float)cfg->rew_scale[i];
-  for (int a = 0; a < 3; ++a) { c.cmd_lo[a] = (float)cfg->command_range[a][0]; c.cmd_hi[a] = (float)cfg->command_range[a][1]; }
-  c.clip_obs = (float)cfg->clip_observations;
-  for (int i = 0; i < 12; ++i) c.default_dof_pos[i] = (float)cfg->default_dof_pos[i];
-  c.max_episode_length = cfg->max_episode_length;
-  c.seed = cfg->seed;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPC_E_NODEVICE, "mpc_task_create: no HIP device");
+  if (bad == taskcfg::kEpisodeLength) return fail(MPC_E_ARG, "mpc_task_create: max_episode_length must be at least 1");
+  const int device = mpchost::current_device();
+  if (device < 0) return fail(MPC_E_NODEVICE, "mpc_task_create: no HIP device");
   mpc_task *t = new mpc_task();
   t->n = n;
-  t->c = c;
-  if (hipGetDevice(&t->device) != hipSuccess) { delete t; return fail(MPC_E_NODEVICE, "mpc_task_create: no HIP device"); }
+  t->device = device;
+  t->c = taskcfg::to_device_config(*cfg);
   hipError_t e;
-  if ((e = hipMalloc(&t->d_episode, sizeof(int) * (size_t)n)) != hipSuccess || (e = hipMemset(t->d_episode, 0, sizeof(int) * (size_t)n)) != hipSuccess ||
-      (e = hipDeviceSynchronize()) != hipSuccess) {
+  if ((e = t->d_episode.alloc_zero((size_t)n)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
     mpc_task_destroy(t);
     return fail(MPC_E_HIP, std::string("mpc_task_create: ") + hipGetErrorString(e));
   }

@@ -6,6 +6,7 @@
 
 #include <cmath>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mpc_terrain.h"
@@ -137,21 +138,15 @@ int mpc_terrain_attach(mpc_sim *s, int rows, int cols, const short *h_heights, d
       org[i] = origin[i];
     }
   DeviceGuard guard_(s->device);
-  short *d_h = nullptr;
-  double *d_o = nullptr;
+  // both new arrays are built first: a failed attach leaves the terrain attached earlier in place (the temporaries free what they hold)
+  mpchost::DeviceArray<short> d_h;
+  mpchost::DeviceArray<double> d_o;
   hipError_t e;
-  if ((e = hipDeviceSynchronize()) != hipSuccess || (e = hipMalloc(&d_h, sizeof(short) * cells)) != hipSuccess ||
-      (e = hipMalloc(&d_o, sizeof(double) * org.size())) != hipSuccess ||
-      (e = hipMemcpy(d_h, h_heights, sizeof(short) * cells, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(d_o, org.data(), sizeof(double) * org.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-    if (d_h) (void)hipFree(d_h);
-    if (d_o) (void)hipFree(d_o);
+  if ((e = hipDeviceSynchronize()) != hipSuccess || (e = d_h.alloc_copy(h_heights, cells)) != hipSuccess ||
+      (e = d_o.alloc_copy(org.data(), org.size())) != hipSuccess)
     return fail(MPC_E_HIP, std::string("mpc_terrain_attach: ") + hipGetErrorString(e));
-  }
-  // (a terrain attached earlier is replaced; the device is idle after the synchronisation above)
-  if (s->d_heights) (void)hipFree(s->d_heights);
-  if (s->d_origin) (void)hipFree(s->d_origin);
-  s->d_heights = d_h; s->d_origin = d_o;
+  // (a terrain attached earlier is replaced and freed; the device is idle after the synchronisation above)
+  s->d_heights = std::move(d_h); s->d_origin = std::move(d_o);
   s->rows = rows; s->cols = cols;
   s->hscale = hscale; s->vscale = vscale; s->x0 = x0; s->y0 = y0;
   HIP_TRY(simint::terrain_launch_init(s, nullptr, s->n, nullptr));

@@ -106,27 +106,39 @@ MPC_HD Contacts contacts_from_forces(const float *cf, int base_index, const int 
 // the toy plant's `fell` flag taken as base contact; it has no knee or hip contacts
 MPC_HD Contacts contacts_from_fell(bool fell) { return Contacts{fell, false, 0}; }
 
-// compute_robot_reward: the reward, and through `reset` the next reset flag.  episode_length is progress_buf after begin_env.
-MPC_HD float reward_reset(const Config &c, const float *root, const float *commands, const float *torques, const Contacts &k, long long episode_length,
-                          bool &reset) {
+// The six products of compute_robot_reward (aliengo.py:381-397) in the order of the enum above, the reference's operations in the reference's order.
+// The terms are the unclipped products.  The reward itself is their sum clipped at 0, so the terms of a tick add up to less than the reward where
+// the clip bit.  (The per-term episode sums, episode_terms.h, accumulate these same values: they are this function's, not a restatement of it.)
+MPC_HD void reward_terms(const rltask::Config &c, const float *root, const float *commands, const float *torques, const rltask::Contacts &k,
+                         float *terms) {
+  using namespace rltask;
   float lin[3], ang[3];
   quat_rotate_inverse(root + 3, root + 7, lin);
   quat_rotate_inverse(root + 3, root + 10, ang);
   const float ex = commands[0] - lin[0], ey = commands[1] - lin[1], ez = commands[2] - ang[2];
   const float lin_vel_error = ex * ex + ey * ey;
   const float ang_vel_error = ez * ez;
-  const float rew_lin_vel_xy = expf(-lin_vel_error / 0.25f) * c.rew[kRewLinVelXY];
-  const float rew_ang_vel_z = expf(-ang_vel_error / 0.25f) * c.rew[kRewAngVelZ];
-  const float rew_lin_vel_z = (lin[2] * lin[2]) * c.rew[kRewLinVelZ];
-  const float rew_ang_vel_xy = (ang[0] * ang[0] + ang[1] * ang[1]) * c.rew[kRewAngVelXY];
-  const float rew_collision = (float)k.knees * c.rew[kRewCollision];
+  terms[kRewLinVelXY] = expf(-lin_vel_error / 0.25f) * c.rew[kRewLinVelXY];
+  terms[kRewAngVelZ] = expf(-ang_vel_error / 0.25f) * c.rew[kRewAngVelZ];
+  terms[kRewLinVelZ] = (lin[2] * lin[2]) * c.rew[kRewLinVelZ];
+  terms[kRewAngVelXY] = (ang[0] * ang[0] + ang[1] * ang[1]) * c.rew[kRewAngVelXY];
+  terms[kRewCollision] = (float)k.knees * c.rew[kRewCollision];
   float t2 = 0.0f;
 #pragma unroll
   for (int i = 0; i < 12; ++i) t2 = t2 + torques[i] * torques[i];
-  const float rew_torque = t2 * c.rew[kRewTorque];
-  const float total = ((((rew_lin_vel_xy + rew_lin_vel_z) + rew_ang_vel_xy) + rew_ang_vel_z) + rew_torque) + rew_collision;
+  terms[kRewTorque] = t2 * c.rew[kRewTorque];
+}
+
+// the reward from its terms: the left-to-right sum (aliengo.py:398), clipped at 0 (torch.clip(total_reward, 0., None))
+MPC_HD float reward_from_terms(const float *t) { return fmaxf(((((t[0] + t[1]) + t[2]) + t[3]) + t[4]) + t[5], 0.0f); }
+
+// compute_robot_reward: the reward, and through `reset` the next reset flag.  episode_length is progress_buf after begin_env.
+MPC_HD float reward_reset(const Config &c, const float *root, const float *commands, const float *torques, const Contacts &k, long long episode_length,
+                          bool &reset) {
+  float terms[kRewTerms];
+  reward_terms(c, root, commands, torques, k, terms);
   reset = k.base || k.knees > 0 || k.hip || episode_length > c.max_episode_length;
-  return fmaxf(total, 0.0f);          // torch.clip(total_reward, 0., None)
+  return reward_from_terms(terms);
 }
 
 // ---- command sampling -----------------------------------------------------------------------------------------------------------------

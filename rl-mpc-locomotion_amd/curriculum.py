@@ -58,7 +58,7 @@ def sim_origin_view(sim):
     ``TerrainCurriculum.update`` writes and the plant's next reset reads."""
     p = C.c_void_p()
     check_terrain(lib().mpc_terrain_origins(sim._handle, C.byref(p)), "mpc_terrain_origins")
-    return _device_view(p.value, (sim.n, 2), "<f8", sim.device)
+    return _lib.device_view(p.value, (sim.n, 2), "<f8", sim.device)
 
 
 class TerrainCurriculum:
@@ -72,7 +72,7 @@ class TerrainCurriculum:
         import torch
         need_gpu("TerrainCurriculum")
         self.grid, self.n, self.seed = grid, int(n), int(seed)
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         self.num_levels, self.num_types = int(grid.num_levels), int(grid.num_types)
         self.env_length = float(grid.env_length if env_length is None else env_length)
         self.episode_length_s = float(episode_length_s)
@@ -93,9 +93,9 @@ class TerrainCurriculum:
         self.origins0 = np.ascontiguousarray(self.tile_origins[self.levels0, self.types])
         p = C.c_void_p()
         check(lib().mpc_curriculum_levels(self._handle, C.byref(p)), "mpc_curriculum_levels")
-        self.levels = _device_view(p.value, (self.n,), "<i4", self.device)
+        self.levels = _lib.device_view(p.value, (self.n,), "<i4", self.device)
         check(lib().mpc_curriculum_counts(self._handle, C.byref(p)), "mpc_curriculum_counts")
-        self.counts = _device_view(p.value, (self.n,), "<i4", self.device)
+        self.counts = _lib.device_view(p.value, (self.n,), "<i4", self.device)
         self._summary = torch.zeros((2 + 2 * self.num_types,), dtype=torch.float64, device=self.device)
         self.sim = None
 
@@ -126,12 +126,3 @@ class TerrainCurriculum:
     def record(values, num_types):
         """``summary().tolist()`` as the two entries of a training record."""
         return {"mean_terrain_level": values[1], "terrain_level_by_type": list(values[2 + num_types:2 + 2 * num_types])}
-
-
-def _device_view(ptr, shape, typestr, device):
-    """A cuda tensor of ``shape`` over the device memory at ``ptr``; the memory is a handle's, so the view is valid while its owner lives."""
-    import torch
-
-    class _Array:
-        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
-    return torch.as_tensor(_Array(), device=device)

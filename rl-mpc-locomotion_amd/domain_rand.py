@@ -234,7 +234,7 @@ class DomainRand:
         if self._handle is None:
             import torch
             _lib.need_gpu("DomainRand")
-            self.device = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+            self.device = _lib.device_of(self.device)
             h = C.c_void_p()
             with torch.cuda.device(self.device):
                 check(lib().mpc_drand_create(C.byref(h), self.n, self.seed), "mpc_drand_create")

@@ -75,7 +75,7 @@ class EpisodeStats:
     def __init__(self, n, window=100, groups=None, num_groups=1, device=None, guard=0):
         need_gpu("EpisodeStats")
         self.n, self.window, self.num_groups = int(n), int(window), int(num_groups)
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         self._handle = C.c_void_p()
         check(lib().mpc_episode_create(C.byref(self._handle), self.n, self.window, self.num_groups), "mpc_episode_create")
         blocks, g = 1 + self.num_groups, int(guard)

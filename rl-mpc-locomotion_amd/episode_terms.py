@@ -27,7 +27,6 @@ from dataclasses import dataclass
 
 from . import _lib
 from ._lib import cd, ci, ll, pvp, text, vp
-from .curriculum import _device_view
 from .rl_task import REWARD_TERMS, TaskConfig
 
 NUM_TERMS = len(REWARD_TERMS)
@@ -101,7 +100,7 @@ class EpisodeTerms:
         lo0, hi0, every = command_curriculum.resolved(self.cfg) if command_curriculum is not None else (0.0, 0.0, 1)
         self.update_every = every
         _lib.need_gpu("EpisodeTerms")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         self.curriculum_enabled = True
         self.tick = 0                      # the last tick close_and_resample was given
         self.terms_buf = None
@@ -114,10 +113,10 @@ class EpisodeTerms:
                                                  0.0 if k is None else float(k.max_curriculum), every), "mpc_episode_terms_create")
         p = [C.c_void_p() for _ in range(4)]
         check(lib().mpc_episode_terms_arrays(self._handle, *(C.byref(x) for x in p)), "mpc_episode_terms_arrays")
-        self.sums = _device_view(p[0].value, (self.n, NUM_TERMS), "<f4", self.device)
-        self.ticks = _device_view(p[1].value, (self.n,), "<i4", self.device)
-        self.counts = _device_view(p[2].value, (self.n,), "<i4", self.device)
-        self.state = _device_view(p[3].value, (STATE_LEN,), "<f8", self.device)      # ranges, window accumulators, widenings
+        self.sums = _lib.device_view(p[0].value, (self.n, NUM_TERMS), "<f4", self.device)
+        self.ticks = _lib.device_view(p[1].value, (self.n,), "<i4", self.device)
+        self.counts = _lib.device_view(p[2].value, (self.n,), "<i4", self.device)
+        self.state = _lib.device_view(p[3].value, (STATE_LEN,), "<f8", self.device)      # ranges, window accumulators, widenings
         self.ranges = self.state[G_RANGES:G_RANGES + 6].view(3, 2)
         self._summary = torch.zeros((SUMMARY_LEN,), dtype=torch.float64, device=self.device)
 
@@ -145,11 +144,7 @@ class EpisodeTerms:
             _lib.tensor_arg(t, torch.float32, numel, name)
         if terms is not None:
             _lib.tensor_arg(terms, torch.float32, n * NUM_TERMS, "terms")
-        fell_ptr = None
-        if fell is not None:
-            if fell.dtype not in (torch.bool, torch.uint8) or not fell.is_cuda or not fell.is_contiguous() or fell.numel() != n:
-                raise ValueError(f"fell must be a contiguous cuda bool / uint8 tensor with {n} elements")
-            fell_ptr = fell.data_ptr()
+        fell_ptr = None if fell is None else _lib.flag_arg(fell, n, "fell").data_ptr()
         check(lib().mpc_episode_terms_accumulate(self._handle, root_states.data_ptr(), commands.data_ptr(), torques.data_ptr(), fell_ptr,
                                                  None if terms is None else terms.data_ptr(), _lib.stream(self.device)), "mpc_episode_terms_accumulate")
 

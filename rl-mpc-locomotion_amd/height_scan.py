@@ -72,7 +72,7 @@ class HeightScan:
         self.offset, self.clip, self.scale, self.obs_clip = float(offset), float(clip), float(scale), float(obs_clip)
         import torch
         need_gpu("HeightScan")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         self._handle = C.c_void_p()
         with torch.cuda.device(self.device):
             check(lib().mpc_hscan_create(C.byref(self._handle), self.n, self.num_points, self.points.ctypes.data, self.offset, self.clip, self.scale,

@@ -24,7 +24,7 @@ class BatchedLocomotion:
         RobotRunnerMin passes, int(27 / (1000 controller_dt)) (RobotRunnerMin.py:21-22: 2 at the reference's controller_dt = 0.01)."""
         import torch
         _lib.need_gpu("BatchedLocomotion")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         torch.cuda.set_device(self.device)
         rt = np.ascontiguousarray(robot_type, dtype=np.int32)
         gi = np.ascontiguousarray(gait_id, dtype=np.int32)

@@ -56,7 +56,7 @@ class ObsNormalizer:
         self.num_obs, self.eps, self.until = int(num_obs), float(eps), None if until is None else int(until)
         if self.until is not None and self.until < 0:
             raise ValueError("until must be None or a row count >= 0")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         self._handle = C.c_void_p()
         check(lib().mpc_obsnorm_create(C.byref(self._handle), self.num_obs, self.eps, -1 if self.until is None else self.until), "mpc_obsnorm_create")
         D, g = self.num_obs, int(guard)

@@ -151,7 +151,7 @@ class ActorCritic(nn.Module):
         if critic_obs is not None:
             need_gpu(what, critic_obs)
         la, lc = self._linears(self.actor), self._linears(self.critic)
-        params = [m.weight for m in la] + [m.bias for m in la] + [m.weight for m in lc] + [m.bias for m in lc] + [self.std]
+        params = self.bind_order()
         ptrs = tuple(p.data_ptr() for p in params)
         if self._handle is None:
             dims = lambda ls: [ls[0].in_features] + [m.out_features for m in ls]
@@ -513,7 +513,7 @@ class PPOTrainer:
         need_gpu("PPOTrainer")
         self.cfg = cfg if cfg is not None else PPOConfig()
         self.env, self.seed = env, int(seed)
-        self.device = torch.device(device if device is not None else getattr(env, "device", f"cuda:{torch.cuda.current_device()}"))
+        self.device = _lib.device_of(device if device is not None else getattr(env, "device", None))
         torch.manual_seed(self.seed)
         c = self.cfg
         self.num_privileged_obs = getattr(env, "num_privileged_obs", None)

@@ -72,10 +72,9 @@ class PrivilegedObs:
     ``assemble`` is the one launch per tick.  ``BatchedRLTask(privileged_obs=...)`` does both."""
 
     def __init__(self, n, device=None):
-        import torch
         self.n = int(n)
         need_gpu("PrivilegedObs")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         self._handle = C.c_void_p()
         check(lib().mpc_privobs_create(C.byref(self._handle), self.n), "mpc_privobs_create")
         self.sim = None

@@ -129,7 +129,7 @@ class TaskPostPhysics:
     def __init__(self, n, cfg=None, device=None):
         import torch
         _lib.need_gpu("TaskPostPhysics")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         torch.cuda.set_device(self.device)
         self.cfg = cfg if cfg is not None else TaskConfig()
         self.n = int(n)
@@ -176,11 +176,7 @@ class TaskPostPhysics:
             if len(knee) != 4 or len(hip) != 4:
                 raise ValueError("knee_indices and hip_indices: four body indices each")
             cf_ptr = contact_forces.data_ptr()
-        fell_ptr = None
-        if fell is not None:
-            if fell.dtype not in (torch.bool, torch.uint8) or not fell.is_cuda or not fell.is_contiguous() or fell.numel() != n:
-                raise ValueError(f"fell must be a contiguous cuda bool / uint8 tensor with {n} elements")
-            fell_ptr = fell.data_ptr()
+        fell_ptr = None if fell is None else _lib.flag_arg(fell, n, "fell").data_ptr()
         check(lib().mpc_task_finish(self._handle, root_states.data_ptr(), dof_state.data_ptr(), actions.data_ptr(), torques.data_ptr(), cf_ptr, bodies,
                                     int(base_index), None if knee is None else knee.ctypes.data, None if hip is None else hip.ctypes.data, fell_ptr,
                                     _lib.stream(self.device)), "mpc_task_finish")

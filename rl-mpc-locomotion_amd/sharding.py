@@ -65,7 +65,7 @@ class PeerExchange:
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         self.n_total, self.lo, self.n_local, self.width = int(n_total), int(lo), int(n_local), int(width)
         if (self.lo * self.width * 4) % 16:
             raise ValueError("PeerExchange: a rank's block must start on a 16-byte boundary of the batch (lo * width * 4 bytes)")

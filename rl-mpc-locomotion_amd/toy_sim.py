@@ -61,7 +61,7 @@ class BatchedToySim:
         if terrain is None and origin is not None:
             raise ValueError("origin needs a terrain")
         _lib.need_gpu("BatchedToySim")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         torch.cuda.set_device(self.device)
         rt = np.ascontiguousarray(robot_type, dtype=np.int32).reshape(-1)
         self.n = len(rt)

@@ -21,7 +21,7 @@ class WeightPolicy:
         obs_scales = (linearVelocityScale, angularVelocityScale, dofPositionScale, dofVelocityScale), cfg/task/*.yaml."""
         import torch
         _lib.need_gpu("WeightPolicy")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.device_of(device)
         torch.cuda.set_device(self.device)
         ws = [np.ascontiguousarray(w, dtype=np.float32) for w, _ in layers]
         bs = [np.ascontiguousarray(b, dtype=np.float32) for _, b in layers]

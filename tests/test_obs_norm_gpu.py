@@ -132,6 +132,22 @@ def test_wide_and_narrow_observations():
         norm(torch.zeros((4, 48), device=DEV), out=torch.zeros((5, 48), device=DEV))
 
 
+def test_the_workspace_grows_with_the_batch():
+    """64 rows, then 5 x 64, then 64 and 5 x 64 again on one normaliser: the second call needs 10 blocks of partials where the first left room for 2, so the
+    workspace is replaced by a larger one, which the later calls keep.  State and output against the model after every call."""
+    D = 48
+    small, large = ref.make_case(64, D, 6448), ref.make_case(5 * 64, D, 32048)
+    model = ref.Model(D)
+    norm = _guarded(D)
+    for t, x in enumerate((small[0], large[1], small[2], large[3])):
+        model.update(x)
+        y = norm(torch.tensor(x, device=DEV))
+        st = _state(norm)
+        ref.check_state(model.snapshot(), *st, f"call {t}, {x.shape[0]} rows")
+        ref.check_output(x, y.cpu().numpy(), st[3], st[5], f"call {t}, {x.shape[0]} rows", updated=model.count > 0)
+    _guards_intact(norm)
+
+
 def test_state_dict_round_trips():
     n, D = 65, 48
     ticks, _ = ref.reference(n, D, 100 * n + D)

@@ -361,6 +361,37 @@ def test_a_smaller_batch_on_a_used_handle_reads_no_stale_workspace(big_reference
     assert all(float(g.abs().max()) > 0 for g in a[0])
 
 
+def test_a_larger_batch_on_a_used_handle_gets_a_handle_for_its_rows(grads_reference):
+    """The 1040-row case on a PPO that has just run the 1-row case (rows > max_rows): the update handle is destroyed and created again for 1040 rows, its
+    workspace with it.  Gradients, terms and learning rate are bit-identical to those of a PPO whose first handle was made for 1040 rows, and the gradients
+    are within test_grads_match_float64_autograd's bound of float64 autograd."""
+    nets = "uneven"
+    cases = grads_reference(nets)
+    gap = max(ref.rel_l2(g32, g64) for case in cases.values() for (g64s, _, _), (g32s, _, _) in case for g32, g64 in zip(g32s, g64s))
+    one_ac, one_st, one_perm = _fixture(nets, "single")
+    ac, st, perm = _fixture(nets, "chunked")
+    assert all(torch.equal(a, b) for a, b in zip(ac.bind_order(), one_ac.bind_order()))         # the same nets with the same weights
+    rows = len(perm)
+    assert len(one_perm) == 1 and rows == 1040
+    dev, dst = _to_device(ac, st)
+    _, one_dst = _to_device(one_ac, one_st)
+    grown = P.PPO(dev, _cfg(nets, 1), backend="hip")
+    grown._device_state(1)
+    assert grown._max_rows == 1
+    _device_grads(grown, one_dst, one_perm, 1)
+    grown._device_state(rows)
+    assert grown._max_rows == rows                                                              # a new handle: the old one held one row
+    a = _device_grads(grown, dst, perm, rows)
+    fresh_dev, _ = _to_device(ac, st)
+    fresh = P.PPO(fresh_dev, _cfg(nets, 1), backend="hip")
+    fresh._device_state(rows)
+    b = _device_grads(fresh, dst, perm, rows)
+    assert all(torch.equal(x, y) for x, y in zip(a[0], b[0])) and torch.equal(a[1], b[1]) and a[2] == b[2]
+    g64s = cases["chunked"][0][0][0]
+    names = _names(ac)
+    _pooled([(names[k], ref.rel_l2(a[0][k], g64s[k]), gap) for k in range(len(names))], "a handle recreated for more rows: gradients")
+
+
 @pytest.fixture(scope="module")
 def apply_reference(grads_reference):
     cache = {}

@@ -96,6 +96,41 @@ def test_initial_state_and_reset():
     assert np.array_equal(sim.root_states[ids].cpu().numpy(), fresh["f64"][ids][:, :13].astype(np.float32))
 
 
+def test_a_second_attach_replaces_the_terrain():
+    """mpc_terrain_attach on a sim that has a terrain already: 64 robots on the 64 x 48 stance field, then a 4 x 4-node field with another grid step, other
+    offsets and other origins on the same handle.  The sim's two terrain arrays are replaced, every robot stands on the new field as the model's fresh
+    robot does, the surface query answers from the new field, and a reset after a few ticks returns to that state."""
+    import torch
+    from rl_mpc_locomotion_amd.toy_sim import check_terrain, lib
+    n = 64
+    first = TT.stance_test_field()
+    rt, yaw, origin = _population(n, first)
+    sim = _sim(rt, first, origin, yaw)
+    on_first = sim.get_state()
+    second = TR.Terrain(np.array([[0, 4, 8, 2], [6, 10, 3, 0], [1, 7, 12, 5], [9, 2, 4, 8]], np.int16), 1.0, 0.005, -1.5, -1.25)
+    origin2 = np.ascontiguousarray(np.stack([np.linspace(-1.4, 1.4, n), np.linspace(1.6, -1.1, n)], 1))
+    check_terrain(lib().mpc_terrain_attach(sim._handle, second.rows, second.cols, second.heights.ctypes.data, second.hscale, second.vscale, second.x0,
+                                           second.y0, origin2.ctypes.data), "mpc_terrain_attach")
+    fresh = sim.get_state()
+    for i in range(n):
+        m = TT.ToyTerrainRobot(ROBOT_TABLE64[rt[i]], second, origin2[i], yaw0=yaw[i])
+        assert m.ik_residual < 1e-12
+        rf, rk = to_record(m)
+        assert (fresh["i32"][i] == rk).all()
+        np.testing.assert_allclose(fresh["f64"][i], rf, rtol=0, atol=1e-12, err_msg=f"robot {i} type {rt[i]} origin {origin2[i]}")
+    assert (fresh["f64"] != on_first["f64"]).any(1).all()
+    pts = np.ascontiguousarray(np.stack([np.linspace(-2.0, 2.0, 70), np.linspace(2.2, -1.8, 70)], 1))          # inside the 3 m x 3 m field and past its edges
+    z, _ = sim.terrain_query(torch.from_numpy(pts).to(DEV), normals=False)
+    assert np.array_equal(z.cpu().numpy(), second.height(pts[:, 0], pts[:, 1]))
+    zero = torch.zeros((n, 12), dtype=torch.float32, device=DEV)
+    for _ in range(5):
+        sim.step(zero)
+    assert (sim.get_state()["f64"] != fresh["f64"]).any(1).all()
+    sim.reset_idx(torch.arange(n, dtype=torch.int32, device=DEV))
+    after = sim.get_state()
+    assert np.array_equal(after["f64"], fresh["f64"]) and np.array_equal(after["i32"], fresh["i32"])
+
+
 def test_one_step_consistency_in_a_device_closed_loop():
     n = 195                                            # 3 types x 65: four waves, the last with 3 lanes
     rng = np.random.default_rng(195)
