@@ -39,6 +39,14 @@ int mpc_privobs_bind(mpc_privobs *h, mpc_sim *s);
  * buffer.  MPC_E_ARG otherwise, for an inv_len that is not finite, or without a bound sim. */
 int mpc_privobs_run(mpc_privobs *h, const float *d_obs, int obs_width, int P, const long long *d_progress, double inv_len, float *d_out,
                     void *stream);
+/* The row with the plant's per-robot record (mpc_plant_rand.h): three more columns after the phase -- (float)payload, (float)(strength - 1.0),
+ * (float)(grav_z + 9.81), each one float64 subtraction (none for the first) and one conversion -- and a width of 16 * ceil((48 + P + 5 + 3) / 16).
+ * mpc_privobs_bind_plant keeps the device address of s's plant record: after mpc_privobs_bind of the same sim, and MPC_E_ARG for a sim that
+ * has none.  mpc_privobs_run_plant is mpc_privobs_run on that row: d_out [n][mpc_privobs_width_plant(P)]; MPC_E_ARG without a bound record. */
+int mpc_privobs_width_plant(int P);
+int mpc_privobs_bind_plant(mpc_privobs *h, mpc_sim *s);
+int mpc_privobs_run_plant(mpc_privobs *h, const float *d_obs, int obs_width, int P, const long long *d_progress, double inv_len, float *d_out,
+                          void *stream);
 const char *mpc_privobs_last_error(void);
 
 #ifdef __cplusplus

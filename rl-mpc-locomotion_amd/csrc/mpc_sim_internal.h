@@ -1,7 +1,8 @@
-// mpc_sim_internal.h -- what the library's other units may know of an mpc_sim (include/mpc_sim.h): its device buffers and, once
-// mpc_terrain_attach (include/mpc_terrain.h) has run, its height field.  mpc_sim.hip owns the handle and the plane kernels; mpc_terrain.hip
-// holds the height-field instantiations of toy_sim.h and is what mpc_sim_step / mpc_sim_reset_device launch for a sim with a terrain
-// (a host-side branch on the handle).  Not part of the C ABI.
+// mpc_sim_internal.h -- what the library's other units may know of an mpc_sim (include/mpc_sim.h): its device buffers, once
+// mpc_terrain_attach (include/mpc_terrain.h) has run its height field, and once mpc_plant_rand_attach (mpc_plant_rand.h) has run its per-robot
+// plant record.  mpc_sim.hip owns the handle and the plane kernels; mpc_terrain.hip holds the height-field instantiations of toy_sim.h and is
+// what mpc_sim_step / mpc_sim_reset_device launch for a sim with a terrain; mpc_plant_rand.hip holds the instantiations of toy_step_plant on both
+// grounds and is what mpc_sim_step launches for a sim with a plant record (host-side branches on the handle).  Not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +22,9 @@ struct mpc_sim {
   mpchost::DeviceArray<double> d_origin;               // [n][2]
   int rows = 0, cols = 0;
   double hscale = 0.0, vscale = 0.0, x0 = 0.0, y0 = 0.0;
+  // the per-robot plant record (null until mpc_plant_rand_attach): [kPlant][n], entry j of robot r at [j * n + r], like the state:
+  // 0 payload [kg], 1 strength [factor], 2 grav_z [m/s^2, absolute]; neutral (0.0, 1.0, kGravZ)
+  mpchost::DeviceArray<double> d_plant;
 };
 
 namespace simint {
@@ -32,5 +36,7 @@ inline dim3 sim_grid(int k) { return dim3((unsigned)((k + kSimThreads - 1) / kSi
 // the terrain instantiations' launches (mpc_terrain.hip); the caller has set the device.  ids null = all n robots.
 hipError_t terrain_launch_init(mpc_sim *s, const int *d_ids, int k, hipStream_t stream);
 hipError_t terrain_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream);
+// the step of a sim with a plant record, on its plane or on its terrain (mpc_plant_rand.hip); the caller has set the device
+hipError_t plant_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream);
 
 }  // namespace simint

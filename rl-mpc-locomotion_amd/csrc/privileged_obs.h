@@ -9,6 +9,10 @@
 //                              (a multiply, not a divide: the same bits whatever the build does with divisions)
 //   zeros                      up to width(P) = 16 * ceil((48 + P + 5) / 16)
 //
+// With the plant's per-robot record (mpc_plant_rand.h: payload, strength, grav_z as float64 [3][n]) three columns follow the phase:
+//   (float)payload    (float)(strength - 1.0)    (float)(grav_z - kGravZ)          one float64 subtraction (none for the first), one conversion
+// and the zeros run up to width_plant(P) = 16 * ceil((48 + P + 5 + 3) / 16).
+//
 // The first 48 + P columns are copies and the rest are conversions and one correctly rounded product, so the row is restated bit for bit in numpy
 // (tests/privileged_obs_ref.py).
 #pragma once
@@ -25,6 +29,8 @@ constexpr int kTaskObs = 48;           // rl_task.h's observation row
 constexpr int kContacts = 4;           // FL FR RL RR
 constexpr int kExtra = kContacts + 1;  // the contacts and the phase
 constexpr int kMaxScan = 208;          // MPC_HSCAN_MAX_POINTS
+constexpr int kPlantCols = 3;          // payload, strength - 1, grav_z - kGravZ
+constexpr double kGravZ = -9.81;       // toy_sim.h's
 
 PRIVOBS_HD inline int width(int P) { return 16 * ((kTaskObs + P + kExtra + 15) / 16); }
 
@@ -37,6 +43,22 @@ PRIVOBS_HD inline float tail_column(int col, int live, const int *contact, int n
   const int k = col - live;
   if (k < kContacts) return contact_flag(contact[(long)k * n + r]);
   if (k == kContacts) return phase(progress, inv_len);
+  return 0.0f;                         // the pad
+}
+
+PRIVOBS_HD inline int width_plant(int P) { return 16 * ((kTaskObs + P + kExtra + kPlantCols + 15) / 16); }
+
+// Plant column j of environment r: `plant` is the sim's float64 record [3][n] (entry j of robot r at plant[j * n + r])
+PRIVOBS_HD inline float plant_column(int j, const double *plant, int n, int r) {
+  const double v = plant[(long)j * n + r];
+  return j == 0 ? (float)v : (j == 1 ? (float)(v - 1.0) : (float)(v - kGravZ));
+}
+
+// tail_column for a row with the plant columns
+PRIVOBS_HD inline float tail_column_plant(int col, int live, const int *contact, const double *plant, int n, int r, long long progress, float inv_len) {
+  const int k = col - live;
+  if (k < kExtra) return tail_column(col, live, contact, n, r, progress, inv_len);
+  if (k < kExtra + kPlantCols) return plant_column(k - kExtra, plant, n, r);
   return 0.0f;                         // the pad
 }
 

@@ -11,6 +11,12 @@
 // in two roles: its height (initial stance, touch-down test and crossing, the anchor's z, the fall test under the base) and its normal for the
 // lift-off test f . n, taken under the leg's anchor.  The (..., gx, gy) signatures are wrappers over Plane.
 //
+// A robot may carry a plant record of its own (kPlant doubles: payload [kg], motor strength [factor], gravity z [m/s^2, absolute]; neutral
+// (0, 1, kGravZ)): toy_step_plant steps with mass + payload, every torque times the strength (stance force and swing-joint acceleration both see
+// the scaled torque) and that gravity.  The inertia is NOT changed by the payload: Isaac Gym's added base mass (legged_gym's randomize_base_mass)
+// changes the body's mass property and leaves its inertia alone as well.  With the neutral record mass + 0.0, tau * 1.0 and kGravZ are exact, so
+// toy_step_plant reproduces toy_step bit for bit.
+//
 // toy_init / toy_step restate ToyRobot.__init__ / ToyRobot.step of the numpy model operation for operation in float64 (same order of the
 // sums, legs 0..3, +0.0 start; 4 IK iterations per substep, 20 at initialisation; 3 x 3 systems solved as LAPACK's dgesv does: partial
 // pivoting, multipliers a * (1 / pivot), forward then backward substitution).  Compile with -ffp-contract=off: no fused multiply-adds.
@@ -42,6 +48,9 @@ constexpr int kColAbad = 0, kColHip = 1, kColKnee = 2, kColHiploc = 3, kColMass 
 // per-robot state record of mpc_sim_get_state / mpc_sim_set_state (include/mpc_sim.h)
 constexpr int kF64 = 49;               // pos3 quat4 (xyzw) v3 w3 q12 qd12 anchor12
 constexpr int kI32 = 9;                // contact4 lift4 fell
+// per-robot plant record (mpc_sim's d_plant, csrc/mpc_plant_rand.h): payload, strength, grav_z
+constexpr int kPlant = 3;
+constexpr int kPlantPayload = 0, kPlantStrength = 1, kPlantGravZ = 2;
 constexpr int kOffPos = 0, kOffQuat = 3, kOffV = 7, kOffW = 10, kOffQ = 13, kOffQd = 25, kOffAnchor = 37;
 
 struct Params {
@@ -307,9 +316,9 @@ MPC_HD void toy_init(State &s, const Params &P, double yaw0, const Ground &g) {
 
 MPC_HD void toy_init(State &s, const Params &P, double yaw0, double gx, double gy) { toy_init(s, P, yaw0, Plane{gx, gy}); }
 
-// ToyRobot.step(tau, dt) on ground g: one tick of kSubsteps substeps
+// ToyRobot.step(tau, dt) on ground g under gravity (0, 0, grav_z): one tick of kSubsteps substeps
 template <class Ground>
-MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, const Ground &g) {
+MPC_HD void toy_step_gravity(State &s, const Params &P, const double *tau, double dt, const Ground &g, double grav_z) {
   const double h = dt / kSubsteps;
   double n[3];
   if constexpr (Ground::kUniformNormal) g.normal(s.pos, n);
@@ -364,7 +373,7 @@ MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, co
       for (int j = 0; j < 3; ++j) Iw[i][j] = RD[i][0] * R[j][0] + RD[i][1] * R[j][1] + RD[i][2] * R[j][2];
     s.v[0] = s.v[0] + h * (0.0 + F[0] / P.mass);
     s.v[1] = s.v[1] + h * (0.0 + F[1] / P.mass);
-    s.v[2] = s.v[2] + h * (kGravZ + F[2] / P.mass);
+    s.v[2] = s.v[2] + h * (grav_z + F[2] / P.mass);
     double Iww[3], gyro[3], rhs[3];
     mat_vec(Iw, s.w, Iww);
     cross(s.w, Iww, gyro);
@@ -452,7 +461,22 @@ MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, co
   if (!finite || R[2][2] < 0.3 || fabs(s.pos[2] - g.height(s.pos)) > 3 * P.height) s.fell = 1;
 }
 
+// ... under the constant kGravZ: the plant every robot of a type shares
+template <class Ground>
+MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, const Ground &g) { toy_step_gravity(s, P, tau, dt, g, kGravZ); }
+
 MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, double gx, double gy) { toy_step(s, P, tau, dt, Plane{gx, gy}); }
+
+// ... with the robot's own plant record: mass + payload, tau * strength, its own gravity (see the head of this file)
+template <class Ground>
+MPC_HD void toy_step_plant(State &s, const Params &P, const double *tau, double dt, const Ground &g, double payload, double strength, double grav_z) {
+  Params Q = P;
+  Q.mass = P.mass + payload;
+  double t[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) t[i] = tau[i] * strength;
+  toy_step_gravity(s, Q, t, dt, g, grav_z);
+}
 
 // the state record of include/mpc_sim.h: f64[kF64], i32[kI32]; `stride` = distance between two consecutive entries of ONE robot
 // (1 on the host; the batch size on the device, whose state is structure-of-arrays)

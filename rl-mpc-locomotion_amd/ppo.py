@@ -659,7 +659,9 @@ class PPOTrainer:
         normalisation on it also carries ``obs_norm_state_dict`` (rsl_rl 2.x's key), and the actor expects normalised observations:
         ``obs_norm.fold_normalizer(ck["model_state_dict"], ck["obs_norm_state_dict"])`` gives the state dict for raw ones.  With privileged observations as well it carries ``critic_obs_norm_state_dict``, the statistics of the critic's
         rows (``fold_normalizer(..., critic_obs_norm_state_dict=)``); ``load`` refuses a checkpoint whose critic reads rows of another width.  On an environment with
-        ``episode_terms`` it carries ``episode_terms_state_dict`` (the x command range, the widenings, the tick), which ``load`` restores when present."""
+        ``episode_terms`` it carries ``episode_terms_state_dict`` (the x command range, the widenings, the tick), which ``load`` restores when present.
+        On an environment with ``plant_rand`` it carries ``plant_rand_state_dict`` (every robot's plant record and draw counter), which ``load``
+        restores when present; a checkpoint without it leaves the record as the task made it."""
         ck = {"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(), "iter": self.iteration,
               "infos": self.infos}
         if self.obs_norm is not None:
@@ -669,6 +671,9 @@ class PPOTrainer:
         terms = getattr(self.env, "episode_terms", None)
         if terms is not None:                                                    # the command range the policy was trained up to
             ck["episode_terms_state_dict"] = terms.state_dict()
+        plant = getattr(self.env, "plant_rand", None)
+        if plant is not None:                                                    # the plants the rollouts continue on
+            ck["plant_rand_state_dict"] = plant.state_dict()
         torch.save(ck, path)
 
     def load(self, path, load_optimizer=True):
@@ -691,6 +696,9 @@ class PPOTrainer:
             terms.load_state_dict(ck["episode_terms_state_dict"])
             if hasattr(self.env, "common_step_counter"):
                 self.env.common_step_counter = terms.tick
+        plant = getattr(self.env, "plant_rand", None)
+        if plant is not None and "plant_rand_state_dict" in ck:
+            plant.load_state_dict(ck["plant_rand_state_dict"])
         self.actor_critic.load_state_dict(ck["model_state_dict"])      # (in place: the kernels keep reading the same addresses)
         if load_optimizer:
             self.alg.optimizer.load_state_dict(ck["optimizer_state_dict"])

@@ -198,18 +198,27 @@ class BatchedRLTask:
     ``privileged_obs`` (a ``privileged_obs.PrivilegedObs`` for as many environments): one more launch per tick, after the height scan and BEFORE the
     observation noise, writes ``privileged_obs_buf`` [N, ``num_privileged_obs``] -- the noise-free row, the foot contacts, the episode phase, a zero
     pad -- which ``get_privileged_observations()`` returns; without it the three are None, as in rsl_rl.
+    ``plant_rand`` (a ``plant_rand.PlantRand`` for as many environments): the sim gets a per-robot plant record (payload, motor strength, gravity)
+    that its step consumes; with ``resample="once"`` every record is drawn when the task is built, with ``"reset"`` the environments being reset
+    draw theirs inside the ``resets`` stage, before ``sim.reset_idx`` (the first tick resets, and so draws, every environment).  A
+    ``PrivilegedObs(n, plant=True)`` shows the record to the critic and needs ``plant_rand``.
     See the module text for what the toy cannot do."""
 
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
-                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, **bridge_args):
+                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, plant_rand=None, **bridge_args):
         import torch
         n_envs = len(np.asarray(robot_type).reshape(-1))
         cfg = cfg if cfg is not None else TaskConfig()
         # everything that can be refused is refused here, before the device is touched: one pass over the options, the first fault raises
-        for unit, holds in ((privileged_obs, "the privileged observations hold"), (episode_terms, "the episode terms hold"), (domain_rand, None),
-                            (height_scan, "the height scan holds"), (curriculum, "the curriculum holds")):
+        for unit, holds in ((plant_rand, None), (privileged_obs, "the privileged observations hold"), (episode_terms, "the episode terms hold"),
+                            (domain_rand, None), (height_scan, "the height scan holds"), (curriculum, "the curriculum holds")):
             if unit is None:
                 continue
+            if unit is plant_rand:         # counts its environments itself, with its payload against the masses of the robot types in use
+                unit.validate(n=n_envs, robot_type=robot_type)
+                continue
+            if unit is privileged_obs and getattr(unit, "plant", False) and plant_rand is None:
+                raise ValueError("privileged_obs has plant=True: the plant columns need plant_rand=")
             if unit is domain_rand:        # counts its environments itself, with its specs against the row's width and its push against the tick
                 unit.validate(n=n_envs, num_obs=NUM_OBS if height_scan is None else height_scan.width(NUM_OBS), dt=cfg.dt)
                 continue
@@ -251,14 +260,22 @@ class BatchedRLTask:
         if domain_rand is not None:
             domain_rand.bind(self.sim, dt=self.cfg.dt)
             self.num_active_obs = NUM_OBS + (height_scan.num_points if height_scan is not None else 0)      # what is not the scan's zero pad
+        self.plant_rand = plant_rand
+        if plant_rand is not None:         # before the privileged row binds the record
+            plant_rand.bind(self.sim)
+            if plant_rand.spec.resample == "once":
+                plant_rand.draw()
         self.episode_terms = episode_terms
         self.privileged_obs, self.privileged_obs_buf, self.num_privileged_obs = privileged_obs, None, None
         if privileged_obs is not None:
             from .privileged_obs import inverse_length, privileged_width
             privileged_obs.bind(self.sim)
+            with_plant = getattr(privileged_obs, "plant", False)
+            if with_plant:
+                privileged_obs.bind_plant(self.sim)
             self._num_scan = height_scan.num_points if height_scan is not None else 0
             self._inv_len = inverse_length(self.cfg.max_episode_length)
-            self.num_privileged_obs = privileged_width(self._num_scan)
+            self.num_privileged_obs = privileged_width(self._num_scan, with_plant)
             self.privileged_obs_buf = torch.zeros((self.n, self.num_privileged_obs), dtype=torch.float32, device=self.device)
         self.common_step_counter = 0       # the ticks this task has stepped, counted on the host: the command curriculum's clock
 
@@ -274,7 +291,7 @@ class BatchedRLTask:
             terrain_curriculum  ``curriculum.update``                      only with a curriculum
             begin               ``task.begin``
             episode_close       ``episode_terms.close_and_resample``       only with episode_terms
-            resets              ``ctl.reset``, ``sim.reset_idx``, ``sim.flags``
+            resets              ``ctl.reset``, ``sim.reset_idx``, ``sim.flags``; with a PlantRand that resamples at reset ``plant_rand.draw`` first
             finish              ``task.finish``
             episode_accumulate  ``episode_terms.accumulate``               only with episode_terms
             height_scan         ``height_scan.measure``                    only with a height scan
@@ -318,6 +335,8 @@ class BatchedRLTask:
             et.close_and_resample(ids, self.commands, self.common_step_counter)
             if mark is not None:
                 mark("episode_close")
+        if self.plant_rand is not None and self.plant_rand.spec.resample == "reset":      # the new episode's plant, before the robot is put back
+            self.plant_rand.draw(ids)
         self.bridge.ctl.reset(ids)                                                                                              # aliengo.py:330-334
         sim.reset_idx(ids)                                                                                                      # aliengo.py:336-342
         _, fell = sim.flags()              # after the reset: a robot that has just been put back standing is not flagged a second time

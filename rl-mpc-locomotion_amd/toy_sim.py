@@ -65,6 +65,7 @@ class BatchedToySim:
         torch.cuda.set_device(self.device)
         rt = np.ascontiguousarray(robot_type, dtype=np.int32).reshape(-1)
         self.n = len(rt)
+        self.robot_type = rt
         sl = None if slope is None else np.ascontiguousarray(np.broadcast_to(np.asarray(slope, dtype=np.float64), (self.n, 2)))
         yw = None if yaw0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(yaw0, dtype=np.float64), (self.n,)))
         tab = np.ascontiguousarray(ROBOT_TABLE64, dtype=np.float64)

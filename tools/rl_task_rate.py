@@ -31,6 +31,11 @@ or with --heights on the terrain grid (240 and 240): the assembly kernel beside 
 with the option against the same task without it.  --baseline times only the task without the option and passes no `mark` (it runs on a tree that
 has neither, for a measurement of a parent commit in the same session).
     python tools/rl_task_rate.py --privileged [--heights] [--baseline] [--out results/privileged_step.json]
+--plant-rand: the per-robot plant record (rl_mpc_locomotion_amd.plant_rand) with ranges on all three axes, on the flat plane: the step with the
+option against the same task without it, and the `controller`, `plant` (the parametrised step kernel against the plain one) and `resets` (which
+holds the draw) stages of both, from events, the tasks alternating; a third task carries a record that stays neutral, which separates the kernel's
+cost from that of robots that differ.  With --privileged all of them assemble the critic's row, with the plant columns where there is a record.
+    python tools/rl_task_rate.py --plant-rand [--privileged] [--out profiles/plant_rand_rate.json]
 The kernel-trace stats of the same step: rocprofv3 --kernel-trace --stats ... -- python tools/rl_task_rate.py --ticks 50 --quick"""
 import argparse
 import os
@@ -49,6 +54,8 @@ from rl_mpc_locomotion_amd.rl_task import REWARD_TERMS, BatchedRLTask, TaskConfi
 TROT = 0
 # the closed-loop golden's trot command (0.5 m/s ahead) as a one-point command range; zero actions are its MPC weights (5 5 5 50 50 50 1 ...)
 CFG = dict(command_x_range=(0.5, 0.5), command_y_range=(0.0, 0.0), command_yaw_range=(0.0, 0.0))
+# --plant-rand: legged_gym's added_mass_range and the usual motor-strength and gravity ranges, all three axes
+PLANT_RANGES = dict(payload=(-1.0, 3.0), strength=(0.9, 1.1), gravity=(-1.0, 1.0))
 
 
 def make(n, dev, cfg=None, **options):
@@ -360,6 +367,46 @@ def privileged_report(args, dev, n, actions):
     return res
 
 
+def plant_rand_report(args, dev, n, actions):
+    """The step, and its controller, plant and resets stages, with and without the per-robot plant record: whole ticks in alternating blocks, then the
+    stages from events, the tasks alternating round by round.  A third task carries the record and never randomises it (no ranges: every draw writes
+    the neutral values): it runs the parametrised kernel and the draw on robots that stay alike, which separates what the kernel costs from what
+    robots that differ cost (lanes of a wave that disagree on a foot's contact run both branches, and the solver's iteration counts differ).
+    --privileged: all three assemble the critic's row, the first two with the plant columns."""
+    from rl_mpc_locomotion_amd.plant_rand import PlantRand, PlantSpec
+    cfg = TaskConfig(**CFG)
+    res = header(args, n, privileged=bool(args.privileged), ranges=PLANT_RANGES)
+
+    def make_task(spec):
+        opts = {}
+        if spec is not None:
+            opts["plant_rand"] = PlantRand(n, spec, seed=0, device=dev)
+        if args.privileged:
+            from rl_mpc_locomotion_amd.privileged_obs import PrivilegedObs
+            opts["privileged_obs"] = PrivilegedObs(n, device=dev, plant=spec is not None)
+        return make(n, dev, cfg, **opts)
+    loops = {"step_with_plant_rand": make_task(PlantSpec(**PLANT_RANGES)), "step_with_neutral_record": make_task(PlantSpec()), "step_without": make_task(None)}
+    blocks(res, args, actions, loops)
+    without = res["step_without"]["ms_per_tick_median"]
+    res["over_step_without_ms_per_tick"] = {k: res[k]["ms_per_tick_median"] / without for k in loops}
+    names = ("controller", "plant", "resets") + (("privileged_obs",) if args.privileged else ())
+    parts = {k: {s: [] for s in names} for k in loops}
+    for _ in range(args.blocks):
+        for k, task in loops.items():
+            got = stage_times(task, actions, max(args.ticks // 2, 1))
+            for s in names:
+                parts[k][s] += list(got[s])
+    res["stages"] = {k: {s: {**spread(v), "events": len(v)} for s, v in d.items()} for k, d in parts.items()}
+    res["over_without_stage_median"] = {k: {s: med(parts[k][s]) / med(parts["step_without"][s]) for s in names} for k in loops}
+    task = loops["step_with_plant_rand"]
+    rec = task.plant_rand.get_params()
+    res["after_timing"] = {"fallen_fraction": fallen(loops), "draw_launches": task.plant_rand.launches,
+                           "draws_per_environment_mean": float(task.plant_rand.get_counters().mean()), "record_min": rec.min(0).tolist(), "record_max": rec.max(0).tolist(),
+                           "neutral_record_stayed_neutral": bool((loops["step_with_neutral_record"].plant_rand.get_params() == np.array([0.0, 1.0, -9.81])).all())}
+    clock(res, "after")
+    return res
+
+
 def default_report(args, dev, n, actions):
     res = header(args, n)
     step, half, bare = make(n, dev), make(n, dev), Bare(n, dev)
@@ -405,17 +452,18 @@ if __name__ == "__main__":
     ap.add_argument("--episode-s", type=float, default=20.0, help="--terms: the episode length of the timed tasks, in seconds")
     ap.add_argument("--privileged", action="store_true", help="time the privileged row's assembly kernel and the step with and without it; with or without --heights")
     ap.add_argument("--baseline", action="store_true", help="--privileged: only the task without the option (runs on a tree without the unit)")
+    ap.add_argument("--plant-rand", action="store_true", help="time the step and its plant and resets stages with and without the per-robot plant record; with --privileged both tasks assemble the critic's row, one with the plant columns")
     ap.add_argument("--out")
     args = ap.parse_args()
     dev, n = "cuda:0", args.robots
     actions = torch.zeros((n, 12), dtype=torch.float32, device=dev)
-    if args.quick and not (args.privileged or args.terms or args.domain_rand or args.heights or args.curriculum):
+    if args.quick and not (args.plant_rand or args.privileged or args.terms or args.domain_rand or args.heights or args.curriculum):
         task = make(n, dev)
         task.reset()
         for _ in range(args.ticks):
             task.step(actions)
         torch.cuda.synchronize()
         sys.exit(0)
-    report = (privileged_report if args.privileged else terms_report if args.terms else domain_rand_report if args.domain_rand else heights_report if args.heights
+    report = (plant_rand_report if args.plant_rand else privileged_report if args.privileged else terms_report if args.terms else domain_rand_report if args.domain_rand else heights_report if args.heights
               else curriculum_report if args.curriculum else default_report)
     emit(report(args, dev, n, actions), args.out)
