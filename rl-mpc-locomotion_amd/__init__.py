@@ -15,8 +15,9 @@ _DOMAIN_RAND = ("DomainRand", "NoiseSpec", "PushSpec")
 _EPISODE_TERMS = ("EpisodeTerms", "CommandCurriculumSpec")
 _PRIVILEGED_OBS = ("PrivilegedObs",)
 _PLANT_RAND = ("PlantRand", "PlantSpec")
+_RECURRENT = ("ActorCriticRecurrent", "Memory", "RecurrentConfig")
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS, "privileged_obs", *_PRIVILEGED_OBS, "plant_rand", *_PLANT_RAND]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS, "privileged_obs", *_PRIVILEGED_OBS, "plant_rand", *_PLANT_RAND, "recurrent", *_RECURRENT]
 
 
 def __getattr__(name):
@@ -48,4 +49,7 @@ def __getattr__(name):
     if name in _PLANT_RAND:
         from . import plant_rand
         return getattr(plant_rand, name)
+    if name in _RECURRENT:
+        from . import recurrent
+        return getattr(recurrent, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -24,7 +24,10 @@ with ``Normal.sample`` is in distribution only, and |eps| <= 5.768 (ppo_rollout.
 ``EmpiricalNormalization``) is opt-in: ``PPOTrainer(..., normalize_obs=True)`` puts ``obs_norm.ObsNormalizer`` between the environment and everything
 that reads an observation.  Privileged critic observations (rsl_rl's ``num_critic_obs`` / ``privileged_observations``; the reference uses none) are opt-in too: an
 environment with ``num_privileged_obs`` (``BatchedRLTask(privileged_obs=...)``) gets an asymmetric actor-critic whose critic reads ``env.privileged_obs_buf``,
-in the collection (``mpc_ac_act_asymmetric``), the storage and both update backends.  Not built: recurrent policies, logging beyond ``infos``.  The runner's episode statistics (mean return and
+in the collection (``mpc_ac_act_asymmetric``), the storage and both update backends.  Recurrent policies (rsl_rl's ``ActorCriticRecurrent``: an LSTM in front of
+each MLP) are opt-in as well: ``PPOTrainer(..., recurrent=RecurrentConfig(...))`` (``recurrent.py``) steps the memories on the device, keeps the state each slot started
+from in the storage, and the torch update back-propagates through time over trajectories cut at the episode ends; the hip update refuses them.  Not built: GRU and
+stacked layers, the device update through time, logging beyond ``infos``.  The runner's episode statistics (mean return and
 length over the last 100 finished episodes) are kept on the device by ``episode.EpisodeStats``; ``PPOTrainer.evaluate`` is the reference's ``cfg.test`` loop.
 
 The device entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
@@ -237,19 +240,28 @@ class RolloutStorage:
     ``sigma`` [T,N,12], ``values``, ``rewards``, ``dones``, ``actions_log_prob``, ``returns``, ``advantages`` [T,N,1].  ``ActorCritic.act``
     writes into ``slot(t)``; ``add`` and ``compute_returns`` are device kernels (a storage on the CPU can be filled by hand and read by
     ``PPO.update``, which is plain torch).  ``num_privileged_obs`` (rsl_rl's; None: no such tensor): ``privileged_observations`` [T,N,Wp], the
-    critic's rows, which the mini-batch generator then yields last."""
+    critic's rows, which the mini-batch generator then yields last.  ``hidden`` = (H_a, H_c) (None: no such tensors): ``saved_h_a``, ``saved_c_a``
+    [T,N,H_a] and ``saved_h_c``, ``saved_c_c`` [T,N,H_c], the state each memory of a recurrent actor-critic started slot t from (written by the cell
+    launch through ``hidden_slot(t)``), which ``recurrent_mini_batch_generator`` reads."""
 
-    def __init__(self, n, T, device, num_obs=48, num_actions=NUM_ACTIONS, num_privileged_obs=None):
+    def __init__(self, n, T, device, num_obs=48, num_actions=NUM_ACTIONS, num_privileged_obs=None, hidden=None):
         self.n, self.T, self.device = int(n), int(T), torch.device(device)
         z = lambda k: torch.zeros((self.T, self.n, k), dtype=torch.float32, device=self.device)
         self.observations, self.actions, self.mu, self.sigma = z(num_obs), z(num_actions), z(num_actions), z(num_actions)
         self.values, self.rewards, self.dones, self.actions_log_prob, self.returns, self.advantages = z(1), z(1), z(1), z(1), z(1), z(1)
         self.privileged_observations = None if num_privileged_obs is None else z(int(num_privileged_obs))
+        self.hidden = None if hidden is None else (int(hidden[0]), int(hidden[1]))
+        if self.hidden is not None:
+            self.saved_h_a, self.saved_c_a, self.saved_h_c, self.saved_c_c = z(self.hidden[0]), z(self.hidden[0]), z(self.hidden[1]), z(self.hidden[1])
         self.step = 0
 
     def slot(self, t):
         """The views of slot t that ``ActorCritic.act(..., out=)`` writes."""
         return dict(actions=self.actions[t], actions_log_prob=self.actions_log_prob[t], values=self.values[t], mu=self.mu[t], sigma=self.sigma[t])
+
+    def hidden_slot(self, t):
+        """The views of slot t that ``ActorCriticRecurrent.act(..., saved=)`` writes: the state the memories started the slot from."""
+        return dict(h_a=self.saved_h_a[t], c_a=self.saved_c_a[t], h_c=self.saved_h_c[t], c_c=self.saved_c_c[t])
 
     def add(self, rew, reset, time_outs, gamma, obs=None):
         """``PPO.process_env_step`` + ``add_transitions`` for the slot ``act`` has just written (``self.step``, then advanced): rewards[t] = rew +
@@ -290,6 +302,31 @@ class RolloutStorage:
                 b = idx[i * size:(i + 1) * size]
                 yield tuple(x[b] for x in flat)
 
+    def recurrent_mini_batch_generator(self, num_mini_batches, num_epochs=8):
+        """rsl_rl's: mini-batches are contiguous blocks of N // num_mini_batches environments, taken in order, the same in every epoch, each with
+        all the trajectories of its environments.  Yields ``RecurrentBatch``: the padded observations [T][n_traj][num_obs] (and the padded critic rows, or
+        None), the masks [T][n_traj], the [T][block] slices of actions, values, advantages, returns, old log-prob, old mu and old sigma, and for each
+        memory (h0, c0) [1][n_traj][H]: the saved state at each trajectory's first step (t = 0, or the step after a done)."""
+        from .recurrent import RecurrentBatch, pad_trajectories, trajectory_masks
+        if self.hidden is None:
+            raise ValueError("the storage keeps no hidden states (RolloutStorage(hidden=))")
+        block = self.n // num_mini_batches
+        if block < 1:
+            raise ValueError("fewer environments than mini-batches")
+        masks, starts = trajectory_masks(self.dones)                               # [T][n_traj]; [N][T]: where a trajectory begins
+        padded_obs = pad_trajectories(self.observations, masks)
+        padded_critic = None if self.privileged_observations is None else pad_trajectories(self.privileged_observations, masks)
+        first = [0] + torch.cumsum(starts.sum(dim=1), 0).tolist()                  # trajectories before environment e (one host read)
+        h0 = [x.transpose(1, 0)[starts] for x in (self.saved_h_a, self.saved_c_a, self.saved_h_c, self.saved_c_c)]      # [n_traj][H], environment-major
+        slices = (self.actions, self.values, self.advantages, self.returns, self.actions_log_prob, self.mu, self.sigma)
+        for _ in range(num_epochs):
+            for i in range(num_mini_batches):
+                e0, e1 = i * block, (i + 1) * block
+                k0, k1 = first[e0], first[e1]
+                hid = [x[k0:k1].unsqueeze(0).contiguous() for x in h0]
+                yield RecurrentBatch(padded_obs[:, k0:k1], None if padded_critic is None else padded_critic[:, k0:k1], masks[:, k0:k1],
+                                     *(x[:, e0:e1] for x in slices), (hid[0], hid[1]), (hid[2], hid[3]))
+
     def clear(self):
         self.step = 0
 
@@ -303,6 +340,9 @@ class PPO:
     def __init__(self, actor_critic, cfg=None, backend="torch"):
         if backend not in ("torch", "hip"):
             raise ValueError("backend is 'torch' or 'hip'")
+        self.recurrent = bool(getattr(actor_critic, "is_recurrent", False))
+        if self.recurrent and backend == "hip":                                   # (before anything asks for the device)
+            raise ValueError('PPO(backend="hip") with a recurrent actor-critic: backward through time on the device is not built; use backend="torch"')
         self.cfg = cfg if cfg is not None else PPOConfig()
         self.actor_critic = actor_critic
         self.backend = backend
@@ -332,13 +372,21 @@ class PPO:
             group["lr"] = self.learning_rate
 
     def losses(self, batch):
-        """(surrogate, value loss, mean entropy, mean kl) of one mini-batch of ``RolloutStorage.mini_batch_generator``; kl carries no gradient."""
+        """(surrogate, value loss, mean entropy, mean kl) of one mini-batch of ``RolloutStorage.mini_batch_generator``; kl carries no gradient.  On a
+        recurrent actor-critic: of one ``RecurrentBatch`` of ``recurrent_mini_batch_generator``, the same formulas, the means over all T x block elements."""
         c = self.cfg
-        obs, actions, old_values, adv, returns, old_logp, old_mu, old_sigma = batch[:8]
-        critic_obs = batch[8] if len(batch) > 8 else None                        # the critic's rows, when the storage keeps them
-        if critic_obs is None and self.actor_critic.num_critic_obs is not None:
-            raise ValueError("the actor-critic was made with num_critic_obs and the batch carries no critic rows (RolloutStorage(num_privileged_obs=))")
-        logp, entropy, value, mu, sigma = self.actor_critic.log_prob_entropy_value(obs, actions, critic_obs)
+        if self.recurrent:
+            b = batch
+            out = self.actor_critic.log_prob_entropy_value(b.obs, b.actions, b.critic_obs, masks=b.masks, hidden_states=(b.hidden_a, b.hidden_c))
+            logp, entropy, value, mu, sigma = (x.flatten(0, 1) for x in out)       # [T][block][..] -> [T block][..], as the feed-forward batch has them
+            actions, old_values, adv, returns, old_logp, old_mu, old_sigma = (x.flatten(0, 1) for x in (b.actions, b.values, b.advantages, b.returns,
+                                                                                                        b.old_log_prob, b.old_mu, b.old_sigma))
+        else:
+            obs, actions, old_values, adv, returns, old_logp, old_mu, old_sigma = batch[:8]
+            critic_obs = batch[8] if len(batch) > 8 else None                    # the critic's rows, when the storage keeps them
+            if critic_obs is None and self.actor_critic.num_critic_obs is not None:
+                raise ValueError("the actor-critic was made with num_critic_obs and the batch carries no critic rows (RolloutStorage(num_privileged_obs=))")
+            logp, entropy, value, mu, sigma = self.actor_critic.log_prob_entropy_value(obs, actions, critic_obs)
         with torch.no_grad():
             kl = torch.sum(torch.log(sigma / old_sigma + 1.e-5) + (torch.square(old_sigma) + torch.square(old_mu - mu)) / (2.0 * torch.square(sigma)) - 0.5,
                            axis=-1).mean()
@@ -473,7 +521,8 @@ class PPO:
             raise ValueError("indices are taken by the hip backend only")
         c = self.cfg
         mean_value, mean_surrogate, k = 0.0, 0.0, 0
-        for batch in storage.mini_batch_generator(c.num_mini_batches, c.num_learning_epochs):
+        generator = storage.recurrent_mini_batch_generator if self.recurrent else storage.mini_batch_generator
+        for batch in generator(c.num_mini_batches, c.num_learning_epochs):
             surrogate, value_loss, entropy, kl = self.losses(batch)
             if c.desired_kl is not None and c.schedule == "adaptive":
                 self.adapt_learning_rate(kl.item())
@@ -507,9 +556,16 @@ class PPOTrainer:
     update backends feed the critic those rows.  With ``normalize_obs`` the critic's rows go through a second normaliser, ``critic_obs_norm``, under
     the same discipline (update, then normalise, once per row); a constant column of theirs -- the zero pad, a contact flag that never changes --
     has zero variance and normalises to 0 / eps = 0.  The checkpoint then carries ``critic_obs_norm_state_dict`` as well.  Without
-    ``num_privileged_obs`` nothing changes: the same launches through the same entry points."""
+    ``num_privileged_obs`` nothing changes: the same launches through the same entry points.
 
-    def __init__(self, env, cfg=None, seed=1, device=None, update="torch", normalize_obs=False, obs_norm_eps=1e-2, obs_norm_until=None):
+    ``recurrent=RecurrentConfig(hidden_size=...)`` (``recurrent.py``; None, the default: today's path and launches) trains an ``ActorCriticRecurrent``:
+    each tick's ``act`` is handed the task's reset tensor of the tick before (the memories start an episode from zero state) and slot t's views of the
+    storage's saved hidden states -- nothing more is copied per tick -- and the update is the torch one over padded trajectories.  The memories read
+    what the MLPs' first layers read otherwise: the normalised observation, the (normalised) privileged rows.  ``update="hip"`` is refused."""
+
+    def __init__(self, env, cfg=None, seed=1, device=None, update="torch", normalize_obs=False, obs_norm_eps=1e-2, obs_norm_until=None, recurrent=None):
+        if recurrent is not None and update == "hip":                            # (PPO's own refusal, before the device is asked for)
+            raise ValueError('PPOTrainer(update="hip") with recurrent=: backward through time on the device is not built; use update="torch"')
         need_gpu("PPOTrainer")
         self.cfg = cfg if cfg is not None else PPOConfig()
         self.env, self.seed = env, int(seed)
@@ -518,9 +574,19 @@ class PPOTrainer:
         c = self.cfg
         self.num_privileged_obs = getattr(env, "num_privileged_obs", None)
         priv = self.num_privileged_obs
-        self.actor_critic = ActorCritic(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std, num_critic_obs=priv).to(self.device)
+        self.recurrent = recurrent
+        self._prev_reset = None                                                  # the task's reset tensor of the tick before (recurrent only)
+        if recurrent is None:
+            self.actor_critic = ActorCritic(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std, num_critic_obs=priv).to(self.device)
+        else:
+            from .recurrent import ActorCriticRecurrent
+            self.actor_critic = ActorCriticRecurrent(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std, num_critic_obs=priv,
+                                                     rnn_type=recurrent.rnn_type, rnn_hidden_size=recurrent.hidden_size,
+                                                     rnn_num_layers=recurrent.num_layers).to(self.device)
         self.alg = PPO(self.actor_critic, c, backend=update)
-        self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions, num_privileged_obs=priv)
+        hidden = None if recurrent is None else (int(recurrent.hidden_size), int(recurrent.hidden_size))
+        self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions, num_privileged_obs=priv,
+                                      **({} if hidden is None else {"hidden": hidden}))
         self.episode_stats = EpisodeStats(env.num_envs, device=self.device)      # rsl_rl's rewbuffer / lenbuffer (deque(maxlen=100)), on the device
         self.iteration, self.tick, self.obs = 0, 0, None
         self.critic_obs = None                                                   # the critic's rows that go with self.obs (None without privileged observations)
@@ -548,10 +614,12 @@ class PPOTrainer:
             self.obs = self._first_obs()
         st.clear()
         norm, cnorm, priv = self.obs_norm, self.critic_obs_norm, self.num_privileged_obs is not None
+        rec = self.recurrent is not None
         with torch.no_grad():
             for t in range(st.T):
                 obs, critic_obs = self.obs, self.critic_obs
-                out = self.actor_critic.act(obs, self.seed, self.tick, out=st.slot(t), return_eps=record_eps is not None, critic_obs=critic_obs)
+                memory = dict(reset=self._prev_reset, saved=st.hidden_slot(t)) if rec else {}      # the memories' state of slot t goes straight into the storage
+                out = self.actor_critic.act(obs, self.seed, self.tick, out=st.slot(t), return_eps=record_eps is not None, critic_obs=critic_obs, **memory)
                 if record_eps is not None:
                     record_eps.append(out["eps"])
                 if norm is None or t == 0:
@@ -559,6 +627,8 @@ class PPOTrainer:
                 if priv and (cnorm is None or t == 0):                           # the critic's rows the values of slot t were computed from
                     st.privileged_observations[t].copy_(critic_obs)
                 self.obs, rew, reset, extras = self.env.step(st.actions[t])
+                if rec:                                                          # (the task's own buffer: read by the next cell launch, before the next step rewrites it)
+                    self._prev_reset = reset
                 if norm is not None:                                             # update, then normalise, into the slot the next tick reads
                     self.obs = norm(self.obs, out=st.observations[t + 1] if t + 1 < st.T else self._obs_held)
                 if priv:                                                         # the task's own buffer, rewritten by its next step; or its normalised copy
@@ -568,7 +638,7 @@ class PPOTrainer:
                 st.add(rew, reset, extras["time_outs"], c.gamma)
                 self.episode_stats.add(rew, reset, extras["time_outs"])
                 self.tick += 1
-            self.last_values = self.actor_critic.evaluate(self.critic_obs if priv else self.obs)
+            self.last_values = self.actor_critic.evaluate(self.critic_obs if priv else self.obs, **({"reset": self._prev_reset} if rec else {}))
             st.compute_returns(self.last_values, c.gamma, c.lam)
 
     def learn(self, num_iterations, init_at_random_ep_len=False):
@@ -634,10 +704,17 @@ class PPOTrainer:
         enabled = terms.curriculum_enabled if terms is not None else None
         if terms is not None:                                                    # an evaluation does not move the command ranges
             terms.curriculum_enabled = False
+        rec = self.recurrent is not None
         try:
             with torch.no_grad():
                 for _ in range(int(num_ticks)):
-                    self.obs, rew, reset, extras = self.env.step(self.actor_critic.act_inference(self.obs))
+                    if rec:                                                      # the actor's memory alone, from zero state where an episode starts
+                        action = self.actor_critic.act_inference(self.obs, reset=self._prev_reset)
+                    else:
+                        action = self.actor_critic.act_inference(self.obs)
+                    self.obs, rew, reset, extras = self.env.step(action)
+                    if rec:
+                        self._prev_reset = reset
                     if norm is not None:                                         # the statistics stay as training left them
                         self.obs = norm(self.obs, out=self._obs_held, update=False)
                     stats.add(rew, reset, extras["time_outs"])
@@ -648,6 +725,9 @@ class PPOTrainer:
             if terms is not None:
                 terms.curriculum_enabled = enabled
         out = stats.read()
+        if rec:                                                                  # the critic's memory has not seen these ticks: both start the next collection from zero
+            self.actor_critic.reset_memory()
+            self._prev_reset = None
         self.episode_stats.restart()
         keys = ("episodes", "time_outs", "terminations", "mean_return", "mean_length")
         result = {k: out[k] for k in keys}
@@ -678,6 +758,10 @@ class PPOTrainer:
 
     def load(self, path, load_optimizer=True):
         ck = torch.load(path, map_location=self.device)
+        ck_recurrent = any(k.startswith("memory_a.") for k in ck["model_state_dict"])
+        if ck_recurrent != (self.recurrent is not None):
+            raise ValueError("the checkpoint holds a recurrent actor-critic (memory_a / memory_c) and this trainer is feed-forward" if ck_recurrent else
+                             "the checkpoint holds a feed-forward actor-critic and this trainer is recurrent (recurrent=)")
         width = int(ck["model_state_dict"]["critic.0.weight"].shape[1])
         if width != self.actor_critic.critic_width:
             raise ValueError(f"the checkpoint's critic reads rows of {width} columns, this trainer's critic rows of {self.actor_critic.critic_width}")
@@ -700,6 +784,9 @@ class PPOTrainer:
         if plant is not None and "plant_rand_state_dict" in ck:
             plant.load_state_dict(ck["plant_rand_state_dict"])
         self.actor_critic.load_state_dict(ck["model_state_dict"])      # (in place: the kernels keep reading the same addresses)
+        if self.recurrent is not None:                                           # (a state the loaded memories did not compute)
+            self.actor_critic.reset_memory()
+            self._prev_reset = None
         if load_optimizer:
             self.alg.optimizer.load_state_dict(ck["optimizer_state_dict"])
             if self.alg.backend == "hip":                                        # the device's copy of the learning rate follows the checkpoint's
@@ -710,7 +797,10 @@ class PPOTrainer:
 
     def get_inference_policy(self):
         """obs [n, num_obs] -> the actor's mean [n, 12] (``ActorCritic.act_inference``; with normalisation on, of the observation normalised with
-        the statistics as they are, without updating them)."""
+        the statistics as they are, without updating them).  A recurrent trainer's policy also takes ``reset=``, the task's reset tensor of the tick
+        before, and advances the actor's memory on every call."""
         if self.obs_norm is None:
             return self.actor_critic.act_inference
+        if self.recurrent is not None:
+            return lambda obs, reset=None: self.actor_critic.act_inference(self.obs_norm(obs, update=False), reset=reset)
         return lambda obs: self.actor_critic.act_inference(self.obs_norm(obs, update=False))

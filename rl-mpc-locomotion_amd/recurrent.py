@@ -1,0 +1,294 @@
+"""A recurrent (LSTM) actor-critic: the device cell step and the trajectories of the update through time (csrc/mpc_recurrent.h, csrc/mpc_recurrent.hip,
+csrc/recurrent_cell.h).
+
+rsl_rl v1.0.2's ``Memory``, ``ActorCriticRecurrent``, ``split_and_pad_trajectories`` / ``unpad_trajectories`` by their published algorithms (rsl_rl
+is an empty submodule in the reference): a one-layer LSTM in front of the actor's MLP and another in front of the critic's, so that the actor can
+infer from the history of its rows what one row does not show -- the payload, the motor strength and the gravity of ``plant_rand``.  The MLPs read the
+memories' outputs: their first layers are ``rnn_hidden_size`` wide (rsl_rl's ``super().__init__(num_actor_obs=rnn_hidden_size, ...)``).
+
+* the **collection half** is HIP: ``ActorCriticRecurrent.act`` is two launches, ``mpc_recurrent_step`` (both memories side by side; the state per
+  environment lives on the device, is zeroed inside the step where the task's reset flag of the tick before is set, and the state the step started from is
+  written straight into slot t of the storage) and then ``ActorCritic.act`` on the two outputs.  The kernel reads the LSTM's parameters where the
+  optimiser updates them in place.
+* the **update half** is torch: ``RolloutStorage.recurrent_mini_batch_generator`` cuts every environment's column into trajectories at the episode
+  ends and pads them, ``log_prob_entropy_value`` runs ``nn.LSTM`` over them from the saved state and autograd goes back through time.
+  ``PPO(backend="hip")`` refuses a recurrent actor-critic: backward through time on the device is not built.
+
+    trainer = PPOTrainer(env, recurrent=RecurrentConfig(hidden_size=256))
+    trainer.learn(num_iterations)
+
+Two stated deviations from v1.0.2.  ``evaluate`` does not advance the critic's memory: rsl_rl's stepping-mode ``evaluate`` advances it on the
+iteration's last row, and the next ``act`` consumes that row a second time; here ``last_values`` is a peek and every row advances each memory exactly
+once.  ``split_and_pad_trajectories`` pads every piece to T, always: v1.0.2 pads to the longest piece, and its ``unpad_trajectories`` then fails when
+every environment had a ``done``.
+
+Not built: GRU, stacked layers, the device update through time, deployment of a recurrent actor in ``WeightPolicy`` / ``RobotRunnerPolicy``.
+
+The torch paths (``step_torch``, ``log_prob_entropy_value``, the split / pad functions) run on the CPU in any dtype; the device entry points need the
+GPU (MpcLibraryError without one) and have no CPU fallback.
+"""
+import ctypes as C
+from collections import namedtuple
+from dataclasses import dataclass
+
+import torch
+from torch import nn
+
+from . import _lib
+from ._lib import ci, need_gpu, pvp, tensor_arg, text, vp
+from .ppo import NUM_ACTIONS, ActorCritic
+
+MEMORIES = 2                           # csrc/mpc_recurrent.h's MPC_RECURRENT_MEMORIES: the actor's, the critic's
+ACTOR, CRITIC = 0, 1
+
+
+class Io(C.Structure):
+    """csrc/mpc_recurrent.h's ``mpc_recurrent_io``."""
+    _fields_ = [(k, vp) for k in ("d_x", "d_h", "d_c", "d_h_saved", "d_c_saved", "d_h_out")]
+
+
+# the entry points of csrc/mpc_recurrent.h (bound here, not in any other module's list)
+DECLS = {
+    "mpc_recurrent_create": (ci, [pvp, ci, vp, vp]),
+    "mpc_recurrent_destroy": (None, [vp]),
+    "mpc_recurrent_bind": (ci, [vp, vp, vp, vp, vp]),
+    "mpc_recurrent_step": (ci, [vp, ci, ci, ci, vp, vp, ci, vp]),
+    "mpc_recurrent_last_error": (text, []),
+}
+SYMBOLS = list(DECLS)
+lib = _lib.binder(DECLS)
+check = _lib.checker(lib, "mpc_recurrent_last_error")
+
+
+@dataclass
+class RecurrentConfig:
+    """rsl_rl's ``rnn_type``, ``rnn_hidden_size`` and ``rnn_num_layers``; one LSTM layer is what is built."""
+    hidden_size: int = 256
+    rnn_type: str = "lstm"
+    num_layers: int = 1
+
+
+# what ``RolloutStorage.recurrent_mini_batch_generator`` yields: padded trajectories and masks, [T][block] slices, each memory's (h0, c0)
+RecurrentBatch = namedtuple("RecurrentBatch", "obs critic_obs masks actions values advantages returns old_log_prob old_mu old_sigma hidden_a hidden_c")
+
+
+def refuse_unbuilt(rnn_type, rnn_num_layers):
+    if str(rnn_type).lower() != "lstm":
+        raise ValueError(f"rnn_type={rnn_type!r}: not built (LSTM only)")
+    if int(rnn_num_layers) != 1:
+        raise ValueError(f"rnn_num_layers={rnn_num_layers}: not built (one layer only)")
+
+
+# ---- trajectories ---------------------------------------------------------------------------------------------------------------------------------
+def trajectory_masks(dones):
+    """dones [T][N][1] -> (masks [T][n_traj] bool, starts [N][T] bool): every environment's column is cut after each done (and after its last
+    slot); trajectory k, counted environment-major, is ``masks[:, k].sum()`` steps long, and ``starts[e][t]`` is set where a trajectory of
+    environment e begins (t = 0, or the step after a done).  One host read (the number of trajectories)."""
+    T = dones.shape[0]
+    d = dones.clone()
+    d[-1] = 1
+    flat = d.transpose(1, 0).reshape(-1) != 0                                  # environment-major
+    ends = flat.nonzero()[:, 0]
+    lengths = ends - torch.cat((ends.new_full((1,), -1), ends[:-1]))
+    masks = lengths.unsqueeze(0) > torch.arange(T, device=dones.device).unsqueeze(1)
+    starts = torch.ones_like(flat).view(-1, T)
+    starts[:, 1:] = flat.view(-1, T)[:, :-1]
+    return masks, starts
+
+
+def split_and_pad_trajectories(tensor, dones):
+    """rsl_rl's: tensor [T][N][F], dones [T][N][1] -> (padded [T][n_traj][F], masks [T][n_traj] bool).  The pieces of every environment's column
+    between its dones, in environment-major order, each padded with zeros to length T -- always T (v1.0.2 pads to the longest piece)."""
+    masks, _ = trajectory_masks(dones)
+    return pad_trajectories(tensor, masks), masks
+
+
+def pad_trajectories(tensor, masks):
+    """tensor [T][N][F] cut and padded by the ``masks`` of its dones (``trajectory_masks``) -> [T][n_traj][F]."""
+    padded = tensor.new_zeros((tensor.shape[0], masks.shape[1]) + tuple(tensor.shape[2:]))
+    padded.transpose(1, 0)[masks.transpose(1, 0)] = tensor.transpose(1, 0).flatten(0, 1)      # consecutive pieces of the environment-major order
+    return padded
+
+
+def unpad_trajectories(x, masks):
+    """The inverse of ``split_and_pad_trajectories``: x [T][n_traj][F] -> [T][envs][F]."""
+    T = x.shape[0]
+    return x.transpose(1, 0)[masks.transpose(1, 0)].view(-1, T, x.shape[-1]).transpose(1, 0)
+
+
+def lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh):
+    """One LSTM step written out (torch's gate order i, f, g, o), in the dtype of its arguments."""
+    gates = nn.functional.linear(x, w_ih, b_ih) + nn.functional.linear(h, w_hh, b_hh)
+    i, f, g, o = gates.chunk(4, dim=-1)
+    c1 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+    return torch.sigmoid(o) * torch.tanh(c1), c1
+
+
+class Memory(nn.Module):
+    """rsl_rl's ``Memory`` with an LSTM: ``rnn = nn.LSTM(input_size, hidden_size, 1)``, so the state dict has rsl_rl's keys
+    (``rnn.weight_ih_l0``, ``weight_hh_l0``, ``bias_ih_l0``, ``bias_hh_l0``).  ``h``, ``c`` [n][H]: the device state, allocated (zero) on first use,
+    advanced by ``mpc_recurrent_step``; ``out`` [n][H]: the step's h', what the MLP behind the memory reads."""
+
+    def __init__(self, input_size, hidden_size=256, rnn_type="lstm", num_layers=1):
+        super().__init__()
+        refuse_unbuilt(rnn_type, num_layers)
+        self.input_size, self.hidden_size = int(input_size), int(hidden_size)
+        self.rnn = nn.LSTM(self.input_size, self.hidden_size, 1)
+        self.h, self.c, self.out = None, None, None
+
+    def parameters_in_bind_order(self):
+        return [self.rnn.weight_ih_l0, self.rnn.weight_hh_l0, self.rnn.bias_ih_l0, self.rnn.bias_hh_l0]
+
+    def state(self, n, device):
+        """(h, c, out) for ``n`` rows on ``device``; a new size or device starts from zero state."""
+        if self.h is None or self.h.shape[0] != n or self.h.device != device:
+            z = lambda: torch.zeros((n, self.hidden_size), dtype=torch.float32, device=device)
+            self.h, self.c, self.out = z(), z(), z()
+        return self.h, self.c, self.out
+
+    def reset(self):
+        if self.h is not None:
+            self.h.zero_()
+            self.c.zero_()
+
+    def step_torch(self, x, state=None, reset=None):
+        """One tick in torch: x [n][I], state (h, c) or None (zero), reset [n] or None -> (h', (h', c'), the state the step started from)."""
+        n = x.shape[0]
+        h, c = state if state is not None else (x.new_zeros((n, self.hidden_size)), x.new_zeros((n, self.hidden_size)))
+        if reset is not None:
+            keep = (reset.reshape(n, 1) == 0).to(x.dtype)
+            h, c = h * keep, c * keep
+        h1, c1 = lstm_cell(x, h, c, *self.parameters_in_bind_order())
+        return h1, (h1, c1), (h, c)
+
+    def forward(self, padded, masks, hidden):
+        """Batch mode: padded [T][n_traj][I] from ``hidden`` = (h0, c0) [1][n_traj][H] -> [T][envs][H]."""
+        out, _ = self.rnn(padded, hidden)
+        return unpad_trajectories(out, masks) if masks is not None else out
+
+
+class ActorCriticRecurrent(ActorCritic):
+    """rsl_rl's ``ActorCriticRecurrent``: ``memory_a`` reads the actor's rows (``num_obs`` wide), ``memory_c`` the critic's (``num_critic_obs`` wide
+    if given, ``num_obs`` otherwise), and the parent's MLPs read the memories' outputs (``rnn_hidden_size`` wide each).  The state dict has rsl_rl's
+    keys: the parent's and ``memory_{a,c}.rnn.{weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0}``.
+
+    ``act`` is the cell launch and then the parent's asymmetric ``act``.  ``reset``: the task's reset tensor (int64 [n]) of the tick before, or None;
+    where it is set the row's state is taken as zero before the step.  ``saved``: dict of ``h_a``, ``c_a``, ``h_c``, ``c_c`` [n][H] views
+    (``RolloutStorage.hidden_slot(t)``) that receive the state the step started from.  ``evaluate`` peeks: it does not advance the critic's memory."""
+    is_recurrent = True
+
+    def __init__(self, num_obs=48, num_actions=NUM_ACTIONS, actor_hidden_dims=(512, 256, 128), critic_hidden_dims=(512, 256, 128), init_noise_std=1.0,
+                 num_critic_obs=None, rnn_type="lstm", rnn_hidden_size=256, rnn_num_layers=1):
+        refuse_unbuilt(rnn_type, rnn_num_layers)
+        H = int(rnn_hidden_size)
+        super().__init__(H, num_actions, actor_hidden_dims, critic_hidden_dims, init_noise_std, num_critic_obs=H)
+        self.obs_width = int(num_obs)                                            # what memory_a reads
+        self.critic_obs_width = int(num_obs if num_critic_obs is None else num_critic_obs)
+        self.privileged = num_critic_obs is not None                             # the critic's memory reads rows of its own
+        self.rnn_hidden_size = H
+        self.memory_a = Memory(self.obs_width, H)
+        self.memory_c = Memory(self.critic_obs_width, H)
+        self._cell_handle, self._cell_ptrs = None, None
+
+    _destroy_cell = _lib.finalizer("mpc_recurrent_destroy", attr="_cell_handle")
+    _destroy_ac = ActorCritic.__del__
+
+    def __del__(self):                                                           # (through the class: at interpreter exit this module's globals are gone)
+        self._destroy_cell()
+        self._destroy_ac()
+
+    def memories(self):
+        return (self.memory_a, self.memory_c)
+
+    def reset_memory(self):
+        """rsl_rl's ``reset()`` for every environment: all state to zero."""
+        for m in self.memories():
+            m.reset()
+
+    # ---- the device path -----------------------------------------------------------------------------------------------------------------------
+    def _cell_ready(self, what, device):
+        need_gpu(what, self.std)
+        if self._cell_handle is None:
+            h = C.c_void_p()
+            sizes = lambda v: C.cast((C.c_int * MEMORIES)(*v), C.c_void_p)
+            check(lib().mpc_recurrent_create(C.byref(h), MEMORIES, sizes([m.input_size for m in self.memories()]),
+                                             sizes([m.hidden_size for m in self.memories()])), "mpc_recurrent_create")
+            self._cell_handle = h
+        params = [m.parameters_in_bind_order() for m in self.memories()]
+        ptrs = tuple(p.data_ptr() for ps in params for p in ps)
+        if ptrs != self._cell_ptrs:
+            for ps in params:
+                for p in ps:
+                    if p.dtype != torch.float32 or not p.is_contiguous() or p.device != device:
+                        raise ValueError("the memories' parameters must be contiguous float32 tensors on the observations' device")
+            arr = lambda k: C.cast((C.c_void_p * MEMORIES)(*[ps[k].data_ptr() for ps in params]), C.c_void_p)
+            with torch.cuda.device(device):
+                check(lib().mpc_recurrent_bind(self._cell_handle, arr(0), arr(1), arr(2), arr(3)), "mpc_recurrent_bind")
+            self._cell_ptrs = ptrs
+
+    def cell_step(self, rows, reset=None, saved=None, commit=True, what="ActorCriticRecurrent.cell_step"):
+        """ONE launch of ``mpc_recurrent_step``.  ``rows``: ``{ACTOR: obs}``, ``{CRITIC: critic rows}`` or both (consecutive memories); returns
+        the stepped memories' ``out`` tensors in that order."""
+        which = sorted(rows)
+        x0 = rows[which[0]]
+        need_gpu(what, *rows.values())
+        n, dev = x0.shape[0], x0.device
+        self._cell_ready(what, dev)
+        if reset is not None:
+            need_gpu(what, reset)
+            tensor_arg(reset, torch.long, n, "reset")
+        io, outs = (Io * len(which))(), []
+        for k, w in enumerate(which):
+            m = self.memories()[w]
+            tensor_arg(rows[w], torch.float32, n * m.input_size, "critic_obs" if w == CRITIC else "obs")
+            h, c, out = m.state(n, dev)
+            sv = (None, None)
+            if saved is not None:
+                sv = (saved["h_c"], saved["c_c"]) if w == CRITIC else (saved["h_a"], saved["c_a"])
+                for t in sv:
+                    tensor_arg(t, torch.float32, n * m.hidden_size, "saved")
+            io[k] = Io(rows[w].data_ptr(), h.data_ptr(), c.data_ptr(), *(t.data_ptr() if t is not None else None for t in sv), out.data_ptr())
+            outs.append(out)
+        check(lib().mpc_recurrent_step(self._cell_handle, n, which[0], len(which), C.cast(io, C.c_void_p), reset.data_ptr() if reset is not None else None,
+                                       int(bool(commit)), _lib.stream(dev)), "mpc_recurrent_step")
+        return outs
+
+    def _critic_rows(self, obs, critic_obs):
+        if critic_obs is None and self.privileged:
+            raise ValueError("this actor-critic was made with num_critic_obs: the critic's memory needs critic_obs")
+        return obs if critic_obs is None else critic_obs
+
+    def act(self, obs, seed, step, out=None, return_eps=False, critic_obs=None, reset=None, saved=None):
+        """Two launches: both memories advance on (obs, critic rows), then ``ActorCritic.act`` on (h_a', h_c') -- the same dict as the parent's."""
+        h_a, h_c = self.cell_step({ACTOR: obs, CRITIC: self._critic_rows(obs, critic_obs)}, reset, saved, True, "ActorCriticRecurrent.act")
+        return super().act(h_a, seed, step, out=out, return_eps=return_eps, critic_obs=h_c)
+
+    def evaluate(self, critic_obs, out=None, reset=None):
+        """The critic's value of rows [n, critic_obs_width] from the critic's memory as it stands (``reset`` applied), WITHOUT advancing it."""
+        h_c, = self.cell_step({CRITIC: critic_obs}, reset, None, False, "ActorCriticRecurrent.evaluate")
+        return super().evaluate(h_c, out=out)
+
+    def act_inference(self, obs, reset=None):
+        """The actor's mean; steps ``memory_a`` only."""
+        h_a, = self.cell_step({ACTOR: obs}, reset, None, True, "ActorCriticRecurrent.act_inference")
+        return super().act_inference(h_a)
+
+    # ---- the torch paths (differentiable, any device, any dtype) ------------------------------------------------------------------------------------
+    def step_torch(self, obs, critic_obs=None, state=None, reset=None):
+        """One tick: ``state`` = ((h_a, c_a), (h_c, c_c)) or None (zero) -> (mu [n,12], value [n,1], the new state, the state the step started
+        from after the reset's zeroing -- what the storage keeps for the slot)."""
+        sa, sc = state if state is not None else (None, None)
+        h_a, new_a, used_a = self.memory_a.step_torch(obs, sa, reset)
+        h_c, new_c, used_c = self.memory_c.step_torch(self._critic_rows(obs, critic_obs), sc, reset)
+        return self.actor(h_a), self.critic(h_c), (new_a, new_c), (used_a, used_c)
+
+    def log_prob_entropy_value(self, obs, actions, critic_obs=None, masks=None, hidden_states=None):
+        """Batch mode: ``obs`` (and ``critic_obs``) are padded trajectories [T][n_traj][width], ``hidden_states`` = ((h0_a, c0_a), (h0_c, c0_c)), each
+        [1][n_traj][H], their first steps' saved states, ``masks`` [T][n_traj]; ``rnn(padded, (h0, c0))``, then unpad, then the MLPs.  ``actions``
+        [T][envs][12] -> (log-prob [T][envs], entropy [T][envs], value [T][envs][1], mu, sigma [T][envs][12])."""
+        if hidden_states is None:
+            raise ValueError("batch mode needs the trajectories' first hidden states")
+        mu = self.actor(self.memory_a(obs, masks, hidden_states[0]))
+        value = self.critic(self.memory_c(self._critic_rows(obs, critic_obs), masks, hidden_states[1]))
+        dist = torch.distributions.Normal(mu, mu * 0. + self.std)
+        return dist.log_prob(actions).sum(dim=-1), dist.entropy().sum(dim=-1), value, mu, dist.stddev

@@ -11,6 +11,11 @@ one on the same task without them, the two trainers alternating repeat by repeat
 columns; 48 against 64 critic columns) or with --heights on the terrain grid (240 columns everywhere: the asymmetric path at equal widths).
 --baseline times the symmetric trainer alone (it runs on a tree without the option, for a measurement of the parent commit in the same session).
     python tools/ppo_rate.py --privileged [--heights] [--baseline] [--out results/privileged_iteration.json]
+--recurrent times the recurrent actor-critic (recurrent.py, an LSTM of --hidden state elements in front of each MLP) against the feed-forward one, the
+two alternating block by block in one process: the cell launch alone, a recurrent `act` (cell launch + act launch) against the feed-forward `act`, and a
+whole iteration (collection + torch update) of each trainer; the cell launch is reported as a share of the 0.82 ms control step and against the weight
+bytes it streams.  --baseline times the feed-forward trainer alone.
+    python tools/ppo_rate.py --recurrent [--hidden 256] [--baseline] [--out profiles/recurrent_rate.json]
 The kernel-trace stats: rocprofv3 --kernel-trace --stats ... -- python tools/ppo_rate.py --quick   (3 collections and one update per backend)"""
 import argparse
 import json
@@ -130,6 +135,77 @@ def privileged_report(args, dev, n):
     return res
 
 
+def recurrent_report(args, dev, n):
+    """The recurrent actor-critic (recurrent.py) against the feed-forward one, in one process and alternating block by block: the cell launch alone, a
+    recurrent ``act`` (cell launch + act launch) against the feed-forward ``act`` launch, and a whole iteration (collection + torch update) of each
+    trainer.  The feed-forward trainer makes the launches it made before the option existed; --baseline times it alone."""
+    from bench import device_state
+    from rl_mpc_locomotion_amd.recurrent import ACTOR, CRITIC, RecurrentConfig
+    cfg = PPOConfig()
+    T, H = cfg.num_steps_per_env, args.hidden
+    trainers = {"feed_forward": PPOTrainer(make_env(n, dev), cfg, seed=1)}
+    if not args.baseline:
+        trainers["recurrent"] = PPOTrainer(make_env(n, dev), cfg, seed=1, recurrent=RecurrentConfig(hidden_size=H))
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "num_steps_per_env": T, "repeats": args.repeats, "update": "torch",
+           "hidden_size": H, "baseline_only": bool(args.baseline), "mini_batches_per_update": cfg.num_learning_epochs * cfg.num_mini_batches,
+           "device_state": {"before": device_state(0)}}
+    for tr in trainers.values():          # warm-up: cold solves, code objects, torch's kernels, Adam's state
+        tr.learn(2)
+    torch.cuda.synchronize()
+    # the launches on fixed inputs: 24 of each per block, one event pair around each
+    obs = {k: tr.obs for k, tr in trainers.items()}
+    launches = {"feed_forward_act": lambda t: trainers["feed_forward"].actor_critic.act(obs["feed_forward"], 1, t, out=trainers["feed_forward"].storage.slot(t))}
+    if not args.baseline:
+        rac, rst = trainers["recurrent"].actor_critic, trainers["recurrent"].storage
+        launches["cell"] = lambda t: rac.cell_step({ACTOR: obs["recurrent"], CRITIC: obs["recurrent"]}, None, rst.hidden_slot(t))
+        launches["recurrent_act"] = lambda t: rac.act(obs["recurrent"], 1, t, out=rst.slot(t), saved=rst.hidden_slot(t))
+    spans = {k: [] for k in launches}
+    names = list(launches)
+    for rep in range(args.repeats):
+        for name in (names if rep % 2 == 0 else names[::-1]):
+            e = [(ev(), ev()) for _ in range(T)]
+            for t in range(T):
+                e[t][0].record()
+                launches[name](t)
+                e[t][1].record()
+            torch.cuda.synchronize()
+            spans[name].extend(a.elapsed_time(b) for a, b in e)
+    res["launches"] = {k: stats(v) for k, v in spans.items()}
+    if not args.baseline:
+        trainers["recurrent"].actor_critic.reset_memory()
+        nets = lambda seq: sum(m.weight.numel() for m in seq if hasattr(m, "weight"))
+        ff = trainers["feed_forward"].actor_critic
+        mlp_bytes, cell_bytes = 4 * (nets(ff.actor) + nets(ff.critic)), 4 * 2 * 4 * H * (ff.num_obs + H)
+        med = lambda k: res["launches"][k]["median_ms"]
+        res["cell_share_of_0p82_ms_control_step"] = med("cell") / 0.82
+        res["cell_over_feed_forward_act"] = med("cell") / med("feed_forward_act")
+        res["weight_bytes"] = {"cell_both_memories": cell_bytes, "feed_forward_act_both_mlps": mlp_bytes, "ratio": cell_bytes / mlp_bytes}
+        res["recurrent_act_over_feed_forward_act"] = med("recurrent_act") / med("feed_forward_act")
+    # a whole iteration of each trainer
+    times = {k: {"collect": [], "update": [], "full": []} for k in trainers}
+    names = list(trainers)
+    for rep in range(args.repeats):       # which one goes first alternates
+        for name in (names if rep % 2 == 0 else names[::-1]):
+            tr = trainers[name]
+            a, b, c = ev(), ev(), ev()
+            a.record()
+            tr.collect()
+            b.record()
+            tr.alg.update(tr.storage)
+            c.record()
+            torch.cuda.synchronize()
+            tb = times[name]
+            tb["collect"].append(a.elapsed_time(b)); tb["update"].append(b.elapsed_time(c)); tb["full"].append(a.elapsed_time(c))
+    for name, tb in times.items():
+        res[name] = {k: stats(v) for k, v in tb.items()}
+        res[name]["robot_ticks_per_s_training"] = n * T / (float(np.median(tb["full"])) * 1e-3)
+    if not args.baseline:
+        res["recurrent_over_feed_forward_median"] = {k: res["recurrent"][k]["median_ms"] / res["feed_forward"][k]["median_ms"] for k in ("collect", "update", "full")}
+        res["collection_added_per_tick_ms"] = (res["recurrent"]["collect"]["median_ms"] - res["feed_forward"]["collect"]["median_ms"]) / T
+    res["device_state"]["after"] = device_state(0, smi=False)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--robots", type=int, default=4096)
@@ -137,14 +213,16 @@ if __name__ == "__main__":
     ap.add_argument("--quick", action="store_true", help="3 collections and one update only (for a kernel trace)")
     ap.add_argument("--privileged", action="store_true", help="one iteration of the asymmetric actor-critic against the symmetric one (see the head of this file)")
     ap.add_argument("--heights", action="store_true", help="--privileged: on the terrain grid with the height scan (240 columns)")
-    ap.add_argument("--baseline", action="store_true", help="--privileged: the symmetric trainer alone (runs on a tree without the option)")
+    ap.add_argument("--baseline", action="store_true", help="--privileged / --recurrent: the symmetric / feed-forward trainer alone (runs on a tree without the option)")
+    ap.add_argument("--recurrent", action="store_true", help="the recurrent actor-critic against the feed-forward one (see the head of this file)")
+    ap.add_argument("--hidden", type=int, default=256, help="--recurrent: the memories' hidden size")
     ap.add_argument("--out")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("ppo_rate.py measures on the GPU; none is visible")
     dev, n = "cuda:0", args.robots
-    if args.privileged:
-        res = privileged_report(args, dev, n)
+    if args.privileged or args.recurrent:
+        res = recurrent_report(args, dev, n) if args.recurrent else privileged_report(args, dev, n)
         print(json.dumps(res, indent=1))
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
