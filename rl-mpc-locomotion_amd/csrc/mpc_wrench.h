@@ -63,8 +63,15 @@ struct RoleRegs<TE, true> {
   };
 };
 
+// D of the foot lane's variables and E of its rows, fetched once in the job's prologue (Solver::load_batched, Dat, Eat): a member of the
+// single-wavefront kernels' threads only -- the long horizons' thread is left exactly as it was (their register allocation moves with anything)
+template <bool ON>
+struct ScaleRegs { double Dv[3], Ev[5]; };
+template <>
+struct ScaleRegs<false> {};
+
 template <int H>
-struct WThread : RoleRegs<Cfg<H>::TE, (Cfg<H>::FOOT0 != 0 && MPC_SHARE_ROLE_REGS)> {
+struct WThread : RoleRegs<Cfg<H>::TE, (Cfg<H>::FOOT0 != 0 && MPC_SHARE_ROLE_REGS)>, ScaleRegs<(Cfg<H>::TW <= 64)> {
   using C = Cfg<H>;
   int tid;
   // ---- tile lane (tid < MTW): my tile of the wrench grid
@@ -120,6 +127,12 @@ struct WThread : RoleRegs<Cfg<H>::TE, (Cfg<H>::FOOT0 != 0 && MPC_SHARE_ROLE_REGS
 #endif
 #ifndef MPC_LOCKSTEP
 #define MPC_LOCKSTEP 0
+#endif
+#ifndef MPC_SCALE_REGS_MAXT    // the largest workgroup that keeps the foot's D and E in registers from the job's prologue on (else: read from the scale record where used)
+#define MPC_SCALE_REGS_MAXT 64
+#endif
+#ifndef MPC_STRUCT_THETA_MAXT  // the largest workgroup that skips the entries of c Theta_ij that are zero by construction (Solver::th_nz)
+#define MPC_STRUCT_THETA_MAXT 64
 #endif
 #ifndef MPC_ADMM_BATCH_LOADS   // which workgroup sizes request every LDS constant of the foot phase in one batch up front (~90 more registers)
 #define MPC_ADMM_BATCH_LOADS(T) ((T) <= 64)
@@ -266,9 +279,29 @@ struct Solver {
 #endif
   }
   // Theta_{ti,tj} = s2 th1 + nn diag(th2):  s2 = sum_{i < m} (i + 1/2)(i + d + 1/2) = m (4 m^2 - 1) / 12 + d m^2 / 2,  nn = m = H - ti,  d = ti - tj
+  // th1 = 2 dt^4 blockdiag(T^T diag(w0..2) T, diag(w3..5)) (mpc_core.h Assembler: exact zeros in the other 24 entries) and th2 is a diagonal, so
+  // c Theta_ij is a dense 3 x 3 block plus three diagonal entries: th_nz(a, b).  The single-wavefront kernels leave out the products with the
+  // zeros -- in the tile products, in dl and in the tile build, where t1 = (c Theta) L_j inherits the pattern (t1_nz; L is lower triangular).
+  // Every term left out is x * (+-0) added to a sum that started at +0 (or 1), the others keep their order: the results are the same bit for
+  // bit for finite data (tests/test_kform_structure.py holds the assembler to the zeros).
+  static constexpr bool kStructTheta = T <= MPC_STRUCT_THETA_MAXT && T <= 64;
+  static_assert(!kStructTheta || TS == 6, "th_nz describes the 6 x 6 wrench tile");
+  static constexpr MPC_HD bool th_nz(int a, int b) { return !kStructTheta || (a < 3 && b < 3) || a == b; }
+  static constexpr MPC_HD bool t1_nz(int a, int b) { return !kStructTheta || (a < 3 ? b < 3 : b <= a); }
   static MPC_HD double th_nn(const Th &t) { return (double)(H - t.ti); }
   static MPC_HD double th_s2(const Th &t) { const double m = (double)(H - t.ti), d = (double)(t.ti - t.tj); return m * (4.0 * m * m - 1.0) / 12.0 + d * (m * m) * 0.5; }
-  MPC_HD double Dat(const Th &t, int c) const { return sc[C::SC_D + 3 * t.fid + c]; }   // D of my variables (scale record; not worth registers)
+  // D of my variables, E of my rows (scale record).  A lone wave waits out every global round trip it makes, and a job made a dozen of these between
+  // its prologue and its stores: the single-wavefront kernels fetch the eight values once, in load_batched()'s batch, and keep them (16 of 512 registers).
+  // The long horizons sit at a 256-register cap and read the record where they need it.
+  static constexpr bool kScaleRegs = T <= MPC_SCALE_REGS_MAXT && T <= 64;
+  MPC_HD double Dat(const Th &t, int c) const {
+    if constexpr (kScaleRegs) return t.Dv[c];
+    else return sc[C::SC_D + 3 * t.fid + c];
+  }
+  MPC_HD double Eat(const Th &t, int r) const {
+    if constexpr (kScaleRegs) return t.Ev[r];
+    else return sc[C::SC_E + 5 * t.fid + r];
+  }
   // rho / 1 / rho of row r of my foot (three uniform values, selected by the row's type code)
   MPC_HD double rho_at(const Th &t, int r) const {
     const int ty = (t.tyb >> (2 * r)) & 3;
@@ -406,6 +439,7 @@ struct Solver {
         for (int aa = 0; aa < TS; ++aa)
 #pragma unroll
           for (int bb = 0; bb < TS; ++bb) {
+            if (KIND != kHeld && !th_nz(aa, bb)) continue;
             double m;
             if (KIND == kHeld) m = t.Mx[aa * TS + bb];
             else m = s.c * (s2v * s.th1[aa * TS + bb] + (aa == bb ? nnv * s.th2[aa] : 0.0));
@@ -577,6 +611,12 @@ struct Solver {
       if (t.foot) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) t.q[c] = q[c];
+        if constexpr (kScaleRegs) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) t.Dv[c] = d[c];
+#pragma unroll
+          for (int r = 0; r < 5; ++r) t.Ev[r] = e[r];
+        }
 #pragma unroll
         for (int k = 0; k < 9; ++k) s.fa[pidx(k, f)] = C::scaled_cone_entry(cone[k], e[kAsPos[k] / 3], d[kAsPos[k] % 3]);
         s.fa[pidx(15, f)] = 0.0;
@@ -723,6 +763,7 @@ struct Solver {
   // (Z_k of the ADMM system is positive definite; a row that is numerically dependent all the same is dropped.)
   MPC_HD void step_factor() {
     ex.template quad_allsum<21>([](Th &t) { return t.zq; });
+    MPC_SUBLAP(10, 2);
     ex.par([&](Th &t) {
       if (t.foot && (t.fid & 3) == 0) {
         const int kk = t.fid >> 2;
@@ -775,6 +816,7 @@ struct Solver {
       }
     });
     step_factor();
+    MPC_SUBLAP(10, 3);
     ex.par([&](Th &t) {
       if (t.foot) {   // G_f = T_k W_f
         double w[18], gf[18];
@@ -788,8 +830,12 @@ struct Solver {
         for (int k = 0; k < 18; ++k) s.Gf[pidx(k, t.fid)] = hs[k];
       }
     });
+    MPC_SUBLAP(10, 4);
     factor_tail();
   }
+  // (-DMPC_PROFILE_SUB=10 / 11: the K-form of the ADMM job's factorisations / of the polish job's in slots 1 .. 5, its tile build alone in slot 6 --
+  //  10: S_f^-1 with what precedes it | put_zf + the quad all-sum | L D L^T and the inverse on the step lanes | G_f | dl;
+  //  11: the polish set-up up to polish_factor | F_f and the column lengths | orth_col | G_f, L to LDS | dl)
   // from L_k (LDS) to the held tiles: dl = diag(M)^-1/2 of my rows, the unit-diagonal tile of Mh, the sweep
   MPC_HD void factor_tail() {
     ex.par([&](Th &t) {
@@ -808,7 +854,8 @@ struct Solver {
           for (int a = 0; a < TS; ++a) {
             double row = 0;
 #pragma unroll
-            for (int bb = 0; bb < TS; ++bb) row += (s2kk * s.th1[a * TS + bb] + (a == bb ? mm * s.th2[a] : 0.0)) * lc[bb];
+            for (int bb = 0; bb < TS; ++bb)
+              if (th_nz(a, bb)) row += (s2kk * s.th1[a * TS + bb] + (a == bb ? mm * s.th2[a] : 0.0)) * lc[bb];
             acc += lc[a] * row;
           }
           const double dv = fast_rsqrt(1.0 + s.c * acc);
@@ -817,6 +864,8 @@ struct Solver {
         }
       }
     });
+    MPC_SUBLAP(10, 5);
+    MPC_SUBLAP(11, 5);
     ex.par([&](Th &t) {
       if (t.mact) {   // Mh tile = dl_i ([i == j] I + L_i^T (c Theta_ij) L_j) dl_j   (L lower triangular); unit diagonal
         const double s2v = th_s2(t), nnv = th_nn(t);
@@ -828,7 +877,8 @@ struct Solver {
           for (int bb = 0; bb < TS; ++bb) {
             double v = 0;
 #pragma unroll
-            for (int k = bb; k < TS; ++k) v += (s.c * (s2v * s.th1[aa * TS + k] + (aa == k ? nnv * s.th2[aa] : 0.0))) * lj[k * TS + bb];
+            for (int k = bb; k < TS; ++k)
+              if (th_nz(aa, k)) v += (s.c * (s2v * s.th1[aa * TS + k] + (aa == k ? nnv * s.th2[aa] : 0.0))) * lj[k * TS + bb];
             t1[aa * TS + bb] = v;
           }
 #pragma unroll
@@ -837,7 +887,8 @@ struct Solver {
           for (int bb = 0; bb < TS; ++bb) {
             double v = (t.dia && aa == bb) ? 1.0 : 0.0;
 #pragma unroll
-            for (int k = aa; k < TS; ++k) v += li[k * TS + aa] * t1[k * TS + bb];
+            for (int k = aa; k < TS; ++k)
+              if (t1_nz(k, bb)) v += li[k * TS + aa] * t1[k * TS + bb];
             t.Mx[aa * TS + bb] = (di[aa] * v) * dj[bb];
           }
       }
@@ -870,6 +921,7 @@ struct Solver {
         s.fr[pidx(9, t.fid)] = 0.0;
       }
     });
+    MPC_SUBLAP(10, 1);
     factor_core([](Th &t) { return t.Si; });
   }
 
@@ -1179,7 +1231,7 @@ struct Solver {
 #pragma unroll
         for (int r = 0; r < 5; ++r) {
           const double rr = ax[r] - z[r];
-          ev[r] = sc[C::SC_E + 5 * t.fid + r];
+          ev[r] = Eat(t, r);
           ei[r] = norm_recip(ev[r]);
           mx[0] = dmax(mx[0], fabs(ei[r] * rr)); mx[1] = dmax(mx[1], fabs(ei[r] * z[r])); mx[2] = dmax(mx[2], fabs(ei[r] * ax[r]));
           mx[3] = dmax(mx[3], fabs(rr)); mx[4] = dmax(mx[4], fabs(z[r])); mx[5] = dmax(mx[5], fabs(ax[r]));
@@ -1406,6 +1458,7 @@ struct Solver {
     }
   }
   MPC_HD void polish_factor() {
+    MPC_SUBLAP(11, 1);
     ex.seq([&](Th &t) {
 #pragma unroll
       for (int r = 0; r < 6; ++r) t.w6[r] = 0.0;
@@ -1430,7 +1483,9 @@ struct Solver {
 #pragma unroll
       for (int r = 0; r < 6; ++r) t.pn[r] = t.w6[r];
     });
+    MPC_SUBLAP(11, 2);
     orth_col<0>();
+    MPC_SUBLAP(11, 3);
     ex.par([&](Th &t) {
       if (t.foot) {
 #pragma unroll
@@ -1444,6 +1499,7 @@ struct Solver {
         }
       }
     });
+    MPC_SUBLAP(11, 4);
     factor_tail();
   }
 
@@ -2654,6 +2710,13 @@ struct Solver {
     if (eps_exact > 0) return ((t.tyb & 0x3ff) == 0x2aa) ? -0.0 : -(Dat(t, c) * t.x[c]);
     return 0.0 - Dat(t, c) * t.x[c];
   }
+  // My lane's index into the records a job stores.  In the single-wavefront kernels it is made opaque: the compiler otherwise forms `record + lane`
+  // in the kernel's head, holds the 64-bit address across every job of the persistent loop and, once the register file is full, spills it.
+  static MPC_HD int store_lane(const Th &t) {
+    int i = t.tid;
+    if constexpr (T <= 64) MPC_LAUNDER(i);
+    return i;
+  }
   // outputs + persistent state (store_solution, auxil.c:528-561; mpc_osqp.cc:788-790: forces = -x).  A non-convex / non-finite
   // problem has no solution: OSQP cold-starts the iterates (auxil.c:539-563); here the whole record is cleared, so that the
   // robot's next call is the cold "osqp_setup" call on clean data (with NaN inputs the vendored OSQP itself stays poisoned).
@@ -2681,8 +2744,9 @@ struct Solver {
       if (t.tid == 0) { s.part[2 * N + 2 * M] = failed ? 0.0 : s.rho; s.part[2 * N + 2 * M + 1] = failed ? 0.0 : 1.0; }
     });
     ex.par([&](Th &t) {      // ... and out with lane-contiguous addresses
-      for (int i = t.tid; i < SL; i += T) MPC_GST(state + i, s.part[i]);
-      if (solved) for (int i = t.tid; i < N; i += T) MPC_GST(forces + i, s.part[SL + i]);
+      const int lane = store_lane(t);
+      for (int i = lane; i < SL; i += T) MPC_GST(state + i, s.part[i]);
+      if (solved) for (int i = lane; i < N; i += T) MPC_GST(forces + i, s.part[SL + i]);
       if (t.tid == 0) {
         const int iv[8] = {s.iter, s.bad ? kStNonCvx : s.status, s.status_polish, s.rho_updates, s.nfact, s.first, eps_exact > 0 ? s.pol_rounds : 0, 0};
 #pragma unroll
@@ -2874,15 +2938,17 @@ struct Solver {
     });
     ex.par([&](Th &t) {
       if (s.status_polish == 1) {
-        for (int i = t.tid; i < N + 2 * M; i += T) MPC_GST(state + i, s.part[i]);
-        for (int i = t.tid; i < N; i += T) MPC_GST(forces + i, s.part[SL + i]);
+        const int lane = store_lane(t);
+        for (int i = lane; i < N + 2 * M; i += T) MPC_GST(state + i, s.part[i]);
+        for (int i = lane; i < N; i += T) MPC_GST(forces + i, s.part[SL + i]);
       }
       if (t.tid == 0) {
         MPC_GST(info + 2, s.status_polish); MPC_GST(info + 4, s.nfact);
         if (prof) {   // (slot 0: the polish job as a whole; the sections add to the ADMM job's under MPC_SECTION_PROFILE)
           if constexpr (T <= 64 && !kSectionLaps) MPC_GST(prof, MPC_CLOCK() - t0);      // (no laps: the sections would add zero, and the ADMM job's store() left 0 in slot 0)
           else {
-            for (int k = 6; k < 15; ++k) if (k != 8 && k != 10) MPC_GST(prof + k, MPC_GLD(prof + k) + tc[k]);
+            for (int k = 6; k < 15; ++k) if (k != 8 && k != 10 && !(k == 6 && MPC_PROFILE_SUB == 10)) MPC_GST(prof + k, MPC_GLD(prof + k) + tc[k]);
+            if (MPC_PROFILE_SUB == 11) for (int k = 1; k <= 6; ++k) MPC_GST(prof + k, tc[k]);      // (this job's K-form alone, over what the ADMM job left there)
             MPC_GST(prof, MPC_GLD(prof) + (MPC_CLOCK() - t0));
           }
         }

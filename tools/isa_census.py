@@ -108,7 +108,10 @@ def loop_stats(txt, H):
         # one-job kernel and the persistent job kernel, whose job loops sit outside: roles go by content.)
         if a.get("rcp", 0) in (3, 6) and a["ins"] < 1000 and a["lds"] > 40:      # (a sweep trip publishes and fetches pivot rows: 100+ LDS instructions)
             a["role"] = "sweep"
-        elif a.get("dpp", 0) and a["ins"] < 700 and not a.get("rcp", 0):
+        elif a.get("dpp", 0) and a["ins"] < 700 and not a.get("rcp", 0) and a["dpp"] < 40:
+            # (ONE round of quad exchanges, 22 DPP moves at every horizon.  The polish's refinement step is the other tight loop with DPP moves and
+            #  no reciprocal: two products, 44 moves.  It was told apart by its size alone, 757-873 instructions, until the structured Theta
+            #  products brought it to 605-654 at h = 10.)
             a["role"] = "admm-iteration"
         elif a["ins"] > 2000 and a.get("dpp", 0):
             a["role"] = "check-loop"
