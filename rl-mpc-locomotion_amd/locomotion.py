@@ -181,11 +181,13 @@ class BatchedLocomotion:
         _lib.check(_lib.lib().mpc_ctrl_fsm_state(self._handle, out.ctypes.data), "mpc_ctrl_fsm_state")
         return out
 
-    def run_policy(self, policy, dof_states, body_states, commands3, prev_weights, request):
+    def run_policy(self, policy, dof_states, body_states, commands3, prev_weights, request, reset=None):
         """The batched ``RobotRunnerPolicy.run`` (robot_runner/RobotRunnerPolicy.py:62-92): StateEstimator.update, the weight
         policy on the fresh estimate (its "previous actions" observation slot carries the previous WEIGHTS, as there:
         ``compute_observations(dof, result, commands, self.weights)``), then the control FSM with those weights.
-        ``policy`` is a ``weight_policy.WeightPolicy``; returns (torques [N,12], weights [N,12])."""
+        ``policy`` is a ``weight_policy.WeightPolicy`` or a ``RecurrentWeightPolicy``; returns (torques [N,12], weights [N,12]).  ``reset`` [N] int64
+        on the device: given, it goes to the policy as ``policy.step(obs, reset=reset)`` -- a recurrent policy starts the flagged robots' memory from
+        zero on this tick."""
         import torch
         stream = _lib.stream(self.device)
         dof_states, body_states, commands3 = self._inputs(dof_states, body_states, commands3)
@@ -195,7 +197,7 @@ class BatchedLocomotion:
         _lib.check(_lib.lib().mpc_ctrl_update_estimate(self._handle, body_states.data_ptr(), stream), "mpc_ctrl_update_estimate")
         # the observations straight from the controller's estimate and ground_normal_yaw (no copies), and the FSM tick without a second StateEstimator.update
         obs = policy.observations_from(self, dof_states, commands3, prev_weights)
-        weights = policy.step(obs)
+        weights = policy.step(obs) if reset is None else policy.step(obs, reset=reset)
         return self.run_fsm(dof_states, body_states, policy.pack_commands(commands3, weights), request, estimated=True), weights
 
     def estimate(self):

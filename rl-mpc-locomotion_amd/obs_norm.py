@@ -128,11 +128,16 @@ def fold_normalizer(model_state_dict, obs_norm_state_dict, eps=1e-2, critic_obs_
     and the reference's loader then run a policy trained with normalisation unchanged.  ``critic_obs_norm_state_dict``: the statistics of the critic's
     own rows (a checkpoint of an asymmetric run carries them), folded into the critic in place of the actor's.
 
+    A recurrent ``model_state_dict`` (``memory_a.rnn.weight_ih_l0``): the observations enter through the memories, so the same formula folds the
+    actor's statistics into ``memory_a.rnn.weight_ih_l0`` / ``bias_ih_l0`` and the critic's (the actor's when there are none) into ``memory_c.rnn``'s;
+    ``actor.0`` / ``critic.0`` read the memories' outputs and pass through.
+
     The limit: where ``|mean_c| >> std_c`` the folded layer computes ``W' x - W' mean`` in float32 and the two cancel; a caller who needs better
     runs ``ObsNormalizer(...)(obs, update=False)`` in front of ``WeightPolicy.step`` instead."""
     out = dict(model_state_dict)
-    for net in ("actor", "critic"):
-        wk, bk = f"{net}.0.weight", f"{net}.0.bias"
+    recurrent = "memory_a.rnn.weight_ih_l0" in out
+    for net, memory in (("actor", "memory_a"), ("critic", "memory_c")):
+        wk, bk = (f"{memory}.rnn.weight_ih_l0", f"{memory}.rnn.bias_ih_l0") if recurrent else (f"{net}.0.weight", f"{net}.0.bias")
         if wk not in out:
             continue
         sd = critic_obs_norm_state_dict if net == "critic" and critic_obs_norm_state_dict is not None else obs_norm_state_dict

@@ -735,7 +735,8 @@ class PPOTrainer:
         return result
 
     def save(self, path):
-        """The checkpoint as rsl_rl writes it; ``WeightPolicy.from_state_dict(torch.load(path)["model_state_dict"])`` loads its actor.  With
+        """The checkpoint as rsl_rl writes it; ``WeightPolicy.from_state_dict(torch.load(path)["model_state_dict"])`` loads its actor.  A recurrent
+        trainer's checkpoint loads through the same call as a ``RecurrentWeightPolicy`` (``memory_a`` and the actor; ``step(obs, reset=)``).  With
         normalisation on it also carries ``obs_norm_state_dict`` (rsl_rl 2.x's key), and the actor expects normalised observations:
         ``obs_norm.fold_normalizer(ck["model_state_dict"], ck["obs_norm_state_dict"])`` gives the state dict for raw ones.  With privileged observations as well it carries ``critic_obs_norm_state_dict``, the statistics of the critic's
         rows (``fold_normalizer(..., critic_obs_norm_state_dict=)``); ``load`` refuses a checkpoint whose critic reads rows of another width.  On an environment with

@@ -22,7 +22,10 @@ iteration's last row, and the next ``act`` consumes that row a second time; here
 once.  ``split_and_pad_trajectories`` pads every piece to T, always: v1.0.2 pads to the longest piece, and its ``unpad_trajectories`` then fails when
 every environment had a ``done``.
 
-Not built: GRU, stacked layers, the device update through time, deployment of a recurrent actor in ``WeightPolicy`` / ``RobotRunnerPolicy``.
+Deployment: ``WeightPolicy.from_state_dict`` on a recurrent checkpoint's ``model_state_dict`` gives a ``weight_policy.RecurrentWeightPolicy``, whose ``step`` is
+``memory_a``'s cell and the actor in one launch (csrc/recurrent_policy.h).
+
+Not built: GRU, stacked layers, the device update through time.
 
 The torch paths (``step_torch``, ``log_prob_entropy_value``, the split / pad functions) run on the CPU in any dtype; the device entry points need the
 GPU (MpcLibraryError without one) and have no CPU fallback.
