@@ -327,6 +327,30 @@ class RolloutStorage:
                 yield RecurrentBatch(padded_obs[:, k0:k1], None if padded_critic is None else padded_critic[:, k0:k1], masks[:, k0:k1],
                                      *(x[:, e0:e1] for x in slices), (hid[0], hid[1]), (hid[2], hid[3]))
 
+    def recurrent_sequence_generator(self, num_mini_batches, num_epochs=8):
+        """The dense form of ``recurrent_mini_batch_generator``: the same blocks of N // num_mini_batches environments in the same order, without
+        padding, ``nonzero`` or a host read.  Yields ``RecurrentSequenceBatch``: the block's observations (and critic rows, or None) as strided views
+        ``[:, e0:e1]`` of the storage, ``reset`` [T][block] int64 (reset[0] = 0, reset[t] = dones[t-1]; built once per call for all blocks), the
+        [T][block] slices, and for each memory (h0, c0) = ``saved_*[0][e0:e1]``.  Equal to the padded trajectories where the saved states are zero
+        after each done, which is how the collection stores them."""
+        from .recurrent import RecurrentSequenceBatch
+        if self.hidden is None:
+            raise ValueError("the storage keeps no hidden states (RolloutStorage(hidden=))")
+        block = self.n // num_mini_batches
+        if block < 1:
+            raise ValueError("fewer environments than mini-batches")
+        reset = torch.zeros((self.T, self.n), dtype=torch.long, device=self.device)
+        reset[1:] = self.dones[:-1, :, 0] != 0
+        used = num_mini_batches * block
+        reset = reset[:, :used].reshape(self.T, num_mini_batches, block).permute(1, 0, 2).contiguous()      # [mini-batch][T][block], dense per block
+        slices = (self.actions, self.values, self.advantages, self.returns, self.actions_log_prob, self.mu, self.sigma)
+        for _ in range(num_epochs):
+            for i in range(num_mini_batches):
+                e0, e1 = i * block, (i + 1) * block
+                yield RecurrentSequenceBatch(self.observations[:, e0:e1], None if self.privileged_observations is None else self.privileged_observations[:, e0:e1],
+                                             reset[i], *(x[:, e0:e1] for x in slices), (self.saved_h_a[0, e0:e1], self.saved_c_a[0, e0:e1]),
+                                             (self.saved_h_c[0, e0:e1], self.saved_c_c[0, e0:e1]))
+
     def clear(self):
         self.step = 0
 
@@ -342,7 +366,8 @@ class PPO:
             raise ValueError("backend is 'torch' or 'hip'")
         self.recurrent = bool(getattr(actor_critic, "is_recurrent", False))
         if self.recurrent and backend == "hip":                                   # (before anything asks for the device)
-            raise ValueError('PPO(backend="hip") with a recurrent actor-critic: backward through time on the device is not built; use backend="torch"')
+            raise ValueError('PPO(backend="hip") with a recurrent actor-critic: the MLPs, the loss head and Adam of a recurrent device update are not built (the '
+                             'memories\' update through time is: RecurrentConfig(update_through_time="hip")); use backend="torch"')
         self.cfg = cfg if cfg is not None else PPOConfig()
         self.actor_critic = actor_critic
         self.backend = backend
@@ -377,7 +402,8 @@ class PPO:
         c = self.cfg
         if self.recurrent:
             b = batch
-            out = self.actor_critic.log_prob_entropy_value(b.obs, b.actions, b.critic_obs, masks=b.masks, hidden_states=(b.hidden_a, b.hidden_c))
+            form = {"reset": b.reset} if hasattr(b, "reset") else {"masks": b.masks}      # the dense roll (recurrent_sequence_generator) or padded trajectories
+            out = self.actor_critic.log_prob_entropy_value(b.obs, b.actions, b.critic_obs, hidden_states=(b.hidden_a, b.hidden_c), **form)
             logp, entropy, value, mu, sigma = (x.flatten(0, 1) for x in out)       # [T][block][..] -> [T block][..], as the feed-forward batch has them
             actions, old_values, adv, returns, old_logp, old_mu, old_sigma = (x.flatten(0, 1) for x in (b.actions, b.values, b.advantages, b.returns,
                                                                                                         b.old_log_prob, b.old_mu, b.old_sigma))
@@ -522,6 +548,8 @@ class PPO:
         c = self.cfg
         mean_value, mean_surrogate, k = 0.0, 0.0, 0
         generator = storage.recurrent_mini_batch_generator if self.recurrent else storage.mini_batch_generator
+        if self.recurrent and getattr(self.actor_critic, "update_through_time", "torch") == "hip":
+            generator = storage.recurrent_sequence_generator                      # the memories' update through time on the device: the dense roll
         for batch in generator(c.num_mini_batches, c.num_learning_epochs):
             surrogate, value_loss, entropy, kl = self.losses(batch)
             if c.desired_kl is not None and c.schedule == "adaptive":
@@ -560,12 +588,15 @@ class PPOTrainer:
 
     ``recurrent=RecurrentConfig(hidden_size=...)`` (``recurrent.py``; None, the default: today's path and launches) trains an ``ActorCriticRecurrent``:
     each tick's ``act`` is handed the task's reset tensor of the tick before (the memories start an episode from zero state) and slot t's views of the
-    storage's saved hidden states -- nothing more is copied per tick -- and the update is the torch one over padded trajectories.  The memories read
-    what the MLPs' first layers read otherwise: the normalised observation, the (normalised) privileged rows.  ``update="hip"`` is refused."""
+    storage's saved hidden states -- nothing more is copied per tick -- and the update is the torch one over padded trajectories, or, with
+    ``RecurrentConfig(update_through_time="hip")``, torch's MLPs, loss and Adam around the memories' roll and backward pass on the device (no padding,
+    no host read besides the adaptive schedule's kl).  The memories read what the MLPs' first layers read otherwise: the normalised observation, the
+    (normalised) privileged rows.  ``update="hip"`` is refused."""
 
     def __init__(self, env, cfg=None, seed=1, device=None, update="torch", normalize_obs=False, obs_norm_eps=1e-2, obs_norm_until=None, recurrent=None):
         if recurrent is not None and update == "hip":                            # (PPO's own refusal, before the device is asked for)
-            raise ValueError('PPOTrainer(update="hip") with recurrent=: backward through time on the device is not built; use update="torch"')
+            raise ValueError('PPOTrainer(update="hip") with recurrent=: the MLPs, the loss head and Adam of a recurrent device update are not built (the memories\' '
+                             'update through time is: RecurrentConfig(update_through_time="hip")); use update="torch"')
         need_gpu("PPOTrainer")
         self.cfg = cfg if cfg is not None else PPOConfig()
         self.env, self.seed = env, int(seed)
@@ -582,7 +613,8 @@ class PPOTrainer:
             from .recurrent import ActorCriticRecurrent
             self.actor_critic = ActorCriticRecurrent(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std, num_critic_obs=priv,
                                                      rnn_type=recurrent.rnn_type, rnn_hidden_size=recurrent.hidden_size,
-                                                     rnn_num_layers=recurrent.num_layers).to(self.device)
+                                                     rnn_num_layers=recurrent.num_layers,
+                                                     update_through_time=getattr(recurrent, "update_through_time", "torch")).to(self.device)
         self.alg = PPO(self.actor_critic, c, backend=update)
         hidden = None if recurrent is None else (int(recurrent.hidden_size), int(recurrent.hidden_size))
         self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions, num_privileged_obs=priv,

@@ -16,6 +16,11 @@ two alternating block by block in one process: the cell launch alone, a recurren
 whole iteration (collection + torch update) of each trainer; the cell launch is reported as a share of the 0.82 ms control step and against the weight
 bytes it streams.  --baseline times the feed-forward trainer alone.
     python tools/ppo_rate.py --recurrent [--hidden 256] [--baseline] [--out profiles/recurrent_rate.json]
+--recurrent --through-time hip times the recurrent trainer with the memories' update through time on the device (RecurrentConfig(update_through_time="hip"),
+csrc/recurrent_bptt.h) against the recurrent trainer with the torch update, the two alternating block by block in one process -- the "torch" trainer makes
+the launches it made before the option existed -- : collection, update and whole iteration of each, and on one mini-batch of the "hip" trainer's storage
+the forward launch, the whole backward call and the weight-gradient GEMMs with their reduction alone (the launch through time is the difference).
+    python tools/ppo_rate.py --recurrent --through-time hip [--hidden 256] [--out profiles/recurrent_bptt_rate.json]
 The kernel-trace stats: rocprofv3 --kernel-trace --stats ... -- python tools/ppo_rate.py --quick   (3 collections and one update per backend)"""
 import argparse
 import json
@@ -206,6 +211,71 @@ def recurrent_report(args, dev, n):
     return res
 
 
+def through_time_report(args, dev, n):
+    """The recurrent trainer with ``update_through_time="hip"`` against the one with the torch update: see the head of this file."""
+    from bench import device_state
+    from rl_mpc_locomotion_amd.recurrent import ACTOR, CRITIC, RecurrentConfig
+    cfg = PPOConfig()
+    T, H = cfg.num_steps_per_env, args.hidden
+    trainers = {k: PPOTrainer(make_env(n, dev), cfg, seed=1, recurrent=RecurrentConfig(hidden_size=H, update_through_time=k)) for k in ("torch", "hip")}
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "num_steps_per_env": T, "repeats": args.repeats, "hidden_size": H,
+           "mini_batches_per_update": cfg.num_learning_epochs * cfg.num_mini_batches, "block_of_environments": n // cfg.num_mini_batches,
+           "device_state": {"before": device_state(0)}}
+    for tr in trainers.values():          # warm-up: cold solves, code objects, torch's kernels, Adam's state, the handle's workspace
+        tr.learn(2)
+    torch.cuda.synchronize()
+    times = {k: {"collect": [], "update": [], "full": []} for k in trainers}
+    names = list(trainers)
+    for rep in range(args.repeats):       # which one goes first alternates
+        for name in (names if rep % 2 == 0 else names[::-1]):
+            tr = trainers[name]
+            a, b, c = ev(), ev(), ev()
+            a.record()
+            tr.collect()
+            b.record()
+            tr.alg.update(tr.storage)
+            c.record()
+            torch.cuda.synchronize()
+            tb = times[name]
+            tb["collect"].append(a.elapsed_time(b)); tb["update"].append(b.elapsed_time(c)); tb["full"].append(a.elapsed_time(c))
+    for name, tb in times.items():
+        res[name] = {k: stats(v) for k, v in tb.items()}
+        res[name]["robot_ticks_per_s_training"] = n * T / (float(np.median(tb["full"])) * 1e-3)
+    res["hip_over_torch_median"] = {k: res["hip"][k]["median_ms"] / res["torch"][k]["median_ms"] for k in ("collect", "update", "full")}
+    res["hip_p90_below_torch_p10"] = {k: bool(res["hip"][k]["p90_ms"] < res["torch"][k]["p10_ms"]) for k in ("update", "full")}
+    # the device calls on their own, on the first mini-batch of the "hip" trainer's storage: both memories in every call
+    tr = trainers["hip"]
+    tr.collect()
+    kernel = tr.actor_critic._seq
+    b = next(tr.storage.recurrent_sequence_generator(cfg.num_mini_batches, 1))
+    B = b.obs.shape[1]
+    rows = (b.obs, b.obs if b.critic_obs is None else b.critic_obs)
+    h0s, c0s = (b.hidden_a[0], b.hidden_c[0]), (b.hidden_a[1], b.hidden_c[1])
+    dys = [torch.randn(T, B, H, device=dev) * 1e-3 for _ in range(2)]
+    calls = {"forward": lambda: kernel.forward((ACTOR, CRITIC), rows, h0s, c0s, b.reset),
+             "backward": lambda: kernel.backward((ACTOR, CRITIC), T, B, dys),
+             "weight_gradients": lambda: kernel.backward((ACTOR, CRITIC), T, B, dys, entry="mpc_recurrent_bptt_weight_gradients")}
+    spans = {k: [] for k in calls}
+    for k in calls:                       # (forward first: the others go back through it)
+        calls[k]()
+    for rep in range(max(args.repeats, 3) * 3):
+        for k in calls:
+            a, c = ev(), ev()
+            a.record()
+            calls[k]()
+            c.record()
+            torch.cuda.synchronize()
+            spans[k].append(a.elapsed_time(c))
+    res["calls_on_one_mini_batch"] = {k: stats(v) for k, v in spans.items()}
+    med = lambda k: res["calls_on_one_mini_batch"][k]["median_ms"]
+    res["calls_on_one_mini_batch"]["through_time_launch_and_transposition_ms"] = med("backward") - med("weight_gradients")
+    res["device_calls_per_update_ms"] = res["mini_batches_per_update"] * (med("forward") + med("backward"))
+    res["workspace_bytes"] = kernel.workspace_bytes()
+    res["workgroups_per_sequence_launch"] = 2 * ((B + 15) // 16)
+    res["device_state"]["after"] = device_state(0, smi=False)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--robots", type=int, default=4096)
@@ -216,13 +286,19 @@ if __name__ == "__main__":
     ap.add_argument("--baseline", action="store_true", help="--privileged / --recurrent: the symmetric / feed-forward trainer alone (runs on a tree without the option)")
     ap.add_argument("--recurrent", action="store_true", help="the recurrent actor-critic against the feed-forward one (see the head of this file)")
     ap.add_argument("--hidden", type=int, default=256, help="--recurrent: the memories' hidden size")
+    ap.add_argument("--through-time", choices=("hip",), help="--recurrent: the update through time on the device against the torch update (see the head of this file)")
     ap.add_argument("--out")
     args = ap.parse_args()
+    if args.through_time and not args.recurrent:
+        ap.error("--through-time goes with --recurrent")
     if not torch.cuda.is_available():
         sys.exit("ppo_rate.py measures on the GPU; none is visible")
     dev, n = "cuda:0", args.robots
     if args.privileged or args.recurrent:
-        res = recurrent_report(args, dev, n) if args.recurrent else privileged_report(args, dev, n)
+        if args.recurrent:
+            res = through_time_report(args, dev, n) if args.through_time else recurrent_report(args, dev, n)
+        else:
+            res = privileged_report(args, dev, n)
         print(json.dumps(res, indent=1))
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
