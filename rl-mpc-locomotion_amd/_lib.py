@@ -161,6 +161,30 @@ def tensor_arg(t, dtype, numel, name):
     return t
 
 
+def int_array(values):
+    """A C ``int`` array of ``values``, as the ``const int *`` argument of a create."""
+    return C.cast((C.c_int * len(values))(*values), C.c_void_p)
+
+
+def ptr_array(addresses):
+    """A C array of pointers, as the ``const float *const *`` argument of a bind."""
+    return C.cast((C.c_void_p * len(addresses))(*addresses), C.c_void_p)
+
+
+def addresses_to_bind(tensors, bound, device, message, like=None):
+    """Bind-by-pointer: the addresses of ``tensors``, for the caller to bind and keep -- or None where they are the tuple ``bound`` of the last
+    bind (None: never bound), the steady state, which costs this comparison alone.  Tensors that have to be bound are checked first: float32,
+    contiguous, on ``device`` and, with ``like``, shaped like their counterparts there; ``ValueError(message)`` otherwise."""
+    ptrs = tuple(t.data_ptr() for t in tensors)
+    if ptrs == bound:
+        return None
+    import torch
+    for i, t in enumerate(tensors):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != device or (like is not None and t.shape != like[i].shape):
+            raise ValueError(message)
+    return ptrs
+
+
 def flag_arg(t, n, name):
     """tensor_arg for a flag array, which may be bool or uint8 (one byte either way)."""
     import torch

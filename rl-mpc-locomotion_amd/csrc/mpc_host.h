@@ -7,6 +7,8 @@
 //                      a plain `T *d_x` is memory of somebody else's
 //   ErrorSlot, HIP_TRY the text behind mpc_*_last_error and the check of a HIP call
 //   round16            a byte rounding
+//   aligned16, present16, Range, any_overlap   the pointer checks in front of 16-byte loads and of a call's output arrays
+//   LdsLimit           a kernel's dynamic-LDS limit, grow-only per device
 //
 // A unit keeps its own slot, and with it its own mpc_*_last_error, and names the slot's setter `fail`:
 //   namespace {
@@ -19,6 +21,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
+#include <map>
+#include <mutex>
 #include <string>
 
 namespace mpchost {
@@ -100,6 +105,44 @@ struct ErrorSlot : std::string {
 };
 
 inline size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// What a kernel's 16-byte loads ask of a pointer.  aligned16 lets null through: an optional array is checked like the others and a required one
+// has its own null check, with its own message, in front.  present16 is for the entry points whose one message is "non-null and 16-byte aligned".
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool present16(const void *p) { return p && aligned16(p); }
+
+// The byte ranges of the arrays a call writes: any_overlap is true where two of them share a byte.  A null range overlaps nothing.
+struct Range { const void *p; size_t bytes; };
+inline bool any_overlap(const Range *r, int n) {
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j) {
+      const uintptr_t a = reinterpret_cast<uintptr_t>(r[i].p), b = reinterpret_cast<uintptr_t>(r[j].p);
+      if (a && b && a < b + r[j].bytes && b < a + r[i].bytes) return true;
+    }
+  return false;
+}
+
+// The dynamic-LDS limit of one kernel (hipFuncAttributeMaxDynamicSharedMemorySize): one value per device and kernel, not one per handle, so it
+// only ever grows -- a handle with a narrow net, made after one with a wide net, must not take the wide one's launches away (DESIGN.md section
+// 8.4, "Two conventions of the C ABI units").  One instance per kernel, in the unit that launches it; raise() runs with the handle's device current.
+class LdsLimit {
+ public:
+  template <typename... Args>
+  explicit LdsLimit(void (*kernel)(Args...)) : kernel_(reinterpret_cast<const void *>(kernel)) {}
+  hipError_t raise(int device, size_t bytes) {
+    std::lock_guard<std::mutex> lock(mutex_);
+    size_t &limit = limit_[device];
+    if (bytes <= limit) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) limit = bytes;
+    return e;
+  }
+
+ private:
+  const void *kernel_;
+  std::mutex mutex_;
+  std::map<int, size_t> limit_;
+};
 
 }  // namespace mpchost
 

@@ -17,15 +17,11 @@
 #include "../../include/mpc_ppo.h"
 #include "mpc_ac_internal.h"
 #include "mpc_host.h"
+#include "policy_mlp.h"
 #include "ppo_rollout.h"
 
-// policy_mlp.h defines its kernels with external linkage and mpc_batch.hip has them already: inside this unit's unnamed namespace the second copy
-// gets internal names.  (Its one system header is included above, so nothing but namespace policy lands in here.)
-namespace {
-#include "policy_mlp.h"
-}
-
 using mpchost::DeviceGuard;
+using mpchost::present16;
 
 namespace {
 thread_local mpchost::ErrorSlot g_err;
@@ -53,7 +49,7 @@ __global__ __launch_bounds__(policy::kThreads) void ac_kernel(Nets nets, int fir
   const int which = first_net + (int)blockIdx.y;
   const policy::Net &net = nets.net[which];
   const float *__restrict__ obs = which == kCritic ? critic_obs : actor_obs;
-  int wmax_even = 0, wmax_odd = 0;     // widest activation held by buffer 0 (layers 0, 2, ...) / buffer 1, as policy::mlp_kernel lays them out
+  int wmax_even = 0, wmax_odd = 0;     // widest activation held by buffer 0 (layers 0, 2, ...) / buffer 1, as mpc_batch.hip's mlp_kernel lays them out
   for (int l = 0; l <= net.n_layers; ++l) {
     int &m = (l & 1) ? wmax_odd : wmax_even;
     m = net.dims[l] > m ? net.dims[l] : m;
@@ -104,6 +100,8 @@ __global__ __launch_bounds__(policy::kThreads) void ac_kernel(Nets nets, int fir
   if (e < policy::kRows && r0 + e < n) out.log_prob[r0 + e] = ppo::log_prob_sum(terms + e * ppo::kActions);
 }
 
+mpchost::LdsLimit g_ac_limit(ac_kernel);
+
 __global__ __launch_bounds__(kLaneThreads) void rollout_add_kernel(int n, float gamma, const float *__restrict__ rew, const long long *__restrict__ reset,
                                                                    const long long *__restrict__ timeout, const float *__restrict__ values_t,
                                                                    float *__restrict__ rewards_t, float *__restrict__ dones_t) {
@@ -151,7 +149,6 @@ __global__ __launch_bounds__(kNormThreads) void normalise_kernel(size_t m, float
   for (size_t i = threadIdx.x; i < m; i += kNormThreads) adv[i] = ppo::normalise_one(adv[i], mean, std);
 }
 
-bool aligned16(const void *p) { return p && (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool unit_interval(double x) { return std::isfinite(x) && x >= 0.0 && x <= 1.0; }
 
 // the limits of mpc_policy_create on one stack, with the width of its output fixed
@@ -238,11 +235,11 @@ int mpc_ac_bind(mpc_ac *ac, const float *const *d_actor_weights, const float *co
   const float *const *b[2] = {d_actor_biases, d_critic_biases};
   for (int k = 0; k < 2; ++k)
     for (int l = 0; l < ac->nets.net[k].n_layers; ++l)
-      if (!aligned16(w[k][l]) || !aligned16(b[k][l])) return fail(MPC_E_ARG, "mpc_ac_bind: every weight and bias pointer must be non-null and 16-byte aligned");
-  if (!aligned16(d_std)) return fail(MPC_E_ARG, "mpc_ac_bind: d_std must be non-null and 16-byte aligned");
+      if (!present16(w[k][l]) || !present16(b[k][l])) return fail(MPC_E_ARG, "mpc_ac_bind: every weight and bias pointer must be non-null and 16-byte aligned");
+  if (!present16(d_std)) return fail(MPC_E_ARG, "mpc_ac_bind: d_std must be non-null and 16-byte aligned");
   const int dev = mpchost::current_device();
   if (dev < 0) return fail(MPC_E_NODEVICE, "mpc_ac_bind: no HIP device");
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(ac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ac->lds) != hipSuccess)
+  if (g_ac_limit.raise(dev, ac->lds) != hipSuccess)
     return fail(MPC_E_HIP, "mpc_ac_bind: device set-up failed");
   for (int k = 0; k < 2; ++k)
     for (int l = 0; l < ac->nets.net[k].n_layers; ++l) {

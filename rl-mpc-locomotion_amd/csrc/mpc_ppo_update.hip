@@ -1,9 +1,9 @@
 // mpc_ppo_update.hip -- the C ABI of include/mpc_ppo_update.h: the update half of a PPO iteration on the device.
-//   pgemm::gemm_kernel   forward, backward-data and backward-weight GEMMs of both nets (ppo_gemm.h), actor and critic in one launch per layer
+//   pgemm::launch        forward, backward-data and backward-weight GEMMs of both nets (mpc_ppo_gemm.hip), actor and critic in one launch per layer
 //   head_kernel          one lane per row: ppo::head_row on the forward pass's mean and value and the indexed storage rows; writes d loss / d mu and
 //                        d loss / d V where the backward pass reads them, and one float64 partial per workgroup and quantity (fixed-order LDS sums)
 //   head_reduce_kernel   ONE workgroup joins the partials in index order: the four terms, d loss / d std, the learning-rate decision
-//   pgemm::reduce_kernel the weight-gradient chunks, and the bias gradients, summed in index order into the .grad tensors
+//   pgemm::reduce        the weight-gradient chunks, and the bias gradients, summed in index order into the .grad tensors
 //   norm_partial_kernel  the sum of squares of every gradient element in float64, one partial per 4096 elements of a tensor (fixed-order LDS tree), and
 //   norm_kernel          ONE workgroup joins the partials in a fixed order, as normalise_kernel of mpc_ppo.hip does
 //   adam_kernel          every parameter tensor in one launch (blockIdx.y picks the tensor): ppo::adam_element
@@ -17,10 +17,11 @@
 #include "../../include/mpc_ppo_update.h"
 #include "mpc_ac_internal.h"
 #include "mpc_host.h"
-#include "ppo_gemm.h"
+#include "ppo_gemm_plan.h"
 #include "ppo_update.h"
 
 using mpchost::DeviceGuard;
+using mpchost::present16;
 
 namespace {
 int fail(int code, const std::string &msg) { return mpc_ppo_set_error(code, msg.c_str()); }      // (mpc_ppo.hip's slot: one mpc_ppo_last_error for both halves)
@@ -175,24 +176,11 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamTable t, ppo::AdamCfg cfg
   t.p[k][i] = p; t.g[k][i] = g; t.m[k][i] = m; t.v[k][i] = v;
 }
 
-bool aligned16(const void *p) { return p && (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 int round16(int x) { return (x + 15) / 16 * 16; }
 
-// the plan (tile, backward-weight chunking, grid) is ppo_gemm_plan.h's; this fills it into the launch and starts the instantiation it names
-template <int KIND>
-int launch_gemm(pgemm::Launch &L, hipStream_t s) {
-  const pgemm::Shape shape[2] = {{L.p[0].M, L.p[0].N, L.p[0].K}, {L.p[1].M, L.p[1].N, L.p[1].K}};
-  const pgemm::Plan plan = pgemm::plan_gemm(KIND, shape);
-  for (int k = 0; k < 2; ++k) {
-    pgemm::Problem &p = L.p[k];
-    p.tiles_m = plan.p[k].tiles_m;
-    p.tiles_n = plan.p[k].tiles_n;
-    p.chunks = plan.p[k].chunks;
-    if (KIND == pgemm::kBackwardWeight) p.chunk_rows = plan.chunk_rows;
-  }
-  if (plan.grid_x == 0) return MPC_OK;
-  if (plan.wide) hipLaunchKernelGGL((pgemm::gemm_kernel<KIND, 2, 2>), dim3(plan.grid_x, 2), dim3(pgemm::kThreads), 0, s, L);
-  else hipLaunchKernelGGL((pgemm::gemm_kernel<KIND, 2, 1>), dim3(plan.grid_x, 2), dim3(pgemm::kThreads), 0, s, L);
+// one GEMM launch of both nets through mpc_ppo_gemm.hip, which fills the plan's tiles and chunks into L
+int launch_gemm(pgemm::Kind kind, pgemm::Launch &L, hipStream_t s) {
+  pgemm::launch(kind, L, s);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
@@ -288,7 +276,7 @@ int mpc_ppo_update_bind(mpc_ppo_update *u, float *const *d_grads, float *const *
   if (!u || !d_grads) return fail(MPC_E_ARG, "mpc_ppo_update_bind: bad argument");
   if ((d_exp_avg == nullptr) != (d_exp_avg_sq == nullptr)) return fail(MPC_E_ARG, "mpc_ppo_update_bind: both moments or neither");
   for (int t = 0; t < u->n_tensors; ++t)
-    if (!aligned16(d_grads[t]) || (d_exp_avg && (!aligned16(d_exp_avg[t]) || !aligned16(d_exp_avg_sq[t]))))
+    if (!present16(d_grads[t]) || (d_exp_avg && (!present16(d_exp_avg[t]) || !present16(d_exp_avg_sq[t]))))
       return fail(MPC_E_ARG, "mpc_ppo_update_bind: every gradient and moment pointer must be non-null and 16-byte aligned");
   for (int t = 0; t < u->n_tensors; ++t) {
     u->grad[t] = d_grads[t];
@@ -303,7 +291,7 @@ int mpc_ppo_update_bind(mpc_ppo_update *u, float *const *d_grads, float *const *
 int mpc_ppo_update_set_storage(mpc_ppo_update *u, long long total_rows, const float *d_obs, const float *d_actions, const float *d_values,
                                const float *d_advantages, const float *d_returns, const float *d_log_prob, const float *d_mu, const float *d_sigma) {
   if (!u || total_rows <= 0 || !d_values || !d_advantages || !d_returns || !d_log_prob) return fail(MPC_E_ARG, "mpc_ppo_update_set_storage: bad argument");
-  if (!aligned16(d_obs) || !aligned16(d_actions) || !aligned16(d_mu) || !aligned16(d_sigma))
+  if (!present16(d_obs) || !present16(d_actions) || !present16(d_mu) || !present16(d_sigma))
     return fail(MPC_E_ARG, "mpc_ppo_update_set_storage: d_obs, d_actions, d_mu and d_sigma must be non-null and 16-byte aligned");
   u->st = Storage{d_obs, d_actions, d_values, d_advantages, d_returns, d_log_prob, d_mu, d_sigma, total_rows};
   u->storage_set = true;
@@ -311,7 +299,7 @@ int mpc_ppo_update_set_storage(mpc_ppo_update *u, long long total_rows, const fl
 }
 
 int mpc_ppo_update_set_critic_storage(mpc_ppo_update *u, const float *d_critic_obs) {
-  if (d_critic_obs && (reinterpret_cast<uintptr_t>(d_critic_obs) & 15u))
+  if (!mpchost::aligned16(d_critic_obs))
     return fail(MPC_E_ARG, "mpc_ppo_update_set_critic_storage: d_critic_obs must be 16-byte aligned");
   if (!u) return fail(MPC_E_ARG, "mpc_ppo_update_set_critic_storage: bad argument");
   u->critic_obs = d_critic_obs;                 // (null: back to the actor's rows)
@@ -354,7 +342,7 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
       p.elu = l + 1 < u->nl[k];
       p.chunks = 1;
     }
-    if (int rc = launch_gemm<pgemm::kForward>(L, s)) return rc;
+    if (int rc = launch_gemm(pgemm::kForward, L, s)) return rc;
   }
 
   // the loss head
@@ -395,10 +383,10 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
       q.M = rows; q.N = nin; q.K = nout;
       q.chunks = 1;
     }
-    if (int rc = launch_gemm<pgemm::kBackwardWeight>(W, s)) return rc;
+    if (int rc = launch_gemm(pgemm::kBackwardWeight, W, s)) return rc;
     for (int k = 0; k < 2; ++k)
       if (u->nl[k] - 1 - sidx >= 0) dw_chunks[k][u->nl[k] - 1 - sidx] = W.p[k].chunks;
-    if (int rc = launch_gemm<pgemm::kBackwardData>(D, s)) return rc;
+    if (int rc = launch_gemm(pgemm::kBackwardData, D, s)) return rc;
   }
 
   // the chunks in index order into .grad
@@ -411,7 +399,7 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
       rt.e[ne++] = pgemm::ReduceEntry{u->dbp[k][l], u->grad[u->b_index(k, l)], nout, dw_chunks[k][l]};
       maxn = nout * nin > maxn ? nout * nin : maxn;
     }
-  hipLaunchKernelGGL(pgemm::reduce_kernel, dim3((unsigned)((maxn + pgemm::kThreads - 1) / pgemm::kThreads), (unsigned)ne), dim3(pgemm::kThreads), 0, s, rt);
+  pgemm::reduce(rt, ne, maxn, s);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
 }

@@ -3,29 +3,26 @@
 //                        activations, c' and the state each step started from in the handle's workspace
 //   transpose_kernel     W_hh -> W_hh^T, once per backward call
 //   seq_backward_kernel  the same grid, t descending: dG[t] to LDS and the workspace, dh_rec = dG[t] W_hh on the MFMA pipe, dc_rec in registers
-//   pgemm::gemm_kernel   backward weight: dW_ih = dG^T X (X through the row index the forward launch wrote), then dW_hh = dG^T h_used; both
-//                        memories in one launch each
+//   pgemm::launch        backward weight (ppo_gemm.h's gemm_kernel, which mpc_ppo_gemm.hip owns): dW_ih = dG^T X (X through the row index the
+//                        forward launch wrote), then dW_hh = dG^T h_used; both memories in one launch each
 //   column_sum_kernel    the column sums of dG per chunk of 256 rows, in float64
-//   pgemm::reduce_kernel the chunks in index order into the caller's gradient arrays
+//   pgemm::reduce        the chunks in index order into the caller's gradient arrays
 // The parameters are read through the caller's pointers.  No atomics, no scratch; nothing synchronises.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <map>
-#include <mutex>
 #include <string>
 
 #include "mpc_host.h"
 #include "mpc_recurrent_bptt.h"
-
-// recurrent_bptt.h brings recurrent_cell.h and ppo_gemm.h with it, which define kernels with external linkage that mpc_recurrent.hip and
-// mpc_ppo_update.hip have already: inside this unit's unnamed namespace the second copies get internal names (mpc_recurrent_policy.hip's arrangement).
-namespace {
 #include "recurrent_bptt.h"
-}
+#include "recurrent_host.h"
 
+using mpchost::aligned16;
+using mpchost::any_overlap;
 using mpchost::DeviceArray;
 using mpchost::DeviceGuard;
+using mpchost::Range;
 
 static_assert(MPC_RECURRENT_BPTT_MEMORIES == recurrent::kMemories, "mpc_recurrent_bptt.h and recurrent_cell.h disagree");
 static_assert(bptt::kSumRows == pgemm::kMinChunk, "the column sums' partials are counted with the GEMMs'");
@@ -34,53 +31,7 @@ namespace {
 thread_local mpchost::ErrorSlot g_err;
 int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-struct Range {
-  const void *p;
-  size_t bytes;
-};
-bool overlap(const Range &a, const Range &b) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
-  return a.p && b.p && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-bool any_overlap(const Range *r, int n) {
-  for (int i = 0; i < n; ++i)
-    for (int j = i + 1; j < n; ++j)
-      if (overlap(r[i], r[j])) return true;
-  return false;
-}
-
-// The kernels' dynamic-LDS limits are one per device, not one per handle: they only ever grow (mpc_recurrent_policy.hip's rule).
-std::mutex g_limit_mutex;
-std::map<int, size_t> g_limit[2];
-hipError_t raise_lds_limit(int device, int which, size_t bytes) {
-  std::lock_guard<std::mutex> lock(g_limit_mutex);
-  size_t &limit = g_limit[which][device];
-  if (bytes <= limit) return hipSuccess;
-  const void *f = which == 0 ? reinterpret_cast<const void *>(bptt::seq_forward_kernel) : reinterpret_cast<const void *>(bptt::seq_backward_kernel);
-  const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) limit = bytes;
-  return e;
-}
-
-// mpc_ppo_update.hip's: the plan (tile, chunking, grid) is ppo_gemm_plan.h's
-int launch_backward_weight(pgemm::Launch &L, hipStream_t s) {
-  const pgemm::Shape shape[2] = {{L.p[0].M, L.p[0].N, L.p[0].K}, {L.p[1].M, L.p[1].N, L.p[1].K}};
-  const pgemm::Plan plan = pgemm::plan_gemm(pgemm::kBackwardWeight, shape);
-  for (int k = 0; k < 2; ++k) {
-    pgemm::Problem &p = L.p[k];
-    p.tiles_m = plan.p[k].tiles_m;
-    p.tiles_n = plan.p[k].tiles_n;
-    p.chunks = plan.p[k].chunks;
-    p.chunk_rows = plan.chunk_rows;
-  }
-  if (plan.grid_x == 0) return MPC_OK;
-  if (plan.wide) hipLaunchKernelGGL((pgemm::gemm_kernel<pgemm::kBackwardWeight, 2, 2>), dim3(plan.grid_x, 2), dim3(pgemm::kThreads), 0, s, L);
-  else hipLaunchKernelGGL((pgemm::gemm_kernel<pgemm::kBackwardWeight, 2, 1>), dim3(plan.grid_x, 2), dim3(pgemm::kThreads), 0, s, L);
-  HIP_TRY(hipGetLastError());
-  return MPC_OK;
-}
+mpchost::LdsLimit g_forward_limit(bptt::seq_forward_kernel), g_backward_limit(bptt::seq_backward_kernel);
 }  // namespace
 
 struct mpc_recurrent_bptt {
@@ -135,8 +86,8 @@ int mpc_recurrent_bptt_create(mpc_recurrent_bptt **out, int memories, const int 
   for (int k = 0; k < memories; ++k) {
     const int I = input_sizes[k], H = hidden_sizes[k];
     const std::string mem = who + "memory " + std::to_string(k) + ": ";
-    if (I <= 0 || I % 16 != 0) return fail(MPC_E_ARG, mem + "the input size " + std::to_string(I) + " is not a positive multiple of 16");
-    if (H <= 0 || H % 16 != 0) return fail(MPC_E_ARG, mem + "the hidden size " + std::to_string(H) + " is not a positive multiple of 16");
+    const std::string why = recurrent::size_refusal(I, H);
+    if (!why.empty()) return fail(MPC_E_ARG, mem + why);
     const size_t f = bptt::forward_lds_bytes(I, H), b = bptt::backward_lds_bytes(H);
     if (f > (size_t)MPC_RECURRENT_BPTT_MAX_LDS)
       return fail(MPC_E_ARG, mem + "the forward pass's two buffers of 16 rows of " + std::to_string(I) + " + " + std::to_string(H) + " floats need " + std::to_string(f) +
@@ -166,12 +117,10 @@ int mpc_recurrent_bptt_create(mpc_recurrent_bptt **out, int memories, const int 
 
 int mpc_recurrent_bptt_bind(mpc_recurrent_bptt *h, const float *const *d_w_ih, const float *const *d_w_hh, const float *const *d_b_ih, const float *const *d_b_hh) {
   const std::string who = "mpc_recurrent_bptt_bind: ";
-  if (!h || !d_w_ih || !d_w_hh || !d_b_ih || !d_b_hh) return fail(MPC_E_ARG, who + "null argument");
-  for (int k = 0; k < h->memories; ++k) {
-    if (!d_w_ih[k] || !d_w_hh[k] || !d_b_ih[k] || !d_b_hh[k]) return fail(MPC_E_ARG, who + "memory " + std::to_string(k) + ": null parameter pointer");
-    if (!aligned16(d_w_ih[k]) || !aligned16(d_w_hh[k]) || !aligned16(d_b_ih[k]) || !aligned16(d_b_hh[k]))
-      return fail(MPC_E_ARG, who + "memory " + std::to_string(k) + ": every parameter pointer must be 16-byte aligned");
-  }
+  if (!h) return fail(MPC_E_ARG, who + "null argument");
+  const recurrent::Parameters params{d_w_ih, d_w_hh, d_b_ih, d_b_hh};
+  const std::string why = recurrent::bind_refusal(params, h->memories);
+  if (!why.empty()) return fail(MPC_E_ARG, who + why);
   if (h->device < 0) {                 // the first bind: the workspace
     const int dev = mpchost::current_device();
     if (dev < 0) return fail(MPC_E_NODEVICE, who + "no HIP device");
@@ -196,16 +145,11 @@ int mpc_recurrent_bptt_bind(mpc_recurrent_bptt *h, const float *const *d_w_ih, c
       w.x_index = h->x_index[k];
       HIP_TRY(hipMemset(w.w_hh_t, 0, sizeof(float) * wt));      // the rows past H stay zero
     }
-    HIP_TRY(raise_lds_limit(dev, 0, h->lds_forward));
-    HIP_TRY(raise_lds_limit(dev, 1, h->lds_backward));
+    HIP_TRY(g_forward_limit.raise(dev, h->lds_forward));
+    HIP_TRY(g_backward_limit.raise(dev, h->lds_backward));
     h->device = dev;
   }
-  for (int k = 0; k < h->memories; ++k) {
-    h->cell[k].w_ih = d_w_ih[k];
-    h->cell[k].w_hh = d_w_hh[k];
-    h->cell[k].b_ih = d_b_ih[k];
-    h->cell[k].b_hh = d_b_hh[k];
-  }
+  recurrent::bind(h->cell, params, h->memories);
   h->bound = true;
   return MPC_OK;
 }
@@ -323,7 +267,7 @@ int backward(const std::string &who, mpc_recurrent_bptt *h, int T, int B, int fi
     p.idx_limit = (((long long)(T - 1) * h->fwd[m].x_stride + (long long)(B - 1) * I) >> 2) + 1;
     p.C = h->part_ih[m]; p.ldc = I;
     p.M = 4 * H; p.N = I; p.K = R;
-    p.chunks = 1;                      // (launch_backward_weight sets the chunking)
+    p.chunks = 1;                      // (pgemm::launch sets the chunking)
     pgemm::Problem &q = Wh.p[k];
     q.A = h->work[m].dG; q.lda = 4 * H;
     q.B = h->work[m].h_used; q.ldb = H;
@@ -331,8 +275,10 @@ int backward(const std::string &who, mpc_recurrent_bptt *h, int T, int B, int fi
     q.M = 4 * H; q.N = H; q.K = R;
     q.chunks = 1;
   }
-  if (int rc = launch_backward_weight(Wi, s)) return rc;
-  if (int rc = launch_backward_weight(Wh, s)) return rc;
+  for (pgemm::Launch *L : {&Wi, &Wh}) {
+    pgemm::launch(pgemm::kBackwardWeight, *L, s);
+    HIP_TRY(hipGetLastError());
+  }
   int maxg = 0;
   for (int k = 0; k < count; ++k) maxg = 4 * h->cell[first + k].H > maxg ? 4 * h->cell[first + k].H : maxg;
   const int sum_chunks = (R + bptt::kSumRows - 1) / bptt::kSumRows;
@@ -350,7 +296,7 @@ int backward(const std::string &who, mpc_recurrent_bptt *h, int T, int B, int fi
     const int big = 4 * H * (I > H ? I : H);
     maxn = big > maxn ? big : maxn;
   }
-  hipLaunchKernelGGL(pgemm::reduce_kernel, dim3((unsigned)((maxn + pgemm::kThreads - 1) / pgemm::kThreads), (unsigned)ne), dim3(pgemm::kThreads), 0, s, rt);
+  pgemm::reduce(rt, ne, maxn, s);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
 }

@@ -7,21 +7,15 @@
 
 #include <cstdint>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "mpc_host.h"
 #include "mpc_recurrent_policy.h"
-
-// recurrent_policy.h brings policy_mlp.h and recurrent_cell.h with it, which define their kernels with external linkage, and mpc_batch.hip and
-// mpc_recurrent.hip have those already: inside this unit's unnamed namespace the second copies get internal names (mpc_ppo.hip's arrangement; the one
-// system header they include is included above, so nothing but the three namespaces lands in here).
-namespace {
+#include "recurrent_host.h"
 #include "recurrent_policy.h"
-}
 
+using mpchost::aligned16;
 using mpchost::DeviceArray;
 using mpchost::DeviceGuard;
 
@@ -29,21 +23,9 @@ namespace {
 thread_local mpchost::ErrorSlot g_err;
 int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 size_t padded8(size_t count) { return (count + 7) / 8 * 8; }      // keeps every array of the one allocation 32-byte aligned
 
-// step_kernel's dynamic-LDS limit is one per device, not one per handle: it only ever grows, so that a handle with a narrow net, created after one
-// with a wide net, does not take the wide one's launches away.  Called on the handle's device.
-std::mutex g_limit_mutex;
-std::map<int, size_t> g_limit;
-hipError_t raise_lds_limit(int device, size_t bytes) {
-  std::lock_guard<std::mutex> lock(g_limit_mutex);
-  size_t &limit = g_limit[device];
-  if (bytes <= limit) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(recurrent_policy::step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) limit = bytes;
-  return e;
-}
+mpchost::LdsLimit g_step_limit(recurrent_policy::step_kernel);
 }  // namespace
 
 struct mpc_recurrent_policy {
@@ -63,8 +45,8 @@ int mpc_recurrent_policy_create(mpc_recurrent_policy **out, int I, int H, const 
                                 const int *dims, const float *const *weights, const float *const *biases, const float *act_scale, const float *act_const) {
   const std::string who = "mpc_recurrent_policy_create: ";
   if (!out || !w_ih || !w_hh || !b_ih || !b_hh || !dims || !weights || !biases || !act_scale || !act_const) return fail(MPC_E_ARG, who + "null argument");
-  if (I <= 0 || I % 16 != 0) return fail(MPC_E_ARG, who + "the input size " + std::to_string(I) + " is not a positive multiple of 16");
-  if (H <= 0 || H % 16 != 0) return fail(MPC_E_ARG, who + "the hidden size " + std::to_string(H) + " is not a positive multiple of 16");
+  const std::string why = recurrent::size_refusal(I, H);
+  if (!why.empty()) return fail(MPC_E_ARG, who + why);
   if (n_layers < 1 || n_layers > policy::kMaxLayers)
     return fail(MPC_E_ARG, who + std::to_string(n_layers) + " layers: 1 .. " + std::to_string(policy::kMaxLayers) + " are built");
   if (dims[0] != H) return fail(MPC_E_ARG, who + "the actor's first layer reads dims[0] = " + std::to_string(dims[0]) + " inputs, the memory gives " + std::to_string(H));
@@ -114,7 +96,7 @@ int mpc_recurrent_policy_create(mpc_recurrent_policy **out, int I, int H, const 
   for (int k = 0; k < dims[n_layers]; ++k) { net.scale[k] = act_scale[k]; net.shift[k] = act_const[k]; }
   p->launch.net = net;
   if (hipMemcpy(p->d_params, host.data(), sizeof(float) * total, hipMemcpyHostToDevice) != hipSuccess ||
-      raise_lds_limit(device, p->lds) != hipSuccess) {
+      g_step_limit.raise(device, p->lds) != hipSuccess) {
     mpc_recurrent_policy_destroy(p);
     return fail(MPC_E_HIP, who + "device set-up failed");
   }

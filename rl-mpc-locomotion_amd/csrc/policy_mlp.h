@@ -4,7 +4,7 @@
 //   RL_Environment/tasks/legged_config_ppo.py:5-9)  ->  clamp to [-1, 1] and the affine map to MPC weights
 //   (WeightPolicy.step, :94-118; Parameters.MPC_param_scale / MPC_param_const, MPC_Controller/Parameters.py:25-33).
 //
-// One fused kernel: a workgroup carries 16 robots through every layer -- 4096 robots are 256 workgroups, one per CU of the chip (32 robots
+// One fused kernel (mpc_batch.hip's mlp_kernel; here is what it shares with ac_kernel and step_kernel): a workgroup carries 16 robots through every layer -- 4096 robots are 256 workgroups, one per CU of the chip (32 robots
 // per workgroup left half the CUs idle); activations stay in LDS, weights stream from L2 (760 KB, shared by all workgroups) as 16-byte
 // loads, the products run on the fp32 MFMA pipe (v_mfma_f32_16x16x4_f32: exact fp32 FMA chains, so the result differs from a CPU sgemm
 // only by the summation order).  Rows of the MFMA tile are robots, columns are output neurons; a wave owns groups of up to four
@@ -99,39 +99,6 @@ __device__ __forceinline__ void layer(const float *in, int in_stride, float *out
   }
 }
 
-// obs [n, dims[0]] -> actions [n, dims[L]] (may be null) and weights [n, dims[L]] = clamp(a, -1, 1) * scale + shift
-__global__ __launch_bounds__(kThreads) void mlp_kernel(Net net, int n, const float *__restrict__ obs, float *__restrict__ actions,
-                                                      float *__restrict__ weights) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  int wmax_even = 0, wmax_odd = 0;   // widest activation held by buffer 0 (layers 0, 2, ...) / buffer 1
-  for (int l = 0; l <= net.n_layers; ++l) {
-    int &m = (l & 1) ? wmax_odd : wmax_even;
-    m = net.dims[l] > m ? net.dims[l] : m;
-  }
-  float *buf[2] = {lds, lds + kRows * (wmax_even + kPad)};
-  const int stride[2] = {wmax_even + kPad, wmax_odd + kPad};
-  const int r0 = blockIdx.x * kRows, d0 = net.dims[0];
-  for (int e = threadIdx.x; e < kRows * d0; e += kThreads) {
-    const int r = e / d0, k = e - r * d0;
-    buf[0][r * stride[0] + k] = (r0 + r < n) ? obs[(size_t)(r0 + r) * d0 + k] : 0.f;
-  }
-  __syncthreads();
-  for (int l = 0; l < net.n_layers; ++l) {
-    layer(buf[l & 1], stride[l & 1], buf[(l + 1) & 1], stride[(l + 1) & 1], net.w[l], net.b[l], net.dims[l], net.dims[l + 1], l + 1 < net.n_layers);
-    __syncthreads();
-  }
-  const int L = net.n_layers, dl = net.dims[L];
-  const float *res = buf[L & 1];
-  for (int e = threadIdx.x; e < kRows * dl; e += kThreads) {
-    const int r = e / dl, k = e - r * dl;
-    if (r0 + r >= n) continue;
-    const float a = res[r * stride[L & 1] + k];
-    if (actions) actions[(size_t)(r0 + r) * dl + k] = a;
-    const float c = fminf(fmaxf(a, -1.f), 1.f);          // torch.clamp(current_action, -1, 1); _rescale_actions(-1, 1, .) is the identity
-    weights[(size_t)(r0 + r) * dl + k] = c * net.scale[k] + net.shift[k];
-  }
-}
-
 inline size_t lds_bytes(const Net &net) {
   int we = 0, wo = 0;
   for (int l = 0; l <= net.n_layers; ++l) {
@@ -139,48 +106,6 @@ inline size_t lds_bytes(const Net &net) {
     m = net.dims[l] > m ? net.dims[l] : m;
   }
   return sizeof(float) * kRows * (size_t)(we + kPad + wo + kPad);
-}
-
-// WeightPolicy.compute_observations (:120-139): [vBody * lin, omegaBody * ang, -ground_normal_yaw, commands * (lin, lin, ang),
-// dof_pos * dps, dof_vel * dvs, previous actions]  (48 floats).  est = [vBody3, omegaBody3, rpy3, R9] as written by the
-// estimator kernel; dof = [12][2] (pos, vel); scales = {lin, ang, dof_pos, dof_vel}.
-// normal: ground_normal_yaw of robot r at normal[r * normal_stride + 0 .. 2] (3: a packed [n, 3] array; sizeof(CtrlState) / 4: the controller's own state records)
-__global__ void observations_kernel(int n, const float *__restrict__ dof, const float *__restrict__ est, const float *__restrict__ normal, int normal_stride,
-                                    const float *__restrict__ cmd3, const float *__restrict__ prev, float lin, float ang, float dps, float dvs,
-                                    float *__restrict__ obs) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * 48) return;
-  const int r = i / 48, k = i - 48 * r;
-  float v;
-  if (k < 3) v = est[18 * r + k] * lin;
-  else if (k < 6) v = est[18 * r + k] * ang;
-  else if (k < 9) v = -normal[(size_t)normal_stride * r + k - 6];
-  else if (k < 12) v = cmd3[3 * r + k - 9] * (k < 11 ? lin : ang);
-  else if (k < 24) v = dof[24 * r + 2 * (k - 12)] * dps;
-  else if (k < 36) v = dof[24 * r + 2 * (k - 24) + 1] * dvs;
-  else v = prev[12 * r + k - 36];
-  obs[i] = v;
-}
-
-// commands of controller.run: np.concatenate((commands[idx], actions_rescale[idx], [0.0])) (RL_Environment/tasks/aliengo.py:251)
-__global__ void pack_commands_kernel(int n, const float *__restrict__ cmd3, const float *__restrict__ w12, float *__restrict__ cmd16) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * 16) return;
-  const int r = i / 16, k = i - 16 * r;
-  cmd16[i] = k < 3 ? cmd3[3 * r + k] : k < 15 ? w12[12 * r + k - 3] : 0.f;
-}
-
-// ... with the rescale of VecTask.pre_physics_step in front of it: actions_rescale = torch.mul(actions, MPC_param_scale).add(MPC_param_const)
-// (RL_Environment/tasks/aliengo.py:237-245) -- a float32 product, then a float32 sum, like torch's two kernels (no fused multiply-add)
-struct Rescale { float scale[12], shift[12]; };
-__global__ void pack_commands_scaled_kernel(int n, const float *__restrict__ cmd3, const float *__restrict__ act12, Rescale rs, float *__restrict__ cmd16) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * 16) return;
-  const int r = i / 16, k = i - 16 * r;
-  float v = 0.f;
-  if (k < 3) v = cmd3[3 * r + k];
-  else if (k < 15) v = __fadd_rn(__fmul_rn(act12[12 * r + k - 3], rs.scale[k - 3]), rs.shift[k - 3]);
-  cmd16[i] = v;
 }
 
 }  // namespace policy

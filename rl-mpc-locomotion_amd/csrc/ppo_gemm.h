@@ -16,7 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "ppo_gemm_plan.h"      // Kind, kChunk, kMinChunk and the launch plan (no HIP in it)
+#include "ppo_gemm_plan.h"      // Kind, kChunk, kMinChunk, the launch plan and the structs a caller fills (no HIP in it)
 
 namespace pgemm {
 
@@ -27,22 +27,6 @@ constexpr int kBK = 32;                // reduction rows per LDS tile
 constexpr int kKQ = kBK / 4;          // 16-byte loads along one row of a reduction-contiguous tile
 constexpr int kPad = 4;
 // kChunk (most rows per backward-weight chunk: the longest fp32 chain) and kMinChunk (fewest: what sizes the workspace) are ppo_gemm_plan.h's
-
-struct Problem {
-  const float *A, *B;                 // see the loaders below for each kind's layout
-  float *C;                           // [M][ldc]; backward weight: [chunks][M][ldc]
-  const float *aux;                   // forward: bias [N]; backward data: the stored activation [M][ldaux]
-  const long long *idx;               // rows of X are idx[row] (forward: of A; backward weight: of B); null: the rows themselves
-  float *dbias;                       // backward weight: [chunks][M] column sums of dY (null: none)
-  long long idx_limit;                // idx values are clamped to [0, idx_limit)
-  int M, N, K;                        // output M x N, reduction K
-  int lda, ldb, ldc, ldaux;
-  int elu;                            // forward: apply ELU
-  int tiles_m, tiles_n, chunks;       // tiles_m = 0: nothing to do
-  int chunk_rows;                     // backward weight: reduction rows per chunk
-};
-
-struct Launch { Problem p[2]; };
 
 __device__ __forceinline__ float4 mask4(float4 v, int left) {   // keep the first `left` components
   if (left < 4) { v.w = 0.f; if (left < 3) v.z = 0.f; if (left < 2) v.y = 0.f; if (left < 1) v.x = 0.f; }
@@ -200,17 +184,7 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(Launch launch) {
   }
 }
 
-// the second half of backward weight: out[e] = sum over the chunks in index order (float64, rounded once) of part[c][e]
-constexpr int kMaxReduce = 32;
-struct ReduceEntry {
-  const float *part;      // [chunks][numel]
-  float *out;             // [numel]
-  int numel, chunks;
-};
-struct ReduceTable {
-  ReduceEntry e[kMaxReduce];
-};
-
+// the second half of backward weight (ppo_gemm_plan.h's ReduceTable): out[e] = sum over the chunks in index order (float64, rounded once) of part[c][e]
 // grid (ceil(max numel / 256), entries)
 __global__ __launch_bounds__(kThreads) void reduce_kernel(ReduceTable t) {
   const ReduceEntry &e = t.e[blockIdx.y];

@@ -62,4 +62,35 @@ inline Plan plan_gemm(int kind, const Shape (&shape)[2]) {
   return plan;
 }
 
+// ---- what a caller of the GEMMs fills; the kernels (ppo_gemm.h) live in mpc_ppo_gemm.hip alone and are reached through launch and reduce below
+struct Problem {
+  const float *A, *B;                 // see ppo_gemm.h's loaders for each kind's layout
+  float *C;                           // [M][ldc]; backward weight: [chunks][M][ldc]
+  const float *aux;                   // forward: bias [N]; backward data: the stored activation [M][ldaux]
+  const long long *idx;               // rows of X are idx[row] (forward: of A; backward weight: of B); null: the rows themselves
+  float *dbias;                       // backward weight: [chunks][M] column sums of dY (null: none)
+  long long idx_limit;                // idx values are clamped to [0, idx_limit)
+  int M, N, K;                        // output M x N, reduction K
+  int lda, ldb, ldc, ldaux;
+  int elu;                            // forward: apply ELU
+  int tiles_m, tiles_n, chunks;       // tiles_m = 0: nothing to do
+  int chunk_rows;                     // backward weight: reduction rows per chunk
+};
+
+struct Launch { Problem p[2]; };
+
+// the second half of backward weight: out[e] = sum over the chunks in index order (float64, rounded once) of part[c][e]
+constexpr int kMaxReduce = 32;
+struct ReduceEntry {
+  const float *part;      // [chunks][numel]
+  float *out;             // [numel]
+  int numel, chunks;
+};
+struct ReduceTable { ReduceEntry e[kMaxReduce]; };
+
+// mpc_ppo_gemm.hip.  launch: plan_gemm's plan filled into L (the caller reads the chunk counts back) and the instantiation it names started on
+// `stream` (a hipStream_t).  reduce: reduce_kernel over the first `entries` of t, the longest max_numel elements.  The caller asks hipGetLastError.
+void launch(Kind kind, Launch &L, void *stream);
+void reduce(const ReduceTable &t, int entries, int max_numel, void *stream);
+
 }  // namespace pgemm

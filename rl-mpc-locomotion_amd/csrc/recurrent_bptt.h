@@ -7,7 +7,7 @@
 //                        h' -- zeroed where reset[t+1] is set -- into the other, so ONE barrier per step stands between every read of a buffer and
 //                        the next write to it); c stays in registers, one element per lane, the same lane every step.  A step is cell_kernel's:
 //                        recurrent::accumulate over I against W_ih, then over H against W_hh, into the four gate accumulators, then cell_kernel's
-//                        epilogue expression for expression -- y[t] equals T launches of cell_kernel bit for bit.  Per step it keeps what the backward
+//                        epilogue, recurrent::finish -- y[t] equals T launches of cell_kernel bit for bit.  Per step it keeps what the backward
 //                        pass reads: the gate activations i, f, g, o, c', and the state the step started from (h_used, c_used).  x[t+1] is staged
 //                        into the other x buffer after step t's products.
 //   transpose_kernel     W_hh [4H][H] -> W_hh^T [H rounded up to 64][4H], once per backward call (the weights change after every optimiser step).
@@ -19,7 +19,7 @@
 //                        CONSECUTIVE blocks of 16 state columns (accumulate's four chains, "H" = 16) and owns the same columns in the element-wise
 //                        part, so dh_rec and dc_rec stay in registers.  Both are zeroed on rows where reset[t] is set: nothing reaches step t - 1.
 //   weight gradients     dW_ih = dG^T X, dW_hh = dG^T h_used over all T B rows: pgemm::gemm_kernel's backward-weight kind (chunk partials,
-//                        reduce_kernel in index order), launched by the unit.  X is read in place from the rollout storage through an index: row
+//                        reduce_kernel in index order), launched by the unit through mpc_ppo_gemm.hip.  X is read in place from the rollout storage through an index: row
 //                        (t, b) starts (t stride + b I) / 4 quads after the block's first row, so with ldb = 4 the index is exact for any slot stride
 //                        that is a multiple of 4 floats.
 //   column_sum_kernel    db = the column sums of dG: per chunk of 256 rows a float64 sum in row order, rounded once; reduce_kernel adds the chunks.
@@ -31,7 +31,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "ppo_gemm.h"
+#include "ppo_gemm_plan.h"
 #include "recurrent_cell.h"
 
 namespace bptt {
@@ -97,8 +97,8 @@ __global__ __launch_bounds__(kThreads) void seq_forward_kernel(Launch a, int fir
     w.x_index[r] = ((long long)t * s.x_stride + (long long)row * I) >> 2;
     if (blockIdx.y == 0) flags[r] = (reset && reset[r] != 0) ? 1 : 0;
   }
-  recurrent::stage(xb, xs, s.x, nullptr, I, r0, B, nullptr);
-  recurrent::stage(hb, hs, s.h0, w.h_used, H, r0, B, reset);      // h_used[0]: h0 with reset[0] applied
+  recurrent::stage<kThreads>(xb, xs, s.x, nullptr, I, r0, B, nullptr);
+  recurrent::stage<kThreads>(hb, hs, s.h0, w.h_used, H, r0, B, reset);      // h_used[0]: h0 with reset[0] applied
   float c[kMaxSlots][4];
 #pragma unroll
   for (int sl = 0; sl < kMaxSlots; ++sl) {
@@ -133,10 +133,8 @@ __global__ __launch_bounds__(kThreads) void seq_forward_kernel(Launch a, int fir
         for (int reg = 0; reg < 4; ++reg) {  // C layout of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
           const int lr = 4 * q + reg, row = r0 + lr;
           const float c0 = c[sl][reg];
-          const float ig = recurrent::sigmoid(acc[0][reg] + bias[0]), fg = recurrent::sigmoid(acc[1][reg] + bias[1]);
-          const float gg = tanhf(acc[2][reg] + bias[2]), og = recurrent::sigmoid(acc[3][reg] + bias[3]);
-          const float c1 = fg * c0 + ig * gg;
-          const float h1 = og * tanhf(c1);
+          const recurrent::Step st = recurrent::finish(acc, bias, reg, c0);
+          const float ig = st.i, fg = st.f, gg = st.g, og = st.o, c1 = st.c, h1 = st.h;
           const bool live = row < B;
           const bool cut = live && rn && rn[row] != 0;      // the next step starts this row from zero
           const float hnext = (live && !cut) ? h1 : 0.f;
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(kThreads) void seq_forward_kernel(Launch a, int fir
         }
       }
     }
-    if (t + 1 < T) recurrent::stage(xb + ((t + 1) & 1) * kRows * xs, xs, s.x + (size_t)(t + 1) * s.x_stride, nullptr, I, r0, B, nullptr);
+    if (t + 1 < T) recurrent::stage<kThreads>(xb + ((t + 1) & 1) * kRows * xs, xs, s.x + (size_t)(t + 1) * s.x_stride, nullptr, I, r0, B, nullptr);
   }
 }
 

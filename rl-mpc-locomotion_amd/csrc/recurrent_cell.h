@@ -14,7 +14,8 @@
 // The state is updated in place.  A workgroup reads the state rows of its own 16 environments only: it stages h (with the reset applied) in
 // LDS, and a barrier stands between that staging and the first store; a lane reads and writes one and the same element of c.
 //
-// LDS: 16 (I + H + 2 kPad) floats -- 33 280 bytes at I = H = 256.
+// LDS: 16 (I + H + 2 kPad) floats -- 33 280 bytes at I = H = 256.  cell_kernel itself is mpc_recurrent.hip's; what it shares with
+// bptt::seq_forward_kernel and recurrent_policy::step_kernel -- accumulate, stage, finish -- is here; the host's share is recurrent_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -83,11 +84,12 @@ __device__ __forceinline__ void accumulate(f32x4 (&acc)[kGates], const float *in
 }
 
 // rows [16][width] of a row-major matrix [n][width] into LDS, 16 bytes per lane and trip; rows past n, and rows whose flag is set, as zeros.
-// `copy` (may be null): the staged rows < n are written there as well, at the same place.  width % 4 == 0.
+// `copy` (may be null): the staged rows < n are written there as well, at the same place.  width % 4 == 0.  THREADS: the workgroup's.
+template <int THREADS>
 __device__ __forceinline__ void stage(float *dst, int stride, const float *__restrict__ src, float *copy, int width, int r0, int n,
                                       const long long *__restrict__ reset) {
   const int quads = width >> 2;
-  for (int e = threadIdx.x; e < kRows * quads; e += kThreads) {
+  for (int e = threadIdx.x; e < kRows * quads; e += THREADS) {
     const int r = e / quads, k = 4 * (e - r * quads), row = r0 + r;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (row < n) {
@@ -99,48 +101,16 @@ __device__ __forceinline__ void stage(float *dst, int stride, const float *__res
   }
 }
 
-// grid (ceil(n / 16), memories); memory = first + blockIdx.y.  reset [n] int64 or null: where non-zero, the state of that row is taken as zero.
-// commit 0: h and c are left as they are and h_out alone is written.
-__global__ __launch_bounds__(kThreads) void cell_kernel(Launch a, int first, int n, const long long *__restrict__ reset, int commit) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int which = first + (int)blockIdx.y;
-  const Cell &m = a.cell[which];
-  const Io &io = a.io[which];
-  const int I = m.I, H = m.H, xs = I + kPad, hs = H + kPad;
-  float *xb = lds, *hb = lds + kRows * xs;
-  const int r0 = blockIdx.x * kRows;
-  stage(xb, xs, io.x, nullptr, I, r0, n, nullptr);
-  stage(hb, hs, io.h, io.h_saved, H, r0, n, reset);
-  __syncthreads();                     // every read of this workgroup's rows of h lies before it, every store to them after it
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
-  for (int nb = wave; nb * 16 < H; nb += kWaves) {
-    f32x4 acc[kGates];
-#pragma unroll
-    for (int g = 0; g < kGates; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-    accumulate(acc, xb, xs, m.w_ih, I, H, nb);
-    accumulate(acc, hb, hs, m.w_hh, H, H, nb);
-    const int j = nb * 16 + col;
-    float bias[kGates];
-#pragma unroll
-    for (int g = 0; g < kGates; ++g) bias[g] = m.b_ih[g * H + j] + m.b_hh[g * H + j];
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {  // C layout of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
-      const int row = r0 + 4 * q + reg;
-      if (row >= n) continue;
-      const size_t o = (size_t)row * H + j;
-      const float c0 = (reset && reset[row] != 0) ? 0.f : io.c[o];
-      const float ig = sigmoid(acc[0][reg] + bias[0]), fg = sigmoid(acc[1][reg] + bias[1]);
-      const float gg = tanhf(acc[2][reg] + bias[2]), og = sigmoid(acc[3][reg] + bias[3]);
-      const float c1 = fg * c0 + ig * gg;
-      const float h1 = og * tanhf(c1);
-      if (io.c_saved) io.c_saved[o] = c0;
-      if (commit) {
-        io.c[o] = c1;
-        io.h[o] = h1;
-      }
-      if (io.h_out) io.h_out[o] = h1;
-    }
-  }
+// The cell once the four gate accumulators are there, for register reg of the tile (C layout of the 16x16 MFMA: col = lane & 15,
+// row = 4 (lane >> 4) + reg) and the element c0 of the state it starts from.  c' = f c + i g is torch's: a product, a product, a sum -- every
+// unit that includes this is compiled without contraction.  cell_kernel, bptt::seq_forward_kernel and recurrent_policy::step_kernel finish
+// their steps here and nowhere else, which is what makes them agree bit for bit; each keeps its own stores, rows past n and resets.
+struct Step { float i, f, g, o, c, h; };      // the gate activations, c', h'
+__device__ __forceinline__ Step finish(const f32x4 (&acc)[kGates], const float (&bias)[kGates], int reg, float c0) {
+  const float ig = sigmoid(acc[0][reg] + bias[0]), fg = sigmoid(acc[1][reg] + bias[1]);
+  const float gg = tanhf(acc[2][reg] + bias[2]), og = sigmoid(acc[3][reg] + bias[3]);
+  const float c1 = fg * c0 + ig * gg;
+  return Step{ig, fg, gg, og, c1, og * tanhf(c1)};
 }
 
 }  // namespace recurrent

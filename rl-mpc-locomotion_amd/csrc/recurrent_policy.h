@@ -5,15 +5,15 @@
 //
 // The shape is the one recurrent_cell.h and policy_mlp.h share: a workgroup carries 16 robots, activations stay in LDS (rows padded by kPad),
 // the weights stream from L2 as 16-byte loads, the products run on v_mfma_f32_16x16x4_f32.  policy::layer strides by policy::kThreads, so the
-// workgroup is that wide (8 waves at the default 512); recurrent::accumulate and recurrent::sigmoid are per wave and are used as they stand,
-// recurrent::stage strides by 256 threads and is restated here for this kernel's thread count.
+// workgroup is that wide (8 waves at the default 512); recurrent::accumulate and recurrent::finish are per wave and recurrent::stage takes the
+// workgroup's thread count, so all three are used as they stand.
 //
 // Phases of a workgroup:
 //   1. x [16][I] and h [16][H] into LDS, 16 bytes per lane and trip; rows past n as zeros, and h as zeros where the row's reset flag is set (x is
 //      the robot's fresh observation: a reset clears the memory, never the row it reads -- cell_kernel's rule).  Barrier: every read of this
 //      workgroup's rows of h lies before it, every store to them after it.
 //   2. the cell: wave w takes the state-column blocks nb = w, w + kWaves, ... with their four gate blocks, K over I against W_ih and then over H
-//      against W_hh into the same four accumulators; biases, sigmoid, tanh, c' and h' in registers, expression for expression cell_kernel's
+//      against W_hh into the same four accumulators; biases, sigmoid, tanh, c' and h' in registers: recurrent::finish, cell_kernel's
 //      epilogue.  c is read from global memory, one element per lane (zero on a flagged row).  c' and h' go to the state in place (rows < n), h'
 //      goes into the LDS buffer the MLP's first layer reads (rows past n: zeros, as mlp_kernel stages them).  The gate pre-activations never
 //      reach LDS or HBM, and h' reaches HBM as the state only.  Barrier.
@@ -47,18 +47,6 @@ struct Launch {
 
 inline size_t lds_bytes(int I, int H, const policy::Net &net) { return recurrent::lds_bytes(I, H) + policy::lds_bytes(net); }
 
-// recurrent::stage for kThreads threads: rows [16][width] of a row-major matrix [n][width] into LDS, 16 bytes per lane and trip; rows past n,
-// and rows whose flag is set, as zeros.  width % 4 == 0.
-__device__ __forceinline__ void stage(float *dst, int stride, const float *src, int width, int r0, int n, const long long *__restrict__ reset) {
-  const int quads = width >> 2;
-  for (int e = threadIdx.x; e < kRows * quads; e += kThreads) {
-    const int r = e / quads, k = 4 * (e - r * quads), row = r0 + r;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row < n && !(reset && reset[row] != 0)) v = *reinterpret_cast<const float4 *>(src + (size_t)row * width + k);
-    *reinterpret_cast<float4 *>(dst + r * stride + k) = v;
-  }
-}
-
 // grid ceil(n / 16).  x [n][I]; h, c [n][H] the state, updated in place; reset [n] int64 or null; actions [n][dims[L]] or null; weights [n][dims[L]].
 __global__ __launch_bounds__(kThreads) void step_kernel(Launch a, int n, const float *__restrict__ x, float *h, float *c, const long long *__restrict__ reset,
                                                        float *__restrict__ actions, float *__restrict__ weights) {
@@ -75,8 +63,8 @@ __global__ __launch_bounds__(kThreads) void step_kernel(Launch a, int n, const f
   float *buf[2] = {hb + kRows * hs, hb + kRows * hs + kRows * (wmax_even + kPad)};
   const int stride[2] = {wmax_even + kPad, wmax_odd + kPad};
   const int r0 = blockIdx.x * kRows;
-  stage(xb, xs, x, I, r0, n, nullptr);
-  stage(hb, hs, h, H, r0, n, reset);
+  recurrent::stage<kThreads>(xb, xs, x, nullptr, I, r0, n, nullptr);
+  recurrent::stage<kThreads>(hb, hs, h, nullptr, H, r0, n, reset);
   __syncthreads();                     // every read of this workgroup's rows of h lies before it, every store to them after it
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
   for (int nb = wave; nb * 16 < H; nb += kWaves) {
@@ -96,12 +84,10 @@ __global__ __launch_bounds__(kThreads) void step_kernel(Launch a, int n, const f
       if (row < n) {
         const size_t o = (size_t)row * H + j;
         const float c0 = (reset && reset[row] != 0) ? 0.f : c[o];
-        const float ig = recurrent::sigmoid(acc[0][reg] + bias[0]), fg = recurrent::sigmoid(acc[1][reg] + bias[1]);
-        const float gg = tanhf(acc[2][reg] + bias[2]), og = recurrent::sigmoid(acc[3][reg] + bias[3]);
-        const float c1 = fg * c0 + ig * gg;
-        h1 = og * tanhf(c1);
-        c[o] = c1;
-        h[o] = h1;
+        const recurrent::Step s = recurrent::finish(acc, bias, reg, c0);
+        h1 = s.h;
+        c[o] = s.c;
+        h[o] = s.h;
       }
       buf[0][(4 * q + reg) * stride[0] + j] = h1;
     }

@@ -154,22 +154,15 @@ class ActorCritic(nn.Module):
         if critic_obs is not None:
             need_gpu(what, critic_obs)
         la, lc = self._linears(self.actor), self._linears(self.critic)
-        params = self.bind_order()
-        ptrs = tuple(p.data_ptr() for p in params)
         if self._handle is None:
             dims = lambda ls: [ls[0].in_features] + [m.out_features for m in ls]
-            da, dc = dims(la), dims(lc)
             h = C.c_void_p()
             create = "mpc_ac_create" if self.num_critic_obs is None else "mpc_ac_create_asymmetric"
-            check(getattr(lib(), create)(C.byref(h), len(la), C.cast((C.c_int * len(da))(*da), C.c_void_p), len(lc),
-                                         C.cast((C.c_int * len(dc))(*dc), C.c_void_p)), create)
+            check(getattr(lib(), create)(C.byref(h), len(la), _lib.int_array(dims(la)), len(lc), _lib.int_array(dims(lc))), create)
             self._handle = h
-        if ptrs != self._bound_ptrs:
-            for p in params:
-                if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.std.device:
-                    raise ValueError("ActorCritic parameters must be contiguous float32 tensors on one device")
-            na, nc = len(la), len(lc)
-            arr = lambda v: C.cast((C.c_void_p * len(v))(*v), C.c_void_p)
+        ptrs = _lib.addresses_to_bind(self.bind_order(), self._bound_ptrs, self.std.device, "ActorCritic parameters must be contiguous float32 tensors on one device")
+        if ptrs is not None:
+            na, nc, arr = len(la), len(lc), _lib.ptr_array
             with torch.cuda.device(self.std.device):
                 check(lib().mpc_ac_bind(self._handle, arr(ptrs[:na]), arr(ptrs[na:2 * na]), arr(ptrs[2 * na:2 * na + nc]),
                                         arr(ptrs[2 * na + nc:2 * na + 2 * nc]), ptrs[-1]), "mpc_ac_bind")
@@ -471,15 +464,12 @@ class PPO:
             with torch.cuda.device(dev):
                 check(update_lib().mpc_ppo_update_create(C.byref(h), ac._handle, int(rows)), "mpc_ppo_update_create")
             self._handle, self._max_rows, self._bound, self._storage_ptrs, self._ac_ptrs = h, int(rows), None, None, ac._bound_ptrs
-        tensors = [[p.grad for p in params], [self.optimizer.state[p]["exp_avg"] for p in params], [self.optimizer.state[p]["exp_avg_sq"] for p in params]]
-        ptrs = tuple(tuple(t.data_ptr() for t in ts) for ts in tensors)
-        if ptrs != self._bound:
-            for ts in tensors:
-                for t, p in zip(ts, params):
-                    if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.shape != p.shape:
-                        raise ValueError("gradients and Adam's moments must be contiguous float32 tensors shaped like their parameters, on their device")
-            arr = lambda v: C.cast((C.c_void_p * len(v))(*v), C.c_void_p)
-            check(update_lib().mpc_ppo_update_bind(self._handle, arr(ptrs[0]), arr(ptrs[1]), arr(ptrs[2])), "mpc_ppo_update_bind")
+        tensors = [p.grad for p in params] + [self.optimizer.state[p][key] for key in ("exp_avg", "exp_avg_sq") for p in params]
+        ptrs = _lib.addresses_to_bind(tensors, self._bound, dev, "gradients and Adam's moments must be contiguous float32 tensors shaped like their parameters, on their device",
+                                      like=3 * params)
+        if ptrs is not None:
+            n, arr = len(params), _lib.ptr_array
+            check(update_lib().mpc_ppo_update_bind(self._handle, arr(ptrs[:n]), arr(ptrs[n:2 * n]), arr(ptrs[2 * n:])), "mpc_ppo_update_bind")
             self._bound = ptrs
         return steps.pop()
 

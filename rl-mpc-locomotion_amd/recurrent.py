@@ -177,6 +177,11 @@ def lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh):
     return torch.sigmoid(o) * torch.tanh(c1), c1
 
 
+def _memory_sizes(memories):
+    """create's two size arrays: the memories' input and hidden sizes."""
+    return _lib.int_array([m.input_size for m in memories]), _lib.int_array([m.hidden_size for m in memories])
+
+
 class SequenceKernel:
     """A handle of csrc/mpc_recurrent_bptt.h over ``memories`` (one ``Memory``, or the actor's and the critic's): the roll over T slots and its
     backward pass.  The handle is made for the first call's (T, B) and made anew for a larger one; the parameters are bound by pointer and bound
@@ -198,21 +203,14 @@ class SequenceKernel:
                 bptt_lib().mpc_recurrent_bptt_destroy(self._handle)
                 self._handle, self._ptrs = None, None
             h = C.c_void_p()
-            sizes = lambda v: C.cast((C.c_int * n)(*v), C.c_void_p)
             steps, rows = max(T, self.max_steps), max(B, self.max_rows)
-            bptt_check(bptt_lib().mpc_recurrent_bptt_create(C.byref(h), n, sizes([m.input_size for m in self.memories]),
-                                                            sizes([m.hidden_size for m in self.memories]), steps, rows), "mpc_recurrent_bptt_create")
+            bptt_check(bptt_lib().mpc_recurrent_bptt_create(C.byref(h), n, *_memory_sizes(self.memories), steps, rows), "mpc_recurrent_bptt_create")
             self._handle, self.max_steps, self.max_rows = h, steps, rows
-        params = [m.parameters_in_bind_order() for m in self.memories]
-        ptrs = tuple(p.data_ptr() for ps in params for p in ps)
-        if ptrs != self._ptrs:
-            for ps in params:
-                for p in ps:
-                    if p.dtype != torch.float32 or not p.is_contiguous() or p.device != device:
-                        raise ValueError("the memories' parameters must be contiguous float32 tensors on the rows' device")
-            arr = lambda k: C.cast((C.c_void_p * n)(*[ps[k].data_ptr() for ps in params]), C.c_void_p)
+        params = [p for m in self.memories for p in m.parameters_in_bind_order()]      # (bind's k-th array is every fourth address from k)
+        ptrs = _lib.addresses_to_bind(params, self._ptrs, device, "the memories' parameters must be contiguous float32 tensors on the rows' device")
+        if ptrs is not None:
             with torch.cuda.device(device):
-                bptt_check(bptt_lib().mpc_recurrent_bptt_bind(self._handle, arr(0), arr(1), arr(2), arr(3)), "mpc_recurrent_bptt_bind")
+                bptt_check(bptt_lib().mpc_recurrent_bptt_bind(self._handle, *(_lib.ptr_array(ptrs[k::4]) for k in range(4))), "mpc_recurrent_bptt_bind")
             self._ptrs = ptrs
 
     def forward(self, which, xs, h0s, c0s, reset, c_last=False, what="SequenceKernel.forward", out=None):
@@ -420,20 +418,13 @@ class ActorCriticRecurrent(ActorCritic):
         need_gpu(what, self.std)
         if self._cell_handle is None:
             h = C.c_void_p()
-            sizes = lambda v: C.cast((C.c_int * MEMORIES)(*v), C.c_void_p)
-            check(lib().mpc_recurrent_create(C.byref(h), MEMORIES, sizes([m.input_size for m in self.memories()]),
-                                             sizes([m.hidden_size for m in self.memories()])), "mpc_recurrent_create")
+            check(lib().mpc_recurrent_create(C.byref(h), MEMORIES, *_memory_sizes(self.memories())), "mpc_recurrent_create")
             self._cell_handle = h
-        params = [m.parameters_in_bind_order() for m in self.memories()]
-        ptrs = tuple(p.data_ptr() for ps in params for p in ps)
-        if ptrs != self._cell_ptrs:
-            for ps in params:
-                for p in ps:
-                    if p.dtype != torch.float32 or not p.is_contiguous() or p.device != device:
-                        raise ValueError("the memories' parameters must be contiguous float32 tensors on the observations' device")
-            arr = lambda k: C.cast((C.c_void_p * MEMORIES)(*[ps[k].data_ptr() for ps in params]), C.c_void_p)
+        params = [p for m in self.memories() for p in m.parameters_in_bind_order()]
+        ptrs = _lib.addresses_to_bind(params, self._cell_ptrs, device, "the memories' parameters must be contiguous float32 tensors on the observations' device")
+        if ptrs is not None:
             with torch.cuda.device(device):
-                check(lib().mpc_recurrent_bind(self._cell_handle, arr(0), arr(1), arr(2), arr(3)), "mpc_recurrent_bind")
+                check(lib().mpc_recurrent_bind(self._cell_handle, *(_lib.ptr_array(ptrs[k::4]) for k in range(4))), "mpc_recurrent_bind")
             self._cell_ptrs = ptrs
 
     def cell_step(self, rows, reset=None, saved=None, commit=True, what="ActorCriticRecurrent.cell_step"):

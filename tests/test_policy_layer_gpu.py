@@ -308,11 +308,11 @@ def _fresh_actor_critic(net, seed):
     return P.ActorCritic(net[0], 12, net[1], net[2]).to(DEV)
 
 
-def test_a_wide_actor_critic_survives_the_bind_of_a_narrow_one():
-    """mpc_ac_bind sets the kernel's dynamic-LDS limit per function: the narrow handle's bind must not take the wide handle's LDS away."""
-    assert net_lds_bytes(WIDE_NET) > 64 * 1024 > net_lds_bytes(NARROW_NET)
-    wide, narrow = _fresh_actor_critic(WIDE_NET, 1), _fresh_actor_critic(NARROW_NET, 2)
-    obs = _obs(33, 48, seed=9)
+def _actor_critic_wide_then_narrow(wide_net, narrow_net, seed):
+    """33 rows (two full workgroups and a partial one) through the wide handle, then a narrow handle is bound and run, then the wide one again on
+    the same rows: it succeeds and answers bit for bit the same."""
+    wide, narrow = _fresh_actor_critic(wide_net, seed), _fresh_actor_critic(narrow_net, seed + 1)
+    obs = _obs(33, 48, seed=seed + 8)
     keys = ("actions", "actions_log_prob", "values", "mu", "sigma")
     before = {k: v.clone() for k, v in wide.act(obs, seed=3, step=1).items()}
     v_before, m_before = wide.evaluate(obs).clone(), wide.act_inference(obs).clone()
@@ -320,22 +320,53 @@ def test_a_wide_actor_critic_survives_the_bind_of_a_narrow_one():
     small = narrow.act(obs, seed=3, step=1)                                      # creates and binds the narrow handle
     assert torch.isfinite(small["mu"]).all() and not torch.equal(small["mu"], before["mu"])
     after = wide.act(obs, seed=3, step=1)
+    torch.cuda.synchronize()                                                     # (a refused launch shows here at the latest)
     for k in keys:
         assert torch.equal(after[k], before[k]), k
     assert torch.equal(wide.evaluate(obs), v_before) and torch.equal(wide.act_inference(obs), m_before)
     assert torch.equal(narrow.act(obs, seed=3, step=1)["mu"], small["mu"])
 
 
-def test_a_wide_weight_policy_survives_the_creation_of_a_narrow_one():
+def _weight_policy_wide_then_narrow(wide_net, narrow_net, seed):
+    """The same for mlp_kernel: mpc_policy_create of a narrow net after a wide one."""
     from rl_mpc_locomotion_amd.weight_policy import WeightPolicy
-    wide_sd, narrow_sd = _fresh_actor_critic(WIDE_NET, 3).state_dict(), _fresh_actor_critic(NARROW_NET, 4).state_dict()
-    obs = _obs(33, 48, seed=10)
+    wide_sd, narrow_sd = _fresh_actor_critic(wide_net, seed).state_dict(), _fresh_actor_critic(narrow_net, seed + 1).state_dict()
+    obs = _obs(33, 48, seed=seed + 7)
     wide = WeightPolicy.from_state_dict(wide_sd, device=DEV)
     w_before, a_before = (t.clone() for t in wide.step(obs, return_actions=True))
     assert torch.isfinite(w_before).all() and torch.isfinite(a_before).all()
-    narrow = WeightPolicy.from_state_dict(narrow_sd, device=DEV)                 # sets mlp_kernel's limit for its own, smaller net
+    narrow = WeightPolicy.from_state_dict(narrow_sd, device=DEV)                 # its smaller need raises nothing: the limit stays the wide net's
     w_small = narrow.step(obs).clone()
     assert torch.isfinite(w_small).all() and not torch.equal(w_small, w_before)
     w_after, a_after = wide.step(obs, return_actions=True)
+    torch.cuda.synchronize()
     assert torch.equal(w_after, w_before) and torch.equal(a_after, a_before)
     assert torch.equal(narrow.step(obs), w_small)
+
+
+def test_a_wide_actor_critic_survives_the_bind_of_a_narrow_one():
+    """ac_kernel's dynamic-LDS limit is one per device and kernel and only grows: the narrow handle's bind must not take the wide handle's LDS away."""
+    assert net_lds_bytes(WIDE_NET) > 64 * 1024 > net_lds_bytes(NARROW_NET)
+    _actor_critic_wide_then_narrow(WIDE_NET, NARROW_NET, 1)
+
+
+def test_a_wide_weight_policy_survives_the_creation_of_a_narrow_one():
+    _weight_policy_wide_then_narrow(WIDE_NET, NARROW_NET, 3)
+
+
+# The same two properties at the LDS need this project has recorded as over a kernel's default limit: 69 632 bytes, the deployed recurrent policy's.
+# 48 observations and hidden widths (544, 544) are the smallest multiples of 16 that reach it: 16 (544 + 4 + 544 + 4) floats = 70 144 bytes.
+NEED = 69632
+NEED_NET, SMALL_NET = (48, (544, 544), (544, 544)), (48, (32,), (32,))
+
+
+def test_the_need_net_is_the_smallest_that_reaches_the_recorded_need():
+    assert net_lds_bytes(NEED_NET) == 70144 >= NEED > net_lds_bytes((48, (528, 528), (528, 528))) and net_lds_bytes(SMALL_NET) < 64 * 1024
+
+
+def test_a_wide_actor_critic_keeps_its_launches_after_the_bind_of_a_narrow_one():
+    _actor_critic_wide_then_narrow(NEED_NET, SMALL_NET, 11)
+
+
+def test_a_wide_weight_policy_keeps_its_launches_after_the_creation_of_a_narrow_one():
+    _weight_policy_wide_then_narrow(NEED_NET, SMALL_NET, 13)

@@ -226,12 +226,14 @@ def test_hip_backend_raises_without_a_gpu(monkeypatch):
 
 
 def test_kernels_compile_for_gfx950_without_scratch(tmp_path):
-    out = tmp_path / "mpc_ppo_update.o"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-c", os.path.join(CSRC, "mpc_ppo_update.hip"), "-o", str(out)], check=True, capture_output=True, text=True)
     found = {}
-    for name, scratch in re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stderr, re.S):
-        found[name] = int(scratch)
+    for unit in ("mpc_ppo_update", "mpc_ppo_gemm"):                              # the update's own kernels, and the GEMMs' one owner in the library
+        out = tmp_path / (unit + ".o")
+        r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
+                            "-c", os.path.join(CSRC, unit + ".hip"), "-o", str(out)], check=True, capture_output=True, text=True)
+        for name, scratch in re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stderr, re.S):
+            assert name not in found, f"{name} is compiled in two units"
+            found[name] = int(scratch)
     assert len(found) >= 11 and all(s == 0 for s in found.values()), found           # six GEMM instances and five other kernels
     for kernel in ("gemm_kernel", "reduce_kernel", "head_kernel", "head_reduce_kernel", "norm_kernel", "adam_kernel"):
         assert any(kernel in k for k in found), (kernel, found)

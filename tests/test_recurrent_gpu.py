@@ -169,6 +169,32 @@ def test_parameters_are_read_in_place():
     _check_gap([dev.memory_a.out, dev.memory_a.c], [h32, c32], [h64, c64], "after an in-place add_")
 
 
+def test_a_wide_cell_survives_the_bind_of_a_narrow_one():
+    """cell_kernel's dynamic-LDS limit is one per device and kernel: the bind of a handle with small memories must not lower what a handle with
+    wide ones launches with.  Wide: the smallest I = H (multiples of 16) whose 64 (I + H + 8) bytes reach 69 632, the deployed policy's need and
+    the one size this project has recorded as over the default limit."""
+    I = H = 544
+    assert 64 * (I + H + 8) >= 69632 > 64 * (I - 16 + H - 16 + 8)
+    n = 33                                                                       # two full workgroups and a partial one
+    _, wide = _pair(I, H, seed=21)
+    _, narrow = _pair(48, 32, seed=22)
+    xs, states = _inputs(n, (I, I), H, seed=23)
+    rows = {A: xs[0].to(DEV), C: xs[1].to(DEV)}
+
+    def run():
+        _set_state(wide, states, n)
+        outs = wide.cell_step(rows)
+        return [t.clone() for t in outs] + [t.clone() for m in wide.memories() for t in (m.h, m.c)]
+    before = run()
+    assert all(bool(torch.isfinite(t).all()) for t in before) and not torch.equal(before[2].cpu(), states[0][0])
+    small_xs, small_states = _inputs(n, (48, 48), 32, seed=24)
+    _set_state(narrow, small_states, n)
+    small = narrow.cell_step({A: small_xs[0].to(DEV), C: small_xs[1].to(DEV)})   # creates and binds the narrow handle
+    assert all(bool(torch.isfinite(t).all()) for t in small)
+    after = run()
+    assert len(after) == 6 and all(torch.equal(a, b) for a, b in zip(after, before))
+
+
 def test_roll_of_eight_ticks_with_resets():
     T, n, I, H = 8, 33, 48, 32
     cpu, dev = _pair(I, H, seed=10)

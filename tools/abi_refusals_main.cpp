@@ -7,8 +7,9 @@
 //
 //   cd rl-mpc-locomotion_amd/csrc
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined -x hip \
-//         ../../tools/abi_refusals_main.cpp mpc_ppo.hip mpc_ppo_update.hip mpc_privileged_obs.hip mpc_task.hip mpc_episode_terms.hip \
+//         ../../tools/abi_refusals_main.cpp mpc_ppo.hip mpc_ppo_update.hip mpc_ppo_gemm.hip mpc_privileged_obs.hip mpc_task.hip mpc_episode_terms.hip \
 //         -o /tmp/abi_refusals && /tmp/abi_refusals
+// (mpc_ppo_gemm.hip: the GEMMs mpc_ppo_update.hip launches live in that unit.)
 //
 // Exit status 0 and "ok" on the last line when every call answered as expected and the sanitizers stayed silent.
 #include <cstdio>
