@@ -58,8 +58,12 @@ typedef double mpc_double2 __attribute__((ext_vector_type(2)));
 // One wait for every global load issued so far (s_waitcnt vmcnt(0), gfx9 encoding: expcnt and lgkmcnt not waited for).  After a batch of
 // independent loads into registers: what follows uses them without a wait per load (mpc_wrench.h Solver::load_batched)
 #define MPC_WAIT_LOADS() __builtin_amdgcn_s_waitcnt(0x0F70)
+// A wait for every LDS access issued so far (s_waitcnt lgkmcnt(0) alone), for the section profile's sub-laps: the clock is read when its instruction
+// issues, not when the loads before it have returned
+#define MPC_WAIT_LDS() __builtin_amdgcn_s_waitcnt(0xC07F)
 #else
 #define MPC_WAIT_LOADS() ((void)0)
+#define MPC_WAIT_LDS() ((void)0)
 #define MPC_GST(p, v) (*(p) = (v))
 #define MPC_GLD(p) (*(p))
 #define MPC_LDS_LOAD128(p, lo, hi) do { (lo) = (p)[0]; (hi) = (p)[1]; } while (0)

@@ -934,6 +934,16 @@ struct Solver {
   // One LDS round trip and one reciprocal (of the block's determinant) per pair: a wave that runs alone on its SIMD has nobody
   // to hide that latency behind, and it was most of the 540 cycles per pivot of the one-pivot form.
   // The loop over the pairs of a tile row is unrolled so that the pair's position inside its tile is static.
+  //
+  // The fetch asks for what the pair's first arithmetic needs first: piv, then the two rows at my tile COLUMN's slots (x and y are made of them), then
+  // the two rows at my tile row's slots (u, v: first used by the cross update).  LDS answers in order and the compiler waits per use, so x and y run
+  // while u and v are still on their way; with the four rows fetched interleaved the first x needed the last load and the whole round trip was exposed.
+  // Measured on top of that and left out: the inverse of the pivot block formed by every reading lane from the raw block (slower:
+  // the reciprocal chain moves onto every lane's critical path behind the first load), the next pair's fetch ahead of the trailing update (the job
+  // kernel holds 505 of 512 registers: scratch with 27, 15 and with piv's 3 doubles carried) and the column lanes' publish as 128-bit stores (six stores
+  // fewer, fourteen register moves more per pair: 589 instructions per trip).
+  // (-DMPC_PROFILE_SUB=12: per pair, in slots 1 .. 5 and over both jobs, the fetch until its last load is back | x, y and the cross | the publish until
+  //  its stores have landed | the trailing update | what lies between two pairs.  The laps wait for the LDS themselves.)
   static constexpr bool kPairSweep = MPC_PAIR_SWEEP(T);
   MPC_HD void sweep_all() {
     static_assert(TS % 2 == 0, "pairs must not straddle tiles");
@@ -957,17 +967,20 @@ struct Solver {
     const bool pub = ktn < G;
     ex.par([&](Th &t) {
       if (t.mact) {
-        double u[TS], v[TS], x[TS], y[TS];
+        double u[TS], v[TS], uj[TS], vj[TS], x[TS], y[TS];
+        MPC_SUBLAP(12, 5);
         const double *bi = s.piv(buf);
         const double b00 = bi[0], b01 = bi[1], b11 = bi[2];
         const double *r0 = s.prow(buf, 0), *r1 = s.prow(buf, 1);
 #pragma unroll
+        for (int a = 0; a < TS; ++a) { uj[a] = r0[TS * t.tj + a]; vj[a] = r1[TS * t.tj + a]; }      // (what x and y wait for: ahead of u and v)
+#pragma unroll
+        for (int a = 0; a < TS; ++a) { u[a] = r0[TS * t.ti + a]; v[a] = r1[TS * t.ti + a]; }
+        if (MPC_PROFILE_SUB == 12) { MPC_WAIT_LDS(); lap(1); }
+#pragma unroll
         for (int a = 0; a < TS; ++a) {
-          u[a] = r0[TS * t.ti + a];
-          v[a] = r1[TS * t.ti + a];
-          const double uj = r0[TS * t.tj + a], vj = r1[TS * t.tj + a];
-          x[a] = b00 * uj + b01 * vj;
-          y[a] = b01 * uj + b11 * vj;
+          x[a] = b00 * uj[a] + b01 * vj[a];
+          y[a] = b01 * uj[a] + b11 * vj[a];
         }
         auto upd = [&](int a, int b) {   // two fused multiply-adds
           double m = t.Mx[a * TS + b];
@@ -985,13 +998,16 @@ struct Solver {
 #pragma unroll
           for (int b = AN; b < AN + 2; ++b)
             if (a != AN && a != AN + 1) upd(a, b);
+        MPC_SUBLAP(12, 2);
         if (pub) publish<AN>(t, buf ^ 1, ktn);
+        if (MPC_PROFILE_SUB == 12) { MPC_WAIT_LDS(); lap(3); }
         MPC_SCHED_FENCE();
 #pragma unroll
         for (int a = 0; a < TS; ++a)
 #pragma unroll
           for (int b = 0; b < TS; ++b)
             if (a != AN && a != AN + 1 && b != AN && b != AN + 1) upd(a, b);
+        MPC_SUBLAP(12, 4);
       }
     });
   }
@@ -2949,6 +2965,7 @@ struct Solver {
           else {
             for (int k = 6; k < 15; ++k) if (k != 8 && k != 10 && !(k == 6 && MPC_PROFILE_SUB == 10)) MPC_GST(prof + k, MPC_GLD(prof + k) + tc[k]);
             if (MPC_PROFILE_SUB == 11) for (int k = 1; k <= 6; ++k) MPC_GST(prof + k, tc[k]);      // (this job's K-form alone, over what the ADMM job left there)
+            if (MPC_PROFILE_SUB == 12) for (int k = 1; k <= 5; ++k) MPC_GST(prof + k, MPC_GLD(prof + k) + tc[k]);      // (the pairs of both jobs' sweeps)
             MPC_GST(prof, MPC_GLD(prof) + (MPC_CLOCK() - t0));
           }
         }

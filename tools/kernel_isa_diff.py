@@ -4,6 +4,7 @@ labels and directives dropped and symbol names and branch-target numbers made an
 compares equal.  A kernel that several units of a tree emit is taken from the first unit listed.
 
     python tools/kernel_isa_diff.py PARENT_TREE CHANGE_TREE [unit ...] > profiles/<name>.txt
+    python tools/kernel_isa_diff.py PARENT_TREE CHANGE_TREE horizon:12 horizon:16 horizon:20      # the solver kernels of single planning horizons
 
 Prints one line per kernel: ``identical``, or the size of the diff with both sides' instruction counts, VGPRs, AGPRs and scratch bytes."""
 import difflib
@@ -18,27 +19,28 @@ UNITS = ["recurrent", "batch", "ppo_update", "ppo_gemm", "ppo", "recurrent_polic
 
 
 def assembly(tree, unit, tmp):
-    src = os.path.join(tree, "rl-mpc-locomotion_amd", "csrc", f"mpc_{unit}.hip")
+    name, _, h = unit.partition(":")      # "horizon:16": the solver kernels of one planning horizon (mpc_horizon.hip -DMPC_H=16, the Makefile's default contraction)
+    src = os.path.join(tree, "rl-mpc-locomotion_amd", "csrc", f"mpc_{name}.hip")
     if not os.path.exists(src):
         return ""
-    out = os.path.join(tmp, f"{unit}.s")
-    extra = ["-DMPC_HORIZON_LIST(X)=X(10)"] if unit == "batch" else []
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", *extra, "--cuda-device-only", "-S", src, "-o", out], check=True,
+    out = os.path.join(tmp, f"{name}{h}.s")
+    extra = ["-DMPC_HORIZON_LIST(X)=X(10)", "-ffp-contract=off"] if unit == "batch" else [f"-DMPC_H={h}"] if h else ["-ffp-contract=off"]
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", *extra, "--cuda-device-only", "-S", src, "-o", out], check=True,
                    capture_output=True)
     return open(out).read()
 
 
 def short_name(mangled):
     """cell_kernel, gemm_kernel<2,2,1>: the kernel's own identifier out of the Itanium name, whatever namespaces stand in front of it, and its
-    integer template arguments."""
+    integer and bool template arguments."""
     i = 3 if mangled.startswith("_ZN") else 2
     while i < len(mangled) and mangled[i].isdigit():
         m = re.match(r"\d+", mangled[i:])
         ident = mangled[i + m.end():i + m.end() + int(m.group())]
         i += m.end() + len(ident)
         if ident.endswith("kernel"):
-            args = re.match(r"I((?:Li\d+E)+)E", mangled[i:])
-            return ident + ("<" + ",".join(re.findall(r"Li(\d+)E", args.group(1))) + ">" if args else "")
+            args = re.match(r"I((?:L[ib]\d+E)+)E", mangled[i:])
+            return ident + ("<" + ",".join(re.findall(r"L[ib](\d+)E", args.group(1))) + ">" if args else "")
     return mangled
 
 
@@ -73,7 +75,7 @@ def main():
     parent, change = sys.argv[1], sys.argv[2]
     units = sys.argv[3:] or UNITS
     a, b = tree_kernels(parent, units), tree_kernels(change, units)
-    print(f"# kernel: parent unit -> change unit: result   (units: {' '.join(units)}; -O3 -ffp-contract=off, gfx950)")
+    print(f"# kernel: parent unit -> change unit: result   (units: {' '.join(units)}; -O3 and the Makefile's contraction flag of each unit, gfx950)")
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
             print(f"{name}: only in the {'parent' if name in a else 'change'}")
