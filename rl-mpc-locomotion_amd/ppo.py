@@ -20,20 +20,18 @@ RL_Environment/tasks/legged_config_ppo.py); rsl_rl itself is an empty submodule 
     policy = WeightPolicy.from_state_dict(torch.load("model.pt")["model_state_dict"])
 
 Not rsl_rl's: the exploration noise is a counter-based generator keyed by (seed, environment, step, action pair), not torch's, so parity
-with ``Normal.sample`` is in distribution only, and |eps| <= 5.768 (ppo_rollout.h).  Observation normalisation (rsl_rl 2.x's
-``EmpiricalNormalization``) is opt-in: ``PPOTrainer(..., normalize_obs=True)`` puts ``obs_norm.ObsNormalizer`` between the environment and everything
-that reads an observation.  Privileged critic observations (rsl_rl's ``num_critic_obs`` / ``privileged_observations``; the reference uses none) are opt-in too: an
-environment with ``num_privileged_obs`` (``BatchedRLTask(privileged_obs=...)``) gets an asymmetric actor-critic whose critic reads ``env.privileged_obs_buf``,
-in the collection (``mpc_ac_act_asymmetric``), the storage and both update backends.  Recurrent policies (rsl_rl's ``ActorCriticRecurrent``: an LSTM in front of
-each MLP) are opt-in as well: ``PPOTrainer(..., recurrent=RecurrentConfig(...))`` (``recurrent.py``) steps the memories on the device, keeps the state each slot started
-from in the storage, and the torch update back-propagates through time over trajectories cut at the episode ends; the hip update refuses them.  Not built: GRU and
-stacked layers, the device update through time, logging beyond ``infos``.  The runner's episode statistics (mean return and
-length over the last 100 finished episodes) are kept on the device by ``episode.EpisodeStats``; ``PPOTrainer.evaluate`` is the reference's ``cfg.test`` loop.
+with ``Normal.sample`` is in distribution only, and |eps| <= 5.768 (ppo_rollout.h).  Opt-in, each described where ``PPOTrainer`` takes it: observation
+normalisation (rsl_rl 2.x's ``EmpiricalNormalization``; ``obs_norm.ObsNormalizer``), privileged critic observations (rsl_rl's ``num_critic_obs``; the
+reference uses none), recurrent policies (rsl_rl's ``ActorCriticRecurrent``: an LSTM in front of each MLP; ``recurrent.py``), the runner's episode
+statistics on the device (``episode.EpisodeStats``); ``PPOTrainer.evaluate`` is the reference's ``cfg.test`` loop.  Not built: GRU and stacked layers,
+a recurrent ``update="hip"``, logging beyond ``infos``.
 
 The device entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
 """
 import ctypes as C
+from collections import namedtuple
 from dataclasses import dataclass
+from itertools import islice
 
 import torch
 from torch import nn
@@ -125,7 +123,11 @@ class ActorCritic(nn.Module):
 
     ``num_critic_obs`` (rsl_rl's; None: the critic reads the actor's rows, as before): the critic's first ``Linear`` has that width and the critic's
     rows are an argument of their own -- ``act(obs, ..., critic_obs=)``, ``evaluate(critic_obs)``, ``log_prob_entropy_value(obs, actions, critic_obs)``
-    -- through the asymmetric entry points (``mpc_ac_create_asymmetric``, ``mpc_ac_act_asymmetric``).  The state dict has the same keys either way."""
+    -- through the asymmetric entry points (``mpc_ac_create_asymmetric``, ``mpc_ac_act_asymmetric``).  The state dict has the same keys either way.
+
+    The call form is ``ActorCriticRecurrent``'s, one for both: ``hidden_sizes`` (None here) is what a ``RolloutStorage`` keeps per slot,
+    ``reset_memory()`` does nothing, ``reset=`` / ``saved=`` must be None (ValueError otherwise)."""
+    hidden_sizes = None
 
     def __init__(self, num_obs=48, num_actions=NUM_ACTIONS, actor_hidden_dims=(512, 256, 128), critic_hidden_dims=(512, 256, 128), init_noise_std=1.0,
                  num_critic_obs=None):
@@ -178,11 +180,20 @@ class ActorCritic(nn.Module):
         la, lc = self._linears(self.actor), self._linears(self.critic)
         return [m.weight for m in la] + [m.bias for m in la] + [m.weight for m in lc] + [m.bias for m in lc] + [self.std]
 
-    def act(self, obs, seed, step, out=None, return_eps=False, critic_obs=None):
+    def reset_memory(self):
+        pass
+
+    @staticmethod
+    def _no_memory(what, *given):
+        if any(x is not None for x in given):
+            raise ValueError(f"{what}: reset= / saved= on a feed-forward actor-critic, which has no memory")
+
+    def act(self, obs, seed, step, out=None, return_eps=False, critic_obs=None, reset=None, saved=None):
         """``ActorCritic.act`` + ``evaluate`` in one launch: obs [n, num_obs] -> a dict of ``actions`` [n,12], ``actions_log_prob`` [n,1],
         ``values`` [n,1], ``mu`` [n,12], ``sigma`` [n,12] (and ``eps`` [n,12] if asked).  ``out``: the same dict of caller's tensors to write
         into (slot t of a RolloutStorage: ``storage.slot(t)``).  The noise of environment r is a function of (seed, r, step) alone.
         ``critic_obs`` [n, critic_width]: the rows the critic reads (required when ``num_critic_obs`` was given); still one launch."""
+        self._no_memory("ActorCritic.act", reset, saved)
         if critic_obs is None and self.num_critic_obs is not None:
             raise ValueError("this actor-critic was made with num_critic_obs: act needs critic_obs")
         n = self._ready("ActorCritic.act", obs, critic_obs=critic_obs)
@@ -204,15 +215,17 @@ class ActorCritic(nn.Module):
             out = dict(out, eps=eps)
         return out
 
-    def evaluate(self, obs, out=None):
+    def evaluate(self, obs, out=None, reset=None):
         """The critic alone: obs [n, critic_width] (the critic's own rows when ``num_critic_obs`` was given) -> values [n, 1]."""
+        self._no_memory("ActorCritic.evaluate", reset)
         n = self._ready("ActorCritic.evaluate", obs, width=self.critic_width)
         values = torch.empty((n, 1), dtype=torch.float32, device=obs.device) if out is None else tensor_arg(out, torch.float32, n, "out")
         check(lib().mpc_ac_evaluate(self._handle, n, obs.data_ptr(), values.data_ptr(), _lib.stream(obs.device)), "mpc_ac_evaluate")
         return values
 
-    def act_inference(self, obs):
+    def act_inference(self, obs, reset=None):
         """The actor's mean: obs [n, num_obs] -> [n, 12], bit for bit the raw action of ``WeightPolicy.step`` on the same weights."""
+        self._no_memory("ActorCritic.act_inference", reset)
         n = self._ready("ActorCritic.act_inference", obs)
         mean = torch.empty((n, 12), dtype=torch.float32, device=obs.device)
         check(lib().mpc_ac_act_inference(self._handle, n, obs.data_ptr(), mean.data_ptr(), _lib.stream(obs.device)), "mpc_ac_act_inference")
@@ -253,8 +266,8 @@ class RolloutStorage:
         return dict(actions=self.actions[t], actions_log_prob=self.actions_log_prob[t], values=self.values[t], mu=self.mu[t], sigma=self.sigma[t])
 
     def hidden_slot(self, t):
-        """The views of slot t that ``ActorCriticRecurrent.act(..., saved=)`` writes: the state the memories started the slot from."""
-        return dict(h_a=self.saved_h_a[t], c_a=self.saved_c_a[t], h_c=self.saved_h_c[t], c_c=self.saved_c_c[t])
+        """The views of slot t that ``ActorCriticRecurrent.act(..., saved=)`` writes: the state the memories started the slot from (None: none are kept)."""
+        return None if self.hidden is None else dict(h_a=self.saved_h_a[t], c_a=self.saved_c_a[t], h_c=self.saved_h_c[t], c_c=self.saved_c_c[t])
 
     def add(self, rew, reset, time_outs, gamma, obs=None):
         """``PPO.process_env_step`` + ``add_transitions`` for the slot ``act`` has just written (``self.step``, then advanced): rewards[t] = rew +
@@ -555,33 +568,134 @@ class PPO:
         return mean_value / k, mean_surrogate / k
 
 
+class _Rows:
+    """One stream of rows from the environment to the nets.  ``source(returned)``: the raw rows after ``returned = env.reset()`` or ``env.step()[0]`` (the
+    actor's are ``returned``, the critic's ``env.privileged_obs_buf``); ``storage`` [T, N, W]: the rollout's tensor for them; ``norm``: an ``ObsNormalizer``
+    or None; ``held`` [N, W]: the normalised rows between collections."""
+
+    def __init__(self, source, storage, norm=None):
+        self.source, self.storage, self.norm = source, storage, norm
+        self.held = None if norm is None else torch.zeros_like(storage[0])
+
+    def read(self, returned, t=None, update=True):
+        """The rows the environment has just produced: as they are, or counted (``update=False``, an evaluation: the statistics stay) and normalised once,
+        by a launch that writes where a ``copy_`` would have -- after the step of slot ``t`` into ``storage[t + 1]``, which the next tick reads; after
+        the last slot, after ``reset()`` and in an evaluation (``t`` None) into ``held``."""
+        rows = self.source(returned)
+        if self.norm is None:
+            return rows
+        return self.norm(rows, out=self.storage[t + 1] if t is not None and t + 1 < len(self.storage) else self.held, update=update)
+
+    def keep(self, t, rows):
+        """The rows slot t's action and value were computed from, into ``storage[t]`` -- unless ``read`` normalised them into it."""
+        if self.norm is None or t == 0:
+            self.storage[t].copy_(rows)
+
+
+# What rides along in the one host read of an iteration: ``summary()`` -> a 1-D float64 device tensor (or None: nothing to read), ``record(values)``
+# -> the entries its slice of the read adds to the iteration's record, ``after()`` -> what follows the read.  Called through the objects at use time.
+_Rider = namedtuple("_Rider", "summary record after", defaults=(None,))
+SCALARS = ("mean_reward", "done_rate", "value_loss", "surrogate_loss", "mean_noise_std")
+
+
+def _riders(trainer):
+    """The riders of ``trainer`` (anything with its ``_scalars``, ``alg``, ``episode_stats``, ``curriculum`` and ``episode_terms``), in the record's order."""
+    alg, curriculum, terms = trainer.alg, trainer.curriculum, trainer.episode_terms
+
+    def learning_rate(values):                                                   # hip backend: the device's value, which the host copies follow
+        if values:
+            alg.sync_learning_rate(values[0])
+        return {"learning_rate": alg.learning_rate}
+
+    def episodes(s):                                                             # rsl_rl's statistics over the last 100 finished episodes
+        return dict(mean_episode_return=s[S_MEAN_RETURN], mean_episode_length=s[S_MEAN_LENGTH], episodes_in_window=int(s[S_WINDOW_COUNT]),
+                    episodes_finished=int(s[S_EPISODES]), timeouts_in_window=int(s[S_WINDOW_TIMEOUTS]))
+    riders = [_Rider(lambda: trainer._scalars, lambda values: dict(zip(SCALARS, values))),
+              _Rider(lambda: alg.lr_device, learning_rate),                    # (None on the torch backend)
+              _Rider(lambda: trainer.episode_stats.summary, episodes)]
+    if curriculum is not None:                                                   # the terrain levels as they stand after the iteration
+        riders.append(_Rider(lambda: curriculum.summary(), lambda values: curriculum.record(values, curriculum.num_types)))
+    if terms is not None:                                                        # the per-term sums of the iteration's closed episodes; the next record covers the next
+        riders.append(_Rider(lambda: terms.summary(), lambda values: {"episode_terms": terms.record(values)}, lambda: terms.new_window()))
+    return riders
+
+
+def _read_riders(riders):
+    """The riders' summaries in ONE host read, each rider's own values to its ``record``: the entries of the iteration's record, in the riders' order."""
+    parts = [r.summary() for r in riders]
+    flat = iter(torch.cat([p for p in parts if p is not None]).tolist())
+    record = {}
+    for r, p in zip(riders, parts):
+        record.update(r.record(list(islice(flat, 0 if p is None else p.numel()))))
+        if r.after is not None:
+            r.after()
+    return record
+
+
+# A part of the checkpoint beside the model and the optimiser: ``obj`` (None: this trainer has none) is saved under ``key`` and loaded when both sides
+# have it, ``after()`` follows a load.  ``missing`` / ``unexpected``: the error when only the trainer / only the checkpoint has it (None: no error).
+_Part = namedtuple("_Part", "key obj missing unexpected after", defaults=(None, None, None))
+
+
+def _checkpoint_parts(trainer):
+    """The parts of ``trainer`` (anything with its ``obs_norm``, ``critic_obs_norm``, ``episode_terms``, ``plant_rand``, ``env`` and ``obs``), in the checkpoint's order."""
+    env, terms = trainer.env, trainer.episode_terms
+
+    def forget_obs():                                                            # (normalised with the statistics before the load)
+        trainer.obs = None
+
+    def set_clock():                                                             # the command curriculum's clock follows the checkpoint's
+        if hasattr(env, "common_step_counter"):
+            env.common_step_counter = terms.tick
+    return (_Part("obs_norm_state_dict", trainer.obs_norm, "this trainer normalises observations and the checkpoint carries no obs_norm_state_dict",
+                  "the checkpoint was written with observation normalisation and this trainer has none", forget_obs),
+            _Part("critic_obs_norm_state_dict", trainer.critic_obs_norm,
+                  "this trainer normalises the critic's rows and the checkpoint carries no critic_obs_norm_state_dict"),
+            _Part("episode_terms_state_dict", terms, after=set_clock),         # the command range the policy was trained up to
+            _Part("plant_rand_state_dict", trainer.plant_rand))                # the plants the rollouts continue on
+
+
+def _save_parts(parts, ck):
+    ck.update({p.key: p.obj.state_dict() for p in parts if p.obj is not None})
+
+
+def _load_parts(parts, ck):
+    for p in parts:
+        have, held = p.obj is not None, p.key in ck
+        error = p.missing if have else p.unexpected
+        if have != held and error is not None:
+            raise ValueError(error)
+        if have and held:
+            p.obj.load_state_dict(ck[p.key])
+            if p.after is not None:
+                p.after()
+
+
 class PPOTrainer:
     """rsl_rl's ``OnPolicyRunner`` for an environment with ``BatchedRLTask``'s members: ``num_envs``, ``num_obs``, ``num_actions``, ``reset()``,
     ``step(actions) -> (obs, rew, reset, extras)`` with ``extras["time_outs"]`` (rew float32, reset and time_outs int64, cuda).
 
     An iteration: T times ``act`` into slot t, ``env.step``, ``add``; then ``evaluate`` and ``compute_returns`` -- nothing of that is copied to
     the host or waits for the device -- and ``PPO.update``.  ``seed`` seeds torch's global generator (weight initialisation, the update's
-    ``randperm``), as the reference's train.py does, and the exploration noise.
+    ``randperm``), as the reference's train.py does, and the exploration noise.  Every option is opt-in, found on the environment with ``getattr`` or
+    asked for here; without it the launches are the plain trainer's.  Each states once what it adds to one of four things:
 
-    ``normalize_obs=True`` (off by default): every observation the environment returns goes once through an ``ObsNormalizer`` (``obs_norm``; ``obs_norm_eps``,
-    ``obs_norm_until`` are its ``eps`` and ``until``) -- counted once, normalised once with the statistics that include it, written by the normalising
-    launch where the tick's ``copy_`` would have written -- and ``act``, the storage, ``evaluate`` and both update backends see the normalised
-    tensor; ``self.obs`` is then the normalised observation.  ``evaluate`` and ``get_inference_policy`` normalise without updating.
+    **Rows** (``_Rows``).  The actor's are what the environment returns (``self.obs``).  An environment with ``num_privileged_obs``
+    (``BatchedRLTask(privileged_obs=...)``) trains an asymmetric actor-critic: the critic's first layer is that wide and reads each tick's
+    ``env.privileged_obs_buf`` (``self.critic_obs``; None otherwise), kept in ``storage.privileged_observations[t]``; ``last_values`` is the critic's of
+    the last such row.  ``normalize_obs=True`` puts an ``ObsNormalizer`` into each stream (``obs_norm``, ``critic_obs_norm``; ``obs_norm_eps``,
+    ``obs_norm_until`` are their ``eps`` and ``until``): every row is counted once and normalised once with the statistics that include it, and ``act``,
+    the storage, ``evaluate`` and both update backends see the normalised tensor; ``evaluate`` and ``get_inference_policy`` normalise without updating.
+    A constant column of the critic's rows (the zero pad, a contact flag that never changes) has zero variance and normalises to 0 / eps = 0.
 
-    An environment with ``num_privileged_obs`` (``BatchedRLTask(privileged_obs=...)``; read with ``getattr``, None otherwise) trains an asymmetric
-    actor-critic: the critic's first layer is that wide, each tick's ``env.privileged_obs_buf`` is kept in ``storage.privileged_observations[t]``
-    beside the actor's observation (the rows the action was computed from), ``last_values`` is the critic's of the last privileged row, and both
-    update backends feed the critic those rows.  With ``normalize_obs`` the critic's rows go through a second normaliser, ``critic_obs_norm``, under
-    the same discipline (update, then normalise, once per row); a constant column of theirs -- the zero pad, a contact flag that never changes --
-    has zero variance and normalises to 0 / eps = 0.  The checkpoint then carries ``critic_obs_norm_state_dict`` as well.  Without
-    ``num_privileged_obs`` nothing changes: the same launches through the same entry points.
+    **Riders** (``_riders``) of an iteration's one host read, each with the entries it adds to the record (``learn``).  **Checkpoint parts**
+    (``_checkpoint_parts``) beside the model and the optimiser (``save``).  A new option supplies a rider, a part, or a stream of rows.
 
-    ``recurrent=RecurrentConfig(hidden_size=...)`` (``recurrent.py``; None, the default: today's path and launches) trains an ``ActorCriticRecurrent``:
-    each tick's ``act`` is handed the task's reset tensor of the tick before (the memories start an episode from zero state) and slot t's views of the
-    storage's saved hidden states -- nothing more is copied per tick -- and the update is the torch one over padded trajectories, or, with
-    ``RecurrentConfig(update_through_time="hip")``, torch's MLPs, loss and Adam around the memories' roll and backward pass on the device (no padding,
-    no host read besides the adaptive schedule's kl).  The memories read what the MLPs' first layers read otherwise: the normalised observation, the
-    (normalised) privileged rows.  ``update="hip"`` is refused."""
+    **Memory.**  ``recurrent=RecurrentConfig(hidden_size=...)`` (``recurrent.py``) trains an ``ActorCriticRecurrent``: each tick's ``act`` is handed
+    the task's reset tensor of the tick before (the memories start an episode from zero state) and slot t's views of the storage's saved hidden states
+    -- nothing more is copied per tick -- and the update is the torch one over padded trajectories, or, with
+    ``RecurrentConfig(update_through_time="hip")``, torch's MLPs, loss and Adam around the memories' roll and backward pass on the device.  The memories
+    read what the MLPs' first layers read otherwise.  ``update="hip"`` is refused.  A feed-forward actor-critic is called the same way and handed None."""
 
     def __init__(self, env, cfg=None, seed=1, device=None, update="torch", normalize_obs=False, obs_norm_eps=1e-2, obs_norm_until=None, recurrent=None):
         if recurrent is not None and update == "hip":                            # (PPO's own refusal, before the device is asked for)
@@ -593,74 +707,64 @@ class PPOTrainer:
         self.device = _lib.device_of(device if device is not None else getattr(env, "device", None))
         torch.manual_seed(self.seed)
         c = self.cfg
-        self.num_privileged_obs = getattr(env, "num_privileged_obs", None)
+        self.num_privileged_obs, self.curriculum, self.episode_terms, self.plant_rand = (
+            getattr(env, name, None) for name in ("num_privileged_obs", "curriculum", "episode_terms", "plant_rand"))
         priv = self.num_privileged_obs
         self.recurrent = recurrent
-        self._prev_reset = None                                                  # the task's reset tensor of the tick before (recurrent only)
-        if recurrent is None:
-            self.actor_critic = ActorCritic(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std, num_critic_obs=priv).to(self.device)
-        else:
+        self._prev_reset = None                                                  # the task's reset tensor of the tick before (kept for a net with memory only)
+        nets = dict(num_obs=env.num_obs, num_actions=env.num_actions, actor_hidden_dims=c.actor_hidden_dims, critic_hidden_dims=c.critic_hidden_dims,
+                    init_noise_std=c.init_noise_std, num_critic_obs=priv)
+        if recurrent is not None:
             from .recurrent import ActorCriticRecurrent
-            self.actor_critic = ActorCriticRecurrent(env.num_obs, env.num_actions, c.actor_hidden_dims, c.critic_hidden_dims, c.init_noise_std, num_critic_obs=priv,
-                                                     rnn_type=recurrent.rnn_type, rnn_hidden_size=recurrent.hidden_size,
-                                                     rnn_num_layers=recurrent.num_layers,
-                                                     update_through_time=getattr(recurrent, "update_through_time", "torch")).to(self.device)
+            nets.update(rnn_type=recurrent.rnn_type, rnn_hidden_size=recurrent.hidden_size, rnn_num_layers=recurrent.num_layers,
+                        update_through_time=getattr(recurrent, "update_through_time", "torch"))
+        self.actor_critic = (ActorCritic if recurrent is None else ActorCriticRecurrent)(**nets).to(self.device)
         self.alg = PPO(self.actor_critic, c, backend=update)
-        hidden = None if recurrent is None else (int(recurrent.hidden_size), int(recurrent.hidden_size))
         self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions, num_privileged_obs=priv,
-                                      **({} if hidden is None else {"hidden": hidden}))
+                                      hidden=self.actor_critic.hidden_sizes)
         self.episode_stats = EpisodeStats(env.num_envs, device=self.device)      # rsl_rl's rewbuffer / lenbuffer (deque(maxlen=100)), on the device
         self.iteration, self.tick, self.obs = 0, 0, None
         self.critic_obs = None                                                   # the critic's rows that go with self.obs (None without privileged observations)
         self.infos = []
-        self.obs_norm, self.critic_obs_norm = None, None
-        if normalize_obs:
-            self.obs_norm = ObsNormalizer(env.num_obs, eps=obs_norm_eps, until=obs_norm_until, device=self.device)
-            self._obs_held = torch.zeros((env.num_envs, env.num_obs), dtype=torch.float32, device=self.device)      # the normalised observation between collections
-            if priv is not None:
-                self.critic_obs_norm = ObsNormalizer(priv, eps=obs_norm_eps, until=obs_norm_until, device=self.device)
-                self._critic_held = torch.zeros((env.num_envs, priv), dtype=torch.float32, device=self.device)
+        norm = lambda width: ObsNormalizer(width, eps=obs_norm_eps, until=obs_norm_until, device=self.device) if normalize_obs else None
+        self._rows = _Rows(lambda returned: returned, self.storage.observations, norm(env.num_obs))
+        self._critic_rows = None if priv is None else _Rows(lambda _: env.privileged_obs_buf, self.storage.privileged_observations, norm(priv))
+        self.obs_norm, self.critic_obs_norm = self._rows.norm, None if priv is None else self._critic_rows.norm
+        self._scalars = None                                                     # the iteration's five scalars (float64, on the device) for the read
+        self._riders = _riders(self)
 
     def _first_obs(self):
         """``env.reset()``'s observation, normalised (and counted) when normalisation is on; ``critic_obs`` follows it."""
-        obs = self.env.reset()
-        if self.num_privileged_obs is not None:
-            rows = self.env.privileged_obs_buf
-            self.critic_obs = rows if self.critic_obs_norm is None else self.critic_obs_norm(rows, out=self._critic_held)
-        return obs if self.obs_norm is None else self.obs_norm(obs, out=self._obs_held)
+        returned = self.env.reset()
+        if self._critic_rows is not None:
+            self.critic_obs = self._critic_rows.read(returned)
+        return self._rows.read(returned)
 
     def collect(self, record_eps=None):
         """The collection half of one iteration (T ticks), entirely on the device.  ``record_eps``: a list that receives each tick's noise."""
-        c, st = self.cfg, self.storage
+        c, st, rows, critic_rows = self.cfg, self.storage, self._rows, self._critic_rows
         if self.obs is None:
             self.obs = self._first_obs()
         st.clear()
-        norm, cnorm, priv = self.obs_norm, self.critic_obs_norm, self.num_privileged_obs is not None
-        rec = self.recurrent is not None
         with torch.no_grad():
-            for t in range(st.T):
-                obs, critic_obs = self.obs, self.critic_obs
-                memory = dict(reset=self._prev_reset, saved=st.hidden_slot(t)) if rec else {}      # the memories' state of slot t goes straight into the storage
-                out = self.actor_critic.act(obs, self.seed, self.tick, out=st.slot(t), return_eps=record_eps is not None, critic_obs=critic_obs, **memory)
+            for t in range(st.T):                                                # (the memories' state of slot t goes straight into the storage)
+                out = self.actor_critic.act(self.obs, self.seed, self.tick, out=st.slot(t), return_eps=record_eps is not None, critic_obs=self.critic_obs,
+                                            reset=self._prev_reset, saved=st.hidden_slot(t))
                 if record_eps is not None:
                     record_eps.append(out["eps"])
-                if norm is None or t == 0:
-                    st.observations[t].copy_(obs)
-                if priv and (cnorm is None or t == 0):                           # the critic's rows the values of slot t were computed from
-                    st.privileged_observations[t].copy_(critic_obs)
-                self.obs, rew, reset, extras = self.env.step(st.actions[t])
-                if rec:                                                          # (the task's own buffer: read by the next cell launch, before the next step rewrites it)
+                rows.keep(t, self.obs)
+                if critic_rows is not None:
+                    critic_rows.keep(t, self.critic_obs)
+                returned, rew, reset, extras = self.env.step(st.actions[t])
+                if st.hidden is not None:                                        # (the task's own buffer: read by the next cell launch, before the next step rewrites it)
                     self._prev_reset = reset
-                if norm is not None:                                             # update, then normalise, into the slot the next tick reads
-                    self.obs = norm(self.obs, out=st.observations[t + 1] if t + 1 < st.T else self._obs_held)
-                if priv:                                                         # the task's own buffer, rewritten by its next step; or its normalised copy
-                    self.critic_obs = self.env.privileged_obs_buf
-                    if cnorm is not None:
-                        self.critic_obs = cnorm(self.critic_obs, out=st.privileged_observations[t + 1] if t + 1 < st.T else self._critic_held)
+                self.obs = rows.read(returned, t)
+                if critic_rows is not None:                                      # the task's own buffer, rewritten by its next step; or its normalised copy
+                    self.critic_obs = critic_rows.read(returned, t)
                 st.add(rew, reset, extras["time_outs"], c.gamma)
                 self.episode_stats.add(rew, reset, extras["time_outs"])
                 self.tick += 1
-            self.last_values = self.actor_critic.evaluate(self.critic_obs if priv else self.obs, **({"reset": self._prev_reset} if rec else {}))
+            self.last_values = self.actor_critic.evaluate(self.obs if critic_rows is None else self.critic_obs, reset=self._prev_reset)
             st.compute_returns(self.last_values, c.gamma, c.lam)
 
     def learn(self, num_iterations, init_at_random_ep_len=False):
@@ -684,31 +788,9 @@ class PPOTrainer:
             self.collect()
             mean_reward, done_rate = self.storage.rewards.mean(), self.storage.dones.mean()
             value_loss, surrogate = self.alg.update(self.storage)
-            stats = torch.stack((mean_reward, done_rate, value_loss, surrogate, self.actor_critic.std.detach().mean())).double()
-            episodes = self.episode_stats.summary                                # float64, on the device: rides along in the one read
-            curriculum = getattr(self.env, "curriculum", None)
-            tail = (episodes,) if curriculum is None else (episodes, curriculum.summary())      # (a terrain curriculum's levels ride along too)
-            terms = getattr(self.env, "episode_terms", None)
-            if terms is not None:                                                # (and the per-term episode sums of the iteration's closed episodes)
-                terms_summary = terms.summary()
-                tail = tail + (terms_summary,)
-            if self.alg.backend == "hip":                                        # and so does the device's learning rate
-                stats = torch.cat((stats, self.alg.lr_device, *tail)).tolist()
-                self.alg.sync_learning_rate(stats[5])
-                ep = stats[6:]
-            else:
-                stats = torch.cat((stats, *tail)).tolist()
-                ep = stats[5:]
+            self._scalars = torch.stack((mean_reward, done_rate, value_loss, surrogate, self.actor_critic.std.detach().mean())).double()
             self.iteration += 1
-            self.infos.append(dict(iter=self.iteration, mean_reward=stats[0], done_rate=stats[1], value_loss=stats[2], surrogate_loss=stats[3],
-                                   mean_noise_std=stats[4], learning_rate=self.alg.learning_rate, mean_episode_return=ep[S_MEAN_RETURN],
-                                   mean_episode_length=ep[S_MEAN_LENGTH], episodes_in_window=int(ep[S_WINDOW_COUNT]),
-                                   episodes_finished=int(ep[S_EPISODES]), timeouts_in_window=int(ep[S_WINDOW_TIMEOUTS])))
-            if curriculum is not None:
-                self.infos[-1].update(curriculum.record(ep[episodes.numel():], curriculum.num_types))
-            if terms is not None:
-                self.infos[-1]["episode_terms"] = terms.record(ep[len(ep) - terms_summary.numel():])
-                terms.new_window()                                               # the next record covers the next iteration's episodes
+            self.infos.append(dict(iter=self.iteration, **_read_riders(self._riders)))
         return self.infos
 
     def evaluate(self, num_ticks, groups=None, num_groups=1):
@@ -721,35 +803,27 @@ class PPOTrainer:
         stats = EpisodeStats(self.env.num_envs, groups=groups, num_groups=num_groups, device=self.device)
         if self.obs is None:
             self.obs = self._first_obs()
-        norm = self.obs_norm
-        terms = getattr(self.env, "episode_terms", None)
+        terms = self.episode_terms
         enabled = terms.curriculum_enabled if terms is not None else None
         if terms is not None:                                                    # an evaluation does not move the command ranges
             terms.curriculum_enabled = False
-        rec = self.recurrent is not None
         try:
             with torch.no_grad():
-                for _ in range(int(num_ticks)):
-                    if rec:                                                      # the actor's memory alone, from zero state where an episode starts
-                        action = self.actor_critic.act_inference(self.obs, reset=self._prev_reset)
-                    else:
-                        action = self.actor_critic.act_inference(self.obs)
-                    self.obs, rew, reset, extras = self.env.step(action)
-                    if rec:
+                for _ in range(int(num_ticks)):                                  # the actor's memory alone, from zero state where an episode starts
+                    action = self.actor_critic.act_inference(self.obs, reset=self._prev_reset)
+                    returned, rew, reset, extras = self.env.step(action)
+                    if self.storage.hidden is not None:
                         self._prev_reset = reset
-                    if norm is not None:                                         # the statistics stay as training left them
-                        self.obs = norm(self.obs, out=self._obs_held, update=False)
+                    self.obs = self._rows.read(returned, update=False)           # the statistics stay as training left them
                     stats.add(rew, reset, extras["time_outs"])
-                if self.num_privileged_obs is not None:                          # the critic's rows that go with self.obs, for the next collection
-                    rows = self.env.privileged_obs_buf
-                    self.critic_obs = rows if self.critic_obs_norm is None else self.critic_obs_norm(rows, out=self._critic_held, update=False)
+                if self._critic_rows is not None:                                # the critic's rows that go with self.obs, for the next collection
+                    self.critic_obs = self._critic_rows.read(None, update=False)
         finally:
             if terms is not None:
                 terms.curriculum_enabled = enabled
         out = stats.read()
-        if rec:                                                                  # the critic's memory has not seen these ticks: both start the next collection from zero
-            self.actor_critic.reset_memory()
-            self._prev_reset = None
+        self.actor_critic.reset_memory()                                         # the critic's memory has not seen these ticks: both start the next collection from zero
+        self._prev_reset = None
         self.episode_stats.restart()
         keys = ("episodes", "time_outs", "terminations", "mean_return", "mean_length")
         result = {k: out[k] for k in keys}
@@ -767,16 +841,7 @@ class PPOTrainer:
         restores when present; a checkpoint without it leaves the record as the task made it."""
         ck = {"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(), "iter": self.iteration,
               "infos": self.infos}
-        if self.obs_norm is not None:
-            ck["obs_norm_state_dict"] = self.obs_norm.state_dict()
-        if self.critic_obs_norm is not None:                                     # the critic's rows have statistics of their own
-            ck["critic_obs_norm_state_dict"] = self.critic_obs_norm.state_dict()
-        terms = getattr(self.env, "episode_terms", None)
-        if terms is not None:                                                    # the command range the policy was trained up to
-            ck["episode_terms_state_dict"] = terms.state_dict()
-        plant = getattr(self.env, "plant_rand", None)
-        if plant is not None:                                                    # the plants the rollouts continue on
-            ck["plant_rand_state_dict"] = plant.state_dict()
+        _save_parts(_checkpoint_parts(self), ck)
         torch.save(ck, path)
 
     def load(self, path, load_optimizer=True):
@@ -788,28 +853,10 @@ class PPOTrainer:
         width = int(ck["model_state_dict"]["critic.0.weight"].shape[1])
         if width != self.actor_critic.critic_width:
             raise ValueError(f"the checkpoint's critic reads rows of {width} columns, this trainer's critic rows of {self.actor_critic.critic_width}")
-        if ("obs_norm_state_dict" in ck) != (self.obs_norm is not None):
-            raise ValueError("the checkpoint was written with observation normalisation and this trainer has none" if self.obs_norm is None else
-                             "this trainer normalises observations and the checkpoint carries no obs_norm_state_dict")
-        if self.obs_norm is not None:
-            self.obs_norm.load_state_dict(ck["obs_norm_state_dict"])
-            self.obs = None                                                      # (normalised with the statistics before the load)
-        if self.critic_obs_norm is not None:
-            if "critic_obs_norm_state_dict" not in ck:
-                raise ValueError("this trainer normalises the critic's rows and the checkpoint carries no critic_obs_norm_state_dict")
-            self.critic_obs_norm.load_state_dict(ck["critic_obs_norm_state_dict"])
-        terms = getattr(self.env, "episode_terms", None)
-        if terms is not None and "episode_terms_state_dict" in ck:
-            terms.load_state_dict(ck["episode_terms_state_dict"])
-            if hasattr(self.env, "common_step_counter"):
-                self.env.common_step_counter = terms.tick
-        plant = getattr(self.env, "plant_rand", None)
-        if plant is not None and "plant_rand_state_dict" in ck:
-            plant.load_state_dict(ck["plant_rand_state_dict"])
+        _load_parts(_checkpoint_parts(self), ck)
         self.actor_critic.load_state_dict(ck["model_state_dict"])      # (in place: the kernels keep reading the same addresses)
-        if self.recurrent is not None:                                           # (a state the loaded memories did not compute)
-            self.actor_critic.reset_memory()
-            self._prev_reset = None
+        self.actor_critic.reset_memory()                                         # (a state the loaded memories did not compute)
+        self._prev_reset = None
         if load_optimizer:
             self.alg.optimizer.load_state_dict(ck["optimizer_state_dict"])
             if self.alg.backend == "hip":                                        # the device's copy of the learning rate follows the checkpoint's
@@ -824,6 +871,5 @@ class PPOTrainer:
         before, and advances the actor's memory on every call."""
         if self.obs_norm is None:
             return self.actor_critic.act_inference
-        if self.recurrent is not None:
-            return lambda obs, reset=None: self.actor_critic.act_inference(self.obs_norm(obs, update=False), reset=reset)
-        return lambda obs: self.actor_critic.act_inference(self.obs_norm(obs, update=False))
+        return lambda obs, reset=None: self.actor_critic.act_inference(self.obs_norm(obs, update=False), reset=reset)
+

@@ -392,6 +392,7 @@ class ActorCriticRecurrent(ActorCritic):
         self.critic_obs_width = int(num_obs if num_critic_obs is None else num_critic_obs)
         self.privileged = num_critic_obs is not None                             # the critic's memory reads rows of its own
         self.rnn_hidden_size = H
+        self.hidden_sizes = (H, H)                                               # what a RolloutStorage keeps per slot: (h, c) of memory_a, of memory_c
         self.memory_a = Memory(self.obs_width, H)
         self.memory_c = Memory(self.critic_obs_width, H)
         self._cell_handle, self._cell_ptrs = None, None

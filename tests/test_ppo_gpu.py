@@ -279,3 +279,69 @@ def test_checkpoint_round_trip(tmp_path):
     assert torch.equal(raw, want)
     fresh.learn(1)                                                               # and training goes on from it
     assert fresh.iteration == 3
+
+
+# every option at once: the riders of learn's one read in their full order, every checkpoint part, both kinds of actor-critic
+RECORD_KEYS = ["iter", "mean_reward", "done_rate", "value_loss", "surrogate_loss", "mean_noise_std", "learning_rate", "mean_episode_return", "mean_episode_length",
+               "episodes_in_window", "episodes_finished", "timeouts_in_window", "mean_terrain_level", "terrain_level_by_type", "episode_terms"]
+CHECKPOINT_KEYS = ["critic_obs_norm_state_dict", "episode_terms_state_dict", "infos", "iter", "model_state_dict", "obs_norm_state_dict", "optimizer_state_dict",
+                   "plant_rand_state_dict"]
+
+
+def _all_options_task(n=64):
+    """64 environments of the three robot types on test_curriculum_gpu's 3 x 2 grid with episodes of 3 ticks, so that resets, episode closes, terrain
+    and command curriculum moves, pushes and plant draws all happen inside a collection of 4 ticks."""
+    from rl_mpc_locomotion_amd import curriculum as K, domain_rand as DR, episode_terms as E, height_scan as HS, plant_rand as PR, privileged_obs as V
+    from tests.test_curriculum_gpu import grid
+    cfg = R.TaskConfig(command_x_range=(0.2, 0.5), command_y_range=(-0.1, 0.1), command_yaw_range=(-0.3, 0.3), episode_length_s=0.03, seed=4)
+    scan = HS.HeightScan(n, device=DEV)
+    return R.BatchedRLTask(
+        [i % 3 for i in range(n)], [TROT] * n, cfg=cfg, horizon=10, device=DEV, yaw0=np.random.default_rng(6).uniform(-np.pi, np.pi, n), height_scan=scan,
+        curriculum=K.TerrainCurriculum(grid(), n, max_init_level=1, seed=2, device=DEV, env_length=0.0002, episode_length_s=cfg.episode_length_s),
+        episode_terms=E.EpisodeTerms(n, cfg, command_curriculum=E.CommandCurriculumSpec(1.5, x_range0=(-0.5, 0.5), step=0.5, threshold=0.0, update_every=1),
+                                     device=DEV),
+        domain_rand=DR.DomainRand(n, observations=DR.NoiseSpec.legged_gym(cfg, height_scan=scan), actions=DR.NoiseSpec("gaussian", "additive", (0.0, 0.05)),
+                                  push=DR.PushSpec(interval_s=0.02, max_vel_xy=0.5), seed=9, device=DEV),
+        plant_rand=PR.PlantRand(n, PR.PlantSpec(payload=(-1.0, 3.0), strength=(0.9, 1.1), gravity=(-1.0, 1.0), resample="reset"), seed=21, device=DEV),
+        privileged_obs=V.PrivilegedObs(n, device=DEV, plant=True))
+
+
+@pytest.mark.parametrize("kind", ["feed_forward_hip_update", "recurrent_through_time_on_the_device"])
+def test_all_options_at_once(kind, tmp_path):
+    from rl_mpc_locomotion_amd.episode_terms import EpisodeTerms
+    from rl_mpc_locomotion_amd.recurrent import RecurrentConfig
+    recurrent = kind.startswith("recurrent")
+    cfg = P.PPOConfig(num_steps_per_env=4, num_learning_epochs=1, num_mini_batches=2, actor_hidden_dims=(64, 32), critic_hidden_dims=(32,))
+    how = dict(update="torch", recurrent=RecurrentConfig(hidden_size=32, update_through_time="hip")) if recurrent else dict(update="hip")
+    task = _all_options_task()
+    cur, et = task.curriculum, task.episode_terms
+    trainer = P.PPOTrainer(task, cfg, seed=3, normalize_obs=True, **how)
+    held, asked, summary, zero = [], [], et.summary, et.new_window
+
+    def new_window():                                                            # what the window held when the trainer read it
+        held.append(summary().tolist())
+        zero()
+    et.summary = lambda: (asked.append(1), summary())[1]
+    et.new_window = new_window
+    infos = trainer.learn(2)
+    assert len(infos) == 2 and all(list(i) == RECORD_KEYS for i in infos) and [i["iter"] for i in infos] == [1, 2]
+    if not recurrent:
+        assert infos[-1]["learning_rate"] == trainer.alg.lr_device.item() == trainer.alg.learning_rate
+    levels = cur.record(cur.summary().tolist(), cur.num_types)
+    assert {k: infos[-1][k] for k in levels} == levels and len(levels["terrain_level_by_type"]) == cur.num_types == 2
+    assert len(asked) == len(held) == 2 and [i["episode_terms"] for i in infos] == [EpisodeTerms.record(h) for h in held]      # one summary read per iteration
+    # the options did their work inside the collections (the first tick's resets close empty episodes, which are not counted: the second window has the closes)
+    assert held[0][0] == 0 and held[1][0] >= 64 and infos[1]["episode_terms"]["command_widenings"] >= 1 and task.plant_rand.get_counters().min() >= 2
+    assert infos[1]["mean_terrain_level"] != infos[0]["mean_terrain_level"]
+    path = str(tmp_path / "all.pt")
+    trainer.save(path)
+    assert sorted(torch.load(path)) == CHECKPOINT_KEYS
+    fresh = P.PPOTrainer(_all_options_task(), cfg, seed=4, normalize_obs=True, **how)
+    obs = torch.randn((64, task.num_obs), generator=torch.Generator().manual_seed(8)).to(DEV)
+    start = dict(reset=torch.ones(64, dtype=torch.long, device=DEV)) if recurrent else {}      # (the actor's memory starts from zero state on either side)
+    want = trainer.get_inference_policy()(obs, **start)
+    assert not torch.equal(fresh.get_inference_policy()(obs, **start), want)
+    fresh.load(path)
+    assert fresh.iteration == 2 and fresh._prev_reset is None and fresh.obs is None
+    assert torch.equal(fresh.get_inference_policy()(obs, **start), want)
+    assert len(fresh.learn(1)) == 3 and fresh.iteration == 3 and list(fresh.infos[-1]) == RECORD_KEYS
