@@ -276,7 +276,7 @@ MPC_HD void leg_update_data(CtrlState &s, const RobotConst &rc, const float *dof
 // ---- first half of the tick -----------------------------------------------------------------
 // dof: [12][2] (pos, vel) leg-major; est: kEstLen floats; cmd: 16 floats (vx vy yaw_rate w[13]).
 // rec: solver input record [56 + 4h] (written only when s.do_solve).
-// The tick's first half comes in two parts so that the device can give every leg its own lane (mpc_batch.hip ctrl_pre_kernel): the legs
+// The tick's first half comes in two parts so that the device can give every leg its own lane (mpc_ctrl.hip ctrl_pre_kernel): the legs
 // [l0, l1) of this call do their own work, everything that concerns the whole robot is computed by every caller alike (and stored by the
 // one with lead = true).  ctrl_pre_legs: joint data, kinematics, foot positions.  Between the two parts the lanes of a robot exchange
 // foot_positions; ctrl_pre_rest needs those of all four legs.  The host and the FSM path call ctrl_pre, i.e. both parts for all legs.

@@ -3,7 +3,7 @@
 // what the solve kernel shares with them (constants, Cfg, the record layouts).  The OSQP iteration itself -- re-expressed in
 // the 6 h-dimensional space of the net body wrenches -- is Solver in mpc_wrench.h.
 //
-//   Device build (mpc_batch.hip): Exec::par(f) = { f(thread); __syncthreads(); } -- the per-thread
+//   Device build (mpc_horizon.hip, DeviceExec of mpc_device.h): Exec::par(f) = { f(thread); __syncthreads(); } -- the per-thread
 //   state lives in VGPRs, the shared structs in LDS.
 //   Host emulation (tests/emu): Exec::par(f) runs f for every emulated thread (in forward or reverse
 //   order, to expose intra-phase races); used only by the CPU tests.

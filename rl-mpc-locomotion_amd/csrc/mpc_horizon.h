@@ -1,4 +1,4 @@
-// mpc_horizon.h -- the seam between the C ABI (mpc_batch.hip) and the per-horizon kernel sets (mpc_horizon.hip).
+// mpc_horizon.h -- the seam between the solver handle (mpc_batch.hip) and the per-horizon kernel sets (mpc_horizon.hip).
 //
 // ConvexMpc accepts any planning_horizon (mpc_osqp.cc:186-190, 508-574; the shipped Python uses 10, ConvexMPCLocomotion.py:27;
 // BASELINE's configurations 10, 16, 20).  The kernels keep their matrices in statically indexed register tiles, so the horizon is a

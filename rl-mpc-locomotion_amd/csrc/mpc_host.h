@@ -8,6 +8,7 @@
 //   ErrorSlot, HIP_TRY the text behind mpc_*_last_error and the check of a HIP call
 //   round16            a byte rounding
 //   aligned16, present16, Range, any_overlap   the pointer checks in front of 16-byte loads and of a call's output arrays
+//   launch_over_ids    one launch over all robots, a host list of ids (uploaded and freed on the stream) or a device list
 //   LdsLimit           a kernel's dynamic-LDS limit, grow-only per device
 //
 // A unit keeps its own slot, and with it its own mpc_*_last_error, and names the slot's setter `fail`:
@@ -15,7 +16,8 @@
 //   thread_local mpchost::ErrorSlot g_err;
 //   int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 //   }
-// (mpc_ppo_update.hip's `fail` forwards to mpc_ppo.hip's slot instead.)  HIP_TRY returns through that `fail`.
+// (Where several units share one mpc_*_last_error, one of them owns the slot and the others' `fail` forwards to it: mpc_ppo_update.hip's to
+// mpc_ppo.hip's, mpc_ctrl.hip's and mpc_policy.hip's to mpc_batch.hip's.)  HIP_TRY returns through that `fail`.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -120,6 +122,27 @@ inline bool any_overlap(const Range *r, int n) {
       if (a && b && a < b + r[j].bytes && b < a + r[i].bytes) return true;
     }
   return false;
+}
+
+// One launch over the robots a reset names: launch(d_ids, count) with (null, n) for all of them (ids null), with the k ids of a device list, or
+// with the k ids of a host list, which are uploaded on the stream in front of the launch and freed on it behind.  Nothing to do for k <= 0.
+enum class Ids { host, device };
+template <typename Launch>
+hipError_t launch_over_ids(const int *ids, int k, int n, Ids where, hipStream_t st, Launch launch) {
+  if (ids && k <= 0) return hipSuccess;
+  if (!ids || where == Ids::device) {
+    launch(ids, ids ? k : n);
+    return hipGetLastError();
+  }
+  int *d_ids = nullptr;
+  hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&d_ids), sizeof(int) * k, st);
+  if (e != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(d_ids, ids, sizeof(int) * k, hipMemcpyHostToDevice, st)) == hipSuccess) {
+    launch(d_ids, k);
+    e = hipGetLastError();
+  }
+  const hipError_t freed = hipFreeAsync(d_ids, st);
+  return e != hipSuccess ? e : freed;
 }
 
 // The dynamic-LDS limit of one kernel (hipFuncAttributeMaxDynamicSharedMemorySize): one value per device and kernel, not one per handle, so it

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(policy::kThreads) void ac_kernel(Nets nets, int fir
   const int which = first_net + (int)blockIdx.y;
   const policy::Net &net = nets.net[which];
   const float *__restrict__ obs = which == kCritic ? critic_obs : actor_obs;
-  int wmax_even = 0, wmax_odd = 0;     // widest activation held by buffer 0 (layers 0, 2, ...) / buffer 1, as mpc_batch.hip's mlp_kernel lays them out
+  int wmax_even = 0, wmax_odd = 0;     // widest activation held by buffer 0 (layers 0, 2, ...) / buffer 1, as mpc_policy.hip's mlp_kernel lays them out
   for (int l = 0; l <= net.n_layers; ++l) {
     int &m = (l & 1) ? wmax_odd : wmax_even;
     m = net.dims[l] > m ? net.dims[l] : m;

@@ -2913,7 +2913,7 @@ struct Solver {
     return true;
   }
 
-  // ---- the OSQP-mode solve as two jobs of a persistent wave (mpc_batch.hip: mpc_solve_jobs_kernel).  The ADMM part of a solve takes
+  // ---- the OSQP-mode solve as two jobs of a persistent wave (mpc_horizon.hip: mpc_solve_jobs_kernel).  The ADMM part of a solve takes
   // 25 ... 250+ iterations, the polish that follows is the same work for every robot and needs nothing of the ADMM part but its
   // result (x, z, y and the two residuals its acceptance test compares with, polish.c:306-345): a separate job that any wave can
   // run, which is what fills the tail of a launch.  admm_job leaves the complete result of a solve whose polish "has not

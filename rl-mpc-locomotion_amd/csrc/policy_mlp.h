@@ -4,7 +4,7 @@
 //   RL_Environment/tasks/legged_config_ppo.py:5-9)  ->  clamp to [-1, 1] and the affine map to MPC weights
 //   (WeightPolicy.step, :94-118; Parameters.MPC_param_scale / MPC_param_const, MPC_Controller/Parameters.py:25-33).
 //
-// One fused kernel (mpc_batch.hip's mlp_kernel; here is what it shares with ac_kernel and step_kernel): a workgroup carries 16 robots through every layer -- 4096 robots are 256 workgroups, one per CU of the chip (32 robots
+// One fused kernel (mpc_policy.hip's mlp_kernel; here is what it shares with ac_kernel and step_kernel): a workgroup carries 16 robots through every layer -- 4096 robots are 256 workgroups, one per CU of the chip (32 robots
 // per workgroup left half the CUs idle); activations stay in LDS, weights stream from L2 (760 KB, shared by all workgroups) as 16-byte
 // loads, the products run on the fp32 MFMA pipe (v_mfma_f32_16x16x4_f32: exact fp32 FMA chains, so the result differs from a CPU sgemm
 // only by the summation order).  Rows of the MFMA tile are robots, columns are output neurons; a wave owns groups of up to four

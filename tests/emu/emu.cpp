@@ -52,7 +52,7 @@ struct HostExec {
     else for (int i = NTHREADS - 1; i >= 0; --i) f(th[i]);
   }
   template <class F> void seq(F &&f) { par(f); --phases; }   // (not an LDS hand-over on the device: not counted)
-  // the device's DPP quad operations (mpc_batch.hip DeviceExec), lane by lane
+  // the device's DPP quad operations (mpc_device.h DeviceExec), lane by lane
   template <int N, class A> void quad_allsum(A &&acc) {
     for (int q = 0; q + 3 < NTHREADS; q += 4)
       for (int i = 0; i < N; ++i) {

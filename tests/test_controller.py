@@ -350,7 +350,7 @@ def test_hip_controller_reset_and_gait_switch():
 
 
 @pytest.mark.gpu
-def test_env_bridge_equals_manual_composition():
+def test_env_bridge_command_record_equals_torch_composition():
     """MpcEnvBridge.pre_physics_step (one fused rescale + pack kernel, then controller.run) against the composition it replaced -- torch.mul(...).add(...),
     three slice copies into the command record, BatchedLocomotion.run (RL_Environment/tasks/aliengo.py:237-258 statement by statement): torques bit-identical
     on every tick, device-side reset_idx included."""

@@ -160,6 +160,37 @@ def test_non_finite_input_fails_cleanly():
     assert np.array_equal(f2[2], good[2]) and np.array_equal(info2[2, :5], _solve(_gpu(wl.mass, wl.inertia_diag, h, wl.dt_mpc, wl.alpha), wl.inputs)[1][2, :5])
 
 
+def test_host_solve_float32_and_float64_records_agree():
+    """mpc_batch_solve_host and mpc_batch_solve_host_f64 are one body: the same float32-representable records through both give the same info and
+    the same forces bit for bit, and the robot whose record is not finite keeps the force row that was passed in, on both paths."""
+    import ctypes as C
+    from rl_mpc_locomotion_amd import _lib
+    n, h = 3, 10
+    wl = make_solver_workload(n, h=h, seed=7, config=2)
+    rec32 = np.ascontiguousarray(wl.inputs, dtype=np.float32)
+    rec32[1, 16:19] = np.inf                       # com_velocity of robot 1
+    rec64 = rec32.astype(np.float64)
+    assert np.array_equal(rec64.astype(np.float32), rec32, equal_nan=True)
+    lib, out = _lib.lib(), {}
+    for name, rec in (("mpc_batch_solve_host", rec32), ("mpc_batch_solve_host_f64", rec64)):
+        handle = C.c_void_p()
+        _lib.check(lib.mpc_batch_create(C.byref(handle), n, h, float(wl.dt_mpc), float(wl.alpha), np.ascontiguousarray(wl.mass, dtype=np.float64).ctypes.data,
+                                        inertia9_from_diag(wl.inertia_diag).ctypes.data), "mpc_batch_create")
+        try:
+            forces = np.full((n, 12 * h), 123.0, dtype=np.float64)
+            info = np.zeros((n, 8), dtype=np.int32)
+            _lib.check(getattr(lib, name)(handle, rec.ctypes.data, forces.ctypes.data, info.ctypes.data), name)
+        finally:
+            lib.mpc_batch_destroy(handle)
+        out[name] = (forces, info)
+    (f32, i32), (f64, i64) = out["mpc_batch_solve_host"], out["mpc_batch_solve_host_f64"]
+    print("host solve f32 / f64: statuses", i32[:, 1].tolist(), i64[:, 1].tolist(), "max |force difference| robots 0, 2:", np.abs(f32[[0, 2]] - f64[[0, 2]]).max())
+    assert (i32[[0, 2], 1] == 1).all() and np.array_equal(i32[[0, 2]], i64[[0, 2]])
+    assert np.array_equal(f32[[0, 2]], f64[[0, 2]]) and not (f32[[0, 2]] == 123.0).all()
+    assert i32[1, 1] != 1 and i64[1, 1] != 1
+    assert (f32[1] == 123.0).all() and (f64[1] == 123.0).all()
+
+
 def test_reset_with_device_ids_equals_host_ids():
     """env_ids as a device tensor (VecTask.reset_idx) takes the stream-ordered device path; same result as host ids."""
     import torch

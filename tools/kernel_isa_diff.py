@@ -15,7 +15,7 @@ import sys
 import tempfile
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-UNITS = ["recurrent", "batch", "ppo_update", "ppo_gemm", "ppo", "recurrent_policy", "recurrent_bptt"]
+UNITS = ["recurrent", "batch", "ctrl", "policy", "ppo_update", "ppo_gemm", "ppo", "recurrent_policy", "recurrent_bptt"]
 
 
 def assembly(tree, unit, tmp):
