@@ -16,8 +16,9 @@ _EPISODE_TERMS = ("EpisodeTerms", "CommandCurriculumSpec")
 _PRIVILEGED_OBS = ("PrivilegedObs",)
 _PLANT_RAND = ("PlantRand", "PlantSpec")
 _RECURRENT = ("ActorCriticRecurrent", "Memory", "RecurrentConfig")
+_REWARD_SHAPING = ("RewardShaping", "ShapingSpec")
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS, "privileged_obs", *_PRIVILEGED_OBS, "plant_rand", *_PLANT_RAND, "recurrent", *_RECURRENT]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS, "privileged_obs", *_PRIVILEGED_OBS, "plant_rand", *_PLANT_RAND, "recurrent", *_RECURRENT, "reward_shaping", *_REWARD_SHAPING]
 
 
 def __getattr__(name):
@@ -52,4 +53,7 @@ def __getattr__(name):
     if name in _RECURRENT:
         from . import recurrent
         return getattr(recurrent, name)
+    if name in _REWARD_SHAPING:
+        from . import reward_shaping
+        return getattr(reward_shaping, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

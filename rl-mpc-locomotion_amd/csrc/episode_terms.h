@@ -63,13 +63,17 @@ MPC_HD void accumulate_env(const float *terms, float *sums, int &ticks) {
   ticks += 1;
 }
 
-// false for NaN and +-inf in any of the six sums
-MPC_HD bool finite_sums(const float *sums) {
+// false for NaN and +-inf in any of the kT sums (reward_shaping.h keeps eight)
+template <int kT>
+MPC_HD bool finite_sums_n(const float *sums) {
   bool ok = true;
 #pragma unroll
-  for (int i = 0; i < kTerms; ++i) ok = ok && fabsf(sums[i]) <= 3.402823466e+38f;
+  for (int i = 0; i < kT; ++i) ok = ok && fabsf(sums[i]) <= 3.402823466e+38f;
   return ok;
 }
+
+// false for NaN and +-inf in any of the six sums
+MPC_HD bool finite_sums(const float *sums) { return finite_sums_n<kTerms>(sums); }
 
 // An environment closes an episode when the task's `begin` has just marked it, its sums hold at least one tick (on the first tick every
 // environment is marked and none has: nothing closes) and all six are finite.
@@ -77,19 +81,26 @@ MPC_HD bool closes(int reset_id, int ticks, const float *sums) { return reset_id
 
 // Word j of one block's partial (0: the closed count, 1 + i: term i; the pad word is 0): the closed environments among the block's `count`, in
 // environment order.  closed[e] != 0 and sums[e * stride + i] are the block's own (the kernel hands its LDS copy, the host the arrays).
-MPC_HD double block_partial_word(int count, const int *closed, const float *sums, int stride, int j) {
+// (the _n forms state the order once for any number of terms kT and any row length kP: reward_shaping.h reduces eight terms in rows of 16)
+template <int kT>
+MPC_HD double block_partial_word_n(int count, const int *closed, const float *sums, int stride, int j) {
   double acc = 0.0;
-  if (j > kTerms) return acc;
+  if (j > kT) return acc;
   for (int e = 0; e < count; ++e)
     if (closed[e]) acc = acc + (j == 0 ? 1.0 : (double)sums[(size_t)e * stride + (j - 1)]);
   return acc;
 }
+MPC_HD double block_partial_word(int count, const int *closed, const float *sums, int stride, int j) {
+  return block_partial_word_n<kTerms>(count, closed, sums, stride, j);
+}
 
 // the join's accumulator of word j over `blocks` partial rows, in block order, continuing from acc
-MPC_HD double join_word(double acc, int blocks, const double *partials, int j) {
-  for (int b = 0; b < blocks; ++b) acc = acc + partials[(size_t)b * kPartial + j];
+template <int kP>
+MPC_HD double join_word_n(double acc, int blocks, const double *partials, int j) {
+  for (int b = 0; b < blocks; ++b) acc = acc + partials[(size_t)b * kP + j];
   return acc;
 }
+MPC_HD double join_word(double acc, int blocks, const double *partials, int j) { return join_word_n<kPartial>(acc, blocks, partials, j); }
 
 // the command curriculum's numbers, as the kernel takes them
 struct Curriculum {

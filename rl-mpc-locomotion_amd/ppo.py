@@ -599,8 +599,9 @@ SCALARS = ("mean_reward", "done_rate", "value_loss", "surrogate_loss", "mean_noi
 
 
 def _riders(trainer):
-    """The riders of ``trainer`` (anything with its ``_scalars``, ``alg``, ``episode_stats``, ``curriculum`` and ``episode_terms``), in the record's order."""
-    alg, curriculum, terms = trainer.alg, trainer.curriculum, trainer.episode_terms
+    """The riders of ``trainer`` (anything with its ``_scalars``, ``alg``, ``episode_stats``, ``curriculum`` and ``episode_terms``; ``reward_shaping`` where
+    it has one), in the record's order."""
+    alg, curriculum, terms, shaping = trainer.alg, trainer.curriculum, trainer.episode_terms, getattr(trainer, "reward_shaping", None)
 
     def learning_rate(values):                                                   # hip backend: the device's value, which the host copies follow
         if values:
@@ -617,6 +618,8 @@ def _riders(trainer):
         riders.append(_Rider(lambda: curriculum.summary(), lambda values: curriculum.record(values, curriculum.num_types)))
     if terms is not None:                                                        # the per-term sums of the iteration's closed episodes; the next record covers the next
         riders.append(_Rider(lambda: terms.summary(), lambda values: {"episode_terms": terms.record(values)}, lambda: terms.new_window()))
+    if shaping is not None:                                                      # the shaping terms' sums of the iteration's closed episodes, window by window
+        riders.append(_Rider(lambda: shaping.summary(), lambda values: {"reward_shaping": shaping.record(values)}, lambda: shaping.new_window()))
     return riders
 
 
@@ -707,8 +710,8 @@ class PPOTrainer:
         self.device = _lib.device_of(device if device is not None else getattr(env, "device", None))
         torch.manual_seed(self.seed)
         c = self.cfg
-        self.num_privileged_obs, self.curriculum, self.episode_terms, self.plant_rand = (
-            getattr(env, name, None) for name in ("num_privileged_obs", "curriculum", "episode_terms", "plant_rand"))
+        self.num_privileged_obs, self.curriculum, self.episode_terms, self.plant_rand, self.reward_shaping = (
+            getattr(env, name, None) for name in ("num_privileged_obs", "curriculum", "episode_terms", "plant_rand", "reward_shaping"))
         priv = self.num_privileged_obs
         self.recurrent = recurrent
         self._prev_reset = None                                                  # the task's reset tensor of the tick before (kept for a net with memory only)
@@ -773,7 +776,8 @@ class PPOTrainer:
         ``mean_episode_length`` over the last 100 finished episodes (0.0 while there are none), ``episodes_in_window``, ``timeouts_in_window`` and
         the cumulative ``episodes_finished``; on an environment with a terrain ``curriculum`` also ``mean_terrain_level`` and ``terrain_level_by_type``
         as they stand after the iteration; on one with ``episode_terms`` also ``episode_terms``: ``rew_<term>`` over the episodes closed during the
-        iteration, ``max_command_x``, ``min_command_x`` and ``command_widenings`` (``EpisodeTerms.record``).  ``init_at_random_ep_len``: before the first collection ``env.progress_buf`` is set to integers
+        iteration, ``max_command_x``, ``min_command_x`` and ``command_widenings`` (``EpisodeTerms.record``); on one with ``reward_shaping`` also ``reward_shaping``: ``rew_<term>`` of the eight shaping terms over
+        the episodes closed during the iteration (``RewardShaping.record``).  ``init_at_random_ep_len``: before the first collection ``env.progress_buf`` is set to integers
         uniform on [0, ``env.cfg.max_episode_length``), drawn from the trainer's seed, so that the environments do not time out on one tick.  As in
         rsl_rl's ``learn``, this happens at the start of EVERY call that sets the flag (the same draw each time: it moves episodes that are under way),
         so set it on the first call only."""

@@ -202,16 +202,21 @@ class BatchedRLTask:
     that its step consumes; with ``resample="once"`` every record is drawn when the task is built, with ``"reset"`` the environments being reset
     draw theirs inside the ``resets`` stage, before ``sim.reset_idx`` (the first tick resets, and so draws, every environment).  A
     ``PrivilegedObs(n, plant=True)`` shows the record to the critic and needs ``plant_rand``.
+    ``reward_shaping`` (a ``reward_shaping.RewardShaping`` for as many environments): eight more reward terms by legged_gym's formulas; its episodes
+    are closed inside the ``resets`` stage, before ``ctl.reset``, and one launch after the height scan (after ``finish`` without one) rewrites
+    ``rew_buf`` with the fourteen terms and feeds its per-term sums.  The unit is made under the task's own ``cfg`` (``RewardShaping(n, spec, cfg=cfg)``; another one is refused), and a non-zero ``base_height`` scale on a terrain needs
+    ``height_scan``.
     See the module text for what the toy cannot do."""
 
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
-                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, plant_rand=None, **bridge_args):
+                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, plant_rand=None, reward_shaping=None, **bridge_args):
         import torch
         n_envs = len(np.asarray(robot_type).reshape(-1))
         cfg = cfg if cfg is not None else TaskConfig()
         # everything that can be refused is refused here, before the device is touched: one pass over the options, the first fault raises
         for unit, holds in ((plant_rand, None), (privileged_obs, "the privileged observations hold"), (episode_terms, "the episode terms hold"),
-                            (domain_rand, None), (height_scan, "the height scan holds"), (curriculum, "the curriculum holds")):
+                            (reward_shaping, "the reward shaping holds"), (domain_rand, None), (height_scan, "the height scan holds"),
+                            (curriculum, "the curriculum holds")):
             if unit is None:
                 continue
             if unit is plant_rand:         # counts its environments itself, with its payload against the masses of the robot types in use
@@ -228,6 +233,10 @@ class BatchedRLTask:
                 raise ValueError("curriculum brings its own terrain and origins: terrain= / origin= exclude it")
             if unit.n != n_envs:
                 raise ValueError(f"{holds} {unit.n} environments, robot_type {n_envs}")
+            if unit is reward_shaping and unit.cfg != cfg:      # its dt, episode length, default_dof_pos and the six scales it re-evaluates are the task's
+                raise ValueError("reward_shaping was made under another TaskConfig than the task's: RewardShaping(n, spec, cfg=cfg)")
+            if unit is reward_shaping and unit.spec.base_height != 0 and height_scan is None and (terrain is not None or curriculum is not None):
+                raise ValueError("reward_shaping has a base_height scale: on a terrain the base height is measured by height_scan=")
             if unit is height_scan and np.float32(unit.obs_clip) != np.float32(cfg.clip_observations):
                 raise ValueError(f"the height scan clips its columns to {unit.obs_clip}, the task's clip_observations is {cfg.clip_observations}")
         if curriculum is not None:
@@ -266,6 +275,9 @@ class BatchedRLTask:
             if plant_rand.spec.resample == "once":
                 plant_rand.draw()
         self.episode_terms = episode_terms
+        self.reward_shaping = reward_shaping
+        if reward_shaping is not None:
+            reward_shaping.bind(self.sim)
         self.privileged_obs, self.privileged_obs_buf, self.num_privileged_obs = privileged_obs, None, None
         if privileged_obs is not None:
             from .privileged_obs import inverse_length, privileged_width
@@ -291,10 +303,11 @@ class BatchedRLTask:
             terrain_curriculum  ``curriculum.update``                      only with a curriculum
             begin               ``task.begin``
             episode_close       ``episode_terms.close_and_resample``       only with episode_terms
-            resets              ``ctl.reset``, ``sim.reset_idx``, ``sim.flags``; with a PlantRand that resamples at reset ``plant_rand.draw`` first
-            finish              ``task.finish``
+            resets              ``ctl.reset``, ``sim.reset_idx``, ``sim.flags``; with a PlantRand that resamples at reset ``plant_rand.draw`` first,
+                                with reward_shaping ``reward_shaping.close`` first
+            finish              ``task.finish``; with reward_shaping and no height scan then ``reward_shaping.run``
             episode_accumulate  ``episode_terms.accumulate``               only with episode_terms
-            height_scan         ``height_scan.measure``                    only with a height scan
+            height_scan         ``height_scan.measure``                    only with a height scan; with reward_shaping then ``reward_shaping.run``
             privileged_obs      ``privileged_obs.assemble``                only with privileged_obs
             observation_noise   the observation-noise launch               only while a DomainRand is enabled and has observation noise
         ``mark``, when given, is called as ``mark(name)`` on the host right after each stage that ran on this tick has been launched, and not for a
@@ -337,12 +350,17 @@ class BatchedRLTask:
                 mark("episode_close")
         if self.plant_rand is not None and self.plant_rand.spec.resample == "reset":      # the new episode's plant, before the robot is put back
             self.plant_rand.draw(ids)
+        rs = self.reward_shaping
+        if rs is not None:                 # close the marked episodes' shaping sums
+            rs.close(ids)
         self.bridge.ctl.reset(ids)                                                                                              # aliengo.py:330-334
         sim.reset_idx(ids)                                                                                                      # aliengo.py:336-342
         _, fell = sim.flags()              # after the reset: a robot that has just been put back standing is not flagged a second time
         if mark is not None:
             mark("resets")
         t.finish(sim.root_states, sim.dof_state, self.actions, self.torques, fell=fell)                                         # aliengo.py:280-281, :337
+        if rs is not None and self.height_scan is None:                        # the tensors finish has just read and written; no heights to wait for
+            rs.run(sim.root_states, sim.dof_state, self.actions, self.commands, self.torques, fell, ids, self.reset_buf, self.progress_buf, self.rew_buf)
         if mark is not None:
             mark("finish")
         if et is not None:                 # the tensors finish has just read, the same base contact
@@ -351,6 +369,9 @@ class BatchedRLTask:
                 mark("episode_accumulate")
         if self.height_scan is not None:   # the same post-reset root states, and the origins the curriculum has just written
             self.height_scan.measure(sim.root_states, t.obs_buf, out=self.obs_buf, heights=self.measured_heights)
+            if rs is not None:             # the same tensors, and the heights in metres the scan has just measured
+                rs.run(sim.root_states, sim.dof_state, self.actions, self.commands, self.torques, fell, ids, self.reset_buf, self.progress_buf, self.rew_buf,
+                       heights=self.measured_heights)
             if mark is not None:
                 mark("height_scan")
         if self.privileged_obs is not None:                                    # the clean copy exists because this launch comes before the noise

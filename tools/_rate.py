@@ -57,9 +57,10 @@ def stage_times(task, actions, ticks, event=ev, synchronize=None):
     return {stage: np.array(ms) for stage, ms in spans.items()}
 
 
-def wall_blocks(loops, ticks, blocks, robots, warmup=20):
+def wall_blocks(loops, ticks, blocks, robots, warmup=20, per_block=False):
     """``loops`` {name: a function that runs one tick}: ``warmup`` ticks each (cold solves, code objects, torch's kernels), then ``blocks`` blocks
-    of ``ticks`` ticks that end in a synchronise, the loops alternating block by block.  {name: the host clock's record, ms per tick}."""
+    of ``ticks`` ticks that end in a synchronise, the loops alternating block by block.  {name: the host clock's record, ms per tick}; with
+    ``per_block`` a record also keeps its blocks' own values (``ms_per_tick_blocks``), for differences block by block."""
     import torch
     for tick in loops.values():
         for _ in range(warmup):
@@ -78,6 +79,8 @@ def wall_blocks(loops, ticks, blocks, robots, warmup=20):
         per = np.array(w) / ticks * 1e3
         out[name] = {"ms_per_tick_median": med(per), "ms_per_tick_p10": float(np.percentile(per, 10)), "ms_per_tick_p90": float(np.percentile(per, 90)),
                      "ms_per_tick_min": float(per.min()), "ms_per_tick_max": float(per.max()), "robot_ticks_per_s": robots * ticks / med(w)}
+        if per_block:
+            out[name]["ms_per_tick_blocks"] = per.tolist()
     return out
 
 

@@ -12,7 +12,8 @@ after the first and after the last collection.  The file uses nothing of the tra
 ``--compare`` takes two runs of the parent and one of the change.  ``storage_first`` must be bitwise the parent's, unconditionally.  Every other field must
 be bitwise the parent's wherever the parent's two runs equal each other; where they do not (an update that is not run-to-run reproducible), a float entry of
 ``infos`` must lie within four times the parent's own largest run-to-run difference for that entry (two samples are a thin estimate of the spread) and a
-tensor's hash is listed as not comparable."""
+tensor's hash is listed as not comparable.  ``--brief`` keeps of the three runs only what they were runs of (the kernel sources' hash, torch's version) beside
+the verdict, not their records: a file small enough to commit."""
 import argparse
 import hashlib
 import json
@@ -172,11 +173,14 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="*", default=CONFIGS, choices=CONFIGS)
     ap.add_argument("--compare", nargs=3, metavar=("PARENT1", "PARENT2", "CHANGE"))
+    ap.add_argument("--brief", action="store_true", help="--compare: write the verdict with the runs' source hashes, without their records")
     ap.add_argument("--out")
     args = ap.parse_args()
     if args.compare:
         runs = [json.load(open(p)) for p in args.compare]
         verdicts, ok = compare(*runs)
+        if args.brief:
+            runs = [{k: r.get(k) for k in ("kernel_source_sha256", "torch")} for r in runs]
         res = {"ok": ok, "verdict": verdicts, "parent": runs[:2], "change": runs[2]}
         print(json.dumps({"ok": ok, "verdict": verdicts}, indent=1))
     else:

@@ -36,6 +36,11 @@ option against the same task without it, and the `controller`, `plant` (the para
 holds the draw) stages of both, from events, the tasks alternating; a third task carries a record that stays neutral, which separates the kernel's
 cost from that of robots that differ.  With --privileged all of them assemble the critic's row, with the plant columns where there is a record.
     python tools/rl_task_rate.py --plant-rand [--privileged] [--out profiles/plant_rand_rate.json]
+--shaping: the opt-in reward shaping terms (rl_mpc_locomotion_amd.reward_shaping) with every scale non-zero; with --heights on the terrain grid with
+the scan (base_height over the measured heights), with --terms beside the per-term episode sums: the step with the option against the same task
+without it, block by block, and the added time per tick from the blocks' differences; the stages that hold the unit's launches (`resets`: close,
+`height_scan` or `finish`: run) of both tasks, and the episode sums' own two stages of the same run as the yardstick.
+    python tools/rl_task_rate.py --shaping --heights --terms [--out profiles/reward_shaping_rate.json]
 The kernel-trace stats of the same step: rocprofv3 --kernel-trace --stats ... -- python tools/rl_task_rate.py --ticks 50 --quick"""
 import argparse
 import os
@@ -126,11 +131,11 @@ class Bare:
         self.sim.step(self.ctl.run(self.sim.dof_state.view(self.n, 12, 2), self.sim.root_states, self.cmd))
 
 
-def blocks(res, args, actions, loops):
+def blocks(res, args, actions, loops, per_block=False):
     """The whole ticks of the tasks ``loops`` names, reset first: their records into ``res``, and the first over ``step_without`` where there are two."""
     for task in loops.values():
         task.reset()
-    res.update(wall_blocks({k: (lambda t=t: t.step(actions)) for k, t in loops.items()}, args.ticks, args.blocks, args.robots))
+    res.update(wall_blocks({k: (lambda t=t: t.step(actions)) for k, t in loops.items()}, args.ticks, args.blocks, args.robots, per_block=per_block))
     if len(loops) == 2:
         res["with_over_without_ms_per_tick"] = res[next(iter(loops))]["ms_per_tick_median"] / res["step_without"]["ms_per_tick_median"]
 
@@ -407,6 +412,60 @@ def plant_rand_report(args, dev, n, actions):
     return res
 
 
+# --shaping: every term live (the values are of legged_gym's order of magnitude; none is a preset)
+SHAPING_SCALES = dict(orientation=-0.2, base_height=-1.0, dof_vel=-1e-4, dof_acc=-2.5e-7, action_rate=-0.01, feet_air_time=1.0, stand_still=-0.1, termination=-2.0,
+                      base_height_target=0.3)
+
+
+def shaping_task(args, dev, n, cfg, with_shaping=True):
+    """The task --shaping times: on the terrain grid with the scan with --heights, beside the episode sums with --terms."""
+    from rl_mpc_locomotion_amd.reward_shaping import RewardShaping, ShapingSpec
+    opts = {}
+    if args.heights:
+        from rl_mpc_locomotion_amd.height_scan import HeightScan
+        grid, curriculum, _ = terrain_grid(n, args.max_init_level, dev, cfg.episode_length_s)
+        opts.update(terrain=grid.terrain, origin=curriculum().origins0, height_scan=HeightScan(n, device=dev))
+    if args.terms:
+        from rl_mpc_locomotion_amd.episode_terms import EpisodeTerms
+        opts["episode_terms"] = EpisodeTerms(n, cfg, device=dev)
+    if with_shaping:
+        opts["reward_shaping"] = RewardShaping(n, ShapingSpec(**SHAPING_SCALES), device=dev, cfg=cfg)
+    return make(n, dev, cfg, **opts)
+
+
+def shaping_report(args, dev, n, actions):
+    from rl_mpc_locomotion_amd.reward_shaping import RewardShaping
+    cfg = TaskConfig(**CFG, episode_length_s=args.episode_s)
+    res = header(args, n, heights=bool(args.heights), terms=bool(args.terms), episode_length_s=cfg.episode_length_s, scales=SHAPING_SCALES,
+                 launches_per_tick={"close": 2, "run": 1})
+    loops = {"step_with_shaping": shaping_task(args, dev, n, cfg), "step_without": shaping_task(args, dev, n, cfg, with_shaping=False)}
+    blocks(res, args, actions, loops, per_block=True)
+    added = (np.array(res["step_with_shaping"]["ms_per_tick_blocks"]) - np.array(res["step_without"]["ms_per_tick_blocks"])) * 1e3
+    res["added_us_per_tick"] = {"p10": float(np.percentile(added, 10)), "median": med(added), "p90": float(np.percentile(added, 90)), "blocks": added.tolist()}
+    run_stage = "height_scan" if args.heights else "finish"
+    names = ("resets", run_stage) + (("episode_close", "episode_accumulate") if args.terms else ())
+    parts = {k: {s: [] for s in names} for k in loops}
+    for _ in range(args.blocks):              # the stages from events, the tasks alternating round by round
+        for k, task in loops.items():
+            got = stage_times(task, actions, max(args.ticks // 2, 1))
+            for s in names:
+                parts[k][s] += list(got[s])
+    res["stages"] = {k: {s: {**spread(v), "events": len(v)} for s, v in d.items()} for k, d in parts.items()}
+    m = {k: {s: med(v) for s, v in d.items()} for k, d in parts.items()}
+    unit = sum(m["step_with_shaping"][s] - m["step_without"][s] for s in ("resets", run_stage))
+    res["unit_from_stage_medians_us"] = {"close_in_resets": (m["step_with_shaping"]["resets"] - m["step_without"]["resets"]) * 1e3,
+                                         "run_in_" + run_stage: (m["step_with_shaping"][run_stage] - m["step_without"][run_stage]) * 1e3, "both": unit * 1e3}
+    if args.terms:
+        both = np.array(parts["step_with_shaping"]["episode_close"]) + np.array(parts["step_with_shaping"]["episode_accumulate"])
+        res["episode_terms_yardstick_us"] = {"p10": float(np.percentile(both, 10)) * 1e3, "median": med(both) * 1e3, "p90": float(np.percentile(both, 90)) * 1e3}
+        y = res["episode_terms_yardstick_us"]
+        res["unit_exceeds_yardstick_by_more_than_its_spread"] = bool(res["added_us_per_tick"]["median"] - y["median"] > y["p90"] - y["p10"])
+    rs = loops["step_with_shaping"].reward_shaping
+    res["after_timing"] = {"fallen_fraction": fallen(loops), "record": RewardShaping.record(rs.summary().tolist())}
+    clock(res, "after")
+    return res
+
+
 def default_report(args, dev, n, actions):
     res = header(args, n)
     step, half, bare = make(n, dev), make(n, dev), Bare(n, dev)
@@ -453,10 +512,18 @@ if __name__ == "__main__":
     ap.add_argument("--privileged", action="store_true", help="time the privileged row's assembly kernel and the step with and without it; with or without --heights")
     ap.add_argument("--baseline", action="store_true", help="--privileged: only the task without the option (runs on a tree without the unit)")
     ap.add_argument("--plant-rand", action="store_true", help="time the step and its plant and resets stages with and without the per-robot plant record; with --privileged both tasks assemble the critic's row, one with the plant columns")
+    ap.add_argument("--shaping", action="store_true", help="time the step with and without the reward shaping terms; with --heights on the terrain with the scan, with --terms beside the episode sums")
     ap.add_argument("--out")
     args = ap.parse_args()
     dev, n = "cuda:0", args.robots
     actions = torch.zeros((n, 12), dtype=torch.float32, device=dev)
+    if args.quick and args.shaping:        # one block of the step with the option, --heights and --terms honoured (for a kernel trace)
+        task = shaping_task(args, dev, n, TaskConfig(**CFG, episode_length_s=args.episode_s))
+        task.reset()
+        for _ in range(args.ticks):
+            task.step(actions)
+        torch.cuda.synchronize()
+        sys.exit(0)
     if args.quick and not (args.plant_rand or args.privileged or args.terms or args.domain_rand or args.heights or args.curriculum):
         task = make(n, dev)
         task.reset()
@@ -464,6 +531,6 @@ if __name__ == "__main__":
             task.step(actions)
         torch.cuda.synchronize()
         sys.exit(0)
-    report = (plant_rand_report if args.plant_rand else privileged_report if args.privileged else terms_report if args.terms else domain_rand_report if args.domain_rand else heights_report if args.heights
+    report = (shaping_report if args.shaping else plant_rand_report if args.plant_rand else privileged_report if args.privileged else terms_report if args.terms else domain_rand_report if args.domain_rand else heights_report if args.heights
               else curriculum_report if args.curriculum else default_report)
     emit(report(args, dev, n, actions), args.out)
