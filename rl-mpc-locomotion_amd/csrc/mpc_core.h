@@ -171,6 +171,11 @@ struct Cfg {
   // LDS diet of the short horizon (q is re-read from the QP record instead of a copy in LDS); the long horizons run one or two
   // robots per CU whatever their LDS size and keep the copy.
   static constexpr bool kQInLds = H > 12;
+  // The assembly's last phase (q and the two 12 x 12 tables U1, U2): q takes the wavefronts of the threads below QT, and where the rest of the
+  // workgroup can carry U1, U2 at three entries per thread or fewer (h = 10, h >= 13) the tables go there alone, so that no wavefront
+  // carries both; elsewhere (a single wavefront left over: five entries per thread) they stay spread over every thread.
+  static constexpr int QT = ((N + 63) / 64) * 64;
+  static constexpr bool kSplitQU = (T - QT) * 3 >= 288;
   // Live-range split points of the tile registers (Scaler::pin_tiles): bits 5 / 6 before / after the Ruiz passes, 7 inside them.
 #ifdef MPC_PIN_MASK
   static constexpr int kPinMask = MPC_PIN_MASK;
@@ -243,9 +248,6 @@ struct ScaleShared {
   MPC_V qs[C::N]; MPC_V As[C::NF * 15];   // scaled problem (the bounds are scaled once, at the end: E times the QP record's)
   MPC_V D[C::N]; MPC_V E[C::M];
   double c, cinv, ctmp;
-  int first;
-  MPC_V xt[C::N];                                       // q of the previous call (osqp_update_P_A scales with it)
-  MPC_V cone[16];
   MPC_V dt_[C::N]; MPC_V et_[C::M];                     // Ruiz pass temporaries
   MPC_V part[C::NP * C::G];                             // [slot][row] partial maxima of the tile row norms
 };
@@ -267,7 +269,7 @@ struct PrepShared {
     AsmShared<H> as;
     ScaleShared<H> sc;
   };
-  MPC_V u12[288];                                       // U1, U2: what the scaling part needs of the assembly (see Assembler::run)
+  MPC_V u12[288 + 16];                                  // what the scaling part needs of the assembly (see Assembler::run): U1, U2, then the 5 x 3 cone block
 };
 #undef MPC_V
 
@@ -281,6 +283,10 @@ struct Thread {
   static constexpr int VPL = (C::N + 63) / 64;   // variables per lane of the first wavefront (Scaler::fold_phase): j = tid + 64 v
   double rm[VPL];                 // their column maxima
   double red[2];                  // wavefront reduction operands: a sum and a maximum
+  // What the prep kernel keeps in registers instead of reading it back from memory: q[tid] of this call (the assembly's q phase -> the
+  // scaling part), and of the state record q[tid] of the previous call and the cold flag (fetched at kernel entry, used by the tile-build phase)
+  double qreg, qold;
+  bool first;
   MPC_HD void init(int id) {
     tid = id;
     for (int u = 0; u < C::NT; ++u) {
@@ -397,6 +403,33 @@ struct Assembler {
 
   // ================================ 1. assembly =================================================
   MPC_HD double in_at(int i) const { return in64 ? in64[i] : (in16 ? half_to_double(in16[i]) : (double)in[i]); }
+  // two entries behind ONE branch on the storage type: both loads are in flight before either is converted
+  MPC_HD void in_at2(int i, int j, double &a, double &b) const {
+    if (in64) { a = in64[i]; b = in64[j]; }
+    else if (in16) { const mpc_half x = in16[i], y = in16[j]; a = half_to_double(x); b = half_to_double(y); }
+    else { const float x = in[i], y = in[j]; a = (double)x; b = (double)y; }
+  }
+  // A phase of the first wavefront alone, handed over to its next phase inside the wavefront (its LDS instructions execute in program
+  // order: no s_barrier, the other wavefronts run on).  An Exec without wave_par -- the host emulation -- runs it as an ordinary phase.
+  template <class E, class F>
+  static MPC_HD auto wave_phase(E &e, F &&f, int) -> decltype(e.wave_par(f)) { return e.wave_par(f); }
+  template <class E, class F>
+  static MPC_HD void wave_phase(E &e, F &&f, long) { e.par(f); }
+  template <class F>
+  MPC_HD void wpar(F &&f) { wave_phase(ex, f, 0); }
+
+  // Phase structure (workgroup barriers: | ; hand-over inside the first wavefront: >):
+  //   fetch, trig | chain: thread 0's products > B rows 6-8   ||   rest: x0, bounds, x_ref, A rows, B rows 9-11, cone | b_exp, U, (A dt) x0, th1, th2 | wanb, sdiff | q, U1 U2 |
+  // Between the barrier after the fetch and the next one the first wavefront (threads 0 .. 63: the chain's lambdas do nothing on the
+  // others) and the rest (threads >= 64) run unordered.  Who touches what in between:
+  //   in, xk[0..7) (trig), sdiff[53..62) (I^-1 body)   written by the fetch phase; READ by both sides, written by neither
+  //   xk[43..55) (fw), xk[64..73) (iw)                 chain only (thread 0 writes, the B rows read)
+  //   b_dt, B6 (and B6 of the QP record)               zeroed by the fetch phase; rows 6-8 of b_dt / 0-2 of B6: chain only; rows 9-11 / 3-5 (the I / m entries):
+  //                                                    rest only; nobody reads them in between
+  //   a_dt                                             zeroed by the fetch phase; written by the rest only, read after the barrier
+  //   u12[288..303) and the QP record's cone, bnd      written by the rest only
+  //   x0, xref                                         written by the rest only, read after the barrier
+  //   everything else (b_exp, a_exp, th1, th2, wanb, sdiff[0 .. 13 H), u12[0..288), xk[7..43))   untouched until after the barrier
   MPC_HD void run() {
     tlast = MPC_CLOCK();
     // ---- A dt, B dt (mpc_osqp.cc:299-336, 606-617, 661-673).  The chain of 3 x 3 products behind them (rotations in both of the
@@ -407,22 +440,34 @@ struct Assembler {
     double *const trig = s.xk, *const fw = s.xk + 43, *const iw = s.xk + 64;
     double *const iib = s.sdiff + 53;
     static_assert(AsmShared<H>::XK >= 73, "xk / sdiff too small for the set-up scratch");
+    static_assert(C::IN_LEN <= T && N <= T && T >= 128, "one input entry and one variable per thread, a wavefront beside the first");
+    // the fetch: every global load of the assembly (the kernel has issued the state record's before it: one wait for all), and the
+    // trigonometry on the wavefronts beside the first -- cos, sin and tan each on a wavefront of its own where the workgroup has four
+    // (the three are different code: lanes of one wavefront would run them one after the other)
+    constexpr int W = T / 64;
+    constexpr int kCosWave = 1, kSinWave = W > 2 ? 2 : 1, kTanWave = W > 3 ? 3 : W - 1;
     ex.par([&](Th &t) {
-      for (int i = t.tid; i < C::IN_LEN; i += T) s.in[i] = in_at(i);
+      // (every thread asks for an inertia entry, an input entry and an angle, the index clamped where it has none: no branch between the
+      // loads, so they are in flight together; the explicit wait also tells the compiler that nothing fetched so far is still on its way)
+      const int lane = t.tid & 63, ka = lane < 3 ? lane : 0;
+      const double ii = mdl.inv_inertia[t.tid >= T - 9 ? t.tid - (T - 9) : 0];
+      double iv, ang;
+      in_at2(t.tid < C::IN_LEN ? t.tid : 0, IN_RPY + ka, iv, ang);
+      MPC_WAIT_LOADS();
+      if (t.tid < C::IN_LEN) s.in[t.tid] = iv;
+      if (t.tid >= T - 9) iib[t.tid - (T - 9)] = ii;
       for (int i = t.tid; i < 169; i += T) s.a_dt[i] = 0;
       for (int i = t.tid; i < 156; i += T) s.b_dt[i] = 0;
       for (int i = t.tid; i < 72; i += T) { qp[C::QP_B6 + i] = 0; s.B6[i] = 0; }
-      if (t.tid >= 64 && t.tid < 67) {          // (one wave-front's worth of trigonometry, off the first wavefront)
-        const int k = t.tid - 64;
-        const double ang = in_at(IN_RPY + k);
-        trig[2 * k] = cos(ang); trig[2 * k + 1] = sin(ang);
-        if (k == 1) trig[6] = tan(ang);
-      } else if (t.tid >= 96 && t.tid < 105) {
-        iib[t.tid - 96] = mdl.inv_inertia[t.tid - 96];
+      if (lane < 3) {
+        const int w = t.tid >> 6;
+        if (w == kCosWave) trig[2 * lane] = cos(ang);
+        if (w == kSinWave) trig[2 * lane + 1] = sin(ang);
+        if (w == kTanWave && lane == 1) trig[6] = tan(ang);
       }
     });
     MPC_SUBLAP(4, 9);
-    ex.par([&](Th &t) {
+    wpar([&](Th &t) {
       if (t.tid == 0) {
         const double cr = trig[0], sr = trig[1], cp = trig[2], sp = trig[3], cy = trig[4], sy = trig[5];
         const double rx[9] = {1.0, 0.0, 0.0, 0.0, cr, -sr, 0.0, sr, cr};      // (entry (v, u) = +sin, (u, v) = -sin about axis x / y / z)
@@ -445,13 +490,46 @@ struct Assembler {
 #pragma unroll
           for (int j = 0; j < 3; ++j) iw[3 * i + j] = t2[3 * i] * rzyx[3 * j] + t2[3 * i + 1] * rzyx[3 * j + 1] + t2[3 * i + 2] * rzyx[3 * j + 2];   // ... rzyx^T (:671)
       }
-      // x0 (:630-633)
-      if (t.tid >= 32 && t.tid < 45) {
-        const int i = t.tid - 32;
-        s.x0[i] = i < 3 ? s.in[IN_RPY + i] : i < 6 ? s.in[IN_POS + i - 3] : i < 9 ? s.in[IN_ANG + i - 6] : i < 12 ? s.in[IN_VEL + i - 9] : -kGravity;
+    });
+    // x0 (:630-633), entry i
+    auto x0_at = [&](int i) { return i < 3 ? s.in[IN_RPY + i] : i < 6 ? s.in[IN_POS + i - 3] : i < 9 ? s.in[IN_ANG + i - 6] : i < 12 ? s.in[IN_VEL + i - 9] : -kGravity; };
+    // what does not depend on thread 0's products, on the threads beside the first wavefront (o: their index, TO: their number); it runs below,
+    // as the phase that ends at the workgroup barrier behind the chain
+    auto rest = [&](Th &t) {
+      constexpr int TO = T - 64;
+      constexpr int bA = TO >= 128 ? 64 : 16, bM = TO >= 192 ? 128 : 32;      // (the A rows' division on a wavefront of its own where there is one)
+      const int o = t.tid - 64;
+      if (o < 0) return;
+      const double dt = mdl.dt;
+      if (o < 13) s.x0[o] = x0_at(o);
+      if (o >= bA && o < bA + 9) {   // A rows 0-2: omega -> rpy rates (:311-312): {cy/cp, sy/cp, 0; -sy, cy, 0; cy tp, sy tp, 1}
+        const int e = o - bA, r = e / 3, c = e - 3 * r;
+        const double cp = trig[2], cy = trig[4], sy = trig[5], tp = trig[6];
+        const double num = c == 0 ? cy : sy;
+        double val;
+        if (c == 2) val = r == 2 ? 1.0 : 0.0;
+        else if (r == 0) val = num / cp;
+        else if (r == 1) val = c == 0 ? -sy : cy;
+        else val = num * tp;
+        s.a_dt[r * 13 + 6 + c] = val * dt;
+      }
+      if (o >= bM && o < bM + 12) {   // B rows 9-11: I / m
+        const int k = o - bM, i = k / 3, r = k - 3 * i;
+        s.b_dt[(9 + r) * 12 + 3 * i + r] = mdl.inv_mass * dt;
+        qp[C::QP_B6 + (3 + r) * 12 + 3 * i + r] = mdl.inv_mass;
+        s.B6[(3 + r) * 12 + 3 * i + r] = mdl.inv_mass;
+      } else if (o >= bM + 12 && o < bM + 15) {
+        const int r = o - (bM + 12);
+        s.a_dt[(3 + r) * 13 + 9 + r] = dt;
+        s.a_dt[(9 + r) * 13 + 12] = s.in[IN_NRM + r] * dt;
+      } else if (o >= bM + 16 && o < bM + 31) {   // the cone block {-1 0 mu; 1 0 mu; 0 -1 mu; 0 1 mu; 0 0 1} (:437-447), an entry per thread
+        const int k = o - (bM + 16), r = k / 3, c = k - 3 * r;
+        const double v = c == 2 ? (r < 4 ? s.in[in_fric<H>() + (r < 4 ? r : 0)] : 1.0) : (r == 2 * c ? -1.0 : r == 2 * c + 1 ? 1.0 : 0.0);
+        qp[C::QP_CONE + k] = v;
+        u12[288 + k] = v;      // (LDS outside the union: the scaling part's copy)
       }
       // bounds (:449-477, 685-688, 720-721)
-      for (int f = t.tid; f < NF; f += T) {
+      for (int f = o; f < NF; f += TO) {
         const double cst = s.in[IN_CONTACT + f];
         const double fzmax = mdl.mass * kGravity * kMaxScale, fzmin = mdl.mass * kGravity * kMinScale;
         const double mu0 = s.in[in_fric<H>()];
@@ -460,7 +538,7 @@ struct Assembler {
         qp[C::QP_BND + 3 * f + 2] = dmin(fzmax * cst, kInfty);               // u of row 4
       }
       // x_ref (:635-659): row r of step i is base_r + dt (i + 1) slope_r  (slope 0 for the constant rows)
-      for (int k = t.tid; k < 13 * H; k += T) {
+      for (int k = o; k < 13 * H; k += TO) {
         const int i = k / 13, r = k - 13 * i;
         const double tt = mdl.dt * (i + 1);
         const int drpy = in_drpy<H>(), dvel = in_dvel<H>(), dang = in_dang<H>(), dpos = in_dpos<H>();
@@ -470,9 +548,9 @@ struct Assembler {
         const double v = (r == 2 || r == 3 || r == 4) ? tt * slope + base : base;
         s.xref[k] = r == 11 ? 0.0 : r == 12 ? -kGravity : v;
       }
-    });
+    };
     MPC_SUBLAP(4, 12);
-    ex.par([&](Th &t) {
+    wpar([&](Th &t) {
       const double dt = mdl.dt;
       if (t.tid < 36) {   // B rows 6-8: I_w^-1 [r_i]x (:324-336); [v]x = {0, -v2, v1; v2, 0, -v0; -v1, v0, 0}
         const int i = t.tid / 9, e = t.tid - 9 * i, r = e / 3, c = e - 3 * r;
@@ -486,31 +564,9 @@ struct Assembler {
         s.b_dt[(6 + r) * 12 + 3 * i + c] = acc * dt;
         qp[C::QP_B6 + r * 12 + 3 * i + c] = acc;          // wrench map B6 = [I_w^-1 [r_i]x ; I / m]  (mpc_wrench.h)
         s.B6[r * 12 + 3 * i + c] = acc;
-      } else if (t.tid < 48) {   // B rows 9-11: I / m
-        const int k = t.tid - 36, i = k / 3, r = k - 3 * i;
-        s.b_dt[(9 + r) * 12 + 3 * i + r] = mdl.inv_mass * dt;
-        qp[C::QP_B6 + (3 + r) * 12 + 3 * i + r] = mdl.inv_mass;
-        s.B6[(3 + r) * 12 + 3 * i + r] = mdl.inv_mass;
-      } else if (t.tid < 57) {   // A rows 0-2: omega -> rpy rates (:311-312): {cy/cp, sy/cp, 0; -sy, cy, 0; cy tp, sy tp, 1}
-        const int e = t.tid - 48, r = e / 3, c = e - 3 * r;
-        const double cp = trig[2], cy = trig[4], sy = trig[5], tp = trig[6];
-        const double num = c == 0 ? cy : sy;
-        double val;
-        if (c == 2) val = r == 2 ? 1.0 : 0.0;
-        else if (r == 0) val = num / cp;
-        else if (r == 1) val = c == 0 ? -sy : cy;
-        else val = num * tp;
-        s.a_dt[r * 13 + 6 + c] = val * dt;
-      } else if (t.tid < 60) {
-        const int r = t.tid - 57;
-        s.a_dt[(3 + r) * 13 + 9 + r] = dt;
-        s.a_dt[(9 + r) * 13 + 12] = s.in[IN_NRM + r] * dt;
-      } else if (t.tid == 60) {
-        const double *fr = s.in + in_fric<H>();
-        const double cb[15] = {-1, 0, fr[0], 1, 0, fr[1], 0, -1, fr[2], 0, 1, fr[3], 0, 0, 1};   // :437-447
-        for (int k = 0; k < 15; ++k) qp[C::QP_CONE + k] = cb[k];
       }
     });
+    ex.par(rest);      // (the workgroup barrier between the chain / the rest and what reads both)
     MPC_SUBLAP(1, 9);
     MPC_SUBLAP(4, 13);
     // exact exponential (mpc_osqp.cc:338-351; M^3 = 0): A_exp = I + A dt + (A dt)^2/2, B_exp = B dt + (A dt)(B dt)/2.
@@ -522,8 +578,10 @@ struct Assembler {
     // (its only column, 12, meets the zero row 12 of B_exp):  A_exp^k B_exp = B_exp + k U,  U = (A dt) B_exp,
     // which is nonzero in rows 0-5 only and meets B_exp in its rows 6-11 only -- where B_exp = B dt (rows 6-12 of A dt are zero up to
     // column 12): U needs no phase of its own.  All k are formed at once (the reference multiplies k times; the two
-    // agree to rounding).  U -> the (unused) a_exp area, (A dt) x0 and (A dt)^2 x0 -> the first 26 slots of sdiff.
+    // agree to rounding).  U -> the (unused) a_exp area, (A dt) x0 and (A dt)^2 x0 -> the first 26 slots of xk (over the
+    // trigonometry, which the rows before the barrier were the last to read; sdiff is left to the next phase, which writes all of it).
     double *const U = s.a_exp;
+    double *const ax1 = s.xk, *const ax2 = s.xk + 13;
     ex.par([&](Th &t) {
       for (int kk = t.tid; kk < 156; kk += T) {
         const int r = kk / 12, c = kk - 12 * r;
@@ -542,10 +600,11 @@ struct Assembler {
         } else {
           const int r = e2 - 72;
           double a1 = 0, a2 = 0;
-          if (r < 3) { for (int j = 6; j < 9; ++j) a1 += s.a_dt[r * 13 + j] * s.x0[j]; }
-          else if (r < 6) { a1 = s.a_dt[r * 13 + r + 6] * s.x0[r + 6]; a2 = (s.a_dt[r * 13 + r + 6] * s.a_dt[(r + 6) * 13 + 12]) * s.x0[12]; }
-          else if (r >= 9 && r < 12) a1 = s.a_dt[r * 13 + 12] * s.x0[12];
-          s.sdiff[r] = a1; s.sdiff[13 + r] = a2;
+          // (x0's entries as x0_at forms them)
+          if (r < 3) { for (int j = 6; j < 9; ++j) a1 += s.a_dt[r * 13 + j] * s.in[IN_ANG + j - 6]; }
+          else if (r < 6) { a1 = s.a_dt[r * 13 + r + 6] * s.in[IN_VEL + r - 3]; a2 = (s.a_dt[r * 13 + r + 6] * s.a_dt[(r + 6) * 13 + 12]) * -kGravity; }
+          else if (r >= 9 && r < 12) a1 = s.a_dt[r * 13 + 12] * -kGravity;
+          ax1[r] = a1; ax2[r] = a2;
         }
       }
       // The wrench-space description of P (mpc_wrench.h): A_exp^k B_exp = Gamma_k B6 with Gamma_k = [dt^2 (k + 1/2) That ; dt I6],
@@ -574,23 +633,24 @@ struct Assembler {
         const double v = r < 6 ? s.b_exp[rc] + (double)k * U[rc] : s.b_exp[rc];
         s.wanb[e] = s.in[IN_W + r] * v;
       }
-      for (int e = t.tid; e < 13 * (H - 1); e += T) {   // (this overwrites the set-up scratch, which is dead by now)
-        const int i = e / 13, r = e - 13 * i;
+      // state_diff (:681): the free response of step i < H - 1 (0 for the last) minus x_ref, formed in one go (sdiff is its only reader;
+      // the set-up scratch in sdiff is dead by now)
+      for (int k = t.tid; k < 13 * H; k += T) {
+        const int i = k / 13, r = k - 13 * i;
         const double kk = i + 1;
-        s.xk[e] = s.x0[r] + kk * s.sdiff[r] + (kk * kk / 2) * s.sdiff[13 + r];
+        double xk = 0.0;
+        if (k < 13 * (H - 1)) xk = s.x0[r] + kk * ax1[r] + (kk * kk / 2) * ax2[r];
+        s.sdiff[k] = xk - s.xref[k];
       }
     });
     MPC_SUBLAP(1, 11);
-    ex.par([&](Th &t) {   // state_diff (:681)
-      for (int k = t.tid; k < 13 * H; k += T) s.sdiff[k] = (k < 13 * (H - 1) ? s.xk[k] : 0.0) - s.xref[k];
-    });
     lap(1);
     // q (:683); and the two 12 x 12 tables from which every thread of the scaling part builds its own tile of P
     // (P = 2 B_qp^T Q B_qp + alpha I = Sigma2 (x) U1 + N (x) U2 + alpha I in the wrench form, mpc_wrench.h; the reference's block
     // recursion :387-434 gives the same numbers to rounding, and only the Ruiz norms read them)
     ex.par([&](Th &t) {
-      for (int jc = t.tid; jc < N; jc += T) {
-        const int j = jc / 12, c = jc - 12 * j;
+      if (t.tid < N) {      // (the thread that the scaling part asks for q[tid]: it keeps it)
+        const int jc = t.tid, j = jc / 12, c = jc - 12 * j;
         double acc = 0;
         for (int i = j; i < H; ++i) {
           const double *bk = s.wanb + (i - j) * 156 + c, *sd = s.sdiff + 13 * i;
@@ -602,9 +662,12 @@ struct Assembler {
           }
           acc += e + o;
         }
-        qp[C::QP_Q + jc] = 2 * acc;
+        t.qreg = 2 * acc;
+        qp[C::QP_Q + jc] = t.qreg;
       }
-      for (int e = t.tid; e < 288; e += T) {
+      // (Cfg::kSplitQU: the tables on the wavefronts that carry no q)
+      for (int e = C::kSplitQU ? t.tid - C::QT : t.tid; e < 288; e += C::kSplitQU ? T - C::QT : T) {
+        if (e < 0) break;
         const int which = e / 144, ab = e - 144 * which, a = ab / 12, b = ab - 12 * a;
         double acc = 0;
         if (which == 0) {
@@ -621,7 +684,7 @@ struct Assembler {
     });
     lap(2);
     if (prof) {
-      ex.par([&](Th &t) {
+      ex.seq([&](Th &t) {      // (thread 0's own counters: nothing handed over)
         if (t.tid == 0) {
           prof[1] = tc[1]; prof[2] = tc[2];
           if (MPC_PROFILE_SUB == 1 || MPC_PROFILE_SUB == 4) for (int k = 9; k <= 13; ++k) prof[k] = tc[k];
@@ -654,6 +717,7 @@ struct Scaler {
   long long *prof = nullptr;   // [kProfLen] slots 3 (tile build + first norms), 4 (the ten passes), 5 (record store) under MPC_SECTION_PROFILE
   long long tc[6] = {0, 0, 0, 0, 0, 0};
   long long tlast = 0;
+  bool prefetched = false;     // the kernel has put the state record's q of the previous call and cold flag into the thread (Thread::qold, first)
   using Tv = TileView;
   template <class F>
   MPC_HD void for_tiles(Th &t, F &&f) {
@@ -684,9 +748,9 @@ struct Scaler {
     for (int e = 0; e < C::NT * TE; ++e) MPC_LAUNDER(ex.th.Mx[e]);
 #endif
   }
-  MPC_HD double q_at(int i) const {
-    if constexpr (C::kQInLds) return s.q[i];
-    else return qp[C::QP_Q + i];
+  MPC_HD double q_own(const Th &t) const {      // q[t.tid] of this call: the assembly's thread kept it (Thread::qreg)
+    if constexpr (C::kQInLds) return s.q[t.tid];
+    else return t.qreg;
   }
 #ifndef MPC_SECTION_PROFILE
   MPC_HD void lap(int) {}
@@ -829,18 +893,24 @@ struct Scaler {
   }
   MPC_HD void scale() {
     tlast = MPC_CLOCK();
+    const double *const cone = u12 + 288;      // the 5 x 3 cone block, left in LDS by the assembly
     ex.par([&](Th &t) {
+      if (!prefetched) {      // what the warm-start record says about the previous call
+        if (t.tid < N) t.qold = state[N + 2 * M + t.tid];
+        t.first = state[2 * N + 2 * M + 1] == 0.0;
+      }
       for_tiles(t, [&](Tv &v, int) { build_tile(v); tile_rownorms(v, nullptr); });
       if (t.tid < N) {
-        s.qs[t.tid] = s.first ? q_at(t.tid) : s.xt[t.tid];   // osqp_update_P_A equilibrates with the PREVIOUS q
+        if constexpr (C::kQInLds) s.q[t.tid] = t.qreg;
+        s.qs[t.tid] = t.first ? t.qreg : t.qold;   // osqp_update_P_A equilibrates with the PREVIOUS q
         s.D[t.tid] = 1.0;
       }
       for_rows(t, [&](int i) {
-        const double *a = s.cone + 3 * (i % 5);
+        const double *a = cone + 3 * (i % 5);
         s.E[i] = 1.0;
         s.et_[i] = row_scale3(a[0], a[1], a[2]);
       });
-      for (int k = t.tid; k < NF * 15; k += T) s.As[k] = s.cone[k % 15];
+      for (int k = t.tid; k < NF * 15; k += T) s.As[k] = cone[k % 15];
       if (t.tid == 0) s.c = 1.0;
     });
     lap(3);
@@ -873,7 +943,7 @@ struct Scaler {
       const double cf = s.ctmp;
       if (t.tid == 0) { sc[C::SC_C] = cf; sc[C::SC_C + 1] = 1.0 / cf; }
       if (t.tid < N) {
-        const double qv = s.first ? s.qs[t.tid] : (s.D[t.tid] * q_at(t.tid)) * cf;      // osqp_update_lin_cost (osqp.c:765-770)
+        const double qv = t.first ? s.qs[t.tid] : (s.D[t.tid] * q_own(t)) * cf;      // osqp_update_lin_cost (osqp.c:765-770)
         sc[C::SC_QS + t.tid] = qv;
         sc[C::SC_D + t.tid] = s.D[t.tid];
       }
@@ -881,22 +951,11 @@ struct Scaler {
     });
     lap(5);
     if (prof) {
-      ex.par([&](Th &t) { if (t.tid == 0) { prof[3] = tc[3]; prof[4] = tc[4]; prof[5] = tc[5]; } });
+      ex.seq([&](Th &t) { if (t.tid == 0) { prof[3] = tc[3]; prof[4] = tc[4]; prof[5] = tc[5]; } });
     }
   }
 
-  // the QP record of the assembly kernel + what the warm-start record says about the previous call
-  MPC_HD void load() {
-    ex.par([&](Th &t) {
-      for (int i = t.tid; i < N; i += T) { if constexpr (C::kQInLds) s.q[i] = qp[C::QP_Q + i]; s.xt[i] = state[N + 2 * M + i]; /* q_old */ }
-      if (t.tid < 15) s.cone[t.tid] = qp[C::QP_CONE + t.tid];
-      if (t.tid == 0) s.first = state[2 * N + 2 * M + 1] == 0.0;
-    });
-  }
-  MPC_HD void run() {
-    load();
-    scale();
-  }
+  MPC_HD void run() { scale(); }
 };
 
 }  // namespace mpc

@@ -37,6 +37,16 @@ struct DeviceExec {
       __builtin_amdgcn_wave_barrier();
     } else __syncthreads();
   }
+  // A phase of the first wavefront alone, handed over to that wavefront's next phase: its LDS instructions execute in program order, so
+  // the compiler's order is all it takes (as in the WAVE case of par).  The other wavefronts skip it and run on to whatever follows, so
+  // nothing they touch before the next par may meet what such phases read or write (mpc_core.h Assembler::run lists it array by array).
+  // Device only: the host emulation has no such member, and the shared headers fall back to par where it is absent.
+  template <class F>
+  __device__ __forceinline__ void wave_par(F &&f) {
+    if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) < 64) f(th);      // (a scalar branch: uniform over the wavefront)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
   // a phase that hands nothing over through LDS (its results stay in registers or go to the quad operations below)
   template <class F>
   __device__ __forceinline__ void seq(F &&f) { f(th); }

@@ -266,9 +266,16 @@ __global__ __launch_bounds__(Cfg<H>::T, (Cfg<H>::T <= MPC_MIN_WAVES_MAX_T && Cfg
   Ex ex{th};
   const RobotModel &mdl = models[robot];
   double *qpr = qp + (size_t)robot * C::QP_LEN;
+  // What the scaling part needs of the state record -- q of the previous call, the cold flag -- depends on the robot index alone: it is asked
+  // for here, in flight together with the assembly's own loads, and waits in registers for the tile-build phase (the scale area in LDS
+  // shares its bytes with the assembly's and cannot take it earlier).
+  const double *st = state + (size_t)robot * state_len<H>();
+  th.qold = st[C::N + 2 * C::M + ((int)threadIdx.x < C::N ? (int)threadIdx.x : 0)];      // (no branch: the threads without a variable ask for q[0])
+  th.first = st[2 * C::N + 2 * C::M + 1] == 0.0;
   Assembler<H, Ex> am{ex, sh.as, mdl, in ? in + (size_t)robot * C::IN_LEN : nullptr, in64 ? in64 + (size_t)robot * C::IN_LEN : nullptr, in16 ? in16 + (size_t)robot * C::IN_LEN : nullptr, sh.u12, qpr, prof ? prof + (size_t)robot * kProfLen : nullptr};
   am.run();
-  Scaler<H, Ex> sk{ex, sh.sc, state + (size_t)robot * state_len<H>(), sh.u12, mdl.alpha, qpr, sc + (size_t)robot * C::SC_LEN, prof ? prof + (size_t)robot * kProfLen : nullptr};
+  Scaler<H, Ex> sk{ex, sh.sc, st, sh.u12, mdl.alpha, qpr, sc + (size_t)robot * C::SC_LEN, prof ? prof + (size_t)robot * kProfLen : nullptr};
+  sk.prefetched = true;
   sk.run();
 }
 

@@ -20,8 +20,33 @@ import sys
 # instantiation mpc_solve_kernel<H, false>; the exact-mode one, <H, true>, is not performance critical)
 KERNELS = {"jobs": r'\n(_ZN[^\n]*mpc_solve_jobs_kernelILi%sEE[^\n:]*):[^\n]*\n(.*?)\n\.Lfunc_end',
            "one": r'\n(_ZN[^\n]*mpc_solve_kernelILi%sELb0E[^\n:]*):[^\n]*\n(.*?)\n\.Lfunc_end'}
+KERNELS["prep"] = r'\n(_Z[^\n]*mpc_prep_kernelILi%sEE[^\n:]*):[^\n]*\n(.*?)\n\.Lfunc_end'
 KERNEL = "jobs"
 KERNEL_RE = KERNELS[KERNEL]
+
+
+def kernel_summary(txt, H, kernel="prep"):
+    """Whole-kernel counts of one kernel of horizon H (inlined device functions included): instructions, s_barrier sites, global loads,
+    s_waitcnt with a vmcnt field, scratch instructions inside loops, and the resource figures of the assembler's kernel footer."""
+    m = re.search(KERNELS[kernel] % H, txt, re.S)
+    if not m:
+        raise KeyError(f"no {kernel} kernel of horizon {H} in the assembly")
+    name, body = m.group(1), m.group(2)
+    ins = _instructions(body)
+    out = dict(instructions=len(ins),
+               barriers=sum(1 for l in ins if l.startswith('\ts_barrier')),
+               global_loads=sum(1 for l in ins if l.startswith('\tglobal_load')),
+               vm_waits=sum(1 for l in ins if l.startswith('\ts_waitcnt') and 'vmcnt' in l),
+               loop_scratch=0)
+    for b in re.split(r'\n(?=\.LBB\d+_\d+:)', body):
+        if _loop_of(b) is not None:
+            out["loop_scratch"] += sum(1 for l in _instructions(b) if l.startswith('\tscratch'))
+    foot = txt[m.end():]
+    foot = foot[:foot.index(".end_amdhsa_kernel")] if ".end_amdhsa_kernel" in foot else foot
+    for key, pat in (("vgprs", r'; NumVgprs: (\d+)'), ("agprs", r'; NumAgprs: (\d+)'), ("scratch_bytes", r'; ScratchSize: (\d+)'),
+                     ("lds_bytes", r'; LDSByteSize: (\d+)'), ("occupancy", r'; Occupancy: (\d+)')):
+        out[key] = int(re.search(pat, foot).group(1))
+    return out
 
 
 def compile_to_asm(csrc_dir, out, horizons=(10, 12, 16, 20), extra=()):
