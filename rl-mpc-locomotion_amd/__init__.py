@@ -17,8 +17,9 @@ _PRIVILEGED_OBS = ("PrivilegedObs",)
 _PLANT_RAND = ("PlantRand", "PlantSpec")
 _RECURRENT = ("ActorCriticRecurrent", "Memory", "RecurrentConfig")
 _REWARD_SHAPING = ("RewardShaping", "ShapingSpec")
+_FRICTION = ("Friction", "FrictionSpec")
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS, "privileged_obs", *_PRIVILEGED_OBS, "plant_rand", *_PLANT_RAND, "recurrent", *_RECURRENT, "reward_shaping", *_REWARD_SHAPING]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS, "privileged_obs", *_PRIVILEGED_OBS, "plant_rand", *_PLANT_RAND, "recurrent", *_RECURRENT, "reward_shaping", *_REWARD_SHAPING, "friction", *_FRICTION]
 
 
 def __getattr__(name):
@@ -56,4 +57,7 @@ def __getattr__(name):
     if name in _REWARD_SHAPING:
         from . import reward_shaping
         return getattr(reward_shaping, name)
+    if name in _FRICTION:
+        from . import friction
+        return getattr(friction, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

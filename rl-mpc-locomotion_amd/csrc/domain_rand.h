@@ -40,6 +40,7 @@ constexpr uint64_t kDomActNoise = 0x44524143544E4F49ull;
 constexpr uint64_t kDomActCorr = 0x4452414354434F52ull;
 constexpr uint64_t kDomPush = 0x445250555348585Aull;
 constexpr uint64_t kDomPlant = 0x4452504C414E5458ull;      // plant_rand.h's payload / motor strength / gravity draws
+constexpr uint64_t kDomFriction = 0x4452465249435458ull;   // friction.h's coefficient draws ("DRFRICTX")
 
 enum { kTargetObs = 0, kTargetAct = 1 };
 

@@ -139,6 +139,10 @@ int mpc_sim_size(mpc_sim *s) { return s ? s->n : 0; }
 int mpc_sim_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, void *stream) {
   if (!s || !d_tau) return fail(MPC_E_ARG, "mpc_sim_step: bad argument");
   DeviceGuard guard_(s->device);
+  if (s->friction) {                   // a friction record is attached (mpc_friction_attach): the Coulomb instantiation of its ground
+    HIP_TRY(simint::friction_launch_step(s, d_tau, d_dof, d_root, reinterpret_cast<hipStream_t>(stream)));
+    return MPC_OK;
+  }
   if (s->d_plant) {                    // a plant record is attached (mpc_plant_rand_attach): the parametrised instantiation of its ground
     HIP_TRY(simint::plant_launch_step(s, d_tau, d_dof, d_root, reinterpret_cast<hipStream_t>(stream)));
     return MPC_OK;

@@ -2,7 +2,9 @@
 // mpc_terrain_attach (include/mpc_terrain.h) has run its height field, and once mpc_plant_rand_attach (mpc_plant_rand.h) has run its per-robot
 // plant record.  mpc_sim.hip owns the handle and the plane kernels; mpc_terrain.hip holds the height-field instantiations of toy_sim.h and is
 // what mpc_sim_step / mpc_sim_reset_device launch for a sim with a terrain; mpc_plant_rand.hip holds the instantiations of toy_step_plant on both
-// grounds and is what mpc_sim_step launches for a sim with a plant record (host-side branches on the handle).  Not part of the C ABI.
+// grounds and is what mpc_sim_step launches for a sim with a plant record; mpc_friction.hip holds the Coulomb instantiations of the step on
+// both grounds and is what mpc_sim_step launches once mpc_friction_attach (mpc_friction.h) has run, with or without a plant record (host-side
+// branches on the handle).  Not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,6 +27,12 @@ struct mpc_sim {
   // the per-robot plant record (null until mpc_plant_rand_attach): [kPlant][n], entry j of robot r at [j * n + r], like the state:
   // 0 payload [kg], 1 strength [factor], 2 grav_z [m/s^2, absolute]; neutral (0.0, 1.0, kGravZ)
   mpchost::DeviceArray<double> d_plant;
+  // the friction record (friction false until mpc_friction_attach): the Coulomb coefficient of every robot's feet, >= 0, +inf = the anchor
+  // holds; and the caller's output arrays of the step, either of which may be null
+  bool friction = false;
+  mpchost::DeviceArray<double> d_mu;                   // [n]
+  float *d_force = nullptr;                            // [n][4][3] the ground reaction of the tick's last substep, world frame [N]
+  float *d_slip = nullptr;                             // [n][4] the distance slid over the tick [m]
 };
 
 namespace simint {
@@ -38,5 +46,7 @@ hipError_t terrain_launch_init(mpc_sim *s, const int *d_ids, int k, hipStream_t 
 hipError_t terrain_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream);
 // the step of a sim with a plant record, on its plane or on its terrain (mpc_plant_rand.hip); the caller has set the device
 hipError_t plant_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream);
+// the step of a sim with a friction record, on either ground, with its plant record or the neutral one (mpc_friction.hip); the caller has set the device
+hipError_t friction_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream);
 
 }  // namespace simint

@@ -4,7 +4,7 @@
 // A TOY, not a physics engine: one rigid body under gravity; a leg in contact holds its foot at a world anchor (no slip) and pushes the
 // body with F = -R J^-T tau, its joint angles following from the anchor by inverse kinematics; a leg that would pull on the ground by more
 // than RELEASE_N lets go; a leg in the air is three independent damped joints of inertia I_J (massless for the body) and touches down where
-// its foot path crosses the ground.  No articulated dynamics, no joint limits, no friction cone on the plant side.
+// its foot path crosses the ground.  No articulated dynamics, no joint limits; no friction cone either unless the step is given one (below).
 //
 // The ground is a template parameter of toy_init / toy_step: Plane (z = gx x + gy y, the numpy ToyRobot's) or HeightField (an int16 grid
 // meshed into triangles as Isaac Gym's convert_heightfield_to_trimesh splits its cells; tests/toy_terrain.py's ToyTerrainRobot).  It appears
@@ -16,6 +16,15 @@
 // the scaled torque) and that gravity.  The inertia is NOT changed by the payload: Isaac Gym's added base mass (legged_gym's randomize_base_mass)
 // changes the body's mass property and leaves its inertia alone as well.  With the neutral record mass + 0.0, tau * 1.0 and kGravZ are exact, so
 // toy_step_plant reproduces toy_step bit for bit.
+//
+// The contact is a template parameter of the step as well: NoFriction (the anchor holds whatever the leg asks of it; what every function named
+// toy_step* steps with) or Coulomb (toy_step_friction): a stance leg's force f, after the lift-off tests, is split along the normal n under its
+// anchor, ft = f - fn n, and where |ft| > mu fn the ground supplies only fn n + mu fn t (t = ft / |ft|) and the massless foot slides: its anchor
+// moves against t by h (|ft| - mu fn) / kSlipDamp, a viscous regularisation, and is put back on the ground.  The lever arm is the foot's position
+// before the slide, the normal the one under the anchor before it; the substep's closing inverse kinematics follows the moved anchor.  No new
+// state.  Coulomb also reports force[4][3], the world-frame ground reaction of the tick's last substep (zero for a leg in the air, a leg that let
+// go or one with fn < 0), and slip[4], the distance slid over the tick.  mu >= 0; with mu = +inf nothing ever exceeds the limit (inf * 0 is NaN
+// and compares false) and the step reproduces the NoFriction one bit for bit; mu = 0 leaves the normal force alone.
 //
 // toy_init / toy_step restate ToyRobot.__init__ / ToyRobot.step of the numpy model operation for operation in float64 (same order of the
 // sums, legs 0..3, +0.0 start; 4 IK iterations per substep, 20 at initialisation; 3 x 3 systems solved as LAPACK's dgesv does: partial
@@ -41,6 +50,7 @@ constexpr int kLiftTicks = 3;          // ticks after lift-off during which a fo
 constexpr double kReleaseN = 5.0;      // pull [N] at which a foot in contact lets go
 constexpr double kReg = 1e-9;          // added to the diagonal of the leg Jacobian systems
 constexpr double kGravZ = -9.81;
+constexpr double kSlipDamp = 200.0;    // viscous coefficient of a sliding foot [N s/m] (Coulomb)
 
 // columns of quadruped.ROBOT_TABLE64 (COL_ABAD ... COL_HEIGHT) and its row length
 constexpr int kColAbad = 0, kColHip = 1, kColKnee = 2, kColHiploc = 3, kColMass = 6, kColInertia = 7, kColHeight = 10, kRobotCols = 25;
@@ -316,14 +326,34 @@ MPC_HD void toy_init(State &s, const Params &P, double yaw0, const Ground &g) {
 
 MPC_HD void toy_init(State &s, const Params &P, double yaw0, double gx, double gy) { toy_init(s, P, yaw0, Plane{gx, gy}); }
 
-// ToyRobot.step(tau, dt) on ground g under gravity (0, 0, grav_z): one tick of kSubsteps substeps
-template <class Ground>
-MPC_HD void toy_step_gravity(State &s, const Params &P, const double *tau, double dt, const Ground &g, double grav_z) {
+// the contact policies of the step (see the head of this file)
+struct NoFriction {
+  static constexpr bool kFriction = false;
+};
+
+struct Coulomb {
+  static constexpr bool kFriction = true;
+  double mu;
+  double force[4][3];                  // out: the ground reaction of the tick's last substep, world frame [N]
+  double slip[4];                      // out: the distance slid over the tick [m]
+};
+
+// ToyRobot.step(tau, dt) on ground g under gravity (0, 0, grav_z) with contact policy c: one tick of kSubsteps substeps
+template <class Ground, class Contact>
+MPC_HD void toy_step_contact(State &s, const Params &P, const double *tau, double dt, const Ground &g, double grav_z, Contact &c) {
   const double h = dt / kSubsteps;
   double n[3];
   if constexpr (Ground::kUniformNormal) g.normal(s.pos, n);
+  if constexpr (Contact::kFriction) {
+#pragma unroll
+    for (int l = 0; l < 4; ++l) c.slip[l] = 0.0;
+  }
 #pragma unroll 1
   for (int sub = 0; sub < kSubsteps; ++sub) {
+    if constexpr (Contact::kFriction) {
+#pragma unroll
+      for (int l = 0; l < 4; ++l) c.force[l][0] = c.force[l][1] = c.force[l][2] = 0.0;
+    }
     double R[3][3];
     quat_to_rot(s.quat, R);
     double F[3] = {0.0, 0.0, 0.0}, T[3] = {0.0, 0.0, 0.0};
@@ -353,13 +383,35 @@ MPC_HD void toy_step_gravity(State &s, const Params &P, const double *tau, doubl
         continue;
       }
       if (fn < 0.0) continue;            // (unilateral contact: no pull, but not yet a lift-off either)
-      double hp[3], r[3], c[3];
+      if constexpr (Contact::kFriction) {
+        double ft[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) ft[i] = f[i] - fn * n[i];
+        const double ftn = norm3(ft), lim = c.mu * fn;
+        if (ftn > lim) {                 // beyond the cone: the ground supplies the limit and the foot slides (NaN, mu = inf and fn = 0: it sticks)
+          double t[3], a[3];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) t[i] = ft[i] / ftn;
+#pragma unroll
+          for (int i = 0; i < 3; ++i) f[i] = fn * n[i] + lim * t[i];
+          const double d = h * ((ftn - lim) / kSlipDamp);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) a[i] = s.anchor[l][i] - d * t[i];
+          a[2] = g.height(a);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) s.anchor[l][i] = a[i];
+          c.slip[l] = c.slip[l] + d;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) c.force[l][i] = f[i];
+      }
+      double hp[3], r[3], cr[3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) { F[i] = F[i] + f[i]; hp[i] = P.hiploc[l][i] + pj[l][i]; }
       mat_vec(R, hp, r);
-      cross(r, f, c);
+      cross(r, f, cr);
 #pragma unroll
-      for (int i = 0; i < 3; ++i) T[i] = T[i] + c[i];
+      for (int i = 0; i < 3; ++i) T[i] = T[i] + cr[i];
     }
     // Iw = (R diag(I)) R^T
     double RD[3][3], Iw[3][3];
@@ -461,6 +513,13 @@ MPC_HD void toy_step_gravity(State &s, const Params &P, const double *tau, doubl
   if (!finite || R[2][2] < 0.3 || fabs(s.pos[2] - g.height(s.pos)) > 3 * P.height) s.fell = 1;
 }
 
+// ... with the anchor that holds (no friction cone): what every plant stepped with before Coulomb, and every toy_step* below still does
+template <class Ground>
+MPC_HD void toy_step_gravity(State &s, const Params &P, const double *tau, double dt, const Ground &g, double grav_z) {
+  NoFriction c;
+  toy_step_contact(s, P, tau, dt, g, grav_z, c);
+}
+
 // ... under the constant kGravZ: the plant every robot of a type shares
 template <class Ground>
 MPC_HD void toy_step(State &s, const Params &P, const double *tau, double dt, const Ground &g) { toy_step_gravity(s, P, tau, dt, g, kGravZ); }
@@ -476,6 +535,17 @@ MPC_HD void toy_step_plant(State &s, const Params &P, const double *tau, double 
 #pragma unroll
   for (int i = 0; i < 12; ++i) t[i] = tau[i] * strength;
   toy_step_gravity(s, Q, t, dt, g, grav_z);
+}
+
+// ... with the robot's own plant record and the Coulomb contact c (c.mu in; c.force, c.slip out).  The neutral record and mu = +inf: toy_step.
+template <class Ground>
+MPC_HD void toy_step_friction(State &s, const Params &P, const double *tau, double dt, const Ground &g, double payload, double strength, double grav_z, Coulomb &c) {
+  Params Q = P;
+  Q.mass = P.mass + payload;
+  double t[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) t[i] = tau[i] * strength;
+  toy_step_contact(s, Q, t, dt, g, grav_z, c);
 }
 
 // the state record of include/mpc_sim.h: f64[kF64], i32[kI32]; `stride` = distance between two consecutive entries of ONE robot

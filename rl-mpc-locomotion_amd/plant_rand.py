@@ -15,7 +15,7 @@ generator state, and a draw does not depend on the batch size::
 that mismatch is what the weight policy is trained to cope with.  Without the option a sim launches the kernels it launched before; with the neutral
 record (0, 1, -9.81) the parametrised kernel computes the same state bit for bit.
 
-Not built: friction (the toy plant has none to scale), COM displacement, inertia scaling.
+Not built: COM displacement, inertia scaling.  (Friction is ``friction.Friction``, an option of its own that works together with this one.)
 
 ``PlantSpec`` and ``PlantRand.validate`` are host arithmetic and need no GPU; the kernels do (MpcLibraryError without one, no CPU fallback).
 """

@@ -641,7 +641,8 @@ _Part = namedtuple("_Part", "key obj missing unexpected after", defaults=(None, 
 
 
 def _checkpoint_parts(trainer):
-    """The parts of ``trainer`` (anything with its ``obs_norm``, ``critic_obs_norm``, ``episode_terms``, ``plant_rand``, ``env`` and ``obs``), in the checkpoint's order."""
+    """The parts of ``trainer`` (anything with its ``obs_norm``, ``critic_obs_norm``, ``episode_terms``, ``plant_rand``, ``env`` and ``obs``; ``friction`` where
+    it has one), in the checkpoint's order."""
     env, terms = trainer.env, trainer.episode_terms
 
     def forget_obs():                                                            # (normalised with the statistics before the load)
@@ -650,7 +651,10 @@ def _checkpoint_parts(trainer):
     def set_clock():                                                             # the command curriculum's clock follows the checkpoint's
         if hasattr(env, "common_step_counter"):
             env.common_step_counter = terms.tick
-    return (_Part("obs_norm_state_dict", trainer.obs_norm, "this trainer normalises observations and the checkpoint carries no obs_norm_state_dict",
+    # (the friction first: both of its refusals come before any part has been loaded)
+    return (_Part("friction_state_dict", getattr(trainer, "friction", None), "this trainer's environment has friction and the checkpoint carries no friction_state_dict",
+                  "the checkpoint was written with friction (friction_state_dict) and this trainer's environment has none"),
+            _Part("obs_norm_state_dict", trainer.obs_norm, "this trainer normalises observations and the checkpoint carries no obs_norm_state_dict",
                   "the checkpoint was written with observation normalisation and this trainer has none", forget_obs),
             _Part("critic_obs_norm_state_dict", trainer.critic_obs_norm,
                   "this trainer normalises the critic's rows and the checkpoint carries no critic_obs_norm_state_dict"),
@@ -710,8 +714,8 @@ class PPOTrainer:
         self.device = _lib.device_of(device if device is not None else getattr(env, "device", None))
         torch.manual_seed(self.seed)
         c = self.cfg
-        self.num_privileged_obs, self.curriculum, self.episode_terms, self.plant_rand, self.reward_shaping = (
-            getattr(env, name, None) for name in ("num_privileged_obs", "curriculum", "episode_terms", "plant_rand", "reward_shaping"))
+        self.num_privileged_obs, self.curriculum, self.episode_terms, self.plant_rand, self.reward_shaping, self.friction = (
+            getattr(env, name, None) for name in ("num_privileged_obs", "curriculum", "episode_terms", "plant_rand", "reward_shaping", "friction"))
         priv = self.num_privileged_obs
         self.recurrent = recurrent
         self._prev_reset = None                                                  # the task's reset tensor of the tick before (kept for a net with memory only)
@@ -842,7 +846,9 @@ class PPOTrainer:
         rows (``fold_normalizer(..., critic_obs_norm_state_dict=)``); ``load`` refuses a checkpoint whose critic reads rows of another width.  On an environment with
         ``episode_terms`` it carries ``episode_terms_state_dict`` (the x command range, the widenings, the tick), which ``load`` restores when present.
         On an environment with ``plant_rand`` it carries ``plant_rand_state_dict`` (every robot's plant record and draw counter), which ``load``
-        restores when present; a checkpoint without it leaves the record as the task made it."""
+        restores when present; a checkpoint without it leaves the record as the task made it.  On an environment with ``friction`` it carries
+        ``friction_state_dict`` (every robot's friction coefficient and draw counter); ``load`` refuses, before anything is loaded, a checkpoint
+        with it on an environment without and a checkpoint without it on an environment with."""
         ck = {"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(), "iter": self.iteration,
               "infos": self.infos}
         _save_parts(_checkpoint_parts(self), ck)

@@ -202,6 +202,10 @@ class BatchedRLTask:
     that its step consumes; with ``resample="once"`` every record is drawn when the task is built, with ``"reset"`` the environments being reset
     draw theirs inside the ``resets`` stage, before ``sim.reset_idx`` (the first tick resets, and so draws, every environment).  A
     ``PrivilegedObs(n, plant=True)`` shows the record to the critic and needs ``plant_rand``.
+    ``friction`` (a ``friction.Friction`` for as many environments): the sim gets a per-robot Coulomb friction coefficient that its step consumes,
+    and fills ``friction.contact_forces`` [N, 4, 3] and ``friction.foot_slip`` [N, 4]; with a spec whose ``resample`` is ``"once"`` every coefficient
+    is drawn when the task is built; inside the ``resets`` stage, next to ``plant_rand.draw``, the environments being reset have their force and
+    slip rows zeroed and, with ``"reset"``, draw their coefficient anew.
     ``reward_shaping`` (a ``reward_shaping.RewardShaping`` for as many environments): eight more reward terms by legged_gym's formulas; its episodes
     are closed inside the ``resets`` stage, before ``ctl.reset``, and one launch after the height scan (after ``finish`` without one) rewrites
     ``rew_buf`` with the fourteen terms and feeds its per-term sums.  The unit is made under the task's own ``cfg`` (``RewardShaping(n, spec, cfg=cfg)``; another one is refused), and a non-zero ``base_height`` scale on a terrain needs
@@ -209,18 +213,21 @@ class BatchedRLTask:
     See the module text for what the toy cannot do."""
 
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
-                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, plant_rand=None, reward_shaping=None, **bridge_args):
+                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, plant_rand=None, reward_shaping=None, friction=None, **bridge_args):
         import torch
         n_envs = len(np.asarray(robot_type).reshape(-1))
         cfg = cfg if cfg is not None else TaskConfig()
         # everything that can be refused is refused here, before the device is touched: one pass over the options, the first fault raises
-        for unit, holds in ((plant_rand, None), (privileged_obs, "the privileged observations hold"), (episode_terms, "the episode terms hold"),
+        for unit, holds in ((plant_rand, None), (friction, None), (privileged_obs, "the privileged observations hold"), (episode_terms, "the episode terms hold"),
                             (reward_shaping, "the reward shaping holds"), (domain_rand, None), (height_scan, "the height scan holds"),
                             (curriculum, "the curriculum holds")):
             if unit is None:
                 continue
             if unit is plant_rand:         # counts its environments itself, with its payload against the masses of the robot types in use
                 unit.validate(n=n_envs, robot_type=robot_type)
+                continue
+            if unit is friction:           # counts its environments itself, with its spec
+                unit.validate(n=n_envs)
                 continue
             if unit is privileged_obs and getattr(unit, "plant", False) and plant_rand is None:
                 raise ValueError("privileged_obs has plant=True: the plant columns need plant_rand=")
@@ -274,6 +281,11 @@ class BatchedRLTask:
             plant_rand.bind(self.sim)
             if plant_rand.spec.resample == "once":
                 plant_rand.draw()
+        self.friction = friction
+        if friction is not None:
+            friction.bind(self.sim)
+            if friction.spec is not None and friction.spec.resample == "once":
+                friction.draw(resample=True)
         self.episode_terms = episode_terms
         self.reward_shaping = reward_shaping
         if reward_shaping is not None:
@@ -304,6 +316,7 @@ class BatchedRLTask:
             begin               ``task.begin``
             episode_close       ``episode_terms.close_and_resample``       only with episode_terms
             resets              ``ctl.reset``, ``sim.reset_idx``, ``sim.flags``; with a PlantRand that resamples at reset ``plant_rand.draw`` first,
+                                with a Friction ``friction.draw`` (the rows of the environments being reset zeroed; a coefficient drawn with "reset"),
                                 with reward_shaping ``reward_shaping.close`` first
             finish              ``task.finish``; with reward_shaping and no height scan then ``reward_shaping.run``
             episode_accumulate  ``episode_terms.accumulate``               only with episode_terms
@@ -350,6 +363,8 @@ class BatchedRLTask:
                 mark("episode_close")
         if self.plant_rand is not None and self.plant_rand.spec.resample == "reset":      # the new episode's plant, before the robot is put back
             self.plant_rand.draw(ids)
+        if self.friction is not None:      # the reset environments' force and slip rows, and with resample "reset" the new episode's coefficient
+            self.friction.draw(ids)
         rs = self.reward_shaping
         if rs is not None:                 # close the marked episodes' shaping sums
             rs.close(ids)

@@ -1,0 +1,345 @@
+"""The Coulomb friction of the toy plant on the MI355X (csrc/mpc_friction.h, rl_mpc_locomotion_amd.friction): the friction step kernels against the
+plain and the plant-record ones (mu = inf: bit for bit) and against the numpy model (tests/toy_friction.py; tests/test_friction.py's tolerances and its
+conditions on the inputs), independence of the batch, the draw kernel against the numpy draw, and the option's way through BatchedRLTask, PPOTrainer
+and its checkpoint.  n = 130 is two full waves and one of two lanes, robot types interleaved: a ragged last wave and more than one workgroup."""
+import functools
+
+import numpy as np
+import pytest
+
+import rl_mpc_locomotion_amd  # noqa: F401
+from rl_mpc_locomotion_amd import friction as FR, plant_rand as PR, rl_task as R, terrain as TR
+from rl_mpc_locomotion_amd.quadruped import ROBOT_TABLE64
+from tests import friction_ref as fref, plant_rand_ref as pref, toy_friction as TF
+from tests.plant_rand_ref import POS_LIKE, VEL_LIKE, from_record, to_record
+from tests.test_height_scan_gpu import DEV, TROT, _cfg, _robots, _yaw
+
+pytestmark = pytest.mark.gpu
+N = 130
+SLOPE = (0.05, -0.03)
+TOL_POS, TOL_VEL, TIE = 1e-9, 1e-7, 1e-9
+MU_LEVELS = (0.2, 0.4, 1.0)
+GROUNDS = ("plane", "field")
+
+
+@functools.lru_cache(maxsize=None)
+def _field():
+    return TR.Terrain.mild(1, rows=128, cols=128)
+
+
+def _slopes(n):
+    return np.array([SLOPE if (i // 3) % 2 else (0.0, 0.0) for i in range(n)])
+
+
+def _origins(n):
+    return np.random.default_rng(2).uniform(0.0, 3.0, (n, 2))
+
+
+def _mus(n):
+    return np.random.default_rng(4).choice(MU_LEVELS, n)
+
+
+def _sim(ground, rows=None):
+    """A BatchedToySim of robots `rows` (default all) of the N-robot layout, on planes or on a 128 x 128 mild height field."""
+    from rl_mpc_locomotion_amd.toy_sim import BatchedToySim
+    k = np.arange(N) if rows is None else np.asarray(rows)
+    rt = np.asarray(_robots(N))[k]
+    if ground == "plane":
+        return BatchedToySim(rt, slope=_slopes(N)[k], yaw0=_yaw(N)[k], device=DEV)
+    return BatchedToySim(rt, yaw0=_yaw(N)[k], device=DEV, terrain=_field(), origin=_origins(N)[k])
+
+
+def _ctl(rows=None):
+    from rl_mpc_locomotion_amd.locomotion import BatchedLocomotion
+    k = np.arange(N) if rows is None else np.asarray(rows)
+    return BatchedLocomotion([int(t) for t in np.asarray(_robots(N))[k]], [TROT] * len(k), horizon=10, device=DEV)
+
+
+def _cmd(n, vx=0.3):
+    """The command record of the closed-loop golden's trot cases (vx, vy, wz, twelve MPC weights, 0): with the robot table's default weights, which
+    leave roll and pitch unweighted, the toy's robots tip over within a hundred ticks."""
+    import torch
+    return torch.tensor([vx, 0.0, 0.0, 5, 5, 5, 50, 50, 50, 1, 1, 1, 1, 1, 1, 0], dtype=torch.float32, device=DEV).repeat(n, 1).contiguous()
+
+
+def _tick(sim, ctl, cmd):
+    tau = ctl.run(sim.dof_state.view(sim.n, 12, 2), sim.root_states, cmd)
+    sim.step(tau)
+    return tau
+
+
+def _snapshot(sim):
+    st = sim.get_state()
+    return st["f64"], st["i32"], sim.dof_state.cpu().numpy(), sim.root_states.cpu().numpy()
+
+
+def _model(ground, i, mu):
+    rt = _robots(N)[i]
+    if ground == "plane":
+        return TF.ToyFrictionRobot(ROBOT_TABLE64[rt], yaw0=_yaw(N)[i], slope=_slopes(N)[i], mu=mu)
+    return TF.ToyFrictionTerrainRobot(ROBOT_TABLE64[rt], _field(), _origins(N)[i], yaw0=_yaw(N)[i], mu=mu)
+
+
+# ---- 7. mu = inf is the old kernels ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ground", GROUNDS)
+def test_mu_inf_is_bit_identical_to_the_kernels_without_friction(ground):
+    records = pref.hand_records(N)
+
+    def build(friction, plant, friction_first=True):
+        """(sim, its controller, its Friction or None); plant None, "neutral" or "records" """
+        sim = _sim(ground)
+        fr = FR.Friction(N, device=DEV) if friction else None                 # mu None: inf everywhere
+        pr = PR.PlantRand(N, device=DEV) if plant else None
+        for unit in ((fr, pr) if friction_first else (pr, fr)):
+            if unit is not None:
+                unit.bind(sim)
+        if plant == "records":
+            pr.set_params(records)
+        return sim, _ctl(), fr, pr
+    # each friction sim beside the sim it must reproduce
+    pairs = [("no plant record", build(False, None), [build(True, None)]),
+             ("the neutral plant record", build(False, "neutral"), [build(True, "neutral", True), build(True, "neutral", False)]),
+             ("hand-set plant records", build(False, "records"), [build(True, "records", True), build(True, "records", False)])]
+    cmd = _cmd(N)
+    for tick in range(100):
+        for _, ref_sim, others in pairs:
+            for sim, ctl, *_ in [ref_sim] + others:
+                _tick(sim, ctl, cmd)
+        if tick % 33 == 0 or tick == 99:
+            for what, ref_sim, others in pairs:
+                want = _snapshot(ref_sim[0])
+                for j, (sim, _, fr, _) in enumerate(others):
+                    for a, b, name in zip(want, _snapshot(sim), ("f64", "i32", "dof_state", "root_states")):
+                        assert np.array_equal(a, b), f"{ground}, {what}, attach order {j}: {name} at tick {tick}"
+                    force, slip = fr.contact_forces.cpu().numpy(), fr.foot_slip.cpu().numpy()
+                    assert not slip.any() and np.isfinite(force).all() and not force[want[1][:, :4] == 0].any()      # (no force on a foot in the air)
+                    standing = int((want[1][:, 8] == 0).sum())
+                    # mid-stride a trot's two stance feet carry every standing robot (tick 0 is the stand-up, tick 99 the moment the pairs change over)
+                    assert tick not in (33, 66) or (np.abs(force[..., 2]) > 1).sum() >= standing
+            if tick == 33:
+                standing_at_33 = int((_snapshot(pairs[0][1][0])[1][:, 8] == 0).sum())
+    plain = pairs[0][1][0].get_state()
+    assert np.array_equal(pairs[0][1][0].get_state()["f64"], pairs[1][1][0].get_state()["f64"])      # (the neutral record is the plain plant)
+    assert not np.array_equal(plain["f64"], pairs[2][1][0].get_state()["f64"])                         # (and the hand-set records are not)
+    assert (plain["i32"][:, :4] == 0).any() and standing_at_33 >= 100          # a trot: feet in the air, the robots standing a third of the way in
+
+
+# ---- 8. the device against the numpy model ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ground", GROUNDS)
+def test_one_step_equals_the_numpy_model(ground):
+    sim, ctl, cmd = _sim(ground), _ctl(), _cmd(N)
+    mus = _mus(N)
+    fr = FR.Friction(N, mu=mus, device=DEV)
+    fr.bind(sim)
+    assert np.array_equal(fr.get_mu(), mus) and set(mus) == set(MU_LEVELS)
+    rng = np.random.default_rng(5)
+    probe = (4, 11, 19, 33, 60)
+    compared = slipping = sticking = 0
+    worst = np.zeros(4)
+    for tick in range(max(probe) + 1):
+        tau = ctl.run(sim.dof_state.view(N, 12, 2), sim.root_states, cmd)
+        if tick in probe:
+            pre, tau_h = sim.get_state(), tau.cpu().numpy().copy()
+        sim.step(tau)
+        if tick not in probe:
+            continue
+        post, force, slip = sim.get_state(), fr.contact_forces.cpu().numpy(), fr.foot_slip.cpu().numpy()
+        alive = np.flatnonzero(pre["i32"][:, 8] == 0)
+        assert len(alive) >= 32, f"tick {tick}: {len(alive)} robots alive"
+        for i in rng.choice(alive, 32, replace=False):
+            what = f"{ground} tick {tick} robot {i} (mu {mus[i]})"
+            m = from_record(_model(ground, i, mus[i]), pre["f64"][i], pre["i32"][i])
+            log = []
+            m.step(tau_h[i], log=log)
+            for l, ftn, lim, slid, *_, pushes in log:                           # tests/test_friction.py's no_tie
+                assert not pushes or not abs(ftn - lim) <= TIE * max(1.0, ftn), f"{what}: leg {l} decides on ftn {ftn!r} against lim {lim!r}"
+            slipping += sum(e[3] for e in log)
+            sticking += sum(not e[3] and e[8] for e in log)
+            rf, rk = to_record(m)
+            assert np.array_equal(post["i32"][i], rk), f"{what}: contact / lift / fell {post['i32'][i].tolist()} against the model's {rk.tolist()}"
+            dpos, dvel = np.abs(post["f64"][i][POS_LIKE] - rf[POS_LIKE]).max(), np.abs(post["f64"][i][VEL_LIKE] - rf[VEL_LIKE]).max()
+            assert dpos <= TOL_POS and dvel <= TOL_VEL, f"{what}: |dpos| {dpos:.3e}, |dvel| {dvel:.3e}"
+            # two doubles within 1e-9 relative round to floats at most one ulp apart; the bound allows twice that.  The slip: 1e-12 m as doubles
+            want_f, want_s = m.force.astype(np.float32), m.slip.astype(np.float32)
+            df, ds = np.abs(force[i] - want_f), np.abs(slip[i] - want_s)
+            assert (df <= 1e-6 + 2.0 ** -22 * np.abs(want_f)).all(), f"{what}: contact_forces {force[i].tolist()} against {want_f.tolist()}"
+            assert (ds <= 1e-12 + 2.0 ** -22 * np.abs(want_s)).all(), f"{what}: foot_slip {slip[i].tolist()} against {want_s.tolist()}"
+            worst = np.maximum(worst, (dpos, dvel, df.max(), ds.max()))
+            compared += 1
+    print(f"{ground}: {compared} robot steps, {slipping} slipping and {sticking} sticking leg-substeps; worst |dpos| {worst[0]:.2e}, |dvel| {worst[1]:.2e}, "
+          f"|dforce| {worst[2]:.2e} N, |dslip| {worst[3]:.2e} m")
+    assert compared == 160 and slipping >= 20 and sticking >= 100
+
+
+# ---- 9. independence ----------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ground", GROUNDS)
+def test_a_robot_alone_is_the_robot_among_130(ground):
+    """The plant of robot 77 alone, driven by the torques the controller gave it among the 130, is bit for bit the robot among the 130."""
+    mus, one = _mus(N), 77
+    out, torques = [], []
+    for rows in (None, [one]):
+        sim = _sim(ground, rows)
+        fr = FR.Friction(sim.n, mu=mus if rows is None else mus[rows], device=DEV)
+        fr.bind(sim)
+        if rows is None:
+            ctl, cmd = _ctl(), _cmd(N)
+            for _ in range(30):
+                torques.append(_tick(sim, ctl, cmd)[one:one + 1].clone())
+        else:
+            for tau in torques:
+                sim.step(tau.contiguous())
+        pick = slice(one, one + 1) if rows is None else slice(0, 1)
+        f64, i32, dof, root = _snapshot(sim)
+        out.append((f64[pick], i32[pick], dof.reshape(sim.n, 24)[pick], root[pick], fr.contact_forces.cpu().numpy()[pick], fr.foot_slip.cpu().numpy()[pick]))
+    for a, b, name in zip(*out, ("f64", "i32", "dof_state", "root_states", "contact_forces", "foot_slip")):
+        assert np.array_equal(a, b), name
+    assert out[0][4].any()
+
+
+def test_draw_touches_the_listed_robots_only_and_a_fallen_robot_reports_zeros():
+    import torch
+    seed = 20261021
+    sim, ctl, cmd = _sim("plane"), _ctl(), _cmd(N)
+    fr = FR.Friction(N, FR.FrictionSpec(range=(0.3, 0.9), buckets=0, resample="reset"), mu=_mus(N), seed=seed, device=DEV)
+    fr.bind(sim)
+    for _ in range(12):
+        _tick(sim, ctl, cmd)
+    before = _snapshot(sim) + (fr.get_mu(), fr.contact_forces.cpu().numpy(), fr.foot_slip.cpu().numpy())
+    assert (np.abs(before[5]).max(axis=(1, 2)) > 0).sum() >= 100               # the robots stand on something
+    ids = np.full(N + 6, -1, np.int32)                                         # one entry per environment as the task's array, and a tail
+    listed = np.array([5, 63, 64, 129])                                        # both sides of the first wave boundary, and the last lane of the ragged wave
+    ids[listed] = listed
+    ids[7], ids[N + 2], ids[N + 4] = N, 1 << 20, -7                            # ids >= n and a negative one that is not -1
+    others = np.setdiff1d(np.arange(N), listed)
+    fr.draw(torch.from_numpy(ids).to(DEV))
+    after = _snapshot(sim) + (fr.get_mu(), fr.contact_forces.cpu().numpy(), fr.foot_slip.cpu().numpy())
+    for a, b, name in zip(before[:4], after[:4], ("f64", "i32", "dof_state", "root_states")):
+        assert np.array_equal(a, b), name                                      # the draw moves no robot
+    for a, b, name in zip(before[4:], after[4:], ("mu", "contact_forces", "foot_slip")):
+        assert np.array_equal(a[others], b[others]), name
+    assert after[4][listed].tobytes() == fref.draw_mu(seed, listed, 0, 0.3, 0.9, 0).astype(np.float64).tobytes()
+    assert not after[5][listed].any() and not after[6][listed].any()           # zero before the next step
+    assert np.array_equal(fr.get_counters(), np.isin(np.arange(N), listed).astype(np.uint32))
+    fr.draw(torch.from_numpy(ids).to(DEV), resample=False)                     # zeroes the rows, draws nothing
+    assert np.array_equal(fr.get_mu(), after[4]) and fr.get_counters().sum() == 4
+    # a fallen robot is frozen and its rows are written as zeros
+    st = sim.get_state()
+    fallen = [3, 64]
+    st["i32"][fallen, 8] = 1
+    sim.set_state(st)
+    fr.contact_forces.fill_(7.0)
+    fr.foot_slip.fill_(7.0)
+    _tick(sim, ctl, cmd)
+    force, slip, now = fr.contact_forces.cpu().numpy(), fr.foot_slip.cpu().numpy(), sim.get_state()
+    assert not force[fallen].any() and not slip[fallen].any() and np.array_equal(now["f64"][fallen], st["f64"][fallen])
+    assert (force != 7.0).all() and (slip != 7.0).all()                       # every row was written
+
+
+# ---- 10. the draws ------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("buckets", (0, 64))
+def test_device_draws_equal_the_restatement_and_round_trip(buckets):
+    seed, lo, hi = 2 ** 63 + 11, 0.5, 1.25
+    sim = _sim("plane")
+    fr = FR.Friction(N, FR.FrictionSpec(range=(lo, hi), buckets=buckets, resample="reset"), seed=seed, device=DEV)
+    fr.bind(sim)
+    assert np.isinf(fr.get_mu()).all() and not fr.get_counters().any()
+    env = np.arange(N)
+    for e in range(3):
+        fr.draw()
+        assert fr.get_mu().tobytes() == fref.draw_mu(seed, env, e, lo, hi, buckets).astype(np.float64).tobytes() and (fr.get_counters() == e + 1).all()
+    state = fr.state_dict()
+    other = FR.Friction(N, FR.FrictionSpec(range=(lo, hi), buckets=buckets, resample="reset"), seed=seed, device=DEV)
+    other.bind(_sim("plane"))
+    other.load_state_dict(state)
+    assert np.array_equal(other.get_mu(), fr.get_mu()) and np.array_equal(other.get_counters(), fr.get_counters())
+    other.draw()
+    assert other.get_mu().tobytes() == fref.draw_mu(seed, env, 3, lo, hi, buckets).astype(np.float64).tobytes()      # and goes on from the counters
+    with pytest.raises(Exception, match="already"):
+        FR.Friction(N, device=DEV).bind(sim)
+    with pytest.raises(Exception, match="negative or NaN"):
+        fr.set_mu(np.where(env == 9, -0.5, 0.4))
+
+
+# ---- 11. end to end -------------------------------------------------------------------------------------------------------------------------------------------
+def _task(n, friction=True, seed=11, episode_length_s=0.2):
+    cfg = _cfg(episode_length_s=episode_length_s, seed=5)
+    fr = FR.Friction(n, FR.FrictionSpec(range=(0.3, 1.25), resample="reset"), seed=seed, device=DEV) if friction else None
+    return R.BatchedRLTask(_robots(n), [TROT] * n, cfg=cfg, device=DEV, yaw0=_yaw(n), friction=fr)
+
+
+def test_task_runs_100_ticks_without_a_host_synchronisation_and_draws_at_resets():
+    import torch
+    seed = 11
+    task = _task(N, seed=seed)
+    fr = task.friction
+    assert task.cfg.max_episode_length == 20 and np.isinf(fr.get_mu()).all()  # resample="reset": nothing is drawn before the first tick
+    actions = torch.zeros((N, 12), dtype=torch.float32, device=DEV)
+    task.step(actions)                                                         # (the first tick resets, and so draws, every environment)
+    assert fr.get_mu().tobytes() == fref.draw_mu(seed, np.arange(N), 0, 0.3, 1.25, 64).astype(np.float64).tobytes()
+    assert not fr.contact_forces.any().item() and not fr.foot_slip.any().item()          # reset after the step: the rows are zero
+    slipped = torch.zeros((), dtype=torch.float32, device=DEV)
+    pushed = torch.zeros((), dtype=torch.float32, device=DEV)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")            # a torch call that waits for the device or copies to the host raises from here on
+    try:
+        for _ in range(99):
+            task.step(actions)
+            slipped += fr.foot_slip.sum()
+            pushed += fr.contact_forces[..., 2].sum()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    counters = fr.get_counters()
+    assert counters.min() >= 4 and fr.launches == 100                          # the first tick's reset and a time-out every 20 ticks
+    assert fr.get_mu().tobytes() == fref.draw_mu(seed, np.arange(N), counters - 1, 0.3, 1.25, 64).astype(np.float64).tobytes()
+    assert slipped.item() > 0 and pushed.item() > 0
+
+
+def test_the_marks_of_a_tick_are_the_same_with_and_without_the_option():
+    import torch
+    n = 8
+    marks = []
+    for friction in (False, True):
+        task = _task(n, friction=friction)
+        seen = []
+        for _ in range(3):
+            task.step(torch.zeros((n, 12), dtype=torch.float32, device=DEV), mark=seen.append)
+        marks.append(seen)
+    assert marks[0] == marks[1] == [s for s in R.STAGES if s in ("actions", "controller", "plant", "begin", "resets", "finish")] * 3
+
+
+@pytest.mark.parametrize("update", ("torch", "hip"))
+def test_trainer_learns_and_checkpoints_the_friction(update, tmp_path):
+    import torch
+    from rl_mpc_locomotion_amd import ppo as P
+    pcfg = lambda: P.PPOConfig(num_steps_per_env=4, num_learning_epochs=1, num_mini_batches=2, actor_hidden_dims=(64, 32), critic_hidden_dims=(32,),
+                               init_noise_std=0.5)
+    n = 64
+    task = _task(n, seed=21, episode_length_s=0.05)
+    trainer = P.PPOTrainer(task, pcfg(), seed=3, update=update)
+    infos = trainer.learn(1)
+    assert np.isfinite(np.asarray([v for v in infos[0].values() if not isinstance(v, dict)], dtype=np.float64)).all()
+    path = str(tmp_path / "ck.pt")
+    trainer.save(path)
+    mu, counters = task.friction.get_mu(), task.friction.get_counters()
+    assert counters.min() >= 1 and len(np.unique(mu)) > 10
+    ck = torch.load(path)
+    assert np.array_equal(ck["friction_state_dict"]["mu"].cpu().numpy(), mu)
+    fresh_task = _task(n, seed=21, episode_length_s=0.05)
+    fresh = P.PPOTrainer(fresh_task, pcfg(), seed=4, update=update)
+    assert not fresh_task.friction.get_counters().any()
+    fresh.load(path)
+    assert np.array_equal(fresh_task.friction.get_mu(), mu) and np.array_equal(fresh_task.friction.get_counters(), counters)
+    # refused before anything is loaded: a trainer without the option, and a trainer with it given a checkpoint that lacks it
+    bare = P.PPOTrainer(_task(n, friction=False, episode_length_s=0.05), pcfg(), seed=4, update=update)
+    weights = [p.detach().clone() for p in bare.actor_critic.parameters()]
+    with pytest.raises(ValueError, match="written with friction"):
+        bare.load(path)
+    assert all(torch.equal(a, b) for a, b in zip(weights, bare.actor_critic.parameters())) and bare.iteration == 0
+    del ck["friction_state_dict"]
+    torch.save(ck, path)
+    other_task = _task(n, seed=21, episode_length_s=0.05)
+    other = P.PPOTrainer(other_task, pcfg(), seed=4, update=update)
+    weights = [p.detach().clone() for p in other.actor_critic.parameters()]
+    with pytest.raises(ValueError, match="carries no friction_state_dict"):
+        other.load(path)
+    assert all(torch.equal(a, b) for a, b in zip(weights, other.actor_critic.parameters())) and np.isinf(other_task.friction.get_mu()).all()

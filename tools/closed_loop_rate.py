@@ -9,6 +9,10 @@ uniform terrain, the same generator with 1 cm steps, or an all-zero field: the p
 (flat_ground=False), and the report gains, per terrain and beside the same legs on the plane, the loop rate, the fallen fraction and the
 plant's step on the plane and on the terrain measured alternately, repeat by repeat, in one process (HIP events: median, p10, p90).
     python tools/closed_loop_rate.py --terrain reference mild --out profiles/r11_toy_terrain.json
+With --friction MU [MU ...] (inf is a value) the plant gets a Coulomb friction record (rl_mpc_locomotion_amd.friction): the friction step at mu = inf
+and at each MU is measured against the plain step kernel in the same run, the closed loops alternating block by block (tools/_rate.py's spread of
+the HIP-event spans around mpc_sim_step), and per MU the fallen share and the mean slip per foot and tick after --ticks ticks are reported.
+    python tools/closed_loop_rate.py --friction inf 0.4 --out profiles/friction_rate.json
 The kernel-trace stats of the same loop: rocprofv3 --kernel-trace --stats ... -- python tools/closed_loop_rate.py --ticks 50 --quick"""
 import argparse
 import json
@@ -78,6 +82,66 @@ def step_ab(robot_type, dev, terrain, origin, repeats=10, block=50):
     return out
 
 
+def friction_ab(robot_type, dev, mus, ticks, repeats=10, block=50):
+    """The plant's step without friction and with a friction record at each of `mus`, alternating block by block in one process: one closed loop a
+    side (each sim with its own controller), `block` ticks of one, then of the next, HIP events around mpc_sim_step alone.  Robots that have fallen
+    are frozen and cost nothing, so every side reports its fallen share with its time, and the ratio of the first repeat -- before a slippery floor
+    has had the time to fell anybody -- stands beside the ratio of the medians.  Then, per mu, a fresh closed loop of `ticks` ticks: the fallen
+    share and the mean slip per foot and tick."""
+    from rl_mpc_locomotion_amd.friction import Friction
+    import _rate                       # (tools/ is the script's directory)
+    n = len(robot_type)
+    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
+    cmd = torch.tensor(GOLDEN_TROT_CMD, dtype=torch.float32, device=dev).repeat(n, 1).contiguous()
+
+    def side(mu):
+        sim = BatchedToySim(robot_type, yaw0=yaw, device=dev)
+        fr = None
+        if mu is not None:
+            fr = Friction(n, mu=mu, device=dev)
+            fr.bind(sim)
+        return sim, BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=True, device=dev), sim.dof_state.view(n, 12, 2), fr
+    name_of = lambda mu: "plain" if mu is None else "mu_" + repr(float(mu))
+    sides = {name_of(mu): side(mu) + ([],) for mu in [None] + list(mus)}
+    for sim, ctl, view, _, _ in sides.values():
+        for _ in range(10):
+            sim.step(ctl.run(view, sim.root_states, cmd))
+    for _ in range(repeats):
+        for sim, ctl, view, _, ms in sides.values():
+            ev = [(_rate.ev(), _rate.ev()) for _ in range(block)]
+            for a, b in ev:
+                tau = ctl.run(view, sim.root_states, cmd)
+                a.record(); sim.step(tau); b.record()
+            torch.cuda.synchronize()
+            ms.append([a.elapsed_time(b) for a, b in ev])
+    out = {"repeats": repeats, "ticks_per_repeat": block, "robots": n, "step": {}}
+    for name, (sim, _, _, _, ms) in sides.items():
+        m = np.array(ms)
+        out["step"][name] = {**_rate.spread(m), "median_ms_per_repeat": [float(x) for x in np.median(m, 1)],
+                             "fallen_fraction_at_end": float(sim.flags()[1].float().mean().item())}
+    plain = out["step"]["plain"]
+    for name, rec in out["step"].items():
+        if name != "plain":
+            rec["over_plain_median"] = rec["median_ms"] / plain["median_ms"]
+            rec["over_plain_first_repeat"] = rec["median_ms_per_repeat"][0] / plain["median_ms_per_repeat"][0]
+    del sides
+    out["closed_loop"] = {"ticks": ticks}
+    for mu in mus:
+        sim, ctl, view, fr = side(mu)
+        slip = torch.zeros((), dtype=torch.float64, device=dev)
+        slipping = torch.zeros((), dtype=torch.float64, device=dev)
+        for _ in range(ticks):
+            sim.step(ctl.run(view, sim.root_states, cmd))
+            slip += fr.foot_slip.sum()
+            slipping += (fr.foot_slip > 0).any(1).sum()
+        fell = sim.flags()[1].cpu().numpy()
+        rt = np.asarray(robot_type)
+        out["closed_loop"][name_of(mu)] = {"fallen_fraction": float(fell.mean()), "fallen_fraction_per_robot_type": {int(t): float(fell[rt == t].mean()) for t in np.unique(rt)},
+                                           "mean_slip_m_per_foot_tick": float(slip.item()) / (4 * n * ticks),
+                                           "robot_ticks_with_a_slip_fraction": float(slipping.item()) / (n * ticks)}
+    return out
+
+
 def run(robot_type, ticks, dev, default_weights=False, terrain=None, origin=None, flat_ground=True):
     n = len(robot_type)
     yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
@@ -125,11 +189,24 @@ if __name__ == "__main__":
     ap.add_argument("--terrain", nargs="+", choices=["none", "reference", "mild", "zero"], default=["none"],
                     help="height fields to run on beside the plane (the controller then runs with flat_ground=False)")
     ap.add_argument("--terrain-seed", type=int, default=0)
+    ap.add_argument("--friction", nargs="+", type=float, metavar="MU",
+                    help="friction coefficients (inf is one): the friction step against the plain one, and the fallen share and slip per MU; nothing else is run")
     ap.add_argument("--out")
     args = ap.parse_args()
     dev = "cuda:0"
     n = args.robots
     res = {"kernel_source_sha256": _lib.kernel_source_hash()}
+    if args.friction:
+        if any(not mu >= 0 for mu in args.friction):
+            ap.error("--friction: every MU must be >= 0")
+        res["device_state"] = {"before": device_state(0)}
+        res["friction_mixed_types"] = friction_ab([i % 3 for i in range(n)], dev, args.friction, args.ticks)
+        res["device_state"]["after"] = device_state(0, smi=False)
+        print(json.dumps(res, indent=1))
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        sys.exit(0)
     clock0 = None if args.quick else device_state(0)
     mixed = [i % 3 for i in range(n)]
     legs = {"mixed_types": (mixed, False)} if args.quick else {"aliengo": ([0] * n, False), "mixed_types": (mixed, False), "mixed_types_default_weights": (mixed, True)}
