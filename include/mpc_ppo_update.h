@@ -7,6 +7,9 @@
  *                          tensors, the four loss terms, and the adaptive schedule's decision applied to a float64 learning rate on the device
  *   mpc_ppo_update_apply   the total gradient norm, clip_grad_norm_'s coefficient and torch.optim.Adam's step over all parameter tensors, the
  *                          learning rate read from the device
+ *   mpc_ppo_update_grads_sequence   the same for a recurrent actor-critic, whose nets read dense rows that two memories wrote: it also writes
+ *                          d loss / d rows for the memories' backward pass, and mpc_ppo_update_bind_extra puts the memories' parameters behind the
+ *                          mpc_ac's in mpc_ppo_update_apply (the end of this file)
  *
  * The GEMMs run on the exact-fp32 MFMA pipe (rl-mpc-locomotion_amd/csrc/ppo_gemm.h); the scalar arithmetic is csrc/ppo_update.h, float32 in
  * rsl_rl's and torch's operation order.  Every sum over rows or elements is taken in a fixed order: a rerun is bit-identical.
@@ -36,6 +39,12 @@ void mpc_ppo_update_destroy(mpc_ppo_update *u);
 /* Number of parameter tensors: 2 (actor layers + critic layers) + 1, in mpc_ac_bind's order: actor weights, actor biases, critic weights, critic
  * biases, std.  -1 for a null handle. */
 int mpc_ppo_update_tensors(const mpc_ppo_update *u);
+/* Bytes of device memory the handle owns: the workspace of mpc_ppo_update_create and the norm's partials of mpc_ppo_update_bind_extra.  -1 for a null
+ * handle. */
+long long mpc_ppo_update_workspace_bytes(const mpc_ppo_update *u);
+/* For tests: *d_out = the workspace's d loss / d (output of `layer` of net 0 = actor, 1 = critic) as the last grads call left it, [rows][*ld] floats (the
+ * last layer's 12 or 1 columns in a row of 16), valid while the handle lives.  No device call. */
+int mpc_ppo_update_layer_gradient(const mpc_ppo_update *u, int net, int layer, float **d_out, int *ld);
 /* The gradient tensors and Adam's moments (exp_avg, exp_avg_sq), each a host array of mpc_ppo_update_tensors() DEVICE pointers in that order, shaped
  * like their parameters, non-null and 16-byte aligned.  Kept, not copied.  d_exp_avg and d_exp_avg_sq may both be NULL: mpc_ppo_update_apply then
  * refuses. */
@@ -56,6 +65,27 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
 /* clip_grad_norm_(max_norm) over the bound gradients (they are scaled in place, as torch scales them), then Adam's step number `step` (>= 1, the
  * host's count) with the learning rate *d_lr. */
 int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, double beta2, double eps, int step, const double *d_lr, void *stream);
+
+/* ---- a recurrent actor-critic: the mpc_ac's nets read the outputs of two memories (csrc/mpc_recurrent_bptt.h), whose parameters are updated with them */
+enum { MPC_PPO_UPDATE_MAX_EXTRA = 8 };
+/* The dense rows [max_rows][actor_dims[0]] and [max_rows][critic_dims[0]] that the two first layers read in mpc_ppo_update_grads_sequence, and the
+ * buffers of the same shapes that receive d loss / d rows.  Kept by pointer, 16-byte aligned; the two gradient buffers overlap neither each other nor
+ * the rows.  Four NULLs clear them. */
+int mpc_ppo_update_set_sequence_rows(mpc_ppo_update *u, const float *d_rows_actor, const float *d_rows_critic, float *d_drows_actor,
+                                     float *d_drows_critic);
+/* mpc_ppo_update_grads for one mini-batch of dense rows: row r of the buffers above goes with storage row d_idx[r].  Layer 0 of both nets reads the
+ * dense rows, forward and in its weight gradient, with no index; the loss head reads the storage through d_idx; after layer 0's weight gradient one
+ * more launch writes d rows_k = dY_0 W_0 (no activation factor) into rows 0 .. rows of the gradient buffers.  Means are over `rows`.  The storage's
+ * d_obs and the critic's storage are not read.  The other arguments, outputs and launches are mpc_ppo_update_grads'. */
+int mpc_ppo_update_grads_sequence(mpc_ppo_update *u, int rows, const long long *d_idx, double clip_param, double value_loss_coef, double entropy_coef,
+                                  int use_clipped_value_loss, int adaptive, double desired_kl, double *d_lr, float *d_terms, void *stream);
+/* count (0 .. MPC_PPO_UPDATE_MAX_EXTRA) more parameter tensors of numel[t] floats each, with their gradients and Adam's moments (host arrays of DEVICE
+ * pointers, non-null and 16-byte aligned, kept; both moment arrays may be NULL: mpc_ppo_update_apply then refuses), which mpc_ppo_update_apply takes
+ * into the total norm, the clip and Adam's step after the mpc_ac's tensors, in the order given.  After mpc_ppo_update_bind.  count = 0 clears them, and
+ * apply is then what it is without this call, bit for bit.  Allocates the norm's partials for the longer list (the one device call, after every
+ * refusal). */
+int mpc_ppo_update_bind_extra(mpc_ppo_update *u, int count, float *const *d_params, float *const *d_grads, float *const *d_exp_avg,
+                              float *const *d_exp_avg_sq, const int *numel);
 
 #ifdef __cplusplus
 }

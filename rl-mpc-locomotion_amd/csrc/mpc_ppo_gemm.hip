@@ -1,6 +1,6 @@
 // mpc_ppo_gemm.hip -- the one owner of ppo_gemm.h's kernels in the library: an internal unit with no C ABI.  mpc_ppo_update.hip and
 // mpc_recurrent_bptt.hip fill ppo_gemm_plan.h's structs and call pgemm::launch (the plan's tile, chunking and grid filled into the launch, then
-// gemm_kernel<KIND, 2, 2> or <KIND, 2, 1>) and pgemm::reduce (reduce_kernel).  Both only enqueue; the caller asks hipGetLastError in its own words.
+// gemm_kernel<KIND, 2, 2> or <KIND, 2, 1>; KIND one of ppo_gemm_plan.h's four) and pgemm::reduce (reduce_kernel).  Both only enqueue; the caller asks hipGetLastError in its own words.
 #include <hip/hip_runtime.h>
 
 #include "ppo_gemm.h"
@@ -27,6 +27,7 @@ void launch(Kind kind, Launch &L, void *stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (kind == kForward) start<kForward>(plan, L, s);
   else if (kind == kBackwardData) start<kBackwardData>(plan, L, s);
+  else if (kind == kBackwardDataLinear) start<kBackwardDataLinear>(plan, L, s);
   else start<kBackwardWeight>(plan, L, s);
 }
 

@@ -7,6 +7,9 @@
 //   norm_partial_kernel  the sum of squares of every gradient element in float64, one partial per 4096 elements of a tensor (fixed-order LDS tree), and
 //   norm_kernel          ONE workgroup joins the partials in a fixed order, as normalise_kernel of mpc_ppo.hip does
 //   adam_kernel          every parameter tensor in one launch (blockIdx.y picks the tensor): ppo::adam_element
+// mpc_ppo_update_grads_sequence is the same sequence on dense first-layer rows (the outputs of a recurrent actor-critic's memories) plus one
+// pgemm::kBackwardDataLinear launch through layer 0 into the rows' gradients; mpc_ppo_update_bind_extra puts up to eight more tensors (the memories'
+// parameters) behind the mpc_ac's in the norm, the clip and Adam.
 // No atomics anywhere, so a rerun is bit-identical; nothing synchronises.
 #include <hip/hip_runtime.h>
 
@@ -32,7 +35,8 @@ constexpr int kHeadQ = 3 + ppo::kActions;      // surrogate, value loss, kl, d s
 constexpr int kHeadStride = 16;                // doubles per workgroup partial
 constexpr int kOutLd = 16;                     // leading dimension of the last layer's output (12 or 1 columns) in the workspace
 constexpr int kNormThreads = 1024;
-constexpr int kMaxTensors = 4 * MPC_AC_MAX_LAYERS + 1;
+constexpr int kMaxExtra = MPC_PPO_UPDATE_MAX_EXTRA;      // tensors of mpc_ppo_update_bind_extra
+constexpr int kMaxTensors = 4 * MPC_AC_MAX_LAYERS + 1 + kMaxExtra;
 
 struct Storage {
   const float *obs, *actions, *values, *adv, *returns, *log_prob, *mu, *sigma;
@@ -193,6 +197,7 @@ struct mpc_ppo_update {
   int dims[2][MPC_AC_MAX_LAYERS + 1] = {};
   int n_tensors = 0;
   mpchost::DeviceArray<float> ws;               // one allocation; the pointers below, down to `norm`, point into it
+  size_t ws_words = 0;
   float *Y[2][MPC_AC_MAX_LAYERS] = {};          // [rows][ld(k, l)] activations after layer l
   float *dY[2][MPC_AC_MAX_LAYERS] = {};         // their gradients
   float *dWp[2][MPC_AC_MAX_LAYERS] = {};        // [chunks][out][in]
@@ -205,6 +210,16 @@ struct mpc_ppo_update {
   bool grads_bound = false, moments_bound = false, storage_set = false;
   Storage st{};
   const float *critic_obs = nullptr;            // [total_rows][dims[kCritic][0]] (mpc_ppo_update_set_critic_storage), or null: the critic reads st.obs
+  const float *seq_rows[2] = {};                // mpc_ppo_update_set_sequence_rows: dense [max_rows][dims[k][0]] inputs of the two first layers ...
+  float *seq_drows[2] = {};                     // ... and what receives d loss / d rows
+  bool sequence_set = false;
+  int n_extra = 0;                              // mpc_ppo_update_bind_extra: tensors n_tensors .. n_tensors + n_extra of the norm, the clip and Adam
+  float *extra_param[kMaxExtra] = {};
+  int extra_numel[kMaxExtra] = {};
+  bool extra_moments = false;
+  mpchost::DeviceArray<double> extra_partials;  // [n_tensors + n_extra][blocks over all of them]: the norm's partials while extras are bound
+  size_t extra_capacity = 0;
+  int extra_blocks = 0;
 
   // the rows layer 0 of net k reads through the index
   const float *rows0(int k) const { return k == kCritic && critic_obs ? critic_obs : st.obs; }
@@ -213,6 +228,7 @@ struct mpc_ppo_update {
   int w_index(int k, int l) const { return (k == kActor ? 0 : 2 * nl[0]) + l; }
   int b_index(int k, int l) const { return (k == kActor ? nl[0] : 2 * nl[0] + nl[1]) + l; }
   int numel(int t) const {
+    if (t >= n_tensors) return t < n_tensors + n_extra ? extra_numel[t - n_tensors] : 0;
     if (t == n_tensors - 1) return ppo::kActions;
     for (int k = 0; k < 2; ++k)
       for (int l = 0; l < nl[k]; ++l) {
@@ -228,6 +244,16 @@ extern "C" {
 void mpc_ppo_update_destroy(mpc_ppo_update *u) { mpchost::destroy_handle(u); }
 
 int mpc_ppo_update_tensors(const mpc_ppo_update *u) { return u ? u->n_tensors : -1; }
+
+int mpc_ppo_update_layer_gradient(const mpc_ppo_update *u, int net, int layer, float **d_out, int *ld) {
+  if (!u || !d_out || !ld) return fail(MPC_E_ARG, "mpc_ppo_update_layer_gradient: bad argument");
+  if (net < 0 || net > 1 || layer < 0 || layer >= u->nl[net]) return fail(MPC_E_ARG, "mpc_ppo_update_layer_gradient: no such net or layer");
+  *d_out = u->dY[net][layer];
+  *ld = u->ld(net, layer);
+  return MPC_OK;
+}
+
+long long mpc_ppo_update_workspace_bytes(const mpc_ppo_update *u) { return u ? (long long)(4 * u->ws_words + 8 * u->extra_capacity) : -1; }
 
 int mpc_ppo_update_create(mpc_ppo_update **out, mpc_ac *ac, int max_rows) {
   mpc_ac_view v;
@@ -257,6 +283,7 @@ int mpc_ppo_update_create(mpc_ppo_update **out, mpc_ac *ac, int max_rows) {
     delete u;
     return fail(MPC_E_HIP, "mpc_ppo_update_create: the workspace could not be allocated");
   }
+  u->ws_words = words;
   float *w = u->ws;
   u->partials = reinterpret_cast<double *>(w); w += 2 * (size_t)u->head_blocks_max * kHeadStride;
   u->norm_partials = reinterpret_cast<double *>(w); w += 2 * (size_t)round16(u->n_tensors * u->norm_blocks);
@@ -306,20 +333,26 @@ int mpc_ppo_update_set_critic_storage(mpc_ppo_update *u, const float *d_critic_o
   return MPC_OK;
 }
 
-int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, double clip_param, double value_loss_coef, double entropy_coef,
-                         int use_clipped_value_loss, int adaptive, double desired_kl, double *d_lr, float *d_terms, void *stream) {
-  if (!u || !d_idx || !d_terms) return fail(MPC_E_ARG, "mpc_ppo_update_grads: bad argument");
-  if (rows <= 0 || rows > u->max_rows) return fail(MPC_E_ARG, "mpc_ppo_update_grads: rows must lie in 1 .. max_rows");
+}  // extern "C"
+
+namespace {
+// mpc_ppo_update_grads (sequence = false: layer 0 reads the storage's rows through d_idx) and mpc_ppo_update_grads_sequence (true: layer 0 reads the
+// dense rows of mpc_ppo_update_set_sequence_rows, and one more launch takes dY_0 W_0 into their gradients); `name` heads the refusals
+int grads(const char *name, bool sequence, mpc_ppo_update *u, int rows, const long long *d_idx, double clip_param, double value_loss_coef,
+          double entropy_coef, int use_clipped_value_loss, int adaptive, double desired_kl, double *d_lr, float *d_terms, void *stream) {
+  if (!u || !d_idx || !d_terms) return fail(MPC_E_ARG, std::string(name) + ": bad argument");
+  if (rows <= 0 || rows > u->max_rows) return fail(MPC_E_ARG, std::string(name) + ": rows must lie in 1 .. max_rows");
   if (!std::isfinite(clip_param) || clip_param <= 0.0 || !std::isfinite(value_loss_coef) || !std::isfinite(entropy_coef))
-    return fail(MPC_E_ARG, "mpc_ppo_update_grads: clip_param must be positive and the coefficients finite");
+    return fail(MPC_E_ARG, std::string(name) + ": clip_param must be positive and the coefficients finite");
   if (adaptive && (!d_lr || !(desired_kl > 0.0) || !std::isfinite(desired_kl)))
-    return fail(MPC_E_ARG, "mpc_ppo_update_grads: the adaptive schedule needs d_lr and a positive desired_kl");
-  if (!u->grads_bound) return fail(MPC_E_ARG, "mpc_ppo_update_grads: no gradients bound (mpc_ppo_update_bind)");
-  if (!u->storage_set) return fail(MPC_E_ARG, "mpc_ppo_update_grads: no storage set (mpc_ppo_update_set_storage)");
+    return fail(MPC_E_ARG, std::string(name) + ": the adaptive schedule needs d_lr and a positive desired_kl");
+  if (!u->grads_bound) return fail(MPC_E_ARG, std::string(name) + ": no gradients bound (mpc_ppo_update_bind)");
+  if (!u->storage_set) return fail(MPC_E_ARG, std::string(name) + ": no storage set (mpc_ppo_update_set_storage)");
+  if (sequence && !u->sequence_set) return fail(MPC_E_ARG, std::string(name) + ": no dense rows set (mpc_ppo_update_set_sequence_rows)");
   mpc_ac_view v;
-  if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return fail(MPC_E_ARG, "mpc_ppo_update_grads: the mpc_ac has no parameters bound");
-  if (v.asymmetric && !u->critic_obs)
-    return fail(MPC_E_ARG, "mpc_ppo_update_grads: an asymmetric mpc_ac needs the critic's rows (mpc_ppo_update_set_critic_storage)");
+  if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return fail(MPC_E_ARG, std::string(name) + ": the mpc_ac has no parameters bound");
+  if (!sequence && v.asymmetric && !u->critic_obs)
+    return fail(MPC_E_ARG, std::string(name) + ": an asymmetric mpc_ac needs the critic's rows (mpc_ppo_update_set_critic_storage)");
   DeviceGuard guard_(u->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int maxl = u->nl[0] > u->nl[1] ? u->nl[0] : u->nl[1];
@@ -331,8 +364,8 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
     for (int k = 0; k < 2; ++k) {
       if (l >= u->nl[k]) continue;
       pgemm::Problem &p = L.p[k];
-      p.A = l == 0 ? u->rows0(k) : u->Y[k][l - 1];
-      p.idx = l == 0 ? d_idx : nullptr;
+      p.A = l == 0 ? (sequence ? u->seq_rows[k] : u->rows0(k)) : u->Y[k][l - 1];
+      p.idx = l == 0 && !sequence ? d_idx : nullptr;
       p.idx_limit = u->st.total_rows;
       p.B = v.w[k][l];
       p.C = u->Y[k][l];
@@ -366,9 +399,9 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
       const int nout = u->dims[k][l + 1], nin = u->dims[k][l];
       pgemm::Problem &p = W.p[k];
       p.A = u->dY[k][l]; p.lda = u->ld(k, l);
-      p.B = l == 0 ? u->rows0(k) : u->Y[k][l - 1];
+      p.B = l == 0 ? (sequence ? u->seq_rows[k] : u->rows0(k)) : u->Y[k][l - 1];
       p.ldb = l == 0 ? nin : u->ld(k, l - 1);
-      p.idx = l == 0 ? d_idx : nullptr;
+      p.idx = l == 0 && !sequence ? d_idx : nullptr;
       p.idx_limit = u->st.total_rows;
       p.C = u->dWp[k][l]; p.ldc = nin;
       p.dbias = u->dbp[k][l];
@@ -388,6 +421,18 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
       if (u->nl[k] - 1 - sidx >= 0) dw_chunks[k][u->nl[k] - 1 - sidx] = W.p[k].chunks;
     if (int rc = launch_gemm(pgemm::kBackwardData, D, s)) return rc;
   }
+  if (sequence) {                        // through layer 0 into the rows' gradients: d rows = dY_0 W_0, no activation in front of these rows
+    pgemm::Launch D{};
+    for (int k = 0; k < 2; ++k) {
+      pgemm::Problem &q = D.p[k];
+      q.A = u->dY[k][0]; q.lda = u->ld(k, 0);
+      q.B = v.w[k][0]; q.ldb = u->dims[k][0];
+      q.C = u->seq_drows[k]; q.ldc = u->dims[k][0];
+      q.M = rows; q.N = u->dims[k][0]; q.K = u->dims[k][1];
+      q.chunks = 1;
+    }
+    if (int rc = launch_gemm(pgemm::kBackwardDataLinear, D, s)) return rc;
+  }
 
   // the chunks in index order into .grad
   pgemm::ReduceTable rt{};
@@ -404,12 +449,98 @@ int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, do
   return MPC_OK;
 }
 
+// [a, a + n) and [b, b + m) floats share an address
+bool overlap(const float *a, size_t n, const float *b, size_t m) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + 4 * m && b0 < a0 + 4 * n;
+}
+}  // namespace
+
+extern "C" {
+
+int mpc_ppo_update_grads(mpc_ppo_update *u, int rows, const long long *d_idx, double clip_param, double value_loss_coef, double entropy_coef,
+                         int use_clipped_value_loss, int adaptive, double desired_kl, double *d_lr, float *d_terms, void *stream) {
+  return grads("mpc_ppo_update_grads", false, u, rows, d_idx, clip_param, value_loss_coef, entropy_coef, use_clipped_value_loss, adaptive, desired_kl, d_lr,
+               d_terms, stream);
+}
+
+int mpc_ppo_update_grads_sequence(mpc_ppo_update *u, int rows, const long long *d_idx, double clip_param, double value_loss_coef, double entropy_coef,
+                                  int use_clipped_value_loss, int adaptive, double desired_kl, double *d_lr, float *d_terms, void *stream) {
+  return grads("mpc_ppo_update_grads_sequence", true, u, rows, d_idx, clip_param, value_loss_coef, entropy_coef, use_clipped_value_loss, adaptive,
+               desired_kl, d_lr, d_terms, stream);
+}
+
+int mpc_ppo_update_set_sequence_rows(mpc_ppo_update *u, const float *d_rows_actor, const float *d_rows_critic, float *d_drows_actor,
+                                     float *d_drows_critic) {
+  const void *all[4] = {d_rows_actor, d_rows_critic, d_drows_actor, d_drows_critic};
+  int given = 0;
+  for (const void *p : all) given += p != nullptr;
+  if (given != 0 && given != 4) return fail(MPC_E_ARG, "mpc_ppo_update_set_sequence_rows: all four buffers, or four NULLs to clear them");
+  for (const void *p : all)
+    if (!mpchost::aligned16(p)) return fail(MPC_E_ARG, "mpc_ppo_update_set_sequence_rows: every buffer must be 16-byte aligned");
+  if (given && (d_drows_actor == d_drows_critic || d_drows_actor == d_rows_actor || d_drows_actor == d_rows_critic || d_drows_critic == d_rows_actor ||
+                d_drows_critic == d_rows_critic))
+    return fail(MPC_E_ARG, "mpc_ppo_update_set_sequence_rows: the gradient buffers must not overlap each other or the rows");
+  if (!u) return fail(MPC_E_ARG, "mpc_ppo_update_set_sequence_rows: bad argument");
+  if (given) {
+    const size_t na = (size_t)u->max_rows * u->dims[kActor][0], nc = (size_t)u->max_rows * u->dims[kCritic][0];
+    if (overlap(d_drows_actor, na, d_drows_critic, nc) || overlap(d_drows_actor, na, d_rows_actor, na) || overlap(d_drows_actor, na, d_rows_critic, nc) ||
+        overlap(d_drows_critic, nc, d_rows_actor, na) || overlap(d_drows_critic, nc, d_rows_critic, nc))
+      return fail(MPC_E_ARG, "mpc_ppo_update_set_sequence_rows: the gradient buffers must not overlap each other or the rows");
+  }
+  u->seq_rows[kActor] = d_rows_actor; u->seq_rows[kCritic] = d_rows_critic;
+  u->seq_drows[kActor] = d_drows_actor; u->seq_drows[kCritic] = d_drows_critic;
+  u->sequence_set = given == 4;
+  return MPC_OK;
+}
+
+int mpc_ppo_update_bind_extra(mpc_ppo_update *u, int count, float *const *d_params, float *const *d_grads, float *const *d_exp_avg,
+                              float *const *d_exp_avg_sq, const int *numel) {
+  if (count < 0 || count > kMaxExtra) return fail(MPC_E_ARG, "mpc_ppo_update_bind_extra: count must lie in 0 .. 8");
+  if (count > 0 && (!d_params || !d_grads || !numel)) return fail(MPC_E_ARG, "mpc_ppo_update_bind_extra: bad argument");
+  if ((d_exp_avg == nullptr) != (d_exp_avg_sq == nullptr)) return fail(MPC_E_ARG, "mpc_ppo_update_bind_extra: both moments or neither");
+  for (int t = 0; t < count; ++t) {
+    if (numel[t] <= 0) return fail(MPC_E_ARG, "mpc_ppo_update_bind_extra: every tensor has at least one element");
+    if (!present16(d_params[t]) || !present16(d_grads[t]) || (d_exp_avg && (!present16(d_exp_avg[t]) || !present16(d_exp_avg_sq[t]))))
+      return fail(MPC_E_ARG, "mpc_ppo_update_bind_extra: every parameter, gradient and moment pointer must be non-null and 16-byte aligned");
+  }
+  if (!u) return fail(MPC_E_ARG, "mpc_ppo_update_bind_extra: bad argument");
+  if (count > 0 && !u->grads_bound) return fail(MPC_E_ARG, "mpc_ppo_update_bind_extra: bind the mpc_ac's tensors first (mpc_ppo_update_bind)");
+  if (count > 0) {                       // the norm's partials over all tensors: the one allocation, after every refusal
+    int maxn = 0;
+    for (int t = 0; t < u->n_tensors; ++t) maxn = u->numel(t) > maxn ? u->numel(t) : maxn;
+    for (int t = 0; t < count; ++t) maxn = numel[t] > maxn ? numel[t] : maxn;
+    const int blocks = (maxn + kNormPerBlock - 1) / kNormPerBlock;
+    const size_t need = (size_t)(u->n_tensors + count) * blocks;
+    if (u->extra_capacity < need) {
+      DeviceGuard guard_(u->device);
+      u->extra_capacity = 0;
+      u->n_extra = 0;                    // (alloc frees what was there: nothing stays bound to it if it fails)
+      if (u->extra_partials.alloc(need) != hipSuccess) return fail(MPC_E_HIP, "mpc_ppo_update_bind_extra: the norm's partials could not be allocated");
+      u->extra_capacity = need;
+    }
+    u->extra_blocks = blocks;
+  }
+  u->n_extra = count;
+  for (int t = 0; t < count; ++t) {
+    const int k = u->n_tensors + t;
+    u->extra_param[t] = d_params[t];
+    u->extra_numel[t] = numel[t];
+    u->grad[k] = d_grads[t];
+    u->exp_avg[k] = d_exp_avg ? d_exp_avg[t] : nullptr;
+    u->exp_avg_sq[k] = d_exp_avg ? d_exp_avg_sq[t] : nullptr;
+  }
+  u->extra_moments = count > 0 && d_exp_avg != nullptr;
+  return MPC_OK;
+}
+
 int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, double beta2, double eps, int step, const double *d_lr, void *stream) {
   if (!u || !d_lr) return fail(MPC_E_ARG, "mpc_ppo_update_apply: bad argument");
   if (!(max_norm > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !std::isfinite(eps))
     return fail(MPC_E_ARG, "mpc_ppo_update_apply: max_norm must be positive, the betas in [0, 1), eps not negative");
   if (step < 1) return fail(MPC_E_ARG, "mpc_ppo_update_apply: step counts from 1");
   if (!u->grads_bound || !u->moments_bound) return fail(MPC_E_ARG, "mpc_ppo_update_apply: no gradients and moments bound (mpc_ppo_update_bind)");
+  if (u->n_extra > 0 && !u->extra_moments) return fail(MPC_E_ARG, "mpc_ppo_update_apply: the extra tensors have no moments bound (mpc_ppo_update_bind_extra)");
   mpc_ac_view v;
   if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return fail(MPC_E_ARG, "mpc_ppo_update_apply: the mpc_ac has no parameters bound");
   DeviceGuard guard_(u->device);
@@ -417,7 +548,10 @@ int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, doubl
   NormTable nt{};
   AdamTable at{};
   int maxn = 0;
-  for (int t = 0; t < u->n_tensors; ++t) {
+  const int total = u->n_tensors + u->n_extra;                      // (no extras: today's tables, partials and grids)
+  const int blocks = u->n_extra > 0 ? u->extra_blocks : u->norm_blocks;
+  double *partials = u->n_extra > 0 ? static_cast<double *>(u->extra_partials) : u->norm_partials;
+  for (int t = 0; t < total; ++t) {
     nt.g[t] = u->grad[t];
     at.g[t] = u->grad[t]; at.m[t] = u->exp_avg[t]; at.v[t] = u->exp_avg_sq[t];
     nt.numel[t] = at.numel[t] = u->numel(t);
@@ -429,12 +563,13 @@ int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, doubl
       at.p[u->b_index(k, l)] = const_cast<float *>(v.b[k][l]);
     }
   at.p[u->n_tensors - 1] = const_cast<float *>(v.std);
-  hipLaunchKernelGGL(norm_partial_kernel, dim3((unsigned)u->norm_blocks, (unsigned)u->n_tensors), dim3(256), 0, s, nt, u->norm_partials);
+  for (int t = 0; t < u->n_extra; ++t) at.p[u->n_tensors + t] = u->extra_param[t];
+  hipLaunchKernelGGL(norm_partial_kernel, dim3((unsigned)blocks, (unsigned)total), dim3(256), 0, s, nt, partials);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(norm_kernel, dim3(1), dim3(kNormThreads), 0, s, u->n_tensors * u->norm_blocks, u->norm_partials, u->norm);
+  hipLaunchKernelGGL(norm_kernel, dim3(1), dim3(kNormThreads), 0, s, total * blocks, partials, u->norm);
   HIP_TRY(hipGetLastError());
   ppo::AdamCfg cfg{beta1, beta2, eps, 1.0 - std::pow(beta1, (double)step), std::pow(1.0 - std::pow(beta2, (double)step), 0.5)};
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((maxn + 255) / 256), (unsigned)u->n_tensors), dim3(256), 0, s, at, cfg, (float)max_norm, u->norm, d_lr);
+  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((maxn + 255) / 256), (unsigned)total), dim3(256), 0, s, at, cfg, (float)max_norm, u->norm, d_lr);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
 }

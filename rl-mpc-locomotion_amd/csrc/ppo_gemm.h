@@ -2,6 +2,8 @@
 // fp32 fma chain per output element, so a result differs from a CPU sgemm only by the summation order), one LDS-tiled kernel template:
 //   forward          Y  = ELU(X W^T + b)        X [rows][K] (layer 0: rows read through the mini-batch index), W [N][K]; Y is all the backward pass needs
 //   backward data    dX = (dY W) * ELU'(X)      ELU' from the stored activation: 1 for y > 0, y + 1 otherwise
+//   ... linear       dX = dY W                  the same loaders and products, no factor: the gradient of rows no activation produced (the outputs of the
+//                                               memories in front of a recurrent actor-critic's first layers)
 //   backward weight  dW = dY^T X                split over the rows into chunks of at most kChunk: chunk c writes its own [N][K] partial (and the column
 //                                               sums of its dY rows) to a workspace; reduce_kernel adds the chunks in index order.  No atomics.
 // A workgroup is 4 waves in a 2 x 2 arrangement, each wave owns TM x TN tiles of 32 x 32 (TM x TN independent accumulator chains), so the block tile is
@@ -90,6 +92,7 @@ __device__ __forceinline__ void store_mcontig(const float4 (&reg)[BT / 32], floa
 // grid (max over the problems of tiles_m tiles_n chunks, 2)
 template <int KIND, int TM, int TN>
 __global__ __launch_bounds__(kThreads) void gemm_kernel(Launch launch) {
+  static_assert(KIND >= kForward && KIND <= kBackwardDataLinear, "the loaders below know four kinds: kBackwardDataLinear takes backward data's by falling through their tests");
   constexpr int BM = 64 * TM, BN = 64 * TN, LDA = BM + kPad, LDB = BN + kPad;
   __shared__ __attribute__((aligned(16))) float As[kBK * LDA];
   __shared__ __attribute__((aligned(16))) float Bs[kBK * LDB];

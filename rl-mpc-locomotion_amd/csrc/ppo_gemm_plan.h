@@ -7,7 +7,7 @@
 
 namespace pgemm {
 
-enum Kind { kForward = 0, kBackwardData = 1, kBackwardWeight = 2 };
+enum Kind { kForward = 0, kBackwardData = 1, kBackwardWeight = 2, kBackwardDataLinear = 3 };      // (3: backward data with no activation factor; planned as 1)
 
 constexpr int kChunk = 1024;          // most rows per backward-weight chunk: the longest fp32 chain
 constexpr int kMinChunk = 256;        // fewest: a workspace holds ceil(max_rows / kMinChunk) partials per layer
@@ -66,7 +66,7 @@ inline Plan plan_gemm(int kind, const Shape (&shape)[2]) {
 struct Problem {
   const float *A, *B;                 // see ppo_gemm.h's loaders for each kind's layout
   float *C;                           // [M][ldc]; backward weight: [chunks][M][ldc]
-  const float *aux;                   // forward: bias [N]; backward data: the stored activation [M][ldaux]
+  const float *aux;                   // forward: bias [N]; backward data: the stored activation [M][ldaux]; backward data linear: not read
   const long long *idx;               // rows of X are idx[row] (forward: of A; backward weight: of B); null: the rows themselves
   float *dbias;                       // backward weight: [chunks][M] column sums of dY (null: none)
   long long idx_limit;                // idx values are clamped to [0, idx_limit)

@@ -24,7 +24,8 @@ with ``Normal.sample`` is in distribution only, and |eps| <= 5.768 (ppo_rollout.
 normalisation (rsl_rl 2.x's ``EmpiricalNormalization``; ``obs_norm.ObsNormalizer``), privileged critic observations (rsl_rl's ``num_critic_obs``; the
 reference uses none), recurrent policies (rsl_rl's ``ActorCriticRecurrent``: an LSTM in front of each MLP; ``recurrent.py``), the runner's episode
 statistics on the device (``episode.EpisodeStats``); ``PPOTrainer.evaluate`` is the reference's ``cfg.test`` loop.  Not built: GRU and stacked layers,
-a recurrent ``update="hip"``, logging beyond ``infos``.
+logging beyond ``infos``.  (A recurrent actor-critic's device update is ``RecurrentConfig(update_through_time="hip", update_heads="hip")``; a recurrent
+``update="hip"`` stays refused.)
 
 The device entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
 """
@@ -66,11 +67,16 @@ UPDATE_DECLS = {
     "mpc_ppo_update_create": (ci, [pvp, vp, ci]),
     "mpc_ppo_update_destroy": (None, [vp]),
     "mpc_ppo_update_tensors": (ci, [vp]),
+    "mpc_ppo_update_workspace_bytes": (ll, [vp]),
+    "mpc_ppo_update_layer_gradient": (ci, [vp, ci, ci, pvp, vp]),
     "mpc_ppo_update_bind": (ci, [vp, vp, vp, vp]),
     "mpc_ppo_update_set_storage": (ci, [vp, ll] + [vp] * 8),
     "mpc_ppo_update_set_critic_storage": (ci, [vp, vp]),
     "mpc_ppo_update_grads": (ci, [vp, ci, vp, cd, cd, cd, ci, ci, cd, vp, vp, vp]),
     "mpc_ppo_update_apply": (ci, [vp, cd, cd, cd, cd, ci, vp, vp]),
+    "mpc_ppo_update_set_sequence_rows": (ci, [vp, vp, vp, vp, vp]),
+    "mpc_ppo_update_grads_sequence": (ci, [vp, ci, vp, cd, cd, cd, ci, ci, cd, vp, vp, vp]),
+    "mpc_ppo_update_bind_extra": (ci, [vp, ci, vp, vp, vp, vp, vp]),
 }
 UPDATE_SYMBOLS = list(UPDATE_DECLS)
 update_lib = _lib.binder(UPDATE_DECLS, base=lib)   # ... with the entry points of the device update bound (and those of ``lib()``)
@@ -365,7 +371,11 @@ class PPO:
     """rsl_rl's ``PPO.update``.  ``backend="torch"`` (the default): plain torch (autograd + Adam) on whatever device the storage lives on.
     ``backend="hip"``: the device update of include/mpc_ppo_update.h on the same parameters, ``.grad`` tensors and optimiser state, with no host
     read: the learning rate of the adaptive schedule lives on the device (``lr_device``, float64) and ``learning_rate`` / the param groups' ``lr``
-    are what the caller last copied from it (``sync_learning_rate``; ``PPOTrainer.learn`` does it once per iteration)."""
+    are what the caller last copied from it (``sync_learning_rate``; ``PPOTrainer.learn`` does it once per iteration).
+
+    A recurrent actor-critic made with ``update_heads="hip"`` takes the device path under ``backend="torch"`` (``_update_recurrent_hip``): the same
+    handle over the MLPs, the memories' roll and backward pass around it, the memories' eight tensors behind the MLPs' in the clip and Adam.
+    ``device_update`` says whether the update runs on the device, whichever way it was asked for; the learning rate then lives there as above."""
 
     def __init__(self, actor_critic, cfg=None, backend="torch"):
         if backend not in ("torch", "hip"):
@@ -377,13 +387,15 @@ class PPO:
         self.cfg = cfg if cfg is not None else PPOConfig()
         self.actor_critic = actor_critic
         self.backend = backend
+        self.device_update = backend == "hip" or (self.recurrent and getattr(actor_critic, "update_heads", "torch") == "hip")
         self.learning_rate = float(self.cfg.learning_rate)
         self.optimizer = torch.optim.Adam(actor_critic.parameters(), lr=self.learning_rate)
         self.last_terms = None
         self._handle, self._max_rows, self._bound, self._storage_ptrs, self._ac_ptrs = None, 0, None, None, None
         self.lr_device, self.record_lr, self.lr_trace = None, False, None       # record_lr (for tests): keep the rate after every decision in lr_trace
-        if backend == "hip":
-            need_gpu('PPO(backend="hip")', actor_critic.std)
+        self._extra_bound, self._seq_rows, self._seq_ptrs, self._seq_store = None, None, None, None      # (the recurrent device update's: the memories' binding, the dense buffers)
+        if self.device_update:
+            need_gpu('PPO(backend="hip")' if backend == "hip" else 'PPO on update_heads="hip"', actor_critic.std)
             group = self.optimizer.param_groups[0]
             if group["amsgrad"] or group["weight_decay"] != 0 or group["maximize"]:
                 raise ValueError("the device update restates plain Adam: no amsgrad, weight decay or maximize")
@@ -448,15 +460,22 @@ class PPO:
         for group in self.optimizer.param_groups:
             group["lr"] = self.learning_rate
 
-    def _device_state(self, rows):
+    def workspace_bytes(self):
+        """Device memory behind the device update as it stands: the handle's workspace and, on a recurrent actor-critic, the four dense row buffers
+        (the memories' own workspace is ``actor_critic._seq.workspace_bytes()``).  0 before the first update."""
+        own = 0 if self._handle is None else int(update_lib().mpc_ppo_update_workspace_bytes(self._handle))
+        return own + (0 if self._seq_store is None else sum(4 * t.numel() for t in self._seq_store))
+
+    def _device_state(self, rows, extra=()):
         """The handle, sized for ``rows`` and bound to the current addresses of the gradients and moments (created here, on the first step, as
-        torch creates them); returns the common step count."""
+        torch creates them); returns the common step count.  ``extra``: the parameters that go behind the ``mpc_ac``'s (``mpc_ppo_update_bind_extra``)."""
         ac = self.actor_critic
         dev = ac.std.device
         ac._ready("PPO.update", torch.empty((1, ac.num_obs), dtype=torch.float32, device=dev))      # (the handle and its binding: nothing is launched)
         params = ac.bind_order()
+        extra = list(extra)
         steps = set()
-        for p in params:
+        for p in params + extra:
             st = self.optimizer.state[p]
             if len(st) == 0:                                                      # torch.optim.Adam._init_group
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
@@ -477,6 +496,7 @@ class PPO:
             with torch.cuda.device(dev):
                 check(update_lib().mpc_ppo_update_create(C.byref(h), ac._handle, int(rows)), "mpc_ppo_update_create")
             self._handle, self._max_rows, self._bound, self._storage_ptrs, self._ac_ptrs = h, int(rows), None, None, ac._bound_ptrs
+            self._extra_bound, self._seq_ptrs = None, None
         tensors = [p.grad for p in params] + [self.optimizer.state[p][key] for key in ("exp_avg", "exp_avg_sq") for p in params]
         ptrs = _lib.addresses_to_bind(tensors, self._bound, dev, "gradients and Adam's moments must be contiguous float32 tensors shaped like their parameters, on their device",
                                       like=3 * params)
@@ -484,6 +504,16 @@ class PPO:
             n, arr = len(params), _lib.ptr_array
             check(update_lib().mpc_ppo_update_bind(self._handle, arr(ptrs[:n]), arr(ptrs[n:2 * n]), arr(ptrs[2 * n:])), "mpc_ppo_update_bind")
             self._bound = ptrs
+        if extra:
+            tensors = extra + [p.grad for p in extra] + [self.optimizer.state[p][key] for key in ("exp_avg", "exp_avg_sq") for p in extra]
+            ptrs = _lib.addresses_to_bind(tensors, self._extra_bound, dev, "the memories' parameters, gradients and Adam's moments must be contiguous float32 tensors "
+                                          "shaped like their parameters, on the MLPs' device", like=4 * extra)
+            if ptrs is not None:
+                n, arr = len(extra), _lib.ptr_array
+                with torch.cuda.device(dev):
+                    check(update_lib().mpc_ppo_update_bind_extra(self._handle, n, arr(ptrs[:n]), arr(ptrs[n:2 * n]), arr(ptrs[2 * n:3 * n]), arr(ptrs[3 * n:]),
+                                                                 _lib.int_array([p.numel() for p in extra])), "mpc_ppo_update_bind_extra")
+                self._extra_bound = ptrs
         return steps.pop()
 
     def _update_hip(self, storage, indices=None):
@@ -540,12 +570,119 @@ class PPO:
         storage.clear()
         return terms[:, 1].mean(), terms[:, 0].mean()
 
+    def _recurrent_plan(self, storage):
+        """What one update of ``_update_recurrent_hip`` sets up, once, on the device and with no host read: the handle bound to all tensors (the
+        memories' eight behind the MLPs'), the storage and the four persistent ``[T B][H]`` buffers ``_seq_rows`` = (y_a, y_c, dy_a, dy_c) set on it,
+        the reset flags ``[mini-batch][T][B]`` as ``recurrent_sequence_generator`` builds them and the row index ``idx[i][t B + b] = t N + i B + b``.
+        Returns a dict for ``_recurrent_grads``; ``step`` is the optimiser's common step count."""
+        from .recurrent import SequenceKernel
+        c, ac = self.cfg, self.actor_critic
+        dev = ac.std.device
+        need_gpu("PPO.update", storage.observations, ac.std)
+        if storage.device != dev:
+            raise _lib.MpcLibraryError("PPO.update: the storage and the parameters live on different devices")
+        if storage.hidden is None:
+            raise ValueError("the storage keeps no hidden states (RolloutStorage(hidden=))")
+        T, N, mb, H = storage.T, storage.n, c.num_mini_batches, ac.rnn_hidden_size
+        B = N // mb
+        if B < 1:
+            raise ValueError("fewer environments than mini-batches")
+        rows, total = T * B, T * N
+        critic_rows = storage.privileged_observations
+        if critic_rows is None:
+            if ac.privileged:
+                raise ValueError("the actor-critic was made with num_critic_obs and the storage keeps no critic rows (RolloutStorage(num_privileged_obs=))")
+            critic_rows = storage.observations
+        memory_params = [p for m in ac.memories() for p in m.parameters_in_bind_order()]
+        step = self._device_state(rows, extra=memory_params)
+        L = update_lib()
+        flat = (storage.observations, storage.actions, storage.values, storage.advantages, storage.returns, storage.actions_log_prob, storage.mu, storage.sigma)
+        widths = (ac.obs_width, NUM_ACTIONS, 1, 1, 1, 1, NUM_ACTIONS, NUM_ACTIONS)
+        ptrs = tuple(tensor_arg(t, torch.float32, total * w, "storage").data_ptr() for t, w in zip(flat, widths))
+        if ptrs != self._storage_ptrs:                                            # (d_obs names the storage; the sequence call does not read it)
+            check(L.mpc_ppo_update_set_storage(self._handle, total, *ptrs), "mpc_ppo_update_set_storage")
+            self._storage_ptrs = ptrs
+        grown = self._seq_store is not None and self._seq_store[0].shape[0] < self._max_rows      # (a new handle for more rows)
+        if self._seq_rows is None or grown or any(t.shape != (rows, H) or t.device != dev for t in self._seq_rows):
+            cap = self._max_rows                                                 # the handle's: what set_sequence_rows takes every buffer to hold
+            if self._seq_store is None or any(t.shape[0] < cap or t.shape[1] != H or t.device != dev for t in self._seq_store):
+                self._seq_store = tuple(torch.zeros((cap, H), dtype=torch.float32, device=dev) for _ in range(4))
+            self._seq_rows = tuple(t[:rows] for t in self._seq_store)
+        seq_ptrs = tuple(tensor_arg(t, torch.float32, rows * H, "a dense row buffer").data_ptr() for t in self._seq_rows)
+        if seq_ptrs != self._seq_ptrs:
+            check(L.mpc_ppo_update_set_sequence_rows(self._handle, *seq_ptrs), "mpc_ppo_update_set_sequence_rows")
+            self._seq_ptrs = seq_ptrs
+        if ac._seq is None:
+            ac._seq = SequenceKernel(ac.memories())
+        used = mb * B
+        reset = torch.zeros((T, N), dtype=torch.long, device=dev)
+        reset[1:] = storage.dones[:-1, :, 0] != 0
+        reset = reset[:, :used].reshape(T, mb, B).permute(1, 0, 2).contiguous()
+        t_, b_, i_ = (torch.arange(n, dtype=torch.long, device=dev) for n in (T, B, mb))
+        idx = ((t_[:, None] * N + b_[None, :]).reshape(1, rows) + (i_ * B)[:, None]).contiguous()
+        return dict(T=T, B=B, rows=rows, mini_batches=mb, step=step, reset=reset, idx=idx, obs=storage.observations, critic_rows=critic_rows,
+                    h0=(storage.saved_h_a, storage.saved_h_c), c0=(storage.saved_c_a, storage.saved_c_c), memory_params=memory_params,
+                    memory_grads=[[p.grad for p in m.parameters_in_bind_order()] for m in ac.memories()], stream=_lib.stream(dev),
+                    adaptive=c.desired_kl is not None and c.schedule == "adaptive")
+
+    def _recurrent_grads(self, plan, i, terms):
+        """Mini-batch ``i`` of ``plan`` up to the gradients: the forward roll into (y_a, y_c), ``mpc_ppo_update_grads_sequence`` (the MLPs' and std's
+        ``.grad``, ``terms`` [4], the learning-rate decision, (dy_a, dy_c)), the backward pass through time into the memories' ``.grad``."""
+        from .recurrent import ACTOR, CRITIC
+        c, seq, which = self.cfg, self.actor_critic._seq, (ACTOR, CRITIC)
+        y_a, y_c, dy_a, dy_c = self._seq_rows
+        T, B = plan["T"], plan["B"]
+        e0, e1 = i * B, (i + 1) * B
+        token = seq.token + 1                                                    # the forward call below: what the backward call must go back through
+        seq.forward(which, (plan["obs"][:, e0:e1], plan["critic_rows"][:, e0:e1]), [h[0, e0:e1] for h in plan["h0"]], [x[0, e0:e1] for x in plan["c0"]],
+                    plan["reset"][i], what='update_heads="hip"', out=((y_a, None), (y_c, None)))
+        adaptive = plan["adaptive"]
+        check(update_lib().mpc_ppo_update_grads_sequence(self._handle, plan["rows"], plan["idx"][i].data_ptr(), float(c.clip_param), float(c.value_loss_coef),
+                                                         float(c.entropy_coef), int(bool(c.use_clipped_value_loss)), int(adaptive),
+                                                         float(c.desired_kl) if adaptive else 0.0, self.lr_device.data_ptr(), terms.data_ptr(), plan["stream"]),
+              "mpc_ppo_update_grads_sequence")
+        seq.backward(which, T, B, (dy_a, dy_c), token, out=plan["memory_grads"])      # (overwrites the memories' .grad)
+
+    def _update_recurrent_hip(self, storage):
+        """``update_heads="hip"``: per mini-batch ``_recurrent_grads`` and one ``mpc_ppo_update_apply`` over the MLPs' and the memories' tensors -- on one
+        stream, with no host read and no autograd.  The mini-batches are ``recurrent_sequence_generator``'s: blocks of N // num_mini_batches
+        environments in order, the same in every epoch, the left-over dropped."""
+        c, ac = self.cfg, self.actor_critic
+        dev = ac.std.device
+        plan = self._recurrent_plan(storage)
+        mb, step = plan["mini_batches"], plan["step"]
+        group = self.optimizer.param_groups[0]
+        beta1, beta2 = group["betas"]
+        k = c.num_learning_epochs * mb
+        terms = torch.empty((k, 4), dtype=torch.float32, device=dev)
+        if self.record_lr:
+            self.lr_trace = torch.empty(k, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            for e in range(c.num_learning_epochs):
+                for i in range(mb):
+                    j = e * mb + i
+                    self._recurrent_grads(plan, i, terms[j])
+                    if self.record_lr:
+                        self.lr_trace[j:j + 1].copy_(self.lr_device)
+                    step += 1
+                    check(update_lib().mpc_ppo_update_apply(self._handle, float(c.max_grad_norm), float(beta1), float(beta2), float(group["eps"]), step,
+                                                            self.lr_device.data_ptr(), plan["stream"]), "mpc_ppo_update_apply")
+        for p in ac.bind_order() + plan["memory_params"]:
+            self.optimizer.state[p]["step"] += float(k)                          # (host tensors: no device work)
+        self.last_terms = tuple(terms[k - 1, q] for q in range(4))
+        storage.clear()
+        return terms[:, 1].mean(), terms[:, 0].mean()
+
     def update(self, storage, indices=None):
         """One update over the storage: num_learning_epochs x num_mini_batches Adam steps.  Returns device tensors (mean value loss, mean
         surrogate loss).  torch backend: the only host read per mini-batch is the kl of the adaptive schedule (as in rsl_rl).  hip backend: no host
         read at all; ``indices`` (for tests) replaces the ``torch.randperm`` over the num_mini_batches * (T N // num_mini_batches) rows."""
         if self.backend == "hip":
             return self._update_hip(storage, indices)
+        if self.device_update:                                                   # a recurrent actor-critic with update_heads="hip"
+            if indices is not None:
+                raise ValueError("indices are taken by the hip backend only")
+            return self._update_recurrent_hip(storage)
         if indices is not None:
             raise ValueError("indices are taken by the hip backend only")
         c = self.cfg
@@ -603,7 +740,7 @@ def _riders(trainer):
     it has one), in the record's order."""
     alg, curriculum, terms, shaping = trainer.alg, trainer.curriculum, trainer.episode_terms, getattr(trainer, "reward_shaping", None)
 
-    def learning_rate(values):                                                   # hip backend: the device's value, which the host copies follow
+    def learning_rate(values):                                                   # a device update: the device's value, which the host copies follow
         if values:
             alg.sync_learning_rate(values[0])
         return {"learning_rate": alg.learning_rate}
@@ -701,7 +838,8 @@ class PPOTrainer:
     **Memory.**  ``recurrent=RecurrentConfig(hidden_size=...)`` (``recurrent.py``) trains an ``ActorCriticRecurrent``: each tick's ``act`` is handed
     the task's reset tensor of the tick before (the memories start an episode from zero state) and slot t's views of the storage's saved hidden states
     -- nothing more is copied per tick -- and the update is the torch one over padded trajectories, or, with
-    ``RecurrentConfig(update_through_time="hip")``, torch's MLPs, loss and Adam around the memories' roll and backward pass on the device.  The memories
+    ``RecurrentConfig(update_through_time="hip")``, torch's MLPs, loss and Adam around the memories' roll and backward pass on the device, or, with
+    ``update_heads="hip"`` as well, all of it on the device with no host read per mini-batch (``PPO._update_recurrent_hip``).  The memories
     read what the MLPs' first layers read otherwise.  ``update="hip"`` is refused.  A feed-forward actor-critic is called the same way and handed None."""
 
     def __init__(self, env, cfg=None, seed=1, device=None, update="torch", normalize_obs=False, obs_norm_eps=1e-2, obs_norm_until=None, recurrent=None):
@@ -724,7 +862,7 @@ class PPOTrainer:
         if recurrent is not None:
             from .recurrent import ActorCriticRecurrent
             nets.update(rnn_type=recurrent.rnn_type, rnn_hidden_size=recurrent.hidden_size, rnn_num_layers=recurrent.num_layers,
-                        update_through_time=getattr(recurrent, "update_through_time", "torch"))
+                        update_through_time=getattr(recurrent, "update_through_time", "torch"), update_heads=getattr(recurrent, "update_heads", "torch"))
         self.actor_critic = (ActorCritic if recurrent is None else ActorCriticRecurrent)(**nets).to(self.device)
         self.alg = PPO(self.actor_critic, c, backend=update)
         self.storage = RolloutStorage(env.num_envs, c.num_steps_per_env, self.device, env.num_obs, env.num_actions, num_privileged_obs=priv,
@@ -869,7 +1007,7 @@ class PPOTrainer:
         self._prev_reset = None
         if load_optimizer:
             self.alg.optimizer.load_state_dict(ck["optimizer_state_dict"])
-            if self.alg.backend == "hip":                                        # the device's copy of the learning rate follows the checkpoint's
+            if self.alg.device_update:                                           # the device's copy of the learning rate follows the checkpoint's
                 self.alg.set_learning_rate(self.alg.optimizer.param_groups[0]["lr"])
         self.iteration = ck["iter"]
         self.infos = list(ck["infos"]) if ck.get("infos") else []

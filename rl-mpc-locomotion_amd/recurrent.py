@@ -19,6 +19,11 @@ memories' outputs: their first layers are ``rnn_hidden_size`` wide (rsl_rl's ``s
   ``mpc_recurrent_bptt_backward``.  The dense roll equals the padded trajectories because the collection stores zero in ``saved_*[t]`` after a done.
   The MLPs, the loss, the clip and Adam stay torch's; ``PPO(backend="hip")`` still refuses a recurrent actor-critic: the MLPs, the loss head and Adam
   of a recurrent device update are not built.
+* ``RecurrentConfig(update_through_time="hip", update_heads="hip")`` (opt-in on top of the former) takes the rest of the update to the device as well:
+  per mini-batch the forward roll into two persistent ``[T B][H]`` buffers, ``mpc_ppo_update_grads_sequence`` (the MLPs on those dense rows, the loss
+  head on the storage through a row index, the MLPs' backward pass down to the gradient of the rows), the backward pass through time straight into the
+  memories' ``.grad``, and ONE clip and Adam step over the MLPs' and the memories' tensors (``mpc_ppo_update_bind_extra``) -- one stream, no host read,
+  no autograd (``PPO._update_recurrent_hip``).  The mini-batches are ``recurrent_sequence_generator``'s blocks.
 
     trainer = PPOTrainer(env, recurrent=RecurrentConfig(hidden_size=256))                                  # update_through_time="hip": see above
     trainer.learn(num_iterations)
@@ -31,7 +36,7 @@ every environment had a ``done``.
 Deployment: ``WeightPolicy.from_state_dict`` on a recurrent checkpoint's ``model_state_dict`` gives a ``weight_policy.RecurrentWeightPolicy``, whose ``step`` is
 ``memory_a``'s cell and the actor in one launch (csrc/recurrent_policy.h).
 
-Not built: GRU, stacked layers, the MLPs / loss head / Adam of a recurrent ``PPO(backend="hip")``.
+Not built: GRU, stacked layers.  ``PPO(backend="hip")`` keeps refusing a recurrent actor-critic: its device update is spelled ``update_heads="hip"``.
 
 The torch paths (``step_torch``, ``log_prob_entropy_value``, ``Memory.forward_sequence`` without the option, the split / pad functions) run on the CPU in
 any dtype; the device entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
@@ -104,17 +109,30 @@ def through_time_option(value):
     return value
 
 
+def heads_option(value, through_time):
+    """``update_heads`` beside ``update_through_time``: the device heads read the device roll's buffers, so "hip" needs "hip" there."""
+    if value not in THROUGH_TIME:
+        raise ValueError(f"update_heads={value!r}: 'torch' or 'hip'")
+    if value == "hip" and through_time != "hip":
+        raise ValueError('update_heads="hip" requires update_through_time="hip": the MLPs, the loss head and Adam on the device read the device roll\'s '
+                         'outputs and feed its backward pass')
+    return value
+
+
 @dataclass
 class RecurrentConfig:
     """rsl_rl's ``rnn_type``, ``rnn_hidden_size`` and ``rnn_num_layers``; one LSTM layer is what is built.  ``update_through_time``: "torch" (the
-    default: ``nn.LSTM`` over padded trajectories, autograd back through time) or "hip" (the dense roll and its backward pass on the device)."""
+    default: ``nn.LSTM`` over padded trajectories, autograd back through time) or "hip" (the dense roll and its backward pass on the device).
+    ``update_heads``: "torch" (the default: torch's MLPs, loss, clip and Adam) or "hip" (those on the device too; needs ``update_through_time="hip"``)."""
     hidden_size: int = 256
     rnn_type: str = "lstm"
     num_layers: int = 1
     update_through_time: str = "torch"
+    update_heads: str = "torch"
 
     def __post_init__(self):
         through_time_option(self.update_through_time)
+        heads_option(self.update_heads, self.update_through_time)
 
 
 # what ``RolloutStorage.recurrent_mini_batch_generator`` yields: padded trajectories and masks, [T][block] slices, each memory's (h0, c0)
@@ -379,13 +397,15 @@ class ActorCriticRecurrent(ActorCritic):
 
     ``act`` is the cell launch and then the parent's asymmetric ``act``.  ``reset``: the task's reset tensor (int64 [n]) of the tick before, or None;
     where it is set the row's state is taken as zero before the step.  ``saved``: dict of ``h_a``, ``c_a``, ``h_c``, ``c_c`` [n][H] views
-    (``RolloutStorage.hidden_slot(t)``) that receive the state the step started from.  ``evaluate`` peeks: it does not advance the critic's memory."""
+    (``RolloutStorage.hidden_slot(t)``) that receive the state the step started from.  ``evaluate`` peeks: it does not advance the critic's memory.
+    ``update_through_time`` / ``update_heads``: ``RecurrentConfig``'s."""
     is_recurrent = True
 
     def __init__(self, num_obs=48, num_actions=NUM_ACTIONS, actor_hidden_dims=(512, 256, 128), critic_hidden_dims=(512, 256, 128), init_noise_std=1.0,
-                 num_critic_obs=None, rnn_type="lstm", rnn_hidden_size=256, rnn_num_layers=1, update_through_time="torch"):
+                 num_critic_obs=None, rnn_type="lstm", rnn_hidden_size=256, rnn_num_layers=1, update_through_time="torch", update_heads="torch"):
         refuse_unbuilt(rnn_type, rnn_num_layers)
         through_time_option(update_through_time)
+        heads_option(update_heads, update_through_time)
         H = int(rnn_hidden_size)
         super().__init__(H, num_actions, actor_hidden_dims, critic_hidden_dims, init_noise_std, num_critic_obs=H)
         self.obs_width = int(num_obs)                                            # what memory_a reads
@@ -397,6 +417,7 @@ class ActorCriticRecurrent(ActorCritic):
         self.memory_c = Memory(self.critic_obs_width, H)
         self._cell_handle, self._cell_ptrs = None, None
         self.update_through_time = update_through_time
+        self.update_heads = update_heads                                         # "hip": PPO.update runs the whole update on the device
         self._seq = None                                                         # the update through time's handle over both memories (first use)
 
     _destroy_cell = _lib.finalizer("mpc_recurrent_destroy", attr="_cell_handle")

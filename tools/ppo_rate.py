@@ -21,6 +21,11 @@ csrc/recurrent_bptt.h) against the recurrent trainer with the torch update, the 
 the launches it made before the option existed -- : collection, update and whole iteration of each, and on one mini-batch of the "hip" trainer's storage
 the forward launch, the whole backward call and the weight-gradient GEMMs with their reduction alone (the launch through time is the difference).
     python tools/ppo_rate.py --recurrent --through-time hip [--hidden 256] [--out profiles/recurrent_bptt_rate.json]
+--recurrent --through-time hip --heads hip times the recurrent trainer with the whole update on the device (RecurrentConfig(update_through_time="hip",
+update_heads="hip"): the MLPs, the loss head, the clip and Adam of include/mpc_ppo_update.h around the memories' roll) against the recurrent trainer with
+update_heads="torch", which makes the launches it made before the option existed; the two alternate block by block in one process (_rate.wall_blocks,
+one iteration per block): update and iteration from HIP events, the iteration also by the host clock, and the device memory behind the update.
+    python tools/ppo_rate.py --recurrent --through-time hip --heads hip [--hidden 256] [--out profiles/recurrent_update_rate.json]
 The kernel-trace stats: rocprofv3 --kernel-trace --stats ... -- python tools/ppo_rate.py --quick   (3 collections and one update per backend)"""
 import argparse
 import json
@@ -276,6 +281,51 @@ def through_time_report(args, dev, n):
     return res
 
 
+def heads_report(args, dev, n):
+    """The recurrent trainer with ``update_heads="hip"`` against the one with ``update_heads="torch"`` (both with the device roll): see the head of this file."""
+    from _rate import wall_blocks
+    from bench import device_state
+    from rl_mpc_locomotion_amd.recurrent import RecurrentConfig
+    cfg = PPOConfig()
+    T, H = cfg.num_steps_per_env, args.hidden
+    trainers = {k: PPOTrainer(make_env(n, dev), cfg, seed=1, recurrent=RecurrentConfig(hidden_size=H, update_through_time="hip", update_heads=k))
+                for k in ("torch", "hip")}
+    res = {"kernel_source_sha256": _lib.kernel_source_hash(), "robots": n, "horizon": 10, "num_steps_per_env": T, "repeats": args.repeats, "hidden_size": H,
+           "mini_batches_per_update": cfg.num_learning_epochs * cfg.num_mini_batches, "block_of_environments": n // cfg.num_mini_batches,
+           "rows_per_mini_batch": T * (n // cfg.num_mini_batches), "device_state": {"before": device_state(0)}}
+    events = {k: [] for k in trainers}
+    warmup = 2                            # cold solves, code objects, torch's kernels, Adam's state, the handles' workspaces
+
+    def iteration(name):
+        tr = trainers[name]
+
+        def run():
+            a, b, c = ev(), ev(), ev()
+            a.record()
+            tr.collect()
+            b.record()
+            tr.alg.update(tr.storage)
+            c.record()
+            events[name].append((a, b, c))
+        return run
+    wall = wall_blocks({k: iteration(k) for k in trainers}, 1, args.repeats, n * T, warmup=warmup)
+    for name, spans in events.items():
+        spans = spans[warmup:]
+        res[name] = {"collect": stats([a.elapsed_time(b) for a, b, _ in spans]), "update": stats([b.elapsed_time(c) for _, b, c in spans]),
+                     "full": stats([a.elapsed_time(c) for a, _, c in spans])}
+        res[name]["robot_ticks_per_s_training"] = n * T / (res[name]["full"]["median_ms"] * 1e-3)
+        res[name]["host_clock_iteration"] = wall[name]
+    res["hip_over_torch_median"] = {k: res["hip"][k]["median_ms"] / res["torch"][k]["median_ms"] for k in ("collect", "update", "full")}
+    res["hip_p90_below_torch_p10"] = {k: bool(res["hip"][k]["p90_ms"] < res["torch"][k]["p10_ms"]) for k in ("update", "full")}
+    res["update_per_mini_batch_ms"] = {k: res[k]["update"]["median_ms"] / res["mini_batches_per_update"] for k in trainers}
+    hip = trainers["hip"]
+    res["workspace_bytes"] = {"update_handle_and_dense_rows": hip.alg.workspace_bytes(), "memories_handle": hip.actor_critic._seq.workspace_bytes(),
+                              "memories_handle_torch_heads": trainers["torch"].actor_critic._seq.workspace_bytes()}
+    res["tensors_in_the_clip_and_adam"] = len(list(hip.actor_critic.parameters()))
+    res["device_state"]["after"] = device_state(0, smi=False)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--robots", type=int, default=4096)
@@ -287,16 +337,19 @@ if __name__ == "__main__":
     ap.add_argument("--recurrent", action="store_true", help="the recurrent actor-critic against the feed-forward one (see the head of this file)")
     ap.add_argument("--hidden", type=int, default=256, help="--recurrent: the memories' hidden size")
     ap.add_argument("--through-time", choices=("hip",), help="--recurrent: the update through time on the device against the torch update (see the head of this file)")
+    ap.add_argument("--heads", choices=("hip",), help="--recurrent --through-time hip: the whole update on the device against torch's MLPs, loss and Adam")
     ap.add_argument("--out")
     args = ap.parse_args()
     if args.through_time and not args.recurrent:
         ap.error("--through-time goes with --recurrent")
+    if args.heads and not args.through_time:
+        ap.error("--heads goes with --recurrent --through-time hip")
     if not torch.cuda.is_available():
         sys.exit("ppo_rate.py measures on the GPU; none is visible")
     dev, n = "cuda:0", args.robots
     if args.privileged or args.recurrent:
         if args.recurrent:
-            res = through_time_report(args, dev, n) if args.through_time else recurrent_report(args, dev, n)
+            res = (heads_report if args.heads else through_time_report)(args, dev, n) if args.through_time else recurrent_report(args, dev, n)
         else:
             res = privileged_report(args, dev, n)
         print(json.dumps(res, indent=1))
