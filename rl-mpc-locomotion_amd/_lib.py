@@ -145,6 +145,50 @@ def finalizer(destroy, attr="_handle"):
     return __del__
 
 
+def host_array(t, dtype):
+    """A tensor or an array of a state dict as a numpy array of ``dtype``."""
+    import numpy as np
+    return (t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)).astype(dtype)
+
+
+class DrawnRecord:
+    """What the per-robot records that are drawn on the device share (``plant_rand.PlantRand``, ``friction.Friction``): the handle once a sim is
+    bound, the ``ids`` argument of a draw, and the draw counters.  A subclass names itself (``WHAT``) and, for the counters, its module's ``lib``
+    and ``check`` and its two entry points (``COUNTERS``); every other entry point is called by name where it is used."""
+
+    def _bound(self):
+        if self.sim is None:
+            raise ValueError(f"the {self.WHAT} is not bound to a sim (bind)")
+        return self._handle
+
+    def _counters(self, which, c):
+        """The get (0) or set (1) entry point of the counters on the bound handle and the array ``c``, which the caller keeps alive."""
+        lib, check, *names = self.COUNTERS
+        check(getattr(lib(), names[which])(self._bound(), c.ctypes.data), names[which])
+
+    def _ids(self, ids):
+        """(address, count) of a draw's ``ids``, a cuda int32 tensor or None for all ``n``."""
+        if ids is None:
+            return None, self.n
+        import torch
+        tensor_arg(ids, torch.int32, ids.numel(), "ids")
+        return ids.data_ptr(), ids.numel()
+
+    def get_counters(self):
+        """How many draws each environment has made: [n] uint32.  Synchronous."""
+        import numpy as np
+        c = np.zeros(self.n, np.uint32)
+        self._counters(0, c)
+        return c
+
+    def set_counters(self, counters):
+        import numpy as np
+        c = np.ascontiguousarray(counters, dtype=np.uint32)
+        if c.shape != (self.n,):
+            raise ValueError(f"counters: [{self.n}] expected")
+        self._counters(1, c)
+
+
 def need_gpu(what, *tensors):
     import torch
     if not torch.cuda.is_available():

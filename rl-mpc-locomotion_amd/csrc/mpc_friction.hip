@@ -1,11 +1,10 @@
 // mpc_friction.hip -- the C ABI of mpc_friction.h: the opt-in Coulomb friction of the toy plant on the device.
 //   friction_draw_kernel        one lane per slot of the id array, the plant's grid: a listed environment has its force and slip rows zeroed
 //                               and, where the draw resamples, reads its draw counter, draws its coefficient (friction.h) and writes both back.
-//   friction_step_plane_kernel  mpc_plant_rand.hip's step kernels with toy_step_friction in place of toy_step_plant: each lane loads its
-//   friction_step_field_kernel  coefficient and, where the sim has a plant record, its three doubles (the neutral constants where not: a branch
-//                               that is uniform over the launch), steps, and writes its twelve force and four slip floats (zeros for a fallen
-//                               robot).  They live here and not beside the other instantiations so that those translation units compile to
-//                               what they compiled to before.
+//   friction_step_plane_kernel  mpc_plant_rand.hip's step kernels with toy_step_friction in place of toy_step_plant (sim_step.h's shell with its
+//   friction_step_field_kernel  CoulombModel): each lane loads its coefficient and, where the sim has a plant record, its three doubles (the
+//                               neutral constants where not: a branch that is uniform over the launch), steps, and writes its twelve force
+//                               and four slip floats (zeros for a fallen robot).
 // No LDS, no atomics, no scratch.
 #include <hip/hip_runtime.h>
 
@@ -22,7 +21,7 @@
 #include "mpc_sim_internal.h"
 #include "toy_sim.h"
 
-using namespace toysim;
+using namespace simstep;               // (and with it toysim)
 using mpchost::DeviceGuard;
 using simint::kSimThreads;
 using simint::sim_grid;
@@ -51,86 +50,14 @@ __global__ __launch_bounds__(kSimThreads) void friction_draw_kernel(int n, int k
   counter[r] = e + 1u;
 }
 
-struct FrictionArgs {
-  int n;
-  double dt;
-  double *f64;                       // [kF64][n]
-  int *i32;                          // [kI32][n]
-  const int *type;                   // [n]
-  const Params *params;              // [n_types]
-  const double *plant;               // [kPlant][n] or null: the neutral record
-  const double *mu;                  // [n]
-  float *force;                      // [n][4][3] or null
-  float *slip;                       // [n][4] or null
-};
-
-struct FieldArgs {
-  const double *origin;              // [n][2]
-  const short *h;                    // [rows][cols]
-  int rows, cols;
-  double hscale, vscale, x0, y0;
-};
-
-template <class Ground>
-__device__ __forceinline__ void step_robot(const FrictionArgs &a, int r, const Ground &g, const float *__restrict__ tau, float *dof, float *root) {
-  State s;
-  unpack(s, a.f64 + r, a.i32 + r, a.n);
-  if (!s.fell) {
-    const size_t n = (size_t)a.n;
-    double payload = 0.0, strength = 1.0, grav_z = kGravZ;
-    if (a.plant) {
-      payload = a.plant[kPlantPayload * n + r]; strength = a.plant[kPlantStrength * n + r]; grav_z = a.plant[kPlantGravZ * n + r];
-    }
-    double t[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) t[i] = (double)tau[(size_t)r * 12 + i];
-    Coulomb c;
-    c.mu = a.mu[r];
-    toy_step_friction(s, a.params[a.type[r]], t, a.dt, g, payload, strength, grav_z, c);
-    pack(s, a.f64 + r, a.i32 + r, a.n);
-    if (a.force) {
-#pragma unroll
-      for (int l = 0; l < 4; ++l)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) a.force[(size_t)r * 12 + 3 * l + i] = (float)c.force[l][i];
-    }
-    if (a.slip) {
-#pragma unroll
-      for (int l = 0; l < 4; ++l) a.slip[(size_t)r * 4 + l] = (float)c.slip[l];
-    }
-  } else {
-    if (a.force) {
-#pragma unroll
-      for (int j = 0; j < 12; ++j) a.force[(size_t)r * 12 + j] = 0.0f;
-    }
-    if (a.slip) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a.slip[(size_t)r * 4 + j] = 0.0f;
-    }
-  }
-  float d[24], b[13];
-  observe(s, d, b);
-  if (dof) {
-#pragma unroll
-    for (int i = 0; i < 24; ++i) dof[(size_t)r * 24 + i] = d[i];
-  }
-  if (root) {
-#pragma unroll
-    for (int i = 0; i < 13; ++i) root[(size_t)r * 13 + i] = b[i];
-  }
+__global__ __launch_bounds__(kSimThreads) void friction_step_plane_kernel(Args a, CoulombModel m, PlaneSource g, const float *__restrict__ tau, float *dof, float *root) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < a.n) step_robot(a, r, g, m, tau, dof, root);
 }
 
-__global__ __launch_bounds__(kSimThreads) void friction_step_plane_kernel(FrictionArgs a, const double *__restrict__ slope, const float *__restrict__ tau, float *dof,
-                                                                          float *root) {
+__global__ __launch_bounds__(kSimThreads) void friction_step_field_kernel(Args a, CoulombModel m, FieldSource f, const float *__restrict__ tau, float *dof, float *root) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.n) return;
-  step_robot(a, r, Plane{slope[2 * r], slope[2 * r + 1]}, tau, dof, root);
-}
-
-__global__ __launch_bounds__(kSimThreads) void friction_step_field_kernel(FrictionArgs a, FieldArgs f, const float *__restrict__ tau, float *dof, float *root) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.n) return;
-  step_robot(a, r, HeightField{f.h, f.rows, f.cols, f.hscale, f.vscale, f.x0, f.y0, f.origin[2 * r], f.origin[2 * r + 1]}, tau, dof, root);
+  if (r < a.n) step_robot(a, r, f, m, tau, dof, root);
 }
 
 // the first entry of mu [n] that is negative or NaN, or -1
@@ -144,13 +71,9 @@ long bad_mu(const double *mu, size_t n) {
 namespace simint {
 
 hipError_t friction_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream) {
-  const FrictionArgs a{s->n, s->dt, s->d_f64, s->d_i32, s->d_type, s->d_params, s->d_plant, s->d_mu, s->d_force, s->d_slip};
-  if (s->d_heights) {
-    const FieldArgs f{s->d_origin, s->d_heights, s->rows, s->cols, s->hscale, s->vscale, s->x0, s->y0};
-    hipLaunchKernelGGL(friction_step_field_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, a, f, d_tau, d_dof, d_root);
-  } else {
-    hipLaunchKernelGGL(friction_step_plane_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, a, (const double *)s->d_slope, d_tau, d_dof, d_root);
-  }
+  const CoulombModel m{s->d_plant, s->d_mu, s->d_force, s->d_slip};
+  if (s->d_heights) hipLaunchKernelGGL(friction_step_field_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, step_args(s), m, field_source(s), d_tau, d_dof, d_root);
+  else hipLaunchKernelGGL(friction_step_plane_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, step_args(s), m, plane_source(s), d_tau, d_dof, d_root);
   return hipGetLastError();
 }
 
@@ -243,8 +166,7 @@ int mpc_friction_get_mu(mpc_friction *h, double *h_mu) {
   if (!h || !h_mu) return fail(MPC_E_ARG, "mpc_friction_get_mu: null argument");
   if (!h->sim) return fail(MPC_E_ARG, "mpc_friction_get_mu: no sim bound (mpc_friction_bind)");
   DeviceGuard guard_(h->device);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h_mu, h->sim->d_mu, sizeof(double) * (size_t)h->n, hipMemcpyDeviceToHost));
+  HIP_TRY(mpchost::sync_copy(h_mu, h->sim->d_mu.get(), (size_t)h->n, hipMemcpyDeviceToHost));
   return MPC_OK;
 }
 
@@ -254,9 +176,7 @@ int mpc_friction_set_mu(mpc_friction *h, const double *h_mu) {
   if (bad >= 0) return fail(MPC_E_ARG, "mpc_friction_set_mu: the mu of robot " + std::to_string(bad) + " is negative or NaN");
   if (!h->sim) return fail(MPC_E_ARG, "mpc_friction_set_mu: no sim bound (mpc_friction_bind)");
   DeviceGuard guard_(h->device);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->sim->d_mu, h_mu, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice));
-  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(mpchost::sync_copy(h->sim->d_mu.get(), h_mu, (size_t)h->n, hipMemcpyHostToDevice));
   return MPC_OK;
 }
 
@@ -264,8 +184,7 @@ int mpc_friction_get_counters(mpc_friction *h, unsigned int *h_counters) {
   if (!h || !h_counters) return fail(MPC_E_ARG, "mpc_friction_get_counters: null argument");
   if (!h->sim) return fail(MPC_E_ARG, "mpc_friction_get_counters: no sim bound (mpc_friction_bind)");
   DeviceGuard guard_(h->device);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h_counters, h->d_counter, sizeof(unsigned) * (size_t)h->n, hipMemcpyDeviceToHost));
+  HIP_TRY(mpchost::sync_copy(h_counters, h->d_counter.get(), (size_t)h->n, hipMemcpyDeviceToHost));
   return MPC_OK;
 }
 
@@ -273,9 +192,7 @@ int mpc_friction_set_counters(mpc_friction *h, const unsigned int *h_counters) {
   if (!h || !h_counters) return fail(MPC_E_ARG, "mpc_friction_set_counters: null argument");
   if (!h->sim) return fail(MPC_E_ARG, "mpc_friction_set_counters: no sim bound (mpc_friction_bind)");
   DeviceGuard guard_(h->device);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_counter, h_counters, sizeof(unsigned) * (size_t)h->n, hipMemcpyHostToDevice));
-  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(mpchost::sync_copy(h->d_counter.get(), h_counters, (size_t)h->n, hipMemcpyHostToDevice));
   return MPC_OK;
 }
 

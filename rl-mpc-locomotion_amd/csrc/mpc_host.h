@@ -5,6 +5,7 @@
 //   destroy_handle     the body of every mpc_*_destroy: guard, synchronise, delete
 //   DeviceArray<T>     the owner of one hipMalloc'd array: a handle's `DeviceArray<T> d_x` is memory the handle owns and `delete` frees,
 //                      a plain `T *d_x` is memory of somebody else's
+//   sync_copy          a synchronous get / set of such an array: synchronise, copy, and after an upload synchronise again
 //   ErrorSlot, HIP_TRY the text behind mpc_*_last_error and the check of a HIP call
 //   round16            a byte rounding
 //   aligned16, present16, Range, any_overlap   the pointer checks in front of 16-byte loads and of a call's output arrays
@@ -99,6 +100,15 @@ void destroy_handle(Handle *h) {
   DeviceGuard guard_(h->device);
   if (h->device >= 0) (void)hipDeviceSynchronize();
   delete h;
+}
+
+// What a synchronous get / set of a handle's array is: wait for the launches that may still write or read it, copy `count` words, and after an
+// upload wait again, so that whatever the caller launches next, on any stream, sees it.  Under the caller's device guard.
+template <typename T>
+hipError_t sync_copy(T *dst, const T *src, size_t count, hipMemcpyKind kind) {
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(dst, src, sizeof(T) * count, kind);
+  return e != hipSuccess || kind != hipMemcpyHostToDevice ? e : hipDeviceSynchronize();
 }
 
 // the text behind a unit's mpc_*_last_error: one thread_local instance per unit

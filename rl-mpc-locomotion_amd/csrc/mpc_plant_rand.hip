@@ -2,10 +2,10 @@
 // kernels of a sim that carries a plant record.
 //   plant_draw_kernel          one lane per slot of the id array, the plant's grid: a listed environment reads its draw counter, draws its
 //                              record (plant_rand.h), writes the three doubles into the structure-of-arrays record and the counter back.
-//   plant_step_plane_kernel    mpc_sim.hip's sim_step_kernel and mpc_terrain.hip's terrain_step_kernel with toy_step_plant in place of toy_step:
-//   plant_step_field_kernel    each lane loads its three doubles (one word per lane per entry, consecutive lanes on consecutive words) and steps
-//                              with mass + payload, its twelve widened torques times strength, and its own gravity.  They live here and not
-//                              beside the plain instantiations so that those translation units compile to what they compiled to before.
+//   plant_step_plane_kernel    mpc_sim.hip's sim_step_kernel and mpc_terrain.hip's terrain_step_kernel with toy_step_plant in place of toy_step
+//   plant_step_field_kernel    (sim_step.h's shell with its PlantRecord model): each lane loads its three doubles (one word per lane per entry,
+//                              consecutive lanes on consecutive words) and steps with mass + payload, its twelve widened torques times strength,
+//                              and its own gravity.
 // No LDS, no atomics, no scratch.
 #include <hip/hip_runtime.h>
 
@@ -21,7 +21,7 @@
 #include "plant_rand.h"
 #include "toy_sim.h"
 
-using namespace toysim;
+using namespace simstep;               // (and with it toysim)
 using mpchost::DeviceGuard;
 using simint::kSimThreads;
 using simint::sim_grid;
@@ -47,72 +47,23 @@ __global__ __launch_bounds__(kSimThreads) void plant_draw_kernel(int n, int k, c
   counter[r] = e + 1u;
 }
 
-struct PlantArgs {
-  int n;
-  double dt;
-  double *f64;                       // [kF64][n]
-  int *i32;                          // [kI32][n]
-  const int *type;                   // [n]
-  const Params *params;              // [n_types]
-  const double *plant;               // [kPlant][n]
-};
-
-struct FieldArgs {
-  const double *origin;              // [n][2]
-  const short *h;                    // [rows][cols]
-  int rows, cols;
-  double hscale, vscale, x0, y0;
-};
-
-template <class Ground>
-__device__ __forceinline__ void step_robot(const PlantArgs &a, int r, const Ground &g, const float *__restrict__ tau, float *dof, float *root) {
-  State s;
-  unpack(s, a.f64 + r, a.i32 + r, a.n);
-  if (!s.fell) {
-    const size_t n = (size_t)a.n;
-    const double payload = a.plant[kPlantPayload * n + r], strength = a.plant[kPlantStrength * n + r], grav_z = a.plant[kPlantGravZ * n + r];
-    double t[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) t[i] = (double)tau[(size_t)r * 12 + i];
-    toy_step_plant(s, a.params[a.type[r]], t, a.dt, g, payload, strength, grav_z);
-    pack(s, a.f64 + r, a.i32 + r, a.n);
-  }
-  float d[24], b[13];
-  observe(s, d, b);
-  if (dof) {
-#pragma unroll
-    for (int i = 0; i < 24; ++i) dof[(size_t)r * 24 + i] = d[i];
-  }
-  if (root) {
-#pragma unroll
-    for (int i = 0; i < 13; ++i) root[(size_t)r * 13 + i] = b[i];
-  }
+__global__ __launch_bounds__(kSimThreads) void plant_step_plane_kernel(Args a, PlantRecord m, PlaneSource g, const float *__restrict__ tau, float *dof, float *root) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < a.n) step_robot(a, r, g, m, tau, dof, root);
 }
 
-__global__ __launch_bounds__(kSimThreads) void plant_step_plane_kernel(PlantArgs a, const double *__restrict__ slope, const float *__restrict__ tau, float *dof,
-                                                                       float *root) {
+__global__ __launch_bounds__(kSimThreads) void plant_step_field_kernel(Args a, PlantRecord m, FieldSource f, const float *__restrict__ tau, float *dof, float *root) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.n) return;
-  step_robot(a, r, Plane{slope[2 * r], slope[2 * r + 1]}, tau, dof, root);
-}
-
-__global__ __launch_bounds__(kSimThreads) void plant_step_field_kernel(PlantArgs a, FieldArgs f, const float *__restrict__ tau, float *dof, float *root) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.n) return;
-  step_robot(a, r, HeightField{f.h, f.rows, f.cols, f.hscale, f.vscale, f.x0, f.y0, f.origin[2 * r], f.origin[2 * r + 1]}, tau, dof, root);
+  if (r < a.n) step_robot(a, r, f, m, tau, dof, root);
 }
 }  // namespace
 
 namespace simint {
 
 hipError_t plant_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream) {
-  const PlantArgs a{s->n, s->dt, s->d_f64, s->d_i32, s->d_type, s->d_params, s->d_plant};
-  if (s->d_heights) {
-    const FieldArgs f{s->d_origin, s->d_heights, s->rows, s->cols, s->hscale, s->vscale, s->x0, s->y0};
-    hipLaunchKernelGGL(plant_step_field_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, a, f, d_tau, d_dof, d_root);
-  } else {
-    hipLaunchKernelGGL(plant_step_plane_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, a, (const double *)s->d_slope, d_tau, d_dof, d_root);
-  }
+  const PlantRecord m{s->d_plant};
+  if (s->d_heights) hipLaunchKernelGGL(plant_step_field_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, step_args(s), m, field_source(s), d_tau, d_dof, d_root);
+  else hipLaunchKernelGGL(plant_step_plane_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, step_args(s), m, plane_source(s), d_tau, d_dof, d_root);
   return hipGetLastError();
 }
 
@@ -202,8 +153,7 @@ int mpc_plant_rand_get_params(mpc_plant_rand *h, double *h_params) {
   DeviceGuard guard_(h->device);
   const size_t n = (size_t)h->n;
   std::vector<double> rec(kPlant * n);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(rec.data(), h->d_plant, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(mpchost::sync_copy(rec.data(), h->d_plant, rec.size(), hipMemcpyDeviceToHost));
   for (size_t r = 0; r < n; ++r)
     for (int j = 0; j < kPlant; ++j) h_params[r * kPlant + j] = rec[j * n + r];
   return MPC_OK;
@@ -225,9 +175,7 @@ int mpc_plant_rand_set_params(mpc_plant_rand *h, const double *h_params, const d
   std::vector<double> rec(kPlant * n);
   for (size_t r = 0; r < n; ++r)
     for (int j = 0; j < kPlant; ++j) rec[j * n + r] = h_params[r * kPlant + j];
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_plant, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(mpchost::sync_copy(h->d_plant, rec.data(), rec.size(), hipMemcpyHostToDevice));
   return MPC_OK;
 }
 
@@ -235,8 +183,7 @@ int mpc_plant_rand_get_counters(mpc_plant_rand *h, unsigned int *h_counters) {
   if (!h || !h_counters) return fail(MPC_E_ARG, "mpc_plant_rand_get_counters: null argument");
   if (!h->d_plant) return fail(MPC_E_ARG, "mpc_plant_rand_get_counters: no sim attached (mpc_plant_rand_attach)");
   DeviceGuard guard_(h->device);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h_counters, h->d_counter, sizeof(unsigned) * (size_t)h->n, hipMemcpyDeviceToHost));
+  HIP_TRY(mpchost::sync_copy(h_counters, h->d_counter.get(), (size_t)h->n, hipMemcpyDeviceToHost));
   return MPC_OK;
 }
 
@@ -244,9 +191,7 @@ int mpc_plant_rand_set_counters(mpc_plant_rand *h, const unsigned int *h_counter
   if (!h || !h_counters) return fail(MPC_E_ARG, "mpc_plant_rand_set_counters: null argument");
   if (!h->d_plant) return fail(MPC_E_ARG, "mpc_plant_rand_set_counters: no sim attached (mpc_plant_rand_attach)");
   DeviceGuard guard_(h->device);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_counter, h_counters, sizeof(unsigned) * (size_t)h->n, hipMemcpyHostToDevice));
-  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(mpchost::sync_copy(h->d_counter.get(), h_counters, (size_t)h->n, hipMemcpyHostToDevice));
   return MPC_OK;
 }
 

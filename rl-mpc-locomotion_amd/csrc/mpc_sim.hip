@@ -1,6 +1,7 @@
 // mpc_sim.hip -- the C ABI of include/mpc_sim.h: the batched toy plant (toy_sim.h) on the device, one lane per robot.
 // The state is structure-of-arrays in HBM (entry j of robot r at [j * n + r]: the lanes of a wave load and store consecutive words); a tick
-// loads a robot's 49 doubles and 9 ints into registers, runs toy_step and writes the state back and the float32 observation out.
+// loads a robot's 49 doubles and 9 ints into registers, runs toy_step and writes the state back and the float32 observation out.  That shell is
+// sim_step.h's, shared with the other units' step kernels; the kernels here are its plane ground and nominal plant.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -11,66 +12,29 @@
 #include "mpc_sim_internal.h"
 #include "toy_sim.h"
 
-using namespace toysim;
+using namespace simstep;               // (and with it toysim)
 using mpchost::DeviceGuard;
 using simint::kSimThreads;
+using simint::plane_source;
 using simint::sim_grid;
+using simint::step_args;
 
 namespace {
 thread_local mpchost::ErrorSlot g_err;
 int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
-struct SimArgs {
-  int n;
-  double dt;
-  double *f64;                       // [kF64][n]
-  int *i32;                          // [kI32][n]
-  const int *type;                   // [n]
-  const double *slope;               // [n][2]
-  const double *yaw0;                // [n]
-  const Params *params;              // [n_types]
-};
-
-__device__ __forceinline__ void write_obs(const State &s, int r, float *dof, float *root) {
-  float d[24], b[13];
-  observe(s, d, b);
-  if (dof) {
-#pragma unroll
-    for (int i = 0; i < 24; ++i) dof[(size_t)r * 24 + i] = d[i];
-  }
-  if (root) {
-#pragma unroll
-    for (int i = 0; i < 13; ++i) root[(size_t)r * 13 + i] = b[i];
-  }
-}
-
 // (re)initialise robots ids[0 .. k) (all n when ids is null)
-__global__ __launch_bounds__(kSimThreads) void sim_init_kernel(SimArgs a, const int *ids, int k) {
+__global__ __launch_bounds__(kSimThreads) void sim_init_kernel(Args a, PlaneSource g, const double *yaw0, const int *ids, int k) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  const int r = ids ? ids[i] : i;
-  if (r < 0 || r >= a.n) return;
-  State s;
-  toy_init(s, a.params[a.type[r]], a.yaw0[r], Plane{a.slope[2 * r], a.slope[2 * r + 1]});
-  pack(s, a.f64 + r, a.i32 + r, a.n);
+  if (i < k) init_robot(a, i, ids, g, yaw0);
 }
 
-__global__ __launch_bounds__(kSimThreads) void sim_step_kernel(SimArgs a, const float *__restrict__ tau, float *dof, float *root) {
+__global__ __launch_bounds__(kSimThreads) void sim_step_kernel(Args a, PlaneSource g, const float *__restrict__ tau, float *dof, float *root) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.n) return;
-  State s;
-  unpack(s, a.f64 + r, a.i32 + r, a.n);
-  if (!s.fell) {
-    double t[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) t[i] = (double)tau[(size_t)r * 12 + i];
-    toy_step(s, a.params[a.type[r]], t, a.dt, a.slope[2 * r], a.slope[2 * r + 1]);
-    pack(s, a.f64 + r, a.i32 + r, a.n);
-  }
-  write_obs(s, r, dof, root);
+  if (r < a.n) step_robot(a, r, g, Nominal{}, tau, dof, root);
 }
 
-__global__ __launch_bounds__(kSimThreads) void sim_observe_kernel(SimArgs a, float *dof, float *root) {
+__global__ __launch_bounds__(kSimThreads) void sim_observe_kernel(Args a, float *dof, float *root) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.n) return;
   State s;
@@ -89,8 +53,7 @@ __global__ __launch_bounds__(kSimThreads) void sim_flags_kernel(int n, const int
 }
 }  // namespace
 
-// (struct mpc_sim: mpc_sim_internal.h)
-static SimArgs sim_args(const mpc_sim *s) { return SimArgs{s->n, s->dt, s->d_f64, s->d_i32, s->d_type, s->d_slope, s->d_yaw, s->d_params}; }
+// (struct mpc_sim and the builders of the launch arguments: mpc_sim_internal.h)
 
 extern "C" {
 
@@ -125,7 +88,7 @@ int mpc_sim_create(mpc_sim **out, int n, const int *robot_type, int n_types, con
     mpc_sim_destroy(s);
     return fail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
   }
-  hipLaunchKernelGGL(sim_init_kernel, sim_grid(n), dim3(kSimThreads), 0, nullptr, sim_args(s), (const int *)nullptr, n);
+  hipLaunchKernelGGL(sim_init_kernel, sim_grid(n), dim3(kSimThreads), 0, nullptr, step_args(s), plane_source(s), (const double *)s->d_yaw, (const int *)nullptr, n);
   if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
     mpc_sim_destroy(s);
     return fail(MPC_E_HIP, std::string("mpc_sim_create: ") + hipGetErrorString(e));
@@ -151,7 +114,7 @@ int mpc_sim_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, vo
     HIP_TRY(simint::terrain_launch_step(s, d_tau, d_dof, d_root, reinterpret_cast<hipStream_t>(stream)));
     return MPC_OK;
   }
-  hipLaunchKernelGGL(sim_step_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), sim_args(s), d_tau, d_dof, d_root);
+  hipLaunchKernelGGL(sim_step_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), step_args(s), plane_source(s), d_tau, d_dof, d_root);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
@@ -159,7 +122,7 @@ int mpc_sim_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, vo
 int mpc_sim_observe(mpc_sim *s, float *d_dof, float *d_root, void *stream) {
   if (!s || (!d_dof && !d_root)) return fail(MPC_E_ARG, "mpc_sim_observe: bad argument");
   DeviceGuard guard_(s->device);
-  hipLaunchKernelGGL(sim_observe_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), sim_args(s), d_dof, d_root);
+  hipLaunchKernelGGL(sim_observe_kernel, sim_grid(s->n), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), step_args(s), d_dof, d_root);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
@@ -172,7 +135,7 @@ int mpc_sim_reset_device(mpc_sim *s, const int *d_ids, int k, void *stream) {
     HIP_TRY(simint::terrain_launch_init(s, d_ids, k, reinterpret_cast<hipStream_t>(stream)));
     return MPC_OK;
   }
-  hipLaunchKernelGGL(sim_init_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), sim_args(s), d_ids, k);
+  hipLaunchKernelGGL(sim_init_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), step_args(s), plane_source(s), (const double *)s->d_yaw, d_ids, k);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
@@ -183,8 +146,7 @@ int mpc_sim_get_state(mpc_sim *s, double *h_f64, int *h_i32) {
   const size_t n = (size_t)s->n;
   std::vector<double> f(kF64 * n);
   std::vector<int> k(kI32 * n);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(f.data(), s->d_f64, sizeof(double) * f.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(mpchost::sync_copy(f.data(), s->d_f64.get(), f.size(), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(k.data(), s->d_i32, sizeof(int) * k.size(), hipMemcpyDeviceToHost));
   for (size_t r = 0; r < n; ++r) {
     for (int j = 0; j < kF64; ++j) h_f64[r * kF64 + j] = f[j * n + r];

@@ -1,15 +1,16 @@
 // mpc_sim_internal.h -- what the library's other units may know of an mpc_sim (include/mpc_sim.h): its device buffers, once
-// mpc_terrain_attach (include/mpc_terrain.h) has run its height field, and once mpc_plant_rand_attach (mpc_plant_rand.h) has run its per-robot
-// plant record.  mpc_sim.hip owns the handle and the plane kernels; mpc_terrain.hip holds the height-field instantiations of toy_sim.h and is
-// what mpc_sim_step / mpc_sim_reset_device launch for a sim with a terrain; mpc_plant_rand.hip holds the instantiations of toy_step_plant on both
-// grounds and is what mpc_sim_step launches for a sim with a plant record; mpc_friction.hip holds the Coulomb instantiations of the step on
-// both grounds and is what mpc_sim_step launches once mpc_friction_attach (mpc_friction.h) has run, with or without a plant record (host-side
-// branches on the handle).  Not part of the C ABI.
+// mpc_terrain_attach (include/mpc_terrain.h) has run its height field, once mpc_plant_rand_attach (mpc_plant_rand.h) has run its per-robot plant
+// record, and once mpc_friction_attach (mpc_friction.h) has run its friction record.  The shell of every init and step kernel of the plant is
+// sim_step.h's, and the builders of its arguments from a handle stand below.  Each unit holds the kernels of its own feature, a bounds check and
+// one call into that shell each: mpc_sim.hip owns the handle and the plane kernels; mpc_terrain.hip holds the height-field kernels, which
+// mpc_sim_step / mpc_sim_reset_device launch for a sim with a terrain; mpc_plant_rand.hip the step with a plant record on both grounds;
+// mpc_friction.hip the Coulomb step on both grounds, with or without a plant record (a host-side branch on the handle).  Not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "mpc_host.h"
+#include "sim_step.h"
 #include "toy_sim.h"
 
 struct mpc_sim {
@@ -40,6 +41,13 @@ namespace simint {
 constexpr int kSimThreads = 64;        // one wave per workgroup: 4096 robots are 64 waves on 64 CUs
 
 inline dim3 sim_grid(int k) { return dim3((unsigned)((k + kSimThreads - 1) / kSimThreads)); }
+
+// sim_step.h's launch arguments of a sim, and its two grounds (the field once a terrain is attached)
+inline simstep::Args step_args(const mpc_sim *s) { return simstep::Args{s->n, s->dt, s->d_f64, s->d_i32, s->d_type, s->d_params}; }
+inline simstep::PlaneSource plane_source(const mpc_sim *s) { return simstep::PlaneSource{s->d_slope}; }
+inline simstep::FieldSource field_source(const mpc_sim *s) {
+  return simstep::FieldSource{s->d_origin, s->d_heights, s->rows, s->cols, s->hscale, s->vscale, s->x0, s->y0};
+}
 
 // the terrain instantiations' launches (mpc_terrain.hip); the caller has set the device.  ids null = all n robots.
 hipError_t terrain_launch_init(mpc_sim *s, const int *d_ids, int k, hipStream_t stream);

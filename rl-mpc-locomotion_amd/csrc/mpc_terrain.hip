@@ -1,7 +1,8 @@
 // mpc_terrain.hip -- the C ABI of include/mpc_terrain.h: toy_sim.h's HeightField instantiations of toy_init / toy_step on the device, one lane
-// per robot as in mpc_sim.hip, a point query of the surface, and the accessors of the origin array (mpc_curriculum.h).  The field is int16 in HBM, read with plain 2-byte loads (four per lookup): a
-// 500 x 500 field is 500 KB and stays in the caches.  mpc_sim.hip owns the handle (mpc_sim_internal.h) and launches these through
-// simint::terrain_launch_* once a terrain is attached.
+// per robot as in mpc_sim.hip (sim_step.h's shell with its field source and the nominal plant), a point query of the surface, and the accessors
+// of the origin array (mpc_curriculum.h).  The field is int16 in HBM, read with plain 2-byte loads (four per lookup): a 500 x 500 field is
+// 500 KB and stays in the caches.  mpc_sim.hip owns the handle (mpc_sim_internal.h) and launches these through simint::terrain_launch_* once a
+// terrain is attached.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,7 +16,7 @@
 #include "mpc_sim_internal.h"
 #include "toy_sim.h"
 
-using namespace toysim;
+using namespace simstep;               // (and with it toysim)
 using mpchost::DeviceGuard;
 using simint::kSimThreads;
 using simint::sim_grid;
@@ -24,68 +25,22 @@ namespace {
 thread_local mpchost::ErrorSlot g_err;
 int fail(int code, const std::string &msg) { return g_err.fail(code, msg); }
 
-struct TerrainArgs {
-  int n;
-  double dt;
-  double *f64;                       // [kF64][n]
-  int *i32;                          // [kI32][n]
-  const int *type;                   // [n]
-  const double *yaw0;                // [n]
-  const Params *params;              // [n_types]
-  const double *origin;              // [n][2]
-  const short *h;                    // [rows][cols]
-  int rows, cols;
-  double hscale, vscale, x0, y0;
-};
-
-__device__ __forceinline__ HeightField field_of(const TerrainArgs &a, int r) {
-  return HeightField{a.h, a.rows, a.cols, a.hscale, a.vscale, a.x0, a.y0, a.origin[2 * r], a.origin[2 * r + 1]};
-}
-
-__device__ __forceinline__ void write_obs(const State &s, int r, float *dof, float *root) {
-  float d[24], b[13];
-  observe(s, d, b);
-  if (dof) {
-#pragma unroll
-    for (int i = 0; i < 24; ++i) dof[(size_t)r * 24 + i] = d[i];
-  }
-  if (root) {
-#pragma unroll
-    for (int i = 0; i < 13; ++i) root[(size_t)r * 13 + i] = b[i];
-  }
-}
-
 // (re)initialise robots ids[0 .. k) (all n when ids is null) standing on the terrain
-__global__ __launch_bounds__(kSimThreads) void terrain_init_kernel(TerrainArgs a, const int *ids, int k) {
+__global__ __launch_bounds__(kSimThreads) void terrain_init_kernel(Args a, FieldSource f, const double *yaw0, const int *ids, int k) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  const int r = ids ? ids[i] : i;
-  if (r < 0 || r >= a.n) return;
-  State s;
-  toy_init(s, a.params[a.type[r]], a.yaw0[r], field_of(a, r));
-  pack(s, a.f64 + r, a.i32 + r, a.n);
+  if (i < k) init_robot(a, i, ids, f, yaw0);
 }
 
-__global__ __launch_bounds__(kSimThreads) void terrain_step_kernel(TerrainArgs a, const float *__restrict__ tau, float *dof, float *root) {
+__global__ __launch_bounds__(kSimThreads) void terrain_step_kernel(Args a, FieldSource f, const float *__restrict__ tau, float *dof, float *root) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.n) return;
-  State s;
-  unpack(s, a.f64 + r, a.i32 + r, a.n);
-  if (!s.fell) {
-    double t[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) t[i] = (double)tau[(size_t)r * 12 + i];
-    toy_step(s, a.params[a.type[r]], t, a.dt, field_of(a, r));
-    pack(s, a.f64 + r, a.i32 + r, a.n);
-  }
-  write_obs(s, r, dof, root);
+  if (r < a.n) step_robot(a, r, f, Nominal{}, tau, dof, root);
 }
 
 // the surface at k points of the terrain's own frame
-__global__ __launch_bounds__(kSimThreads) void terrain_query_kernel(TerrainArgs a, const double *__restrict__ xy, int k, double *z, double *normal) {
+__global__ __launch_bounds__(kSimThreads) void terrain_query_kernel(FieldSource f, const double *__restrict__ xy, int k, double *z, double *normal) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= k) return;
-  const HeightField g{a.h, a.rows, a.cols, a.hscale, a.vscale, a.x0, a.y0, 0.0, 0.0};
+  const HeightField g = f.at(0.0, 0.0);
   const double p[2] = {xy[2 * (size_t)i], xy[2 * (size_t)i + 1]};
   z[i] = g.height(p);
   if (normal) {
@@ -95,22 +50,17 @@ __global__ __launch_bounds__(kSimThreads) void terrain_query_kernel(TerrainArgs 
     for (int j = 0; j < 3; ++j) normal[3 * (size_t)i + j] = nn[j];
   }
 }
-
-TerrainArgs terrain_args(const mpc_sim *s) {
-  return TerrainArgs{s->n, s->dt, s->d_f64, s->d_i32, s->d_type, s->d_yaw, s->d_params, s->d_origin, s->d_heights, s->rows, s->cols,
-                     s->hscale, s->vscale, s->x0, s->y0};
-}
 }  // namespace
 
 namespace simint {
 
 hipError_t terrain_launch_init(mpc_sim *s, const int *d_ids, int k, hipStream_t stream) {
-  hipLaunchKernelGGL(terrain_init_kernel, sim_grid(k), dim3(kSimThreads), 0, stream, terrain_args(s), d_ids, k);
+  hipLaunchKernelGGL(terrain_init_kernel, sim_grid(k), dim3(kSimThreads), 0, stream, step_args(s), field_source(s), (const double *)s->d_yaw, d_ids, k);
   return hipGetLastError();
 }
 
 hipError_t terrain_launch_step(mpc_sim *s, const float *d_tau, float *d_dof, float *d_root, hipStream_t stream) {
-  hipLaunchKernelGGL(terrain_step_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, terrain_args(s), d_tau, d_dof, d_root);
+  hipLaunchKernelGGL(terrain_step_kernel, sim_grid(s->n), dim3(kSimThreads), 0, stream, step_args(s), field_source(s), d_tau, d_dof, d_root);
   return hipGetLastError();
 }
 
@@ -161,7 +111,7 @@ int mpc_terrain_query(mpc_sim *s, const double *d_xy, int k, double *d_z, double
   if (!s->d_heights) return fail(MPC_E_ARG, "mpc_terrain_query: the sim has no terrain attached");
   if (k == 0) return MPC_OK;
   DeviceGuard guard_(s->device);
-  hipLaunchKernelGGL(terrain_query_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), terrain_args(s), d_xy, k, d_z, d_normal);
+  hipLaunchKernelGGL(terrain_query_kernel, sim_grid(k), dim3(kSimThreads), 0, reinterpret_cast<hipStream_t>(stream), simint::field_source(s), d_xy, k, d_z, d_normal);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
 }
@@ -180,8 +130,7 @@ int mpc_terrain_get_origins(mpc_sim *s, double *h_origin) {
   if (!s) return fail(MPC_E_ARG, "mpc_terrain_get_origins: null sim handle");
   if (!s->d_origin) return fail(MPC_E_ARG, "mpc_terrain_get_origins: the sim has no terrain attached");
   DeviceGuard guard_(s->device);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h_origin, s->d_origin, sizeof(double) * 2 * (size_t)s->n, hipMemcpyDeviceToHost));
+  HIP_TRY(mpchost::sync_copy(h_origin, s->d_origin.get(), 2 * (size_t)s->n, hipMemcpyDeviceToHost));
   return MPC_OK;
 }
 

@@ -176,11 +176,7 @@ class DomainRand:
         self.push_interval = None
         self._handle, self._scales, self.sim = None, {}, None
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib._LIB is not None:
-            _lib._LIB.mpc_drand_destroy(h)
-            self._handle = None
+    __del__ = _lib.finalizer("mpc_drand_destroy")
 
     @classmethod
     def from_dr_params(cls, n, dr_params, seed=0, push=None, device=None):

@@ -89,12 +89,14 @@ def _mu_array(mu, n):
     return np.ascontiguousarray(m)
 
 
-class Friction:
+class Friction(_lib.DrawnRecord):
     """The friction coefficients of ``n`` environments and the step's two outputs.  ``bind(sim)`` attaches the record to a ``BatchedToySim`` (whose
     ``step`` consumes it from then on and fills ``contact_forces`` and ``foot_slip``), ``draw(ids)`` is the one launch per reset;
     ``BatchedRLTask(friction=...)`` does both.  ``spec``: a ``FrictionSpec`` to draw from, or None for coefficients that are only ever set; ``mu``:
     the coefficients before the first draw, a number or [n] (None: inf, the anchor holds).  ``get_mu`` / ``set_mu`` move the coefficients [n]
     between host and device, ``state_dict`` / ``load_state_dict`` the coefficients and the draw counters."""
+    WHAT, COUNTERS = "friction", (lib, check, "mpc_friction_get_counters", "mpc_friction_set_counters")
+    __del__ = _lib.finalizer("mpc_friction_destroy")
 
     def __init__(self, n, spec=None, mu=None, seed=0, device=None):
         self.n = int(n)
@@ -110,23 +112,12 @@ class Friction:
         self._handle, self.sim = None, None
         self.contact_forces, self.foot_slip = None, None
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib._LIB is not None:
-            _lib._LIB.mpc_friction_destroy(h)
-            self._handle = None
-
     def validate(self, n=None):
         """Everything that can be refused without the device; the task calls it with its batch size."""
         if n is not None and int(n) != self.n:
             raise ValueError(f"the friction holds {self.n} environments, the task {int(n)}")
         if self.spec is not None:
             self.spec.validate()
-
-    def _bound(self):
-        if self.sim is None:
-            raise ValueError("the friction is not bound to a sim (bind)")
-        return self._handle
 
     def bind(self, sim):
         """Give ``sim`` (a ``BatchedToySim`` with ``n`` robots) its friction record and its two output tensors, and this object its draw counters,
@@ -154,17 +145,12 @@ class Friction:
         """One launch: every environment listed in ``ids`` (a cuda int32 tensor as ``TaskPostPhysics.begin`` returns it -- r where environment r is
         reset, -1 elsewhere; None: all of them) has its force and slip rows zeroed and, where ``resample`` (None: the spec's resample is
         ``"reset"``), draws its coefficient anew and counts the draw.  Stream-ordered, no host synchronisation."""
-        import torch
         h = self._bound()
         if resample is None:
             resample = self.spec is not None and self.spec.resample == "reset"
         if resample and self.spec is None:
             raise ValueError("the friction has no spec to draw from")
-        if ids is None:
-            ptr, k = None, self.n
-        else:
-            _lib.tensor_arg(ids, torch.int32, ids.numel(), "ids")
-            ptr, k = ids.data_ptr(), ids.numel()
+        ptr, k = self._ids(ids)
         lo, hi, buckets = (0.0, 0.0, 0) if self.spec is None else (float(self.spec.range[0]), float(self.spec.range[1]), int(self.spec.buckets))
         check(lib().mpc_friction_draw(h, ptr, k, lo, hi, buckets, int(bool(resample)), _lib.stream(self.device)), "mpc_friction_draw")
         self.launches += 1
@@ -177,26 +163,13 @@ class Friction:
 
     def set_mu(self, mu):
         """Overwrite the coefficients from a number or a host array [n] (>= 0, not NaN).  Synchronous."""
-        m = _mu_array(mu, self.n)
+        m = _mu_array(mu, self.n)                      # (a local: the array lives until the call has returned)
         check(lib().mpc_friction_set_mu(self._bound(), m.ctypes.data), "mpc_friction_set_mu")
-
-    def get_counters(self):
-        """How many draws each environment has made: [n] uint32.  Synchronous."""
-        c = np.zeros(self.n, np.uint32)
-        check(lib().mpc_friction_get_counters(self._bound(), c.ctypes.data), "mpc_friction_get_counters")
-        return c
-
-    def set_counters(self, counters):
-        c = np.ascontiguousarray(counters, dtype=np.uint32)
-        if c.shape != (self.n,):
-            raise ValueError(f"counters: [{self.n}] expected")
-        check(lib().mpc_friction_set_counters(self._bound(), c.ctypes.data), "mpc_friction_set_counters")
 
     def state_dict(self):
         import torch
         return {"mu": torch.from_numpy(self.get_mu()), "counters": torch.from_numpy(self.get_counters().astype(np.int64))}
 
     def load_state_dict(self, state):
-        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
-        self.set_mu(host(state["mu"]).astype(np.float64))
-        self.set_counters(host(state["counters"]).astype(np.uint32))
+        self.set_mu(_lib.host_array(state["mu"], np.float64))
+        self.set_counters(_lib.host_array(state["counters"], np.uint32))

@@ -89,10 +89,12 @@ class PlantSpec:
                     raise ValueError(f"plant: a payload of {lo} kg leaves robot type {rt} (mass {mass} kg) without a positive mass")
 
 
-class PlantRand:
+class PlantRand(_lib.DrawnRecord):
     """The plant records of ``n`` environments.  ``bind(sim)`` attaches the record to a ``BatchedToySim`` (whose ``step`` consumes it from then
     on), ``draw(ids)`` is the one launch per reset; ``BatchedRLTask(plant_rand=...)`` does both.  ``get_params`` / ``set_params`` move the record
     [n, 3] (payload, strength, grav_z) between host and device, ``state_dict`` / ``load_state_dict`` the record and the draw counters."""
+    WHAT, COUNTERS = "plant randomisation", (lib, check, "mpc_plant_rand_get_counters", "mpc_plant_rand_set_counters")
+    __del__ = _lib.finalizer("mpc_plant_rand_destroy")
 
     def __init__(self, n, spec=None, seed=0, device=None):
         self.n = int(n)
@@ -106,12 +108,6 @@ class PlantRand:
         self._handle, self.sim, self._mass = None, None, None
         self._present = (C.c_int * 3)(*[int(r is not None) for r in self.spec.ranges()])
         self._ranges = (C.c_double * 6)(*[float(v) for r in self.spec.ranges() for v in (r if r is not None else (0.0, 0.0))])
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h and _lib._LIB is not None:
-            _lib._LIB.mpc_plant_rand_destroy(h)
-            self._handle = None
 
     def validate(self, n=None, robot_type=None):
         """Everything that can be refused without the device; the task calls it with its batch size and its robot types."""
@@ -130,11 +126,6 @@ class PlantRand:
             self._handle = h
         return self._handle
 
-    def _bound(self):
-        if self.sim is None:
-            raise ValueError("the plant randomisation is not bound to a sim (bind)")
-        return self._handle
-
     def bind(self, sim):
         """Give ``sim`` (a ``BatchedToySim`` with ``n`` robots) its plant record, neutral, and this object its draw counters, zero.  Once."""
         check(lib().mpc_plant_rand_attach(self._ensure(), sim._handle), "mpc_plant_rand_attach")
@@ -145,13 +136,8 @@ class PlantRand:
     def draw(self, ids=None):
         """One launch: every environment listed in ``ids`` (a cuda int32 tensor as ``TaskPostPhysics.begin`` returns it -- r where environment r is
         reset, -1 elsewhere; None: all of them) draws its record anew and counts the draw.  Stream-ordered, no host synchronisation."""
-        import torch
         h = self._bound()
-        if ids is None:
-            ptr, k = None, self.n
-        else:
-            _lib.tensor_arg(ids, torch.int32, ids.numel(), "ids")
-            ptr, k = ids.data_ptr(), ids.numel()
+        ptr, k = self._ids(ids)
         check(lib().mpc_plant_rand_draw(h, ptr, k, self._present, self._ranges, _lib.stream(self.device)), "mpc_plant_rand_draw")
         self.launches += 1
 
@@ -169,23 +155,10 @@ class PlantRand:
         h = self._bound()
         check(lib().mpc_plant_rand_set_params(h, p.ctypes.data, None if self._mass is None else self._mass.ctypes.data), "mpc_plant_rand_set_params")
 
-    def get_counters(self):
-        """How many draws each environment has made: [n] uint32.  Synchronous."""
-        c = np.zeros(self.n, np.uint32)
-        check(lib().mpc_plant_rand_get_counters(self._bound(), c.ctypes.data), "mpc_plant_rand_get_counters")
-        return c
-
-    def set_counters(self, counters):
-        c = np.ascontiguousarray(counters, dtype=np.uint32)
-        if c.shape != (self.n,):
-            raise ValueError(f"counters: [{self.n}] expected")
-        check(lib().mpc_plant_rand_set_counters(self._bound(), c.ctypes.data), "mpc_plant_rand_set_counters")
-
     def state_dict(self):
         import torch
         return {"params": torch.from_numpy(self.get_params()), "counters": torch.from_numpy(self.get_counters().astype(np.int64))}
 
     def load_state_dict(self, state):
-        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
-        self.set_params(host(state["params"]).astype(np.float64))
-        self.set_counters(host(state["counters"]).astype(np.uint32))
+        self.set_params(_lib.host_array(state["params"], np.float64))
+        self.set_counters(_lib.host_array(state["counters"], np.uint32))

@@ -260,6 +260,17 @@ def test_device_draws_equal_the_restatement_and_round_trip(buckets):
         fr.set_mu(np.where(env == 9, -0.5, 0.4))
 
 
+def test_set_mu_takes_a_number_and_arrays_it_has_to_convert():
+    """A number, another dtype and a strided view all make set_mu build a new [n] float64 array, which nobody else holds: it has to live until
+    the library has copied it."""
+    fr = FR.Friction(N, device=DEV)
+    fr.bind(_sim("plane"))
+    f32, strided = np.linspace(0.25, 2.0, N, dtype=np.float32), np.linspace(0.0, 3.0, 2 * N)[::2]
+    for mu, want in ((0.4, np.full(N, 0.4)), (f32, f32.astype(np.float64)), (strided, strided.copy()), (np.inf, np.full(N, np.inf))):
+        fr.set_mu(mu)
+        assert fr.get_mu().tobytes() == want.tobytes()
+
+
 # ---- 11. end to end -------------------------------------------------------------------------------------------------------------------------------------------
 def _task(n, friction=True, seed=11, episode_length_s=0.2):
     cfg = _cfg(episode_length_s=episode_length_s, seed=5)

@@ -457,3 +457,24 @@ def test_kernels_compile_for_gfx950_and_the_step_kernels_use_no_more_scratch_tha
         assert mine[1] <= plain[ground][1] and mine[2] == 0
     priv = _resources("mpc_privileged_obs", tmp_path)
     assert len(priv) == 2 and all(v[1:] == (0, 0) for v in priv.values()), priv
+
+
+# the kernels of the four units whose init and step kernels share csrc/sim_step.h's shell: each unit keeps its own, by name
+PLANT_KERNELS = {
+    "mpc_sim": {"sim_init_kernel", "sim_step_kernel", "sim_observe_kernel", "sim_flags_kernel"},
+    "mpc_terrain": {"terrain_init_kernel", "terrain_step_kernel", "terrain_query_kernel"},
+    "mpc_plant_rand": {"plant_draw_kernel", "plant_step_plane_kernel", "plant_step_field_kernel"},
+    "mpc_friction": {"friction_draw_kernel", "friction_step_plane_kernel", "friction_step_field_kernel"},
+}
+
+
+@pytest.mark.parametrize("unit", sorted(PLANT_KERNELS))
+def test_the_plant_units_keep_their_kernels_and_the_shared_shell_costs_no_scratch_and_no_lds(unit, tmp_path):
+    """Compiled alone, a unit emits exactly its kernels, and every init and step kernel uses 0 bytes of LDS and 0 bytes of scratch: what each of
+    them compiled to (terrain's included) before the shell was shared."""
+    found = {re.search(r"\d+([a-z_]+_kernel)E", name).group(1): v for name, v in _resources(unit, tmp_path).items()}
+    assert set(found) == PLANT_KERNELS[unit], found
+    for name, (vgprs, scratch, lds) in found.items():
+        if "_init_" in name or "_step_" in name:
+            print(f"{name}: {vgprs} VGPRs, {scratch} scratch bytes, {lds} LDS bytes")
+            assert (scratch, lds) == (0, 0), (name, scratch, lds)

@@ -1,5 +1,6 @@
 """What the *_rate.py tools share: HIP events and the percentiles of their spans, the stage timer over BatchedRLTask.step's marks, the
-alternating-blocks wall-clock loop, legged_gym's terrain grid with a set of origins, and the head and the tail of a JSON record."""
+alternating-blocks wall-clock loop, legged_gym's terrain grid with a set of origins, the head and the tail of a JSON record, and the speed
+verdict over closed_loop_rate.py --variants runs of a parent's library and a change's (also the command at the foot of this file)."""
 import json
 import os
 import sys
@@ -109,9 +110,35 @@ def clock(res, when):
     res["device_state"][when] = device_state(0, smi=False)
 
 
+def variants_verdict(parent, change):
+    """``parent``, ``change``: the records of ``closed_loop_rate.py --variants`` runs with the parent's library and with the change's (one process
+    per library, alternating, one session).  Per variant the runs' medians P and C, the bound max(P) + (max(P) - min(P)) -- the parent's own
+    run-to-run range in that session is the margin -- and whether median(C) holds it."""
+    runs = {"parent": parent, "change": change}
+    step = lambda r, name: r["variants_mixed_types"]["step"][name]
+    out = {"bound": "median(change) <= max(parent) + (max(parent) - min(parent)), per-run medians of the HIP-event spans around mpc_sim_step [ms]",
+           "kernel_source_sha256": change[0]["kernel_source_sha256"], "device_state": {s: [r["device_state"] for r in rs] for s, rs in runs.items()}, "variants": {}}
+    for name in parent[0]["variants_mixed_types"]["step"]:
+        P, C = ([step(r, name)["median_ms"] for r in rs] for rs in (parent, change))
+        bound = max(P) + (max(P) - min(P))
+        out["variants"][name] = {"parent_median_ms_per_run": P, "change_median_ms_per_run": C, "median_change_ms": med(C), "bound_ms": bound, "holds": med(C) <= bound,
+                                 "fallen_fraction_at_end": {s: [step(r, name)["fallen_fraction_at_end"] for r in rs] for s, rs in runs.items()}}
+    return out
+
+
 def emit(res, out=None):
     print(json.dumps(res, indent=1))
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as fh:
             json.dump(res, fh, indent=1)
+
+
+if __name__ == "__main__":               # python tools/_rate.py OUT.json --parent P1.json P2.json ... --change C1.json C2.json ...
+    import argparse
+    ap = argparse.ArgumentParser(description="variants_verdict over the records of closed_loop_rate.py --variants runs of two libraries")
+    ap.add_argument("out")
+    ap.add_argument("--parent", nargs="+", required=True)
+    ap.add_argument("--change", nargs="+", required=True)
+    a = ap.parse_args()
+    emit(variants_verdict(*([json.load(open(f)) for f in files] for files in (a.parent, a.change))), a.out)

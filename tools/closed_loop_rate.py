@@ -13,6 +13,9 @@ With --friction MU [MU ...] (inf is a value) the plant gets a Coulomb friction r
 and at each MU is measured against the plain step kernel in the same run, the closed loops alternating block by block (tools/_rate.py's spread of
 the HIP-event spans around mpc_sim_step), and per MU the fallen share and the mean slip per foot and tick after --ticks ticks are reported.
     python tools/closed_loop_rate.py --friction inf 0.4 --out profiles/friction_rate.json
+With --variants the six step kernels (plane and an all-zero field, each plain, with the neutral plant record and with mu = inf: one trajectory) are
+the alternating sides of one process, and nothing else is run: what a change to the kernels' shared shell (csrc/sim_step.h) is measured with.
+    python tools/closed_loop_rate.py --variants --out results/variants.json
 The kernel-trace stats of the same loop: rocprofv3 --kernel-trace --stats ... -- python tools/closed_loop_rate.py --ticks 50 --quick"""
 import argparse
 import json
@@ -31,6 +34,7 @@ from rl_mpc_locomotion_amd.locomotion import BatchedLocomotion  # noqa: E402
 from rl_mpc_locomotion_amd.terrain import Terrain, spread_origins  # noqa: E402
 from rl_mpc_locomotion_amd.toy_sim import BatchedToySim  # noqa: E402
 from bench import device_state  # noqa: E402
+import _rate  # noqa: E402  (tools/ is the script's directory)
 
 TROT = 0
 # the command record of the closed-loop golden's trot cases (tests/golden/closed_loop_h10.npz: vx, vy, wz, then 12 MPC weights and 0).  The
@@ -49,85 +53,86 @@ def make_terrain(kind, n, seed=0):
     return t, spread_origins(n, t, margin=3.0)
 
 
-def step_ab(robot_type, dev, terrain, origin, repeats=10, block=50):
-    """The plant's step on the plane and on the terrain, alternating repeat by repeat in one process: two closed loops (each sim with its own
-    controller, flat_ground=False), `block` ticks of one, then of the other, HIP events around mpc_sim_step alone.  Robots that have fallen are
-    frozen and cost nothing, so each side's fallen fraction at the end is reported with its time."""
+def side(robot_type, dev, flat_ground=True, mu=None, plant=False, **ground):
+    """One closed loop: (sim, controller, dof view, Friction or None).  `ground`: BatchedToySim's terrain and origin; `plant` attaches the neutral
+    plant record, `mu` a friction record with that coefficient."""
     n = len(robot_type)
-    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
-    cmd = torch.tensor(GOLDEN_TROT_CMD, dtype=torch.float32, device=dev).repeat(n, 1).contiguous()
-    sides = {}
-    for name, kw in (("plane", {}), ("terrain", {"terrain": terrain, "origin": origin})):
-        sim = BatchedToySim(robot_type, yaw0=yaw, device=dev, **kw)
-        ctl = BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=False, device=dev)
-        sides[name] = (sim, ctl, sim.dof_state.view(n, 12, 2), [])
+    sim = BatchedToySim(robot_type, yaw0=np.random.default_rng(0).uniform(-np.pi, np.pi, n), device=dev, **ground)
+    fr = None
+    if plant:
+        from rl_mpc_locomotion_amd.plant_rand import PlantRand
+        sim._plant_rand = PlantRand(n, device=dev)
+        sim._plant_rand.bind(sim)
+    if mu is not None:
+        from rl_mpc_locomotion_amd.friction import Friction
+        fr = Friction(n, mu=mu, device=dev)
+        fr.bind(sim)
+    return sim, BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=flat_ground, device=dev), sim.dof_state.view(n, 12, 2), fr
+
+
+def trot_cmd(n, dev):
+    return torch.tensor(GOLDEN_TROT_CMD, dtype=torch.float32, device=dev).repeat(n, 1).contiguous()
+
+
+def alternate(sides, repeats=10, block=50):
+    """The plant's step of each of `sides` {name: side(...)}, alternating in one process: ten warm-up ticks each, then `repeats` times `block` ticks
+    of one closed loop, then of the next, HIP events around mpc_sim_step alone.  Robots that have fallen are frozen and cost nothing, so every side's
+    fallen share at the end is reported with its times."""
+    sim0 = next(iter(sides.values()))[0]
+    cmd, ms = trot_cmd(sim0.n, sim0.device), {name: [] for name in sides}
+    for sim, ctl, view, _ in sides.values():
         for _ in range(10):
-            sim.step(ctl.run(sides[name][2], sim.root_states, cmd))
+            sim.step(ctl.run(view, sim.root_states, cmd))
     for _ in range(repeats):
-        for name, (sim, ctl, view, ms) in sides.items():
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(block)]
+        for name, (sim, ctl, view, _) in sides.items():
+            ev = [(_rate.ev(), _rate.ev()) for _ in range(block)]
             for a, b in ev:
                 tau = ctl.run(view, sim.root_states, cmd)
                 a.record(); sim.step(tau); b.record()
             torch.cuda.synchronize()
-            ms.append([a.elapsed_time(b) for a, b in ev])
-    out = {"repeats": repeats, "ticks_per_repeat": block, "robots": n}
-    for name, (sim, _, _, ms) in sides.items():
-        m = np.array(ms)
-        out[name] = {"step_ms_median": float(np.median(m)), "step_ms_p10": float(np.percentile(m, 10)), "step_ms_p90": float(np.percentile(m, 90)),
-                     "step_ms_median_per_repeat": [float(x) for x in np.median(m, 1)], "fallen_fraction_at_end": float(sim.flags()[1].float().mean().item())}
+            ms[name].append([a.elapsed_time(b) for a, b in ev])
+    step = {name: {**_rate.spread(np.array(m)), "median_ms_per_repeat": [float(x) for x in np.median(m, 1)],
+                   "fallen_fraction_at_end": float(sides[name][0].flags()[1].float().mean().item())} for name, m in ms.items()}
+    return {"repeats": repeats, "ticks_per_repeat": block, "robots": sim0.n, "step": step}
+
+
+def step_ab(robot_type, dev, terrain, origin):
+    """The plant's step on the plane and on the terrain (each sim with its own controller, flat_ground=False), alternating repeat by repeat."""
+    out = alternate({"plane": side(robot_type, dev, flat_ground=False), "terrain": side(robot_type, dev, flat_ground=False, terrain=terrain, origin=origin)})
+    keys = {"median_ms": "step_ms_median", "p10_ms": "step_ms_p10", "p90_ms": "step_ms_p90", "median_ms_per_repeat": "step_ms_median_per_repeat",
+            "fallen_fraction_at_end": "fallen_fraction_at_end"}            # (this record's keys are older than _rate.spread's)
+    out.update({name: {keys[k]: v for k, v in rec.items()} for name, rec in out.pop("step").items()})
     out["terrain_over_plane_median"] = out["terrain"]["step_ms_median"] / out["plane"]["step_ms_median"]
     # the first repeat alone: before robots have had the time to fall on the rougher ground
     out["terrain_over_plane_first_repeat"] = out["terrain"]["step_ms_median_per_repeat"][0] / out["plane"]["step_ms_median_per_repeat"][0]
     return out
 
 
-def friction_ab(robot_type, dev, mus, ticks, repeats=10, block=50):
-    """The plant's step without friction and with a friction record at each of `mus`, alternating block by block in one process: one closed loop a
-    side (each sim with its own controller), `block` ticks of one, then of the next, HIP events around mpc_sim_step alone.  Robots that have fallen
-    are frozen and cost nothing, so every side reports its fallen share with its time, and the ratio of the first repeat -- before a slippery floor
-    has had the time to fell anybody -- stands beside the ratio of the medians.  Then, per mu, a fresh closed loop of `ticks` ticks: the fallen
-    share and the mean slip per foot and tick."""
-    from rl_mpc_locomotion_amd.friction import Friction
-    import _rate                       # (tools/ is the script's directory)
-    n = len(robot_type)
-    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
-    cmd = torch.tensor(GOLDEN_TROT_CMD, dtype=torch.float32, device=dev).repeat(n, 1).contiguous()
+def variants_ab(robot_type, dev):
+    """All six step kernels as sides of one process: the plane and an all-zero field, each plain, with the neutral plant record, and with the
+    Coulomb contact at mu = inf -- six loops with one trajectory, so that every side steps the same robots through the same states."""
+    terrain, origin = make_terrain("zero", len(robot_type))
+    return alternate({f"{ground}_{model}": side(robot_type, dev, **kw, **gkw)
+                      for ground, gkw in (("plane", {}), ("field", {"terrain": terrain, "origin": origin}))
+                      for model, kw in (("plain", {}), ("plant", {"plant": True}), ("coulomb", {"mu": float("inf")}))})
 
-    def side(mu):
-        sim = BatchedToySim(robot_type, yaw0=yaw, device=dev)
-        fr = None
-        if mu is not None:
-            fr = Friction(n, mu=mu, device=dev)
-            fr.bind(sim)
-        return sim, BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=True, device=dev), sim.dof_state.view(n, 12, 2), fr
+
+def friction_ab(robot_type, dev, mus, ticks):
+    """The plant's step without friction and with a friction record at each of `mus`, alternating block by block; the ratio of the first repeat --
+    before a slippery floor has had the time to fell anybody -- stands beside the ratio of the medians.  Then, per mu, a fresh closed loop of
+    `ticks` ticks: the fallen share and the mean slip per foot and tick."""
+    n = len(robot_type)
+    cmd = trot_cmd(n, dev)
     name_of = lambda mu: "plain" if mu is None else "mu_" + repr(float(mu))
-    sides = {name_of(mu): side(mu) + ([],) for mu in [None] + list(mus)}
-    for sim, ctl, view, _, _ in sides.values():
-        for _ in range(10):
-            sim.step(ctl.run(view, sim.root_states, cmd))
-    for _ in range(repeats):
-        for sim, ctl, view, _, ms in sides.values():
-            ev = [(_rate.ev(), _rate.ev()) for _ in range(block)]
-            for a, b in ev:
-                tau = ctl.run(view, sim.root_states, cmd)
-                a.record(); sim.step(tau); b.record()
-            torch.cuda.synchronize()
-            ms.append([a.elapsed_time(b) for a, b in ev])
-    out = {"repeats": repeats, "ticks_per_repeat": block, "robots": n, "step": {}}
-    for name, (sim, _, _, _, ms) in sides.items():
-        m = np.array(ms)
-        out["step"][name] = {**_rate.spread(m), "median_ms_per_repeat": [float(x) for x in np.median(m, 1)],
-                             "fallen_fraction_at_end": float(sim.flags()[1].float().mean().item())}
+    out = alternate({name_of(mu): side(robot_type, dev, mu=mu) for mu in [None] + list(mus)})
     plain = out["step"]["plain"]
     for name, rec in out["step"].items():
         if name != "plain":
             rec["over_plain_median"] = rec["median_ms"] / plain["median_ms"]
             rec["over_plain_first_repeat"] = rec["median_ms_per_repeat"][0] / plain["median_ms_per_repeat"][0]
-    del sides
     out["closed_loop"] = {"ticks": ticks}
     for mu in mus:
-        sim, ctl, view, fr = side(mu)
+        sim, ctl, view, fr = side(robot_type, dev, mu=mu)
         slip = torch.zeros((), dtype=torch.float64, device=dev)
         slipping = torch.zeros((), dtype=torch.float64, device=dev)
         for _ in range(ticks):
@@ -144,13 +149,9 @@ def friction_ab(robot_type, dev, mus, ticks, repeats=10, block=50):
 
 def run(robot_type, ticks, dev, default_weights=False, terrain=None, origin=None, flat_ground=True):
     n = len(robot_type)
-    yaw = np.random.default_rng(0).uniform(-np.pi, np.pi, n)
-    ground = {} if terrain is None else {"terrain": terrain, "origin": origin}
-    sim = BatchedToySim(robot_type, yaw0=yaw, device=dev, **ground)
-    ctl = BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=flat_ground, device=dev)
+    sim, ctl, view, _ = side(robot_type, dev, flat_ground, **({} if terrain is None else {"terrain": terrain, "origin": origin}))
     cmd = torch.tensor(GOLDEN_TROT_CMD[:3] if default_weights else GOLDEN_TROT_CMD, dtype=torch.float32, device=dev).repeat(n, 1).contiguous()
-    view = sim.dof_state.view(n, 12, 2)
-    for _ in range(10):            # warm-up (first solves are cold)
+    for _ in range(10):           # warm-up (first solves are cold)
         sim.step(ctl.run(view, sim.root_states, cmd))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -158,8 +159,7 @@ def run(robot_type, ticks, dev, default_weights=False, terrain=None, origin=None
         sim.step(ctl.run(view, sim.root_states, cmd))
     torch.cuda.synchronize()
     loop_s = time.perf_counter() - t0
-    _, fell = sim.flags()
-    fell = fell.cpu().numpy()
+    fell = sim.flags()[1].cpu().numpy()
     rt = np.asarray(robot_type)
     out = {"robots": n, "ticks": ticks, "flat_ground": flat_ground, "weights": "robot table defaults" if default_weights else "closed-loop golden trot", "loop_s": loop_s,
            "robot_ticks_per_s": n * ticks / loop_s, "ms_per_tick": loop_s / ticks * 1e3, "fallen_fraction": float(fell.mean()),
@@ -167,10 +167,8 @@ def run(robot_type, ticks, dev, default_weights=False, terrain=None, origin=None
     if default_weights or terrain is not None or not flat_ground:       # (with --terrain the plant's step is step_ab's)
         return out
     # the plant alone, HIP events around mpc_sim_step inside the same closed loop (a fresh batch: every robot standing at the start)
-    sim = BatchedToySim(robot_type, yaw0=yaw, device=dev)
-    ctl = BatchedLocomotion(robot_type, [TROT] * n, horizon=10, flat_ground=True, device=dev)
-    view = sim.dof_state.view(n, 12, 2)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(ticks)]
+    sim, ctl, view, _ = side(robot_type, dev)
+    ev = [(_rate.ev(), _rate.ev()) for _ in range(ticks)]
     for a, b in ev:
         tau = ctl.run(view, sim.root_states, cmd)
         a.record(); sim.step(tau); b.record()
@@ -191,24 +189,25 @@ if __name__ == "__main__":
     ap.add_argument("--terrain-seed", type=int, default=0)
     ap.add_argument("--friction", nargs="+", type=float, metavar="MU",
                     help="friction coefficients (inf is one): the friction step against the plain one, and the fallen share and slip per MU; nothing else is run")
+    ap.add_argument("--variants", action="store_true", help="the six step kernels (plane / zero field x plain / neutral plant record / mu = inf) against each other; nothing else is run")
     ap.add_argument("--out")
     args = ap.parse_args()
     dev = "cuda:0"
     n = args.robots
     res = {"kernel_source_sha256": _lib.kernel_source_hash()}
-    if args.friction:
-        if any(not mu >= 0 for mu in args.friction):
+    mixed = [i % 3 for i in range(n)]
+    if args.friction or args.variants:
+        if any(not mu >= 0 for mu in args.friction or []):
             ap.error("--friction: every MU must be >= 0")
         res["device_state"] = {"before": device_state(0)}
-        res["friction_mixed_types"] = friction_ab([i % 3 for i in range(n)], dev, args.friction, args.ticks)
-        res["device_state"]["after"] = device_state(0, smi=False)
-        print(json.dumps(res, indent=1))
-        if args.out:
-            with open(args.out, "w") as fh:
-                json.dump(res, fh, indent=1)
+        if args.friction:
+            res["friction_mixed_types"] = friction_ab(mixed, dev, args.friction, args.ticks)
+        else:
+            res["variants_mixed_types"] = variants_ab(mixed, dev)
+        _rate.clock(res, "after")
+        _rate.emit(res, args.out)
         sys.exit(0)
     clock0 = None if args.quick else device_state(0)
-    mixed = [i % 3 for i in range(n)]
     legs = {"mixed_types": (mixed, False)} if args.quick else {"aliengo": ([0] * n, False), "mixed_types": (mixed, False), "mixed_types_default_weights": (mixed, True)}
     for name, (rt, dw) in legs.items():
         res[name] = run(rt, args.ticks, dev, default_weights=dw)
