@@ -18,8 +18,9 @@ _PLANT_RAND = ("PlantRand", "PlantSpec")
 _RECURRENT = ("ActorCriticRecurrent", "Memory", "RecurrentConfig")
 _REWARD_SHAPING = ("RewardShaping", "ShapingSpec")
 _FRICTION = ("Friction", "FrictionSpec")
+_CONTACT_TERMS = ("ContactTerms", "ContactSpec")
 
-__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS, "privileged_obs", *_PRIVILEGED_OBS, "plant_rand", *_PLANT_RAND, "recurrent", *_RECURRENT, "reward_shaping", *_REWARD_SHAPING, "friction", *_FRICTION]
+__all__ = ["layout", "quadruped", "gait", "synthetic", "toy_sim", "rl_task", "BatchedRLTask", "TaskConfig", "TaskPostPhysics", "ppo", *_PPO, "episode", *_EPISODE, "obs_norm", *_OBS_NORM, "curriculum", *_CURRICULUM, "height_scan", *_HEIGHT_SCAN, "domain_rand", *_DOMAIN_RAND, "episode_terms", *_EPISODE_TERMS, "privileged_obs", *_PRIVILEGED_OBS, "plant_rand", *_PLANT_RAND, "recurrent", *_RECURRENT, "reward_shaping", *_REWARD_SHAPING, "friction", *_FRICTION, "contact_terms", *_CONTACT_TERMS]
 
 
 def __getattr__(name):
@@ -60,4 +61,7 @@ def __getattr__(name):
     if name in _FRICTION:
         from . import friction
         return getattr(friction, name)
+    if name in _CONTACT_TERMS:
+        from . import contact_terms
+        return getattr(contact_terms, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

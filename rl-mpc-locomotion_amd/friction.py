@@ -16,8 +16,9 @@ device with a counter-based generator keyed by (seed, environment, draw index): 
 The MPC controller keeps planning with the robot table's mu = 0.4 while the plant disagrees.  Works together with ``plant_rand.PlantRand`` in either
 bind order.  ``Friction(n, mu=0.4)`` without a spec is a fixed coefficient (a scalar or [n]) and never draws.
 
-Not built: a friction column in the privileged row, per-level terrain friction, ``feet_slip`` / ``feet_contact_forces`` / stumble reward terms,
-passing the plant's mu to the controller.
+``contact_terms.ContactTerms`` reads the two outputs and the coefficients: ``feet_slip`` / ``feet_contact_forces`` / ``feet_stumble`` reward terms and a
+friction column with the ground reactions in the critic's privileged row.  Not built: per-level terrain friction, passing the plant's mu to the
+controller.
 
 ``FrictionSpec`` and ``Friction.validate`` are host arithmetic and need no GPU; the kernels do (MpcLibraryError without one, no CPU fallback).
 """

@@ -736,9 +736,10 @@ SCALARS = ("mean_reward", "done_rate", "value_loss", "surrogate_loss", "mean_noi
 
 
 def _riders(trainer):
-    """The riders of ``trainer`` (anything with its ``_scalars``, ``alg``, ``episode_stats``, ``curriculum`` and ``episode_terms``; ``reward_shaping`` where
-    it has one), in the record's order."""
+    """The riders of ``trainer`` (anything with its ``_scalars``, ``alg``, ``episode_stats``, ``curriculum`` and ``episode_terms``; ``reward_shaping`` and
+    ``contact_terms`` where it has one), in the record's order."""
     alg, curriculum, terms, shaping = trainer.alg, trainer.curriculum, trainer.episode_terms, getattr(trainer, "reward_shaping", None)
+    contact = getattr(trainer, "contact_terms", None)
 
     def learning_rate(values):                                                   # a device update: the device's value, which the host copies follow
         if values:
@@ -757,6 +758,8 @@ def _riders(trainer):
         riders.append(_Rider(lambda: terms.summary(), lambda values: {"episode_terms": terms.record(values)}, lambda: terms.new_window()))
     if shaping is not None:                                                      # the shaping terms' sums of the iteration's closed episodes, window by window
         riders.append(_Rider(lambda: shaping.summary(), lambda values: {"reward_shaping": shaping.record(values)}, lambda: shaping.new_window()))
+    if contact is not None:                                                      # the contact terms' sums, in the same way
+        riders.append(_Rider(lambda: contact.summary(), lambda values: {"contact_terms": contact.record(values)}, lambda: contact.new_window()))
     return riders
 
 
@@ -852,8 +855,8 @@ class PPOTrainer:
         self.device = _lib.device_of(device if device is not None else getattr(env, "device", None))
         torch.manual_seed(self.seed)
         c = self.cfg
-        self.num_privileged_obs, self.curriculum, self.episode_terms, self.plant_rand, self.reward_shaping, self.friction = (
-            getattr(env, name, None) for name in ("num_privileged_obs", "curriculum", "episode_terms", "plant_rand", "reward_shaping", "friction"))
+        self.num_privileged_obs, self.curriculum, self.episode_terms, self.plant_rand, self.reward_shaping, self.friction, self.contact_terms = (
+            getattr(env, name, None) for name in ("num_privileged_obs", "curriculum", "episode_terms", "plant_rand", "reward_shaping", "friction", "contact_terms"))
         priv = self.num_privileged_obs
         self.recurrent = recurrent
         self._prev_reset = None                                                  # the task's reset tensor of the tick before (kept for a net with memory only)
@@ -919,7 +922,8 @@ class PPOTrainer:
         the cumulative ``episodes_finished``; on an environment with a terrain ``curriculum`` also ``mean_terrain_level`` and ``terrain_level_by_type``
         as they stand after the iteration; on one with ``episode_terms`` also ``episode_terms``: ``rew_<term>`` over the episodes closed during the
         iteration, ``max_command_x``, ``min_command_x`` and ``command_widenings`` (``EpisodeTerms.record``); on one with ``reward_shaping`` also ``reward_shaping``: ``rew_<term>`` of the eight shaping terms over
-        the episodes closed during the iteration (``RewardShaping.record``).  ``init_at_random_ep_len``: before the first collection ``env.progress_buf`` is set to integers
+        the episodes closed during the iteration (``RewardShaping.record``); on one with ``contact_terms`` also ``contact_terms``: ``rew_<term>`` of the three contact terms
+        (``ContactTerms.record``).  ``init_at_random_ep_len``: before the first collection ``env.progress_buf`` is set to integers
         uniform on [0, ``env.cfg.max_episode_length``), drawn from the trainer's seed, so that the environments do not time out on one tick.  As in
         rsl_rl's ``learn``, this happens at the start of EVERY call that sets the flag (the same draw each time: it moves episodes that are under way),
         so set it on the first call only."""

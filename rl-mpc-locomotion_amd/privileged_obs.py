@@ -15,7 +15,8 @@ environment::
 
 With ``PrivilegedObs(n, plant=True)`` and a ``plant_rand.PlantRand`` in the task, three columns follow the phase -- the plant's per-robot record as
 ``float32(payload)``, ``float32(strength - 1.0)``, ``float32(grav_z + 9.81)`` -- and the row is 16 * ceil((48 + P + 5 + 3) / 16) wide: still 64 without
-a scan, 256 with the default one.  Not in the row: friction -- the toy plant has none.
+a scan, 256 with the default one.  Not in this row: friction -- ``contact_terms.ContactTerms(privileged=True)`` widens the row by the
+plant's friction coefficient and its ground reactions (sixteen columns, one more launch).
 
 The entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
 """

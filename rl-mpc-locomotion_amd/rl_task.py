@@ -210,17 +210,24 @@ class BatchedRLTask:
     are closed inside the ``resets`` stage, before ``ctl.reset``, and one launch after the height scan (after ``finish`` without one) rewrites
     ``rew_buf`` with the fourteen terms and feeds its per-term sums.  The unit is made under the task's own ``cfg`` (``RewardShaping(n, spec, cfg=cfg)``; another one is refused), and a non-zero ``base_height`` scale on a terrain needs
     ``height_scan``.
+    ``contact_terms`` (a ``contact_terms.ContactTerms`` for as many environments, made under the task's own ``cfg``; needs ``friction``): three more
+    reward terms that read the plant's ground reactions and foot slides -- ``feet_slip``, ``feet_contact_forces``, ``feet_stumble`` -- inside the
+    reward's clip; its episodes are closed inside the ``resets`` stage, next to ``reward_shaping.close``, and one launch right after
+    ``reward_shaping.run`` (after ``finish`` without shaping) rewrites ``rew_buf`` and feeds its per-term sums.  With ``privileged=True`` (needs
+    ``privileged_obs``) the privileged row is assembled into a narrow buffer of the task's own and one more launch inside the ``privileged_obs``
+    stage writes ``privileged_obs_buf`` sixteen columns wider: the row, the friction coefficient, the twelve force components, three zeros.
     See the module text for what the toy cannot do."""
 
     def __init__(self, robot_type, gait_id, cfg=None, horizon=10, slope=None, yaw0=None, flat_ground=False, device=None, terrain=None, origin=None,
-                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, plant_rand=None, reward_shaping=None, friction=None, **bridge_args):
+                 curriculum=None, height_scan=None, domain_rand=None, episode_terms=None, privileged_obs=None, plant_rand=None, reward_shaping=None, friction=None, contact_terms=None,
+                 **bridge_args):
         import torch
         n_envs = len(np.asarray(robot_type).reshape(-1))
         cfg = cfg if cfg is not None else TaskConfig()
         # everything that can be refused is refused here, before the device is touched: one pass over the options, the first fault raises
         for unit, holds in ((plant_rand, None), (friction, None), (privileged_obs, "the privileged observations hold"), (episode_terms, "the episode terms hold"),
-                            (reward_shaping, "the reward shaping holds"), (domain_rand, None), (height_scan, "the height scan holds"),
-                            (curriculum, "the curriculum holds")):
+                            (reward_shaping, "the reward shaping holds"), (contact_terms, "the contact terms hold"), (domain_rand, None),
+                            (height_scan, "the height scan holds"), (curriculum, "the curriculum holds")):
             if unit is None:
                 continue
             if unit is plant_rand:         # counts its environments itself, with its payload against the masses of the robot types in use
@@ -242,6 +249,12 @@ class BatchedRLTask:
                 raise ValueError(f"{holds} {unit.n} environments, robot_type {n_envs}")
             if unit is reward_shaping and unit.cfg != cfg:      # its dt, episode length, default_dof_pos and the six scales it re-evaluates are the task's
                 raise ValueError("reward_shaping was made under another TaskConfig than the task's: RewardShaping(n, spec, cfg=cfg)")
+            if unit is contact_terms and unit.cfg != cfg:        # its dt, episode length, clip_observations and the six scales it re-evaluates are the task's
+                raise ValueError("contact_terms was made under another TaskConfig than the task's: ContactTerms(n, spec, cfg=cfg)")
+            if unit is contact_terms and friction is None:
+                raise ValueError("contact_terms reads the plant's ground reactions, foot slides and friction coefficients: give friction=")
+            if unit is contact_terms and unit.privileged and privileged_obs is None:
+                raise ValueError("contact_terms has privileged=True: the columns widen the privileged row of privileged_obs=")
             if unit is reward_shaping and unit.spec.base_height != 0 and height_scan is None and (terrain is not None or curriculum is not None):
                 raise ValueError("reward_shaping has a base_height scale: on a terrain the base height is measured by height_scan=")
             if unit is height_scan and np.float32(unit.obs_clip) != np.float32(cfg.clip_observations):
@@ -290,6 +303,13 @@ class BatchedRLTask:
         self.reward_shaping = reward_shaping
         if reward_shaping is not None:
             reward_shaping.bind(self.sim)
+        self.contact_terms = contact_terms
+        if contact_terms is not None:      # after the friction has given the sim its record and its rows
+            contact_terms.bind(self.sim)
+            self._shaping_scales = None
+            if reward_shaping is not None:                 # the reward's unclipped chain is rebuilt from the shaping unit's terms of the tick
+                self._shaping_scales = reward_shaping.spec.scales(self.cfg.dt)
+                self._shaping_terms = torch.zeros((self.n, len(self._shaping_scales)), dtype=torch.float32, device=self.device)  # (without a terms_buf)
         self.privileged_obs, self.privileged_obs_buf, self.num_privileged_obs = privileged_obs, None, None
         if privileged_obs is not None:
             from .privileged_obs import inverse_length, privileged_width
@@ -301,6 +321,10 @@ class BatchedRLTask:
             self._inv_len = inverse_length(self.cfg.max_episode_length)
             self.num_privileged_obs = privileged_width(self._num_scan, with_plant)
             self.privileged_obs_buf = torch.zeros((self.n, self.num_privileged_obs), dtype=torch.float32, device=self.device)
+            if contact_terms is not None and contact_terms.privileged:     # assemble writes the narrow row, extend the wide one
+                self._narrow_privileged = self.privileged_obs_buf
+                self.num_privileged_obs = contact_terms.width(self.num_privileged_obs)
+                self.privileged_obs_buf = torch.zeros((self.n, self.num_privileged_obs), dtype=torch.float32, device=self.device)
         self.common_step_counter = 0       # the ticks this task has stepped, counted on the host: the command curriculum's clock
 
     def step(self, actions, mark=None):
@@ -317,11 +341,14 @@ class BatchedRLTask:
             episode_close       ``episode_terms.close_and_resample``       only with episode_terms
             resets              ``ctl.reset``, ``sim.reset_idx``, ``sim.flags``; with a PlantRand that resamples at reset ``plant_rand.draw`` first,
                                 with a Friction ``friction.draw`` (the rows of the environments being reset zeroed; a coefficient drawn with "reset"),
-                                with reward_shaping ``reward_shaping.close`` first
-            finish              ``task.finish``; with reward_shaping and no height scan then ``reward_shaping.run``
+                                with reward_shaping ``reward_shaping.close`` and with contact_terms ``contact_terms.close`` first
+            finish              ``task.finish``; with reward_shaping and no height scan then ``reward_shaping.run``; with contact_terms then
+                                ``contact_terms.run``, unless ``reward_shaping.run`` waits for the height scan
             episode_accumulate  ``episode_terms.accumulate``               only with episode_terms
             height_scan         ``height_scan.measure``                    only with a height scan; with reward_shaping then ``reward_shaping.run``
-            privileged_obs      ``privileged_obs.assemble``                only with privileged_obs
+                                and with contact_terms ``contact_terms.run`` behind it
+            privileged_obs      ``privileged_obs.assemble``                only with privileged_obs; with a privileged contact_terms then
+                                ``contact_terms.extend``
             observation_noise   the observation-noise launch               only while a DomainRand is enabled and has observation noise
         ``mark``, when given, is called as ``mark(name)`` on the host right after each stage that ran on this tick has been launched, and not for a
         stage whose option is absent; a caller that records an event on the current stream in it times the stages (tools/rl_task_rate.py).  It must
@@ -368,6 +395,9 @@ class BatchedRLTask:
         rs = self.reward_shaping
         if rs is not None:                 # close the marked episodes' shaping sums
             rs.close(ids)
+        ct = self.contact_terms
+        if ct is not None:                 # and the contact sums; friction.draw has zeroed the marked environments' force and slip rows
+            ct.close(ids)
         self.bridge.ctl.reset(ids)                                                                                              # aliengo.py:330-334
         sim.reset_idx(ids)                                                                                                      # aliengo.py:336-342
         _, fell = sim.flags()              # after the reset: a robot that has just been put back standing is not flagged a second time
@@ -375,7 +405,10 @@ class BatchedRLTask:
             mark("resets")
         t.finish(sim.root_states, sim.dof_state, self.actions, self.torques, fell=fell)                                         # aliengo.py:280-281, :337
         if rs is not None and self.height_scan is None:                        # the tensors finish has just read and written; no heights to wait for
-            rs.run(sim.root_states, sim.dof_state, self.actions, self.commands, self.torques, fell, ids, self.reset_buf, self.progress_buf, self.rew_buf)
+            rs.run(sim.root_states, sim.dof_state, self.actions, self.commands, self.torques, fell, ids, self.reset_buf, self.progress_buf, self.rew_buf,
+                   terms=self._terms_for_contact())
+        if ct is not None and (rs is None or self.height_scan is None):        # right after the shaping launch, or after finish without one
+            self._run_contact_terms(fell, ids)
         if mark is not None:
             mark("finish")
         if et is not None:                 # the tensors finish has just read, the same base contact
@@ -386,11 +419,17 @@ class BatchedRLTask:
             self.height_scan.measure(sim.root_states, t.obs_buf, out=self.obs_buf, heights=self.measured_heights)
             if rs is not None:             # the same tensors, and the heights in metres the scan has just measured
                 rs.run(sim.root_states, sim.dof_state, self.actions, self.commands, self.torques, fell, ids, self.reset_buf, self.progress_buf, self.rew_buf,
-                       heights=self.measured_heights)
+                       heights=self.measured_heights, terms=self._terms_for_contact())
+                if ct is not None:
+                    self._run_contact_terms(fell, ids)
             if mark is not None:
                 mark("height_scan")
         if self.privileged_obs is not None:                                    # the clean copy exists because this launch comes before the noise
-            self.privileged_obs.assemble(self.obs_buf, self.progress_buf, self._inv_len, num_scan=self._num_scan, out=self.privileged_obs_buf)
+            wide = ct is not None and ct.privileged
+            self.privileged_obs.assemble(self.obs_buf, self.progress_buf, self._inv_len, num_scan=self._num_scan,
+                                         out=self._narrow_privileged if wide else self.privileged_obs_buf)
+            if wide:                                                           # the row, the friction coefficient and the ground reactions behind it
+                ct.extend(self._narrow_privileged, self.privileged_obs_buf)
             if mark is not None:
                 mark("privileged_obs")
         if dr is not None and dr.specs["observations"] is not None:                                                             # :331-337, in place
@@ -399,6 +438,19 @@ class BatchedRLTask:
                 mark("observation_noise")
         self.extras["time_outs"] = self.timeout_buf
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
+
+    def _terms_for_contact(self):
+        """The tensor ``reward_shaping.run`` writes its eight terms to: the user's ``terms_buf`` where set (None lets ``run`` pick it), else the task's
+        own where the contact terms read them, else None."""
+        if self.contact_terms is None or self.reward_shaping.terms_buf is not None:
+            return None
+        return self._shaping_terms
+
+    def _run_contact_terms(self, fell, ids):
+        rs = self.reward_shaping
+        shaping_terms = None if rs is None else (rs.terms_buf if rs.terms_buf is not None else self._shaping_terms)
+        self.contact_terms.run(self.sim.root_states, self.commands, self.torques, fell, ids, self.rew_buf, shaping_terms=shaping_terms,
+                               shaping_scales=self._shaping_scales)
 
     def get_privileged_observations(self):
         """rsl_rl's ``VecEnv.get_privileged_observations``: ``privileged_obs_buf`` (rewritten by every step), or None without ``privileged_obs``."""

@@ -41,6 +41,12 @@ the scan (base_height over the measured heights), with --terms beside the per-te
 without it, block by block, and the added time per tick from the blocks' differences; the stages that hold the unit's launches (`resets`: close,
 `height_scan` or `finish`: run) of both tasks, and the episode sums' own two stages of the same run as the yardstick.
     python tools/rl_task_rate.py --shaping --heights --terms [--out profiles/reward_shaping_rate.json]
+--contact: the opt-in contact terms (rl_mpc_locomotion_amd.contact_terms) with every scale non-zero on a plant with a friction record drawn below and
+above the controller's mu, with --privileged the critic's sixteen columns as well; --shaping, --heights and --terms as above, for all three tasks:
+the step with the option against the same task without it, block by block, and the added time per tick; the stages that hold the unit's launches
+(`resets`: close, `height_scan` or `finish`: run, `privileged_obs`: extend) of both tasks; and with --shaping a third task without the shaping terms
+either, whose difference to the second is the yardstick of the same run: reward_shaping's three launches.
+    python tools/rl_task_rate.py --contact --shaping --heights --terms --privileged [--out profiles/contact_terms_rate.json]
 The kernel-trace stats of the same step: rocprofv3 --kernel-trace --stats ... -- python tools/rl_task_rate.py --ticks 50 --quick"""
 import argparse
 import os
@@ -466,6 +472,74 @@ def shaping_report(args, dev, n, actions):
     return res
 
 
+# --contact: every term live (the values are of legged_gym's order of magnitude; none is a preset), and the friction range of the timed plants
+CONTACT_SCALES = dict(feet_slip=-0.1, feet_contact_forces=-0.01, feet_stumble=-0.5, max_contact_force=100.0)
+CONTACT_FRICTION = dict(range=(0.2, 1.25), buckets=64, resample="reset")
+
+
+def contact_task(args, dev, n, cfg, with_contact=True, with_shaping=True):
+    """The task --contact times: a plant with friction drawn at resets; --shaping, --heights, --terms and --privileged as they are given."""
+    from rl_mpc_locomotion_amd.contact_terms import ContactSpec, ContactTerms
+    from rl_mpc_locomotion_amd.friction import Friction, FrictionSpec
+    opts = dict(friction=Friction(n, FrictionSpec(**CONTACT_FRICTION), seed=3, device=dev))
+    if args.heights:
+        from rl_mpc_locomotion_amd.height_scan import HeightScan
+        grid, curriculum, _ = terrain_grid(n, args.max_init_level, dev, cfg.episode_length_s)
+        opts.update(terrain=grid.terrain, origin=curriculum().origins0, height_scan=HeightScan(n, device=dev))
+    if args.terms:
+        from rl_mpc_locomotion_amd.episode_terms import EpisodeTerms
+        opts["episode_terms"] = EpisodeTerms(n, cfg, device=dev)
+    if args.shaping and with_shaping:
+        from rl_mpc_locomotion_amd.reward_shaping import RewardShaping, ShapingSpec
+        opts["reward_shaping"] = RewardShaping(n, ShapingSpec(**SHAPING_SCALES), device=dev, cfg=cfg)
+    if args.privileged:
+        from rl_mpc_locomotion_amd.privileged_obs import PrivilegedObs
+        opts["privileged_obs"] = PrivilegedObs(n, device=dev)
+    if with_contact:
+        opts["contact_terms"] = ContactTerms(n, ContactSpec(**CONTACT_SCALES), device=dev, cfg=cfg, privileged=bool(args.privileged))
+    return make(n, dev, cfg, **opts)
+
+
+def contact_report(args, dev, n, actions):
+    from rl_mpc_locomotion_amd.contact_terms import ContactTerms
+    cfg = TaskConfig(**CFG, episode_length_s=args.episode_s)
+    res = header(args, n, heights=bool(args.heights), terms=bool(args.terms), shaping=bool(args.shaping), privileged=bool(args.privileged),
+                 episode_length_s=cfg.episode_length_s, scales=CONTACT_SCALES, friction=CONTACT_FRICTION,
+                 launches_per_tick={"close": 2, "run": 1, "extend": 1 if args.privileged else 0})
+    loops = {"step_with_contact": contact_task(args, dev, n, cfg), "step_without": contact_task(args, dev, n, cfg, with_contact=False)}
+    if args.shaping:                          # the yardstick's baseline: neither unit
+        loops["step_without_shaping"] = contact_task(args, dev, n, cfg, with_contact=False, with_shaping=False)
+    blocks(res, args, actions, loops, per_block=True)
+    per = {k: np.array(res[k]["ms_per_tick_blocks"]) * 1e3 for k in loops}
+    pct = lambda v: {"p10": float(np.percentile(v, 10)), "median": med(v), "p90": float(np.percentile(v, 90)), "blocks": v.tolist()}
+    res["added_us_per_tick"] = pct(per["step_with_contact"] - per["step_without"])
+    run_stage = "height_scan" if args.heights and args.shaping else "finish"
+    names = ("resets", run_stage) + (("privileged_obs",) if args.privileged else ())
+    parts = {k: {s: [] for s in names} for k in loops}
+    for _ in range(args.blocks):              # the stages from events, the tasks alternating round by round
+        for k, task in loops.items():
+            got = stage_times(task, actions, max(args.ticks // 2, 1))
+            for s in names:
+                parts[k][s] += list(got[s])
+    res["stages"] = {k: {s: {**spread(v), "events": len(v)} for s, v in d.items()} for k, d in parts.items()}
+    m = {k: {s: med(v) for s, v in d.items()} for k, d in parts.items()}
+    diff = lambda a, b, s: (m[a][s] - m[b][s]) * 1e3
+    unit = {"close_in_resets": diff("step_with_contact", "step_without", "resets"), "run_in_" + run_stage: diff("step_with_contact", "step_without", run_stage)}
+    unit["close_and_run"] = unit["close_in_resets"] + unit["run_in_" + run_stage]
+    if args.privileged:
+        unit["extend_in_privileged_obs"] = diff("step_with_contact", "step_without", "privileged_obs")
+    res["unit_from_stage_medians_us"] = unit
+    if args.shaping:                          # reward_shaping's three launches, in the same run: from the blocks and from the two stages that hold them
+        y = pct(per["step_without"] - per["step_without_shaping"])
+        y["from_stage_medians"] = diff("step_without", "step_without_shaping", "resets") + diff("step_without", "step_without_shaping", run_stage)
+        res["reward_shaping_yardstick_us"] = y
+        res["close_and_run_exceed_yardstick_by_more_than_its_spread"] = bool(unit["close_and_run"] - y["from_stage_medians"] > y["p90"] - y["p10"])
+    ct = loops["step_with_contact"].contact_terms
+    res["after_timing"] = {"fallen_fraction": fallen(loops), "record": ContactTerms.record(ct.summary().tolist())}
+    clock(res, "after")
+    return res
+
+
 def default_report(args, dev, n, actions):
     res = header(args, n)
     step, half, bare = make(n, dev), make(n, dev), Bare(n, dev)
@@ -513,10 +587,18 @@ if __name__ == "__main__":
     ap.add_argument("--baseline", action="store_true", help="--privileged: only the task without the option (runs on a tree without the unit)")
     ap.add_argument("--plant-rand", action="store_true", help="time the step and its plant and resets stages with and without the per-robot plant record; with --privileged both tasks assemble the critic's row, one with the plant columns")
     ap.add_argument("--shaping", action="store_true", help="time the step with and without the reward shaping terms; with --heights on the terrain with the scan, with --terms beside the episode sums")
+    ap.add_argument("--contact", action="store_true", help="time the step with and without the contact terms on a plant with friction; --shaping, --heights, --terms and --privileged are honoured")
     ap.add_argument("--out")
     args = ap.parse_args()
     dev, n = "cuda:0", args.robots
     actions = torch.zeros((n, 12), dtype=torch.float32, device=dev)
+    if args.quick and args.contact:        # one block of the step with the option (for a kernel trace)
+        task = contact_task(args, dev, n, TaskConfig(**CFG, episode_length_s=args.episode_s))
+        task.reset()
+        for _ in range(args.ticks):
+            task.step(actions)
+        torch.cuda.synchronize()
+        sys.exit(0)
     if args.quick and args.shaping:        # one block of the step with the option, --heights and --terms honoured (for a kernel trace)
         task = shaping_task(args, dev, n, TaskConfig(**CFG, episode_length_s=args.episode_s))
         task.reset()
@@ -531,6 +613,6 @@ if __name__ == "__main__":
             task.step(actions)
         torch.cuda.synchronize()
         sys.exit(0)
-    report = (shaping_report if args.shaping else plant_rand_report if args.plant_rand else privileged_report if args.privileged else terms_report if args.terms else domain_rand_report if args.domain_rand else heights_report if args.heights
+    report = (contact_report if args.contact else shaping_report if args.shaping else plant_rand_report if args.plant_rand else privileged_report if args.privileged else terms_report if args.terms else domain_rand_report if args.domain_rand else heights_report if args.heights
               else curriculum_report if args.curriculum else default_report)
     emit(report(args, dev, n, actions), args.out)
