@@ -8,6 +8,7 @@
  *   mpc_ac_act_asymmetric the same launch for an asymmetric actor-critic: the critic reads privileged rows of its own width
  *   mpc_ac_evaluate       the critic alone (the iteration's last_values)
  *   mpc_ac_act_inference  the actor's mean alone (ActorCritic.act_inference)
+ *   mpc_ac_act_distill    the same launch over two handles: a student's actor samples, a teacher's actor labels the rows with its mean
  *   mpc_rollout_add       PPO.process_env_step: the time-out bootstrap r' = r + gamma (v to) and the done flag into slot t, read from the task's own
  *                         int64 reset / time-out buffers
  *   mpc_rollout_returns   RolloutStorage.compute_returns over [T][N] storage, then advantages = (A - mean) / (std + 1e-8)
@@ -63,6 +64,13 @@ int mpc_ac_act_asymmetric(mpc_ac *ac, int n, const float *d_obs, const float *d_
                           float *d_log_prob, float *d_values, float *d_mean, float *d_sigma, float *d_eps, void *stream);
 int mpc_ac_evaluate(mpc_ac *ac, int n, const float *d_obs, float *d_values, void *stream);
 int mpc_ac_act_inference(mpc_ac *ac, int n, const float *d_obs, float *d_mean, void *stream);
+/* Collection for policy distillation, still ONE launch on a grid of (ceil(n / 16), 2): the student's actor acts on d_obs [n][student actor_dims[0]]
+ * and samples (d_actions, d_mean, d_sigma and, unless NULL, d_eps as mpc_ac_act writes them, bit for bit, with the same (seed, environment, step,
+ * pair) key; no log-prob and no value), and beside it the TEACHER's actor reads d_teacher_obs [n][teacher actor_dims[0]] and writes its mean, the
+ * label, to d_teacher_actions [n][12]: bit for bit mpc_ac_act_inference(teacher, d_teacher_obs).  Two handles, both bound, on one device; depths and
+ * widths are independent and neither critic is read.  The teacher's parameters are only read. */
+int mpc_ac_act_distill(mpc_ac *student, mpc_ac *teacher, int n, const float *d_obs, const float *d_teacher_obs, unsigned long long seed, unsigned int step,
+                       float *d_actions, float *d_mean, float *d_sigma, float *d_teacher_actions, float *d_eps, void *stream);
 /* d_rew [n] float32, d_reset [n] and d_timeout [n] int64 (0 / 1; the task's buffers as they are), d_values_t [n] (slot t, as written by mpc_ac_act)
  * -> d_rewards_t [n] = r + gamma (v to), d_dones_t [n] = reset != 0 as float32.  gamma in [0, 1], used as its float32 value. */
 int mpc_rollout_add(int n, double gamma, const float *d_rew, const long long *d_reset, const long long *d_timeout, const float *d_values_t,

@@ -10,6 +10,8 @@
  *   mpc_ppo_update_grads_sequence   the same for a recurrent actor-critic, whose nets read dense rows that two memories wrote: it also writes
  *                          d loss / d rows for the memories' backward pass, and mpc_ppo_update_bind_extra puts the memories' parameters behind the
  *                          mpc_ac's in mpc_ppo_update_apply (the end of this file)
+ *   mpc_ppo_update_grads_distill / mpc_ppo_update_apply_actor   policy distillation: the actor alone, a behaviour-cloning loss against a teacher's
+ *                          actions (mpc_ppo_update_set_distill_targets), and the clip and Adam over the actor's tensors alone (the end of this file)
  *
  * The GEMMs run on the exact-fp32 MFMA pipe (rl-mpc-locomotion_amd/csrc/ppo_gemm.h); the scalar arithmetic is csrc/ppo_update.h, float32 in
  * rsl_rl's and torch's operation order.  Every sum over rows or elements is taken in a fixed order: a rerun is bit-identical.
@@ -86,6 +88,22 @@ int mpc_ppo_update_grads_sequence(mpc_ppo_update *u, int rows, const long long *
  * refusal). */
 int mpc_ppo_update_bind_extra(mpc_ppo_update *u, int count, float *const *d_params, float *const *d_grads, float *const *d_exp_avg,
                               float *const *d_exp_avg_sq, const int *numel);
+
+/* ---- policy distillation: behaviour cloning of a teacher's actions into the ACTOR of the (student's) mpc_ac, on this handle's workspace, bound
+ * gradients and moments.  The critic's tensors and std, their gradients and their moments are neither read nor written by the two calls below. */
+/* The labels: d_teacher_actions [total_rows][12], 16-byte aligned, indexed by d_idx like the storage's d_obs (mpc_ac_act_distill writes a slot of
+ * it per tick).  Kept by pointer; NULL clears it. */
+int mpc_ppo_update_set_distill_targets(mpc_ppo_update *u, const float *d_teacher_actions);
+/* One mini-batch: the forward pass of the actor alone over the rows d_idx names in the storage's d_obs (the GEMM launches of mpc_ppo_update_grads with
+ * the critic's slot empty), the behaviour-cloning head, the actor's backward pass into its bound gradients.  With d = mu[r][k] - target[d_idx[r]][k]
+ * over the 12 rows elements: loss_type 0 (mse): loss = mean d^2, d loss / d mu = 2 d / (12 rows); 1 (huber, delta = 1): the mean of 0.5 d^2 where
+ * |d| <= 1 and |d| - 0.5 otherwise, d loss / d mu = clamp(d, -1, 1) / (12 rows).  Elements in float32 as torch's mse_loss / huber_loss take them;
+ * the sums in float64 in a fixed order, no atomics.  d_terms [2] = (loss, mean |d|) as float32.  Refused with MPC_E_ARG, before the device is touched:
+ * rows outside 1 .. max_rows, an unknown loss_type, no gradients bound, no storage set, no targets set. */
+int mpc_ppo_update_grads_distill(mpc_ppo_update *u, int rows, const long long *d_idx, int loss_type, float *d_terms, void *stream);
+/* mpc_ppo_update_apply over the actor's weight and bias tensors alone: clip_grad_norm_(max_norm) and torch.optim.Adam's step over
+ * actor.parameters().  Refused without gradients and moments bound. */
+int mpc_ppo_update_apply_actor(mpc_ppo_update *u, double max_norm, double beta1, double beta2, double eps, int step, const double *d_lr, void *stream);
 
 #ifdef __cplusplus
 }

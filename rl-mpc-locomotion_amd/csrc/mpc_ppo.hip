@@ -3,7 +3,8 @@
 //                      actor's instead of after them.  A workgroup carries 16 environments through its net's layers with policy::layer
 //                      (policy_mlp.h, unchanged): the mean is the k-ordered MFMA chain of mpc_policy_step.  The actor's workgroups end in the sampling
 //                      / log-prob epilogue (one lane per environment and action pair, then one lane per environment for the ordered sum), the
-//                      critic's write the value.  The weights are read through the caller's pointers: nothing is copied at bind time or later.
+//                      critic's write the value (the second net's whole output row: mpc_ac_act_distill puts a teacher's actor there, whose row is
+//                      its twelve-column mean).  The weights are read through the caller's pointers: nothing is copied at bind time or later.
 //   rollout_add_kernel one lane per environment: bootstrapped reward and done flag into slot t.
 //   returns_kernel     one lane per environment walks t = T-1 .. 0 over [T][N] storage (consecutive lanes on consecutive words).
 //   normalise_kernel   ONE workgroup: lane i sums elements i, i + 1024, ... in float64, a fixed-order LDS tree joins the lanes; mean, then squared
@@ -41,6 +42,8 @@ struct ActOut {
 };
 
 // grid (ceil(n / 16), nets); net = first_net + blockIdx.y.  sample: the actor's epilogue draws actions (mpc_ac_act); otherwise it writes the mean alone.
+// The second net writes its whole output row to out.values [n][its outputs]: one column for a critic, twelve where mpc_ac_act_distill has put a
+// teacher's actor there (out.log_prob is then null and not written).
 // actor_obs [n][actor dims[0]] and critic_obs [n][critic dims[0]]: each net's workgroups stage their own rows at their own width (the same pointer
 // twice where both nets read the same observations); the pointer of a net that the launch does not run is never read.
 __global__ __launch_bounds__(policy::kThreads) void ac_kernel(Nets nets, int first_net, int sample, int n, const float *__restrict__ actor_obs,
@@ -70,8 +73,9 @@ __global__ __launch_bounds__(policy::kThreads) void ac_kernel(Nets nets, int fir
   const float *res = buf[L & 1];
   const int rs = stride[L & 1];
   const int e = threadIdx.x;
-  if (which == kCritic) {
-    if (e < policy::kRows && r0 + e < n) out.values[r0 + e] = res[e * rs];
+  if (which == kCritic) {                // the second net's output row, as wide as it is: a critic's value, or (mpc_ac_act_distill) a teacher's mean
+    const int w = net.dims[L], r = e / w, k = e - r * w;
+    if (e < policy::kRows * w && r0 + r < n) out.values[(size_t)(r0 + r) * w + k] = res[r * rs + k];
     return;
   }
   // the actor's epilogue.  terms: the other activation buffer, free since the last barrier (it holds at least 16 x (16 + 4) words: the last
@@ -97,7 +101,7 @@ __global__ __launch_bounds__(policy::kThreads) void ac_kernel(Nets nets, int fir
   }
   if (!sample) return;
   __syncthreads();
-  if (e < policy::kRows && r0 + e < n) out.log_prob[r0 + e] = ppo::log_prob_sum(terms + e * ppo::kActions);
+  if (out.log_prob && e < policy::kRows && r0 + e < n) out.log_prob[r0 + e] = ppo::log_prob_sum(terms + e * ppo::kActions);
 }
 
 mpchost::LdsLimit g_ac_limit(ac_kernel);
@@ -252,14 +256,19 @@ int mpc_ac_bind(mpc_ac *ac, const float *const *d_actor_weights, const float *co
   return MPC_OK;
 }
 
-static int ac_launch(mpc_ac *ac, int n, const float *d_obs, const float *d_critic_obs, int first_net, int nets, int sample, unsigned long long seed,
-                     unsigned int step, const ActOut &o, void *stream) {
-  DeviceGuard guard_(ac->device);
+static int launch_nets(const Nets &pair, size_t lds, int device, int n, const float *d_obs, const float *d_critic_obs, int first_net, int nets, int sample,
+                       unsigned long long seed, unsigned int step, const ActOut &o, void *stream) {
+  DeviceGuard guard_(device);
   const dim3 grid((unsigned)((n + policy::kRows - 1) / policy::kRows), (unsigned)nets);
-  hipLaunchKernelGGL(ac_kernel, grid, dim3(policy::kThreads), ac->lds, reinterpret_cast<hipStream_t>(stream), ac->nets, first_net, sample, n, d_obs, d_critic_obs,
+  hipLaunchKernelGGL(ac_kernel, grid, dim3(policy::kThreads), lds, reinterpret_cast<hipStream_t>(stream), pair, first_net, sample, n, d_obs, d_critic_obs,
                      seed, step, o);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
+}
+
+static int ac_launch(mpc_ac *ac, int n, const float *d_obs, const float *d_critic_obs, int first_net, int nets, int sample, unsigned long long seed,
+                     unsigned int step, const ActOut &o, void *stream) {
+  return launch_nets(ac->nets, ac->lds, ac->device, n, d_obs, d_critic_obs, first_net, nets, sample, seed, step, o, stream);
 }
 
 int mpc_ac_act(mpc_ac *ac, int n, const float *d_obs, unsigned long long seed, unsigned int step, float *d_actions, float *d_log_prob, float *d_values,
@@ -294,6 +303,26 @@ int mpc_ac_act_inference(mpc_ac *ac, int n, const float *d_obs, float *d_mean, v
   if (!ac || n <= 0 || !d_obs || !d_mean || (reinterpret_cast<uintptr_t>(d_mean) & 7u)) return fail(MPC_E_ARG, "mpc_ac_act_inference: bad argument");
   if (!ac->bound) return fail(MPC_E_ARG, "mpc_ac_act_inference: no parameters bound (mpc_ac_bind)");
   return ac_launch(ac, n, d_obs, nullptr, kActor, 1, 0, 0, 0, ActOut{nullptr, nullptr, nullptr, d_mean, nullptr, nullptr}, stream);
+}
+
+// ac_kernel's two halves over two handles: the student's actor with the sampling epilogue, and the teacher's actor where a critic sits otherwise.
+// The dynamic LDS is the larger of the two handles' own (ac_kernel's limit on this device holds both since their binds).
+int mpc_ac_act_distill(mpc_ac *student, mpc_ac *teacher, int n, const float *d_obs, const float *d_teacher_obs, unsigned long long seed, unsigned int step,
+                       float *d_actions, float *d_mean, float *d_sigma, float *d_teacher_actions, float *d_eps, void *stream) {
+  if (!student || !teacher || n <= 0 || !d_obs || !d_actions || !d_mean || !d_sigma) return fail(MPC_E_ARG, "mpc_ac_act_distill: bad argument");
+  if (!d_teacher_obs || !d_teacher_actions) return fail(MPC_E_ARG, "mpc_ac_act_distill: d_teacher_obs or d_teacher_actions is null");
+  if ((reinterpret_cast<uintptr_t>(d_actions) | reinterpret_cast<uintptr_t>(d_mean) | reinterpret_cast<uintptr_t>(d_sigma) | reinterpret_cast<uintptr_t>(d_eps)) & 7u)
+    return fail(MPC_E_ARG, "mpc_ac_act_distill: d_actions, d_mean, d_sigma and d_eps must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_teacher_actions) & 3u) return fail(MPC_E_ARG, "mpc_ac_act_distill: d_teacher_actions must be 4-byte aligned");
+  if (!student->bound) return fail(MPC_E_ARG, "mpc_ac_act_distill: the student has no parameters bound (mpc_ac_bind)");
+  if (!teacher->bound) return fail(MPC_E_ARG, "mpc_ac_act_distill: the teacher has no parameters bound (mpc_ac_bind)");
+  if (student->device != teacher->device) return fail(MPC_E_ARG, "mpc_ac_act_distill: the student and the teacher are bound on different devices");
+  Nets pair{};
+  pair.net[0] = student->nets.net[kActor];
+  pair.net[1] = teacher->nets.net[kActor];
+  pair.std = student->nets.std;
+  return launch_nets(pair, student->lds > teacher->lds ? student->lds : teacher->lds, student->device, n, d_obs, d_teacher_obs, 0, 2, 1, seed, step,
+                     ActOut{d_actions, nullptr, d_teacher_actions, d_mean, d_sigma, d_eps}, stream);
 }
 
 int mpc_rollout_add(int n, double gamma, const float *d_rew, const long long *d_reset, const long long *d_timeout, const float *d_values_t,

@@ -10,6 +10,9 @@
 // mpc_ppo_update_grads_sequence is the same sequence on dense first-layer rows (the outputs of a recurrent actor-critic's memories) plus one
 // pgemm::kBackwardDataLinear launch through layer 0 into the rows' gradients; mpc_ppo_update_bind_extra puts up to eight more tensors (the memories'
 // parameters) behind the mpc_ac's in the norm, the clip and Adam.
+// mpc_ppo_update_grads_distill (policy distillation) is the sequence over the ACTOR alone, the critic's slot of every GEMM launch empty, with
+// bc_head_kernel / bc_reduce_kernel (ppo::bc_element against the teacher's actions) for the loss head; mpc_ppo_update_apply_actor is the norm, the
+// clip and Adam over the actor's weights and biases alone.  Neither reads or writes anything of the critic's or std's.
 // No atomics anywhere, so a rerun is bit-identical; nothing synchronises.
 #include <hip/hip_runtime.h>
 
@@ -121,6 +124,74 @@ __global__ __launch_bounds__(kHeadThreads) void head_reduce_kernel(int blocks, i
   }
 }
 
+// The head of policy distillation (mpc_ppo_update_grads_distill): one lane per row, ppo::bc_element on the actor's mean and the teacher's action of
+// storage row idx[row]; writes d loss / d mu where the backward pass reads it, and per workgroup the float64 sums of the loss terms and of |d| --
+// a row's twelve elements in action order, then head_kernel's fixed-order LDS sums over the rows
+constexpr int kBcQ = 2;                        // loss, |mu - target|
+__global__ __launch_bounds__(kHeadThreads) void bc_head_kernel(int rows, const long long *__restrict__ idx, long long total_rows, int loss_type, float norm,
+                                                               const float *__restrict__ targets, const float *__restrict__ mu, float *__restrict__ dmu,
+                                                               double *__restrict__ partials) {
+  __shared__ double vals[kBcQ][kHeadThreads];
+  __shared__ double mid[kBcQ][16];
+  const int t = threadIdx.x, row = blockIdx.x * kHeadThreads + t;
+  double loss = 0.0, gap = 0.0;
+  if (row < rows) {
+    long long r = idx[row];
+    r = r < 0 ? 0 : (r >= total_rows ? total_rows - 1 : r);
+    float m[ppo::kActions], a[ppo::kActions], g[ppo::kActions];
+#pragma unroll
+    for (int k = 0; k < ppo::kActions; k += 4) {
+      *reinterpret_cast<float4 *>(m + k) = *reinterpret_cast<const float4 *>(mu + (size_t)row * kOutLd + k);
+      *reinterpret_cast<float4 *>(a + k) = *reinterpret_cast<const float4 *>(targets + (size_t)r * ppo::kActions + k);
+    }
+#pragma unroll
+    for (int k = 0; k < ppo::kActions; ++k) {
+      float value, d;
+      ppo::bc_element(loss_type, norm, m[k], a[k], value, g[k], d);
+      loss += (double)value;
+      gap += (double)d;
+    }
+#pragma unroll
+    for (int k = 0; k < ppo::kActions; k += 4)
+      *reinterpret_cast<float4 *>(dmu + (size_t)row * kOutLd + k) = *reinterpret_cast<const float4 *>(g + k);
+  }
+  vals[0][t] = loss; vals[1][t] = gap;
+  __syncthreads();
+  if (t < kBcQ * 16) {                   // 16 consecutive rows each, in row order
+    const int q = t >> 4, j = t & 15;
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) sum += vals[q][16 * j + i];
+    mid[q][j] = sum;
+  }
+  __syncthreads();
+  if (t < kBcQ) {
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) sum += mid[t][j];
+    partials[(size_t)blockIdx.x * kHeadStride + t] = sum;
+  }
+}
+
+// ONE workgroup joins bc_head_kernel's partials as head_reduce_kernel does: terms = (mean loss, mean |d|) over the 12 rows elements
+__global__ __launch_bounds__(64) void bc_reduce_kernel(int blocks, int rows, const double *__restrict__ partials, float *__restrict__ terms) {
+  __shared__ double mid[kBcQ][16];
+  const int t = threadIdx.x;
+  if (t < kBcQ * 16) {
+    const int q = t >> 4, j = t & 15, per = (blocks + 15) / 16;
+    const int b1 = (j + 1) * per < blocks ? (j + 1) * per : blocks;
+    double sum = 0.0;
+    for (int b = j * per; b < b1; ++b) sum += partials[(size_t)b * kHeadStride + q];
+    mid[q][j] = sum;
+  }
+  __syncthreads();
+  if (t >= kBcQ) return;
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) s += mid[t][j];
+  terms[t] = (float)(s / ((double)ppo::kActions * (double)rows));
+}
+
 struct NormTable {
   const float *g[kMaxTensors];
   int numel[kMaxTensors];
@@ -210,6 +281,7 @@ struct mpc_ppo_update {
   bool grads_bound = false, moments_bound = false, storage_set = false;
   Storage st{};
   const float *critic_obs = nullptr;            // [total_rows][dims[kCritic][0]] (mpc_ppo_update_set_critic_storage), or null: the critic reads st.obs
+  const float *distill_targets = nullptr;       // [total_rows][12] (mpc_ppo_update_set_distill_targets): the teacher's actions, indexed like st.obs
   const float *seq_rows[2] = {};                // mpc_ppo_update_set_sequence_rows: dense [max_rows][dims[k][0]] inputs of the two first layers ...
   float *seq_drows[2] = {};                     // ... and what receives d loss / d rows
   bool sequence_set = false;
@@ -336,6 +408,9 @@ int mpc_ppo_update_set_critic_storage(mpc_ppo_update *u, const float *d_critic_o
 }  // extern "C"
 
 namespace {
+int forward_pass(mpc_ppo_update *u, const mpc_ac_view &v, int nets, bool sequence, int rows, const long long *d_idx, hipStream_t s);
+int backward_pass(mpc_ppo_update *u, const mpc_ac_view &v, int nets, bool sequence, int rows, const long long *d_idx, hipStream_t s);
+
 // mpc_ppo_update_grads (sequence = false: layer 0 reads the storage's rows through d_idx) and mpc_ppo_update_grads_sequence (true: layer 0 reads the
 // dense rows of mpc_ppo_update_set_sequence_rows, and one more launch takes dY_0 W_0 into their gradients); `name` heads the refusals
 int grads(const char *name, bool sequence, mpc_ppo_update *u, int rows, const long long *d_idx, double clip_param, double value_loss_coef,
@@ -355,13 +430,32 @@ int grads(const char *name, bool sequence, mpc_ppo_update *u, int rows, const lo
     return fail(MPC_E_ARG, std::string(name) + ": an asymmetric mpc_ac needs the critic's rows (mpc_ppo_update_set_critic_storage)");
   DeviceGuard guard_(u->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int maxl = u->nl[0] > u->nl[1] ? u->nl[0] : u->nl[1];
+  if (int rc = forward_pass(u, v, 2, sequence, rows, d_idx, s)) return rc;
+
+  // the loss head
+  ppo::HeadCfg cfg{(float)clip_param, (float)value_loss_coef, (float)entropy_coef, use_clipped_value_loss ? 1 : 0, 1.0f / (float)rows};
+  const int hb = (rows + kHeadThreads - 1) / kHeadThreads;
+  const int la = u->nl[kActor] - 1, lc = u->nl[kCritic] - 1;
+  hipLaunchKernelGGL(head_kernel, dim3((unsigned)hb), dim3(kHeadThreads), 0, s, rows, d_idx, u->st, cfg, u->Y[kActor][la], u->Y[kCritic][lc], v.std,
+                     u->dY[kActor][la], u->dY[kCritic][lc], u->partials);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(kHeadThreads), 0, s, hb, rows, u->partials, v.std, (float)entropy_coef, adaptive ? 1 : 0, desired_kl, d_lr,
+                     d_terms, u->grad[u->n_tensors - 1]);
+  HIP_TRY(hipGetLastError());
+  return backward_pass(u, v, 2, sequence, rows, d_idx, s);
+}
+
+// The passes of `grads` over the first `nets` nets: 2 is actor and critic side by side; 1 is the actor alone (mpc_ppo_update_grads_distill), the
+// critic's slot of every launch empty and nothing of the critic's read or written.
+int forward_pass(mpc_ppo_update *u, const mpc_ac_view &v, int nets, bool sequence, int rows, const long long *d_idx, hipStream_t s) {
+  int maxl = 0;
+  for (int k = 0; k < nets; ++k) maxl = u->nl[k] > maxl ? u->nl[k] : maxl;
 
   // forward: layer l of both nets side by side.  (tests/test_ppo_gemm_plan.py restates this sequence of launches and their (M, N, K), here and in the
   // backward loop below, to pin which kernels the tests reach: a launch added, dropped or reshaped here has to be restated there)
   for (int l = 0; l < maxl; ++l) {
     pgemm::Launch L{};
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < nets; ++k) {
       if (l >= u->nl[k]) continue;
       pgemm::Problem &p = L.p[k];
       p.A = l == 0 ? (sequence ? u->seq_rows[k] : u->rows0(k)) : u->Y[k][l - 1];
@@ -377,23 +471,18 @@ int grads(const char *name, bool sequence, mpc_ppo_update *u, int rows, const lo
     }
     if (int rc = launch_gemm(pgemm::kForward, L, s)) return rc;
   }
+  return MPC_OK;
+}
 
-  // the loss head
-  ppo::HeadCfg cfg{(float)clip_param, (float)value_loss_coef, (float)entropy_coef, use_clipped_value_loss ? 1 : 0, 1.0f / (float)rows};
-  const int hb = (rows + kHeadThreads - 1) / kHeadThreads;
-  const int la = u->nl[kActor] - 1, lc = u->nl[kCritic] - 1;
-  hipLaunchKernelGGL(head_kernel, dim3((unsigned)hb), dim3(kHeadThreads), 0, s, rows, d_idx, u->st, cfg, u->Y[kActor][la], u->Y[kCritic][lc], v.std,
-                     u->dY[kActor][la], u->dY[kCritic][lc], u->partials);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(kHeadThreads), 0, s, hb, rows, u->partials, v.std, (float)entropy_coef, adaptive ? 1 : 0, desired_kl, d_lr,
-                     d_terms, u->grad[u->n_tensors - 1]);
-  HIP_TRY(hipGetLastError());
+int backward_pass(mpc_ppo_update *u, const mpc_ac_view &v, int nets, bool sequence, int rows, const long long *d_idx, hipStream_t s) {
+  int maxl = 0;
+  for (int k = 0; k < nets; ++k) maxl = u->nl[k] > maxl ? u->nl[k] : maxl;
 
   // backward: from the last layer of each net towards the first; dW partials, then dX into the layer below
   int dw_chunks[2][MPC_AC_MAX_LAYERS] = {};
   for (int sidx = 0; sidx < maxl; ++sidx) {
     pgemm::Launch W{}, D{};
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < nets; ++k) {
       const int l = u->nl[k] - 1 - sidx;
       if (l < 0) continue;
       const int nout = u->dims[k][l + 1], nin = u->dims[k][l];
@@ -417,13 +506,13 @@ int grads(const char *name, bool sequence, mpc_ppo_update *u, int rows, const lo
       q.chunks = 1;
     }
     if (int rc = launch_gemm(pgemm::kBackwardWeight, W, s)) return rc;
-    for (int k = 0; k < 2; ++k)
+    for (int k = 0; k < nets; ++k)
       if (u->nl[k] - 1 - sidx >= 0) dw_chunks[k][u->nl[k] - 1 - sidx] = W.p[k].chunks;
     if (int rc = launch_gemm(pgemm::kBackwardData, D, s)) return rc;
   }
   if (sequence) {                        // through layer 0 into the rows' gradients: d rows = dY_0 W_0, no activation in front of these rows
     pgemm::Launch D{};
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < nets; ++k) {
       pgemm::Problem &q = D.p[k];
       q.A = u->dY[k][0]; q.lda = u->ld(k, 0);
       q.B = v.w[k][0]; q.ldb = u->dims[k][0];
@@ -437,7 +526,7 @@ int grads(const char *name, bool sequence, mpc_ppo_update *u, int rows, const lo
   // the chunks in index order into .grad
   pgemm::ReduceTable rt{};
   int ne = 0, maxn = 0;
-  for (int k = 0; k < 2; ++k)
+  for (int k = 0; k < nets; ++k)
     for (int l = 0; l < u->nl[k]; ++l) {
       const int nout = u->dims[k][l + 1], nin = u->dims[k][l];
       rt.e[ne++] = pgemm::ReduceEntry{u->dWp[k][l], u->grad[u->w_index(k, l)], nout * nin, dw_chunks[k][l]};
@@ -534,36 +623,44 @@ int mpc_ppo_update_bind_extra(mpc_ppo_update *u, int count, float *const *d_para
   return MPC_OK;
 }
 
-int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, double beta2, double eps, int step, const double *d_lr, void *stream) {
-  if (!u || !d_lr) return fail(MPC_E_ARG, "mpc_ppo_update_apply: bad argument");
+}  // extern "C"
+
+namespace {
+// mpc_ppo_update_apply (actor_only = false: every tensor of the mpc_ac and the extras behind them) and mpc_ppo_update_apply_actor (true: the actor's
+// weights and biases, which head mpc_ac_bind's order; no other tensor, gradient or moment enters a table)
+int apply(const char *name, bool actor_only, mpc_ppo_update *u, double max_norm, double beta1, double beta2, double eps, int step, const double *d_lr,
+          void *stream) {
+  const std::string who(name);
+  if (!u || !d_lr) return fail(MPC_E_ARG, who + ": bad argument");
   if (!(max_norm > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !std::isfinite(eps))
-    return fail(MPC_E_ARG, "mpc_ppo_update_apply: max_norm must be positive, the betas in [0, 1), eps not negative");
-  if (step < 1) return fail(MPC_E_ARG, "mpc_ppo_update_apply: step counts from 1");
-  if (!u->grads_bound || !u->moments_bound) return fail(MPC_E_ARG, "mpc_ppo_update_apply: no gradients and moments bound (mpc_ppo_update_bind)");
-  if (u->n_extra > 0 && !u->extra_moments) return fail(MPC_E_ARG, "mpc_ppo_update_apply: the extra tensors have no moments bound (mpc_ppo_update_bind_extra)");
+    return fail(MPC_E_ARG, who + ": max_norm must be positive, the betas in [0, 1), eps not negative");
+  if (step < 1) return fail(MPC_E_ARG, who + ": step counts from 1");
+  if (!u->grads_bound || !u->moments_bound) return fail(MPC_E_ARG, who + ": no gradients and moments bound (mpc_ppo_update_bind)");
+  const int n_extra = actor_only ? 0 : u->n_extra;
+  if (n_extra > 0 && !u->extra_moments) return fail(MPC_E_ARG, who + ": the extra tensors have no moments bound (mpc_ppo_update_bind_extra)");
   mpc_ac_view v;
-  if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return fail(MPC_E_ARG, "mpc_ppo_update_apply: the mpc_ac has no parameters bound");
+  if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return fail(MPC_E_ARG, who + ": the mpc_ac has no parameters bound");
   DeviceGuard guard_(u->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   NormTable nt{};
   AdamTable at{};
   int maxn = 0;
-  const int total = u->n_tensors + u->n_extra;                      // (no extras: today's tables, partials and grids)
-  const int blocks = u->n_extra > 0 ? u->extra_blocks : u->norm_blocks;
-  double *partials = u->n_extra > 0 ? static_cast<double *>(u->extra_partials) : u->norm_partials;
+  const int total = actor_only ? 2 * u->nl[kActor] : u->n_tensors + n_extra;      // (no extras: today's tables, partials and grids)
+  const int blocks = n_extra > 0 ? u->extra_blocks : u->norm_blocks;
+  double *partials = n_extra > 0 ? static_cast<double *>(u->extra_partials) : u->norm_partials;
   for (int t = 0; t < total; ++t) {
     nt.g[t] = u->grad[t];
     at.g[t] = u->grad[t]; at.m[t] = u->exp_avg[t]; at.v[t] = u->exp_avg_sq[t];
     nt.numel[t] = at.numel[t] = u->numel(t);
     maxn = at.numel[t] > maxn ? at.numel[t] : maxn;
   }
-  for (int k = 0; k < 2; ++k)
+  for (int k = 0; k < (actor_only ? 1 : 2); ++k)
     for (int l = 0; l < u->nl[k]; ++l) {
       at.p[u->w_index(k, l)] = const_cast<float *>(v.w[k][l]);
       at.p[u->b_index(k, l)] = const_cast<float *>(v.b[k][l]);
     }
-  at.p[u->n_tensors - 1] = const_cast<float *>(v.std);
-  for (int t = 0; t < u->n_extra; ++t) at.p[u->n_tensors + t] = u->extra_param[t];
+  if (!actor_only) at.p[u->n_tensors - 1] = const_cast<float *>(v.std);
+  for (int t = 0; t < n_extra; ++t) at.p[u->n_tensors + t] = u->extra_param[t];
   hipLaunchKernelGGL(norm_partial_kernel, dim3((unsigned)blocks, (unsigned)total), dim3(256), 0, s, nt, partials);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(norm_kernel, dim3(1), dim3(kNormThreads), 0, s, total * blocks, partials, u->norm);
@@ -572,6 +669,45 @@ int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, doubl
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((maxn + 255) / 256), (unsigned)total), dim3(256), 0, s, at, cfg, (float)max_norm, u->norm, d_lr);
   HIP_TRY(hipGetLastError());
   return MPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mpc_ppo_update_apply(mpc_ppo_update *u, double max_norm, double beta1, double beta2, double eps, int step, const double *d_lr, void *stream) {
+  return apply("mpc_ppo_update_apply", false, u, max_norm, beta1, beta2, eps, step, d_lr, stream);
+}
+
+int mpc_ppo_update_apply_actor(mpc_ppo_update *u, double max_norm, double beta1, double beta2, double eps, int step, const double *d_lr, void *stream) {
+  return apply("mpc_ppo_update_apply_actor", true, u, max_norm, beta1, beta2, eps, step, d_lr, stream);
+}
+
+int mpc_ppo_update_set_distill_targets(mpc_ppo_update *u, const float *d_teacher_actions) {
+  if (!mpchost::aligned16(d_teacher_actions)) return fail(MPC_E_ARG, "mpc_ppo_update_set_distill_targets: d_teacher_actions must be 16-byte aligned");
+  if (!u) return fail(MPC_E_ARG, "mpc_ppo_update_set_distill_targets: bad argument");
+  u->distill_targets = d_teacher_actions;       // (null: cleared)
+  return MPC_OK;
+}
+
+int mpc_ppo_update_grads_distill(mpc_ppo_update *u, int rows, const long long *d_idx, int loss_type, float *d_terms, void *stream) {
+  if (!u || !d_idx || !d_terms) return fail(MPC_E_ARG, "mpc_ppo_update_grads_distill: bad argument");
+  if (rows <= 0 || rows > u->max_rows) return fail(MPC_E_ARG, "mpc_ppo_update_grads_distill: rows must lie in 1 .. max_rows");
+  if (loss_type != ppo::kBcMse && loss_type != ppo::kBcHuber) return fail(MPC_E_ARG, "mpc_ppo_update_grads_distill: loss_type is 0 (mse) or 1 (huber)");
+  if (!u->grads_bound) return fail(MPC_E_ARG, "mpc_ppo_update_grads_distill: no gradients bound (mpc_ppo_update_bind)");
+  if (!u->storage_set) return fail(MPC_E_ARG, "mpc_ppo_update_grads_distill: no storage set (mpc_ppo_update_set_storage)");
+  if (!u->distill_targets) return fail(MPC_E_ARG, "mpc_ppo_update_grads_distill: no targets set (mpc_ppo_update_set_distill_targets)");
+  mpc_ac_view v;
+  if (!mpc_ac_get_view(u->ac, &v) || !v.bound) return fail(MPC_E_ARG, "mpc_ppo_update_grads_distill: the mpc_ac has no parameters bound");
+  DeviceGuard guard_(u->device);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = forward_pass(u, v, 1, false, rows, d_idx, s)) return rc;
+  const int hb = (rows + kHeadThreads - 1) / kHeadThreads, la = u->nl[kActor] - 1;
+  hipLaunchKernelGGL(bc_head_kernel, dim3((unsigned)hb), dim3(kHeadThreads), 0, s, rows, d_idx, u->st.total_rows, loss_type, ppo::bc_norm(loss_type, rows),
+                     u->distill_targets, u->Y[kActor][la], u->dY[kActor][la], u->partials);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(bc_reduce_kernel, dim3(1), dim3(64), 0, s, hb, rows, u->partials, d_terms);
+  HIP_TRY(hipGetLastError());
+  return backward_pass(u, v, 1, false, rows, d_idx, s);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 //                   gradient of  loss = surrogate + value_loss_coef * value_loss - entropy_coef * entropy  (means over the B rows of the mini-batch)
 //                   with respect to the actor's mean, the critic's value and std
 //   entropy_row     Normal.entropy summed over the actions (the same for every row: std does not depend on the observation)
+//   bc_element      one element of the behaviour-cloning loss of policy distillation (mse or huber) and its gradient
 //   adapt_lr        PPO.adapt_learning_rate on a float64 learning rate
 //   adam_element    one element of torch.optim.Adam's step (no weight decay, no amsgrad), behind clip_grad_norm_'s multiplication
 // float32 in rsl_rl's / torch's operation order; compile with -ffp-contract=off.
@@ -98,6 +99,26 @@ MPC_HD void head_row(const HeadCfg &c, const float *mu, float V, const float *st
     dvl = -2.0f * e;
   }
   o.dv = (c.value_coef * dvl) * c.inv_rows;
+}
+
+// ---- behaviour cloning (policy distillation): one element of torch.nn.functional.mse_loss / huber_loss (delta = 1) with mean reduction over the
+// 12 B elements of a mini-batch, d = mu - target.  `value` is the element's term of the sum the mean is taken of; `grad` is d loss / d mu as
+// torch's backward kernels write it: norm * d with norm = 2 / (12 B) for mse, norm * clamp(d, -1, 1) with norm = 1 / (12 B) for huber, norm the
+// float32 value of the float64 quotient.
+enum { kBcMse = 0, kBcHuber = 1 };
+
+MPC_HD float bc_norm(int loss_type, int rows) { return (float)((loss_type == kBcMse ? 2.0 : 1.0) / (double)((long long)kActions * rows)); }
+
+MPC_HD void bc_element(int loss_type, float norm, float mu, float target, float &value, float &grad, float &gap) {
+  const float d = mu - target;
+  gap = fabsf(d);
+  if (loss_type == kBcMse) {
+    value = d * d;
+    grad = norm * d;
+  } else {
+    value = gap < 1.0f ? (0.5f * d) * d : gap - 0.5f;
+    grad = d < -1.0f ? -norm : (d > 1.0f ? norm : norm * d);
+  }
 }
 
 // PPO.adapt_learning_rate: lr / 1.5 (not below 1e-5) if kl > 2 desired_kl, lr * 1.5 (not above 1e-2) if 0 < kl < desired_kl / 2

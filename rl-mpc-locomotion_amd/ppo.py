@@ -25,7 +25,8 @@ normalisation (rsl_rl 2.x's ``EmpiricalNormalization``; ``obs_norm.ObsNormalizer
 reference uses none), recurrent policies (rsl_rl's ``ActorCriticRecurrent``: an LSTM in front of each MLP; ``recurrent.py``), the runner's episode
 statistics on the device (``episode.EpisodeStats``); ``PPOTrainer.evaluate`` is the reference's ``cfg.test`` loop.  Not built: GRU and stacked layers,
 logging beyond ``infos``.  (A recurrent actor-critic's device update is ``RecurrentConfig(update_through_time="hip", update_heads="hip")``; a recurrent
-``update="hip"`` stays refused.)
+``update="hip"`` stays refused.)  Teacher-student policy distillation -- a teacher whose actor reads the privileged row, a student that is labelled with its
+actions, PPO fine-tuning of the student -- is ``distill.py`` (``TeacherEnv``, ``Distiller``), with nothing changed here.
 
 The device entry points need the GPU (MpcLibraryError without one) and have no CPU fallback.
 """
@@ -54,6 +55,7 @@ DECLS = {
     "mpc_ac_act_asymmetric": (ci, [vp, ci, vp, vp, C.c_ulonglong, C.c_uint, vp, vp, vp, vp, vp, vp, vp]),
     "mpc_ac_evaluate": (ci, [vp, ci, vp, vp, vp]),
     "mpc_ac_act_inference": (ci, [vp, ci, vp, vp, vp]),
+    "mpc_ac_act_distill": (ci, [vp, vp, ci, vp, vp, C.c_ulonglong, C.c_uint, vp, vp, vp, vp, vp, vp]),
     "mpc_rollout_add": (ci, [ci, cd, vp, vp, vp, vp, vp, vp, vp]),
     "mpc_rollout_returns": (ci, [ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp]),
     "mpc_ppo_last_error": (text, []),
@@ -77,6 +79,9 @@ UPDATE_DECLS = {
     "mpc_ppo_update_set_sequence_rows": (ci, [vp, vp, vp, vp, vp]),
     "mpc_ppo_update_grads_sequence": (ci, [vp, ci, vp, cd, cd, cd, ci, ci, cd, vp, vp, vp]),
     "mpc_ppo_update_bind_extra": (ci, [vp, ci, vp, vp, vp, vp, vp]),
+    "mpc_ppo_update_set_distill_targets": (ci, [vp, vp]),
+    "mpc_ppo_update_grads_distill": (ci, [vp, ci, vp, ci, vp, vp]),
+    "mpc_ppo_update_apply_actor": (ci, [vp, cd, cd, cd, cd, ci, vp, vp]),
 }
 UPDATE_SYMBOLS = list(UPDATE_DECLS)
 update_lib = _lib.binder(UPDATE_DECLS, base=lib)   # ... with the entry points of the device update bound (and those of ``lib()``)
@@ -735,6 +740,12 @@ _Rider = namedtuple("_Rider", "summary record after", defaults=(None,))
 SCALARS = ("mean_reward", "done_rate", "value_loss", "surrogate_loss", "mean_noise_std")
 
 
+def episode_record(s):
+    """``EpisodeStats.summary``'s values as a record's entries: rsl_rl's statistics over the last 100 finished episodes."""
+    return dict(mean_episode_return=s[S_MEAN_RETURN], mean_episode_length=s[S_MEAN_LENGTH], episodes_in_window=int(s[S_WINDOW_COUNT]),
+                episodes_finished=int(s[S_EPISODES]), timeouts_in_window=int(s[S_WINDOW_TIMEOUTS]))
+
+
 def _riders(trainer):
     """The riders of ``trainer`` (anything with its ``_scalars``, ``alg``, ``episode_stats``, ``curriculum`` and ``episode_terms``; ``reward_shaping`` and
     ``contact_terms`` where it has one), in the record's order."""
@@ -746,12 +757,9 @@ def _riders(trainer):
             alg.sync_learning_rate(values[0])
         return {"learning_rate": alg.learning_rate}
 
-    def episodes(s):                                                             # rsl_rl's statistics over the last 100 finished episodes
-        return dict(mean_episode_return=s[S_MEAN_RETURN], mean_episode_length=s[S_MEAN_LENGTH], episodes_in_window=int(s[S_WINDOW_COUNT]),
-                    episodes_finished=int(s[S_EPISODES]), timeouts_in_window=int(s[S_WINDOW_TIMEOUTS]))
     riders = [_Rider(lambda: trainer._scalars, lambda values: dict(zip(SCALARS, values))),
               _Rider(lambda: alg.lr_device, learning_rate),                    # (None on the torch backend)
-              _Rider(lambda: trainer.episode_stats.summary, episodes)]
+              _Rider(lambda: trainer.episode_stats.summary, episode_record)]
     if curriculum is not None:                                                   # the terrain levels as they stand after the iteration
         riders.append(_Rider(lambda: curriculum.summary(), lambda values: curriculum.record(values, curriculum.num_types)))
     if terms is not None:                                                        # the per-term sums of the iteration's closed episodes; the next record covers the next
